@@ -137,6 +137,27 @@ def _timed_loop(step, steps: int, warmup: int):
     return time.perf_counter() - t0, start.elapsed_time(stop)
 
 
+DUMP_BYTES_MAX = 60 * 10**6  # --dump-outputs: array bytes in all (the files, .npy headers included, stay under 64 MB)
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """`--dump-outputs DIR`: what the timed path handed its caller in its last step, `DIR/<name>.npy` in float32, env
+    axis first (every rank's envs in global id order). The inputs are seeded, so two builds run with the same arguments
+    can be compared array for array. Beyond DUMP_BYTES_MAX in all, the same fixed, seeded sample of envs is kept of
+    every array."""
+    import numpy as np
+
+    arrays = {name: np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32) for name, t in arrays.items()}
+    envs = len(next(iter(arrays.values())))
+    per_env = sum(a.nbytes for a in arrays.values()) // envs
+    if envs * per_env > DUMP_BYTES_MAX:
+        keep = np.sort(np.random.default_rng(0).choice(envs, DUMP_BYTES_MAX // per_env, replace=False))
+        arrays = {name: a[keep] for name, a in arrays.items()}
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+
+
 def secondary_c3(envs: int = 16384, steps: int = STEADY_STEPS, warmup: int = STEADY_WARMUP, seed: int = 0, horizon: int = 16) -> dict:
     """BASELINE.json configs[2] as SURVEY.md section 8d writes it (C3):
     UpkieBaseVelocity (the MPC balancer in front of UpkieGyropod,
@@ -556,6 +577,9 @@ def main_c5(args, sim_factory=None, backend=None, keep_group: bool = False):
         steady = timed(STEADY_STEPS)
     advance(args.warmup)
     elapsed, device_ms, resets = timed(args.steps)
+    if args.dump_outputs and rank == 0:
+        obs, reward, terminated, truncated = (t.flatten(0, 1)[:counted_envs] for t in env.blob.views(env.gather.last()[:, 0]))
+        dump_outputs(args.dump_outputs, {"obs": obs, "reward": reward, "terminated": terminated, "truncated": truncated})
     if rank != 0:
         env.shutdown(destroy_group=not keep_group)
         base.close()  # (the handle is `base`'s: ShardedVecEnv leaves a caller's handle open)
@@ -652,6 +676,8 @@ def main(argv=None, sim_factory=None, backend=None, json_out=None) -> None:
                              "gathered chunk, upkie_rollout_gae); c5: UpkieServos with push / inertia randomisation (BASELINE configs[4]: 4096 envs per GPU, "
                              "32768 at --gpus 8), every env kind's sharded runner")
     parser.add_argument("--law", choices=("torque", "velocity"), default="torque", help="--config c5: the servo-level law evaluated inside the launch")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed steps, write what the last of them returned (obs, reward, terminated, truncated of every env) as DIR/<name>.npy")
     args = parser.parse_args(argv)
     explicit_envs = args.envs_per_gpu is not None
     if args.envs_per_gpu is None:
@@ -670,7 +696,7 @@ def main(argv=None, sim_factory=None, backend=None, json_out=None) -> None:
 
         def block(config, envs_per_gpu, keep_group):
             a = copy.copy(args)
-            a.config, a.envs_per_gpu, a.no_fused, a.no_cpu_baseline = config, envs_per_gpu, True, True
+            a.config, a.envs_per_gpu, a.no_fused, a.no_cpu_baseline, a.dump_outputs = config, envs_per_gpu, True, True, None
             try:
                 if config == "c5":
                     out = main_c5(a, sim_factory=sim_factory, backend=backend, keep_group=keep_group)
@@ -801,6 +827,8 @@ def run_pendulum(args, sim_factory=None, backend=None, keep_group: bool = False)
         steady = timed(STEADY_STEPS, 1)
     advance(args.warmup, args.steps_per_launch)
     elapsed, device_ms, launches, autoresets = timed(args.steps, args.steps_per_launch)
+    # records [world, B, 8] of the last timed step, copied before the fused block below moves the ring on
+    last = env.gather.last().clone() if args.dump_outputs and rank == 0 else None
     # beside it: the same number of steps fused STEPS_PER_LAUNCH per launch (the on-device agent needs nothing from the host between steps)
     fused = None
     if not args.no_fused and args.steps_per_launch == 1:
@@ -812,6 +840,9 @@ def run_pendulum(args, sim_factory=None, backend=None, keep_group: bool = False)
         return None
 
     total_envs = counted_envs
+    if last is not None:
+        records = last.flatten(0, 1)[:total_envs]  # (not the ghost envs of strong scaling)
+        dump_outputs(args.dump_outputs, {"obs": records[:, :4], "reward": records[:, 4], "terminated": records[:, 5], "truncated": records[:, 6]})
     value = total_envs * args.steps / elapsed
     step_us = device_ms * 1e3 / args.steps  # device time per env.step() of the batch, this rank
     launch_us = device_ms * 1e3 / launches  # avg per-launch device time (HIP events on the launching stream)

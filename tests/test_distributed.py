@@ -260,6 +260,65 @@ def test_bench_launch_line_on_cpu_doubles(world, flags, total, per_rank, ghosts)
         assert cfg["baseline_config"].startswith("weak-scaling line of configs[1]") and "--config c4" in cfg["baseline_config"]
 
 
+def test_bench_dump_outputs_on_cpu_doubles(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step returned, every counted env in global id order:
+    the same arrays whatever the number of ranks (no ghost envs) and with or without the fused block behind the timed
+    region, identical from run to run, and another step's arrays when --steps changes."""
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    double = os.path.join(root, "tests", "bench_double.py")
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+
+    def run(world, flags, name):
+        launch = [sys.executable] if world == 1 else [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
+                                                      "--master-addr", "127.0.0.1", "--master-port", str(free_port())]
+        out = tmp_path / name
+        result = subprocess.run(launch + [double, "--gpus", str(world), "--warmup", "3", "--gather-chunk", "4", "--dump-outputs", str(out)] + flags,
+                                capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert result.returncode == 0, result.stderr[-3000:]
+        assert len([line for line in result.stdout.splitlines() if line.startswith("{")]) == 1
+        return {p.stem: np.load(p) for p in sorted(out.glob("*.npy"))}
+
+    pendulum = ["--total-envs", "7"]
+    two_ranks = run(2, pendulum + ["--steps", "5"], "two_ranks")
+    one_rank = run(1, pendulum + ["--steps", "5", "--no-fused"], "one_rank")
+    again = run(1, pendulum + ["--steps", "5", "--no-fused"], "again")
+    later = run(1, pendulum + ["--steps", "6", "--no-fused"], "later")
+    assert sorted(one_rank) == ["obs", "reward", "terminated", "truncated"]
+    assert one_rank["obs"].shape == (7, 4) and all(one_rank[k].shape == (7,) for k in ("reward", "terminated", "truncated"))
+    assert all(a.dtype == np.float32 for a in one_rank.values())
+    for name in one_rank:
+        assert np.array_equal(two_ranks[name], one_rank[name]) and np.array_equal(again[name], one_rank[name]), name
+    assert not np.array_equal(later["obs"], one_rank["obs"])
+    servos = run(1, ["--config", "c5", "--envs-per-gpu", "5", "--steps", "3"], "servos")
+    assert servos["obs"].shape == (5, 6, 5) and servos["reward"].shape == (5,) and np.isfinite(servos["obs"]).all()
+
+
+def test_bench_dump_outputs_keeps_a_fixed_sample_of_a_large_output(tmp_path):
+    """Beyond its byte budget `bench.dump_outputs` keeps the same seeded sample of envs in every array, in env order."""
+    import numpy as np
+
+    import bench
+
+    envs = 3 * 10**6  # 28 B per env: 84 MB
+    ids = torch.arange(envs, dtype=torch.float32)
+    arrays = {"obs": ids[:, None].repeat(1, 4), "reward": ids, "terminated": ids, "truncated": torch.zeros(envs, dtype=torch.uint8)}
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), arrays)
+    files = sorted((tmp_path / "a").glob("*.npy"))
+    assert sum(p.stat().st_size for p in files) < 64 * 10**6
+    out = {p.stem: np.load(p) for p in files}
+    keep = out["reward"]
+    assert len(keep) == bench.DUMP_BYTES_MAX // 28 and np.all(np.diff(keep) > 0)
+    assert np.array_equal(out["obs"], np.repeat(keep[:, None], 4, axis=1)) and np.array_equal(out["terminated"], keep)
+    assert out["truncated"].dtype == np.float32 and not out["truncated"].any()
+    assert all(np.array_equal(np.load(tmp_path / "b" / p.name), out[p.stem]) for p in files)
+
+
 def test_a_flush_ships_only_the_steps_it_has_not_shipped(monkeypatch):
     """A flush in the middle of a chunk (the end of bench.py's timed region: the driver times 20 steps against a
     64-step chunk) sends the steps produced since the last flush, not the whole chunk buffer, and the completed
