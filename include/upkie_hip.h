@@ -204,7 +204,8 @@ enum UpkieStructId {
   UPKIE_STRUCT_OBSERVER_CONFIG = 6,
   UPKIE_STRUCT_OBSERVER_INPUT = 7,
   UPKIE_STRUCT_OBSERVER_OUTPUT = 8,
-  UPKIE_STRUCT_COUNT = 9
+  UPKIE_STRUCT_MLP_SHAPE = 9,
+  UPKIE_STRUCT_COUNT = 10
 };
 int64_t upkie_hip_struct_bytes(int which);
 
@@ -802,6 +803,67 @@ int upkie_observers_step(UpkieObservers* observers, float* state, const UpkieObs
 int upkie_linear_policy(int32_t num_envs, int32_t obs_dim, int32_t act_dim, const float* obs,
                         const float* weights, const float* bias, double clip, float* act,
                         void* stream);
+
+/* ---- MLP actor-critic policy (one launch per rollout step) ---------------
+ * The policy side of a rollout step as one launch: what Stable-Baselines3's
+ * MlpPolicy evaluates between two env steps (separate actor and critic towers,
+ * one activation, a diagonal Gaussian with a state-independent log_std,
+ * optionally frozen VecNormalize statistics), computed on fp32 MFMA
+ * (csrc/policy_mlp.hpp). For each env n < num_envs:
+ *   x        = clamp((obs - obs_mean) / obs_std, -clip_obs, clip_obs)
+ *              (obs_std = sqrt(var + eps); x = obs when normalize == 0)
+ *   mean     = actor(x)                      [act_dim]
+ *   value    = critic(x)                     (scalar)
+ *   action   = mean + exp(log_std) * z       (action = mean when deterministic)
+ *   log_prob = sum_a -(action_a - mean_a)^2 / (2 sigma_a^2) - log_std_a - log(2 pi) / 2
+ *              (SB3's DiagGaussianDistribution.log_prob of the UNCLIPPED action)
+ *   env_action = clamp(action, action_low, action_high), per dimension.
+ * A tower is 1-4 hidden layers of 1-256 units (critic_layers == 0: no critic)
+ * and a linear head; 1 <= obs_dim <= 256, 1 <= act_dim <= 64.
+ *
+ * Sampling. z of action a of env n is normal a & 3 of Philox4x32-10 block
+ *   counter = (n, calls[n], 0, (4 << 24) | (a >> 2)), key = (seed lo, seed hi),
+ * where calls[n] is the env's uint32 call counter in device memory (read by the
+ * launch, incremented by one after it; deterministic launches neither read nor
+ * advance it, so no host argument changes between calls and the launch can be
+ * captured in a hipGraph). The block's words r0..r3 give two Box-Muller pairs,
+ *   u1 = ((r[2p] >> 8) + 1) / 2^24 in (0, 1] (never 0), u2 = (r[2p+1] >> 8) / 2^24,
+ *   z[2p] = sqrt(-2 ln u1) cos(2 pi u2), z[2p+1] = sqrt(-2 ln u1) sin(2 pi u2).
+ * (Tag 4 in the top byte of counter word 3 keeps these draws apart from the
+ * step kernels' streams, tags 0-3.)
+ *
+ * Weights are read from one packed fp32 buffer of upkie_mlp_packed_words(shape)
+ * words in MFMA fragment order (layout: csrc/policy_mlp.hpp;
+ * upkie_amd/policies.py packs it from torch modules, on the device). */
+#define UPKIE_MLP_MAX_LAYERS 4
+enum UpkieMlpActivation { UPKIE_MLP_TANH = 0, UPKIE_MLP_RELU = 1 };
+typedef struct {
+  int32_t obs_dim;
+  int32_t act_dim;
+  int32_t activation; /* UpkieMlpActivation, for every hidden layer of both towers */
+  int32_t actor_layers;
+  int32_t actor_widths[UPKIE_MLP_MAX_LAYERS];
+  int32_t critic_layers; /* 0: no critic */
+  int32_t critic_widths[UPKIE_MLP_MAX_LAYERS];
+  int32_t normalize; /* 1: observation normalisation with the packed obs_mean / obs_std */
+  float clip_obs;    /* VecNormalize's clip_obs (> 0 when normalize) */
+} UpkieMlpShape;
+
+/* Words of the packed weight buffer of `shape`, or -1 (with the reason in
+ * upkie_sim_last_error(NULL)) when the shape is out of range. */
+int64_t upkie_mlp_packed_words(const UpkieMlpShape* shape);
+
+/* One launch of the policy for num_envs envs: obs [num_envs][obs_dim], packed
+ * [upkie_mlp_packed_words(shape)], calls [num_envs] (uint32, may be NULL when
+ * deterministic), outputs norm_obs [num_envs][obs_dim], mean, action and
+ * env_action [num_envs][act_dim], value and log_prob [num_envs]: contiguous
+ * device buffers, every output may be NULL. With mean, action, env_action and
+ * log_prob all NULL the actor does not run (and no counter advances); with
+ * value NULL the critic does not run. No CPU fallback: UPKIE_ERR_NO_DEVICE
+ * without a HIP device. Errors are reported through upkie_sim_last_error(NULL). */
+int upkie_mlp_actor_critic(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* obs,
+                           uint32_t* calls, uint64_t seed, int32_t deterministic, float* norm_obs, float* mean,
+                           float* action, float* env_action, float* value, float* log_prob, void* stream);
 
 /* ---- Rollout consumer (BASELINE.json configs[3]) ---
  * Generalized advantage estimation over a rollout resident in HBM: rewards,

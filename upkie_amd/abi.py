@@ -280,6 +280,25 @@ class UpkieObserverOutput(C.Structure):
     ]
 
 
+MLP_MAX_LAYERS = 4  # UPKIE_MLP_MAX_LAYERS
+MLP_TANH = 0  # enum UpkieMlpActivation
+MLP_RELU = 1
+
+
+class UpkieMlpShape(C.Structure):
+    _fields_ = [
+        ("obs_dim", C.c_int32),
+        ("act_dim", C.c_int32),
+        ("activation", C.c_int32),
+        ("actor_layers", C.c_int32),
+        ("actor_widths", C.c_int32 * MLP_MAX_LAYERS),
+        ("critic_layers", C.c_int32),
+        ("critic_widths", C.c_int32 * MLP_MAX_LAYERS),
+        ("normalize", C.c_int32),
+        ("clip_obs", C.c_float),
+    ]
+
+
 # enum UpkieStructId -> the mirror of that struct here (`upkie_hip_struct_bytes`: lib.load() compares sizes)
 STRUCT_IDS = {
     0: UpkieModel,
@@ -291,7 +310,11 @@ STRUCT_IDS = {
     6: UpkieObserverConfig,
     7: UpkieObserverInput,
     8: UpkieObserverOutput,
+    9: UpkieMlpShape,
 }
+# structs that only newer, optional entry points read: a build without that entry point (an older library loaded through
+# UPKIE_HIP_LIBRARY for an A/B run) answers -1 for them, and lib.load() still accepts it
+OPTIONAL_STRUCTS = {9: "upkie_mlp_actor_critic"}
 MAX_GRAPH_CAPTURES = 8  # UPKIE_MAX_GRAPH_CAPTURES
 
 # observer memory words (enum UpkieObserverStateWord)

@@ -16,6 +16,7 @@
 #include <string>
 #include <type_traits>
 
+#include "policy_mlp.hpp"
 #include "rollout.hpp"
 
 #include "step_kernels.hpp"
@@ -332,6 +333,7 @@ extern "C" int64_t upkie_hip_struct_bytes(int which) {
     case UPKIE_STRUCT_OBSERVER_CONFIG: return (int64_t)sizeof(UpkieObserverConfig);
     case UPKIE_STRUCT_OBSERVER_INPUT: return (int64_t)sizeof(UpkieObserverInput);
     case UPKIE_STRUCT_OBSERVER_OUTPUT: return (int64_t)sizeof(UpkieObserverOutput);
+    case UPKIE_STRUCT_MLP_SHAPE: return (int64_t)sizeof(UpkieMlpShape);
     default: return -1;
   }
 }
@@ -1210,6 +1212,77 @@ extern "C" int upkie_observers_step(UpkieObservers* h, float* state, const Upkie
                      *in, *out);
   hipError_t err = hipGetLastError();
   return err == hipSuccess ? UPKIE_OK : observers_fail(h, UPKIE_ERR_HIP, hipGetErrorString(err));
+}
+
+// ============================================================ MLP actor-critic policy
+extern "C" int64_t upkie_mlp_packed_words(const UpkieMlpShape* shape) {
+  if (!shape) {
+    g_create_error = "null shape";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  const int64_t words = upkie::mlp_layout(*shape, nullptr);
+  if (words < 0) g_create_error = "MLP shape out of range (obs_dim 1-256, act_dim 1-64, 1-4 actor / 0-4 critic layers of 1-256 units, tanh or relu, clip_obs > 0)";
+  return words < 0 ? UPKIE_ERR_INVALID_ARGUMENT : words;
+}
+
+template <int W>
+static void launch_mlp(int activation, dim3 grid, hipStream_t stream, const upkie::MlpDev& P, const float* packed, const float* obs,
+                       uint32_t* calls, const upkie::MlpOutputs& out) {
+  if (activation == UPKIE_MLP_TANH)
+    hipLaunchKernelGGL((upkie::mlp_actor_critic_kernel<W, UPKIE_MLP_TANH>), grid, dim3(128), 0, stream, P, packed, obs, calls, out);
+  else
+    hipLaunchKernelGGL((upkie::mlp_actor_critic_kernel<W, UPKIE_MLP_RELU>), grid, dim3(128), 0, stream, P, packed, obs, calls, out);
+}
+
+extern "C" int upkie_mlp_actor_critic(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* obs, uint32_t* calls,
+                                      uint64_t seed, int32_t deterministic, float* norm_obs, float* mean, float* action, float* env_action,
+                                      float* value, float* log_prob, void* stream) {
+  if (num_envs <= 0) {
+    g_create_error = "num_envs must be positive";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (!shape || !packed || !obs) {
+    g_create_error = "null argument";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  upkie::MlpDev P;
+  if (upkie::mlp_layout(*shape, &P) < 0)
+    return (int)upkie_mlp_packed_words(shape);  // (sets the message)
+  P.num_envs = num_envs;
+  P.run_actor = mean || action || env_action || log_prob;
+  P.run_critic = value != nullptr;
+  P.sample = P.run_actor && !deterministic;
+  if (P.run_critic && shape->critic_layers == 0) {
+    g_create_error = "a value output needs a critic (critic_layers > 0)";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (P.sample && !calls) {
+    g_create_error = "sampling needs the per-env call counters";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  P.seed_lo = (unsigned)(seed & 0xffffffffu);
+  P.seed_hi = (unsigned)(seed >> 32);
+  if (upkie_hip_device_count() <= 0) {
+    g_create_error = "no HIP device visible";
+    return UPKIE_ERR_NO_DEVICE;
+  }
+  if (!P.run_actor && !P.run_critic && !norm_obs) return UPKIE_OK;
+  const upkie::MlpOutputs out{norm_obs, mean, action, env_action, value, log_prob};
+  const dim3 grid((unsigned)((num_envs + 15) / 16));
+  const hipStream_t s = (hipStream_t)stream;
+  switch (upkie::mlp_width_class(*shape)) {
+    case 16: launch_mlp<16>(shape->activation, grid, s, P, packed, obs, calls, out); break;
+    case 32: launch_mlp<32>(shape->activation, grid, s, P, packed, obs, calls, out); break;
+    case 64: launch_mlp<64>(shape->activation, grid, s, P, packed, obs, calls, out); break;
+    case 128: launch_mlp<128>(shape->activation, grid, s, P, packed, obs, calls, out); break;
+    default: launch_mlp<256>(shape->activation, grid, s, P, packed, obs, calls, out); break;
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) {
+    g_create_error = hipGetErrorString(err);
+    return UPKIE_ERR_HIP;
+  }
+  return UPKIE_OK;
 }
 
 // ============================================================ rollout consumer

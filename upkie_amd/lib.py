@@ -29,6 +29,7 @@ SOURCES = [
     os.path.join(_HERE, "csrc", "octet.hpp"),
     os.path.join(_HERE, "csrc", "observers.hpp"),
     os.path.join(_HERE, "csrc", "rollout.hpp"),
+    os.path.join(_HERE, "csrc", "policy_mlp.hpp"),
     os.path.join(_HERE, "csrc", "wave_io.hpp"),
     os.path.join(_HERE, "..", "include", "upkie_hip.h"),
 ]
@@ -90,6 +91,8 @@ EXPORTED_SYMBOLS = (
     "upkie_observers_step",
     "upkie_rollout_gae",
     "upkie_linear_policy",
+    "upkie_mlp_packed_words",
+    "upkie_mlp_actor_critic",
 )
 
 
@@ -196,6 +199,8 @@ def _check_struct_sizes(lib) -> None:
     lib.upkie_hip_struct_bytes.argtypes = [C.c_int]
     for which, cls in abi.STRUCT_IDS.items():
         theirs, ours = int(lib.upkie_hip_struct_bytes(which)), C.sizeof(cls)
+        if theirs == -1 and which in abi.OPTIONAL_STRUCTS and not hasattr(lib, abi.OPTIONAL_STRUCTS[which]):
+            continue  # (a build that predates the struct and the entry point reading it: those calls are refused by name)
         if theirs != ours:
             raise UpkieRuntimeError(
                 f"{LIB_PATH} was built from another version of include/upkie_hip.h: sizeof({cls.__name__}) is {theirs} B there, "
@@ -346,6 +351,11 @@ def load() -> C.CDLL:
     if hasattr(lib, "upkie_linear_policy"):  # (round 4; older builds loaded for A/B runs lack it)
         lib.upkie_linear_policy.restype = C.c_int
         lib.upkie_linear_policy.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_double, vp, vp]
+    if hasattr(lib, "upkie_mlp_actor_critic"):  # (newer entry points: an older build loaded for an A/B run lacks them)
+        lib.upkie_mlp_packed_words.restype = C.c_int64
+        lib.upkie_mlp_packed_words.argtypes = [C.POINTER(abi.UpkieMlpShape)]
+        lib.upkie_mlp_actor_critic.restype = C.c_int
+        lib.upkie_mlp_actor_critic.argtypes = [C.c_int32, C.POINTER(abi.UpkieMlpShape), vp, vp, vp, C.c_uint64, C.c_int32] + [vp] * 7
     lib.upkie_rollout_gae.restype = C.c_int
     lib.upkie_rollout_gae.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
     _lib = lib

@@ -5,13 +5,15 @@ clamp(gains . obs)``; examples/pybullet/pd_balancing.py). Evaluated with torch
 ops on the device -- ``(obs @ W).clamp(-c, c)`` -- it is two or three launches
 of 2-5 us each (rocBLAS's gemv for a four-column matrix: 4.9 us) behind a
 14.5 us step; `LinearPolicy` is one launch (`upkie_linear_policy`,
-csrc/rollout.hpp) writing into a persistent action buffer."""
+csrc/rollout.hpp) writing into a persistent action buffer. `MlpActorCritic` / `MlpPolicy` do the same for the
+MLP policies of Stable-Baselines3 (csrc/policy_mlp.hpp)."""
 
+import ctypes as C
 from typing import Optional
 
 import torch
 
-from . import lib
+from . import abi, lib
 from .exceptions import UpkieRuntimeError
 
 
@@ -59,3 +61,412 @@ class LinearPolicy:
         if status < 0:
             lib.check(status, None)
         return self._act
+
+
+# ------------------------------------------------------------------ MLP actor-critic
+# What sits between two env steps of a PPO rollout with Stable-Baselines3's MlpPolicy -- two towers of addmm +
+# activation, the Gaussian draw, its log-probability, the clamp, the buffer copies: about 20 small launches as torch
+# ops -- as ONE launch (`upkie_mlp_actor_critic`, csrc/policy_mlp.hpp) that writes straight into the rollout buffer and
+# can be captured in a hipGraph together with the step.
+
+_ACTIVATIONS = {"tanh": 0, "relu": 1}  # enum UpkieMlpActivation
+OUTPUT_NAMES = ("norm_obs", "mean", "action", "env_action", "value", "log_prob")  # the kernel's outputs, in argument order
+
+
+def _tiles(width: int) -> int:
+    return (int(width) + 15) // 16
+
+
+def _width_class(shape) -> int:
+    w = max([shape.obs_dim, shape.act_dim] + list(shape.actor_widths[: shape.actor_layers]) + list(shape.critic_widths[: shape.critic_layers]))
+    for c in (16, 32, 64, 128, 256):
+        if w <= c:
+            return c
+    raise ValueError(f"MLP width {w} above 256")
+
+
+def pack_index(shape, sizes):
+    """Gather map of the packed weight buffer (layout: csrc/policy_mlp.hpp): for each packed word, the index of its
+    value in the concatenation of the flattened source tensors (`sizes`: their element counts, in the order of
+    `MlpActorCritic.sources()`), or ``sum(sizes)`` -- one zero word appended to the concatenation -- for padding."""
+    import numpy as np
+
+    starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    zero = int(starts[-1])
+    src = iter(range(len(sizes)))
+    pair = 2 if _width_class(shape) >= 32 else 1
+    D, A = int(shape.obs_dim), int(shape.act_dim)
+    blocks = []
+
+    def vector(n, padded):
+        i = next(src)
+        idx = np.full(padded, zero, dtype=np.int64)
+        idx[:n] = starts[i] + np.arange(n)
+        blocks.append(idx)
+
+    def mfma_layer(n_in, n_out, first):
+        wi, bi = next(src), next(src)
+        in_t, out_t = _tiles(n_in), (_tiles(n_out) + pair - 1) // pair * pair
+        o, t, lane, s = np.meshgrid(np.arange(out_t), np.arange(in_t), np.arange(64), np.arange(4), indexing="ij")
+        unit = 16 * o + (lane & 15)
+        k = 16 * t + (4 * s + (lane >> 4) if first else 4 * (lane >> 4) + s)
+        blocks.append(np.where((unit < n_out) & (k < n_in), starts[wi] + unit * n_in + k, zero).reshape(-1))
+        unit = np.arange(16 * out_t)
+        blocks.append(np.where(unit < n_out, starts[bi] + unit, zero))
+
+    def dot_layer(n_in):
+        wi, bi = next(src), next(src)
+        k = np.arange(16 * _tiles(n_in))
+        blocks.append(np.where(k < n_in, starts[wi] + k, zero))
+        blocks.append(np.array([starts[bi], zero, zero, zero], dtype=np.int64))
+
+    def tower(layers, widths, outputs):
+        n_in = D
+        for i in range(layers):
+            mfma_layer(n_in, int(widths[i]), i == 0)
+            n_in = int(widths[i])
+        if outputs == 1:
+            dot_layer(n_in)
+        else:
+            mfma_layer(n_in, outputs, layers == 0)
+
+    dp = (D + 3) // 4 * 4
+    vector(D, dp)  # obs_mean
+    vector(D, dp)  # obs_std
+    for _ in range(3):  # action_low, action_high, log_std
+        vector(A, 16 * _tiles(A))
+    tower(int(shape.actor_layers), shape.actor_widths, A)
+    if shape.critic_layers > 0:
+        tower(int(shape.critic_layers), shape.critic_widths, 1)
+    return np.concatenate(blocks)
+
+
+def mlp_shape(actor_dims, critic_dims, activation: str, normalize: bool = False, clip_obs: float = 10.0) -> abi.UpkieMlpShape:
+    """`abi.UpkieMlpShape` of an actor (and critic) given as the ``[out, in]`` shapes of their Linear weights, head
+    last (``critic_dims`` empty: no critic)."""
+    if activation not in _ACTIVATIONS:
+        raise ValueError(f"activation must be one of {sorted(_ACTIVATIONS)}")
+    if not 2 <= len(actor_dims) <= abi.MLP_MAX_LAYERS + 1:
+        raise ValueError(f"the actor needs 1-{abi.MLP_MAX_LAYERS} hidden layers and a head")
+    if len(critic_dims) == 1 or len(critic_dims) > abi.MLP_MAX_LAYERS + 1:
+        raise ValueError(f"the critic needs 1-{abi.MLP_MAX_LAYERS} hidden layers and a head (or nothing)")
+    for what, dims in (("actor", actor_dims), ("critic", critic_dims)):
+        for i, d in enumerate(dims):
+            if len(d) != 2:
+                raise ValueError(f"{what} layer {i}: weights must be [out, in]")
+            if i and d[1] != dims[i - 1][0]:
+                raise ValueError(f"{what} layer {i} takes {d[1]} inputs, the layer before gives {dims[i - 1][0]}")
+    shape = abi.UpkieMlpShape()
+    shape.obs_dim, shape.act_dim = int(actor_dims[0][1]), int(actor_dims[-1][0])
+    if critic_dims and (critic_dims[0][1] != shape.obs_dim or critic_dims[-1][0] != 1):
+        raise ValueError(f"the critic must map {shape.obs_dim} inputs to 1 value")
+    if not 1 <= shape.obs_dim <= 256 or not 1 <= shape.act_dim <= 64:
+        raise ValueError("obs_dim must be in 1-256, act_dim in 1-64")
+    shape.activation = _ACTIVATIONS[activation]
+    shape.actor_layers = len(actor_dims) - 1
+    shape.critic_layers = max(len(critic_dims) - 1, 0)
+    for widths, dims in ((shape.actor_widths, actor_dims), (shape.critic_widths, critic_dims)):
+        for i, d in enumerate(dims[:-1]):
+            if not 1 <= d[0] <= 256:
+                raise ValueError(f"hidden widths must be in 1-256, got {d[0]}")
+            widths[i] = int(d[0])
+    shape.normalize = int(bool(normalize))
+    shape.clip_obs = float(clip_obs)
+    if normalize and not shape.clip_obs > 0.0:
+        raise ValueError("clip_obs must be positive")
+    return shape
+
+
+def sb3_parameters(state_dict):
+    """(actor weights, actor biases, critic weights, critic biases, log_std) of the ``state_dict()`` of
+    Stable-Baselines3's ``ActorCriticPolicy`` with separate networks, heads last: ``mlp_extractor.policy_net.{0,2,..}``
+    + ``action_net``, ``mlp_extractor.value_net.{0,2,..}`` + ``value_net``, ``log_std``. (Key names only: SB3 is not
+    imported.)"""
+    if any(k.startswith("mlp_extractor.shared_net") for k in state_dict):
+        raise ValueError("shared actor-critic layers are not supported (separate policy_net / value_net only)")
+    for key in ("action_net.weight", "action_net.bias", "log_std"):
+        if key not in state_dict:
+            raise KeyError(f"state dict has no {key!r} (not an SB3 ActorCriticPolicy with a Gaussian action)")
+
+    def stack(prefix):
+        idx = sorted({int(k[len(prefix):].split(".")[0]) for k in state_dict if k.startswith(prefix) and k.endswith(".weight")})
+        return [state_dict[f"{prefix}{i}.weight"] for i in idx], [state_dict[f"{prefix}{i}.bias"] for i in idx]
+
+    aw, ab = stack("mlp_extractor.policy_net.")
+    cw, cb = stack("mlp_extractor.value_net.")
+    aw, ab = aw + [state_dict["action_net.weight"]], ab + [state_dict["action_net.bias"]]
+    if "value_net.weight" in state_dict:
+        cw, cb = cw + [state_dict["value_net.weight"]], cb + [state_dict["value_net.bias"]]
+    else:
+        cw, cb = [], []
+    return aw, ab, cw, cb, state_dict["log_std"]
+
+
+def _linear_stack(seq, what: str):
+    """(weights, biases, activation name) of an ``nn.Sequential`` of Linear layers with one activation between them
+    (hidden layers) and none after the last (the head)."""
+    import torch.nn as nn
+
+    if not isinstance(seq, nn.Sequential):
+        raise TypeError(f"{what} must be an nn.Sequential of Linear and Tanh / ReLU modules")
+    mods = list(seq)
+    linears, act = [], None
+    for i, m in enumerate(mods):
+        if isinstance(m, nn.Linear):
+            if m.bias is None:
+                raise ValueError(f"{what}: Linear layers need a bias")
+            linears.append(m)
+            nxt = mods[i + 1] if i + 1 < len(mods) else None
+            if nxt is None:
+                continue
+            name = "tanh" if isinstance(nxt, nn.Tanh) else "relu" if isinstance(nxt, nn.ReLU) else None
+            if name is None:
+                raise ValueError(f"{what}: a hidden Linear must be followed by Tanh or ReLU, not {type(nxt).__name__}")
+            if act not in (None, name):
+                raise ValueError(f"{what}: one activation per network (found {act} and {name})")
+            act = name
+        elif not isinstance(m, (nn.Tanh, nn.ReLU)):
+            raise ValueError(f"{what}: unsupported module {type(m).__name__}")
+    if not linears or not isinstance(mods[-1], nn.Linear):
+        raise ValueError(f"{what} must end with a Linear head")
+    return [m.weight for m in linears], [m.bias for m in linears], act
+
+
+class MlpActorCritic:
+    """An SB3-style MLP actor-critic on the device, one launch per call.
+
+    ``act(obs)`` returns ``(env_action, action, value, log_prob)``: the action clamped to the action bounds (what the
+    env gets), the raw Gaussian sample, the critic's value and the log-probability of the raw sample -- what PPO's
+    rollout buffer stores. The tensors are the policy's persistent buffers, rewritten by every call, or the ones given
+    in ``out=`` (a dict over `OUTPUT_NAMES`, e.g. ``{"action": buffer.actions[t], "value": buffer.values[t],
+    "log_prob": buffer.log_probs[t], "norm_obs": buffer.observations[t]}``), which the kernel writes directly.
+
+    Randomness: Philox4x32-10 keyed by ``seed``, counted by a per-env call counter in device memory (include/
+    upkie_hip.h documents the mapping), so a call has no host argument that changes between calls and can be replayed
+    from a hipGraph. ``reseed(seed)`` resets the counters (a new seed value is a new launch argument: re-capture).
+    The first call fixes the batch size N (outputs and counters are allocated once; a call with another N raises).
+    Observation normalisation uses frozen VecNormalize statistics. Build with `from_modules` or
+    `from_sb3_state_dict`; after an optimiser step on those modules, `update_from` re-packs on the device."""
+
+    def __init__(self, actor_weights, actor_biases, critic_weights, critic_biases, log_std, activation: str, action_low=None,
+                 action_high=None, obs_mean=None, obs_var=None, clip_obs: float = 10.0, eps: float = 1e-8, seed: int = 0, device=None):
+        critic_weights, critic_biases = list(critic_weights or []), list(critic_biases or [])
+        shape = mlp_shape([tuple(w.shape) for w in actor_weights], [tuple(w.shape) for w in critic_weights], activation,
+                          obs_mean is not None or obs_var is not None, clip_obs)
+        for w, b in zip(list(actor_weights) + critic_weights, list(actor_biases) + critic_biases):
+            if tuple(b.shape) != (w.shape[0],):
+                raise ValueError(f"bias of shape {tuple(b.shape)} for a weight of shape {tuple(w.shape)}")
+        if len(actor_biases) != len(actor_weights) or len(critic_biases) != len(critic_weights):
+            raise ValueError("one bias per weight")
+        self.device = torch.device(device) if device is not None else actor_weights[0].device
+        if self.device.type != "cuda":
+            raise UpkieRuntimeError("MlpActorCritic runs on the HIP device only (there is no CPU fallback): give device='cuda:0'")
+        D, A = shape.obs_dim, shape.act_dim
+        self.shape = shape
+        self.activation = activation
+        self.clip_obs, self.eps = float(clip_obs), float(eps)
+        self._lib = lib.load()
+        if not hasattr(self._lib, "upkie_mlp_actor_critic"):
+            raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_mlp_actor_critic")
+        words = int(self._lib.upkie_mlp_packed_words(C.byref(shape)))
+        if words < 0:
+            lib.check(words, None)
+
+        def vec(v, n, fill, name):
+            t = torch.full((n,), fill, dtype=torch.float64) if v is None else torch.as_tensor(v, dtype=torch.float64).detach().cpu().reshape(-1)
+            if t.numel() != n:
+                raise ValueError(f"{name} needs {n} values")
+            return t
+
+        mean = vec(obs_mean, D, 0.0, "obs_mean")
+        std = torch.sqrt(vec(obs_var, D, 1.0, "obs_var") + self.eps)  # (fp64, as VecNormalize)
+        low = vec(action_low, A, float("-inf"), "action_low")
+        high = vec(action_high, A, float("inf"), "action_high")
+        if bool((low > high).any()):
+            raise ValueError("action_low must not exceed action_high")
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self._fixed = [mean.to(**f32), std.to(**f32), low.to(**f32), high.to(**f32)]
+        self.action_low, self.action_high = self._fixed[2], self._fixed[3]
+        self._params = None
+        self._set_params(actor_weights, actor_biases, critic_weights, critic_biases, log_std)
+        sizes = [t.numel() for t in self.sources()]
+        index = pack_index(shape, sizes)
+        if index.size != words:
+            raise UpkieRuntimeError(f"packed layout of {index.size} words here, {words} in the library: rebuild it")
+        self._index = torch.as_tensor(index, device=self.device)
+        self.packed = torch.empty(words, **f32)
+        self._zero = torch.zeros(1, **f32)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.calls = None  # [N] int32 words read as uint32 call counters by the kernel
+        self._out = {}
+        self.update_from()
+
+    # ---- construction
+    @classmethod
+    def from_modules(cls, actor, critic, log_std, action_low, action_high, obs_mean=None, obs_var=None, clip_obs: float = 10.0,
+                     eps: float = 1e-8, seed: int = 0, device=None):
+        """``actor``: nn.Sequential(Linear, act, ..., Linear) to the action mean; ``critic``: the same to one value (or
+        None); ``log_std``: [act_dim] tensor; act is Tanh or ReLU, the same in both. The modules stay referenced:
+        `update_from()` re-packs their current parameters."""
+        aw, ab, act = _linear_stack(actor, "actor")
+        cw, cb, cact = ([], [], None) if critic is None else _linear_stack(critic, "critic")
+        if act is not None and cact is not None and act != cact:
+            raise ValueError("one activation for both towers")
+        self = cls(aw, ab, cw, cb, log_std, act or cact or "tanh", action_low, action_high, obs_mean, obs_var, clip_obs, eps, seed,
+                   device if device is not None else aw[0].device)
+        self._modules = (actor, critic, log_std)
+        return self
+
+    @classmethod
+    def from_sb3_state_dict(cls, state_dict, activation: str, action_space, obs_mean=None, obs_var=None, clip_obs: float = 10.0,
+                            eps: float = 1e-8, seed: int = 0, device="cuda:0"):
+        """From the ``state_dict()`` of Stable-Baselines3's ``ActorCriticPolicy`` (MlpPolicy, separate networks):
+        ``mlp_extractor.policy_net.{0,2,..}``, ``mlp_extractor.value_net.{0,2,..}``, ``action_net``, ``value_net``,
+        ``log_std``. ``action_space``: a Box (``.low`` / ``.high``) or a ``(low, high)`` pair. SB3 is not imported;
+        ``activation`` ("tanh" or "relu") is the ``activation_fn`` the policy was built with (not in the state dict)."""
+        aw, ab, cw, cb, log_std = sb3_parameters(state_dict)
+        low, high = (action_space.low, action_space.high) if hasattr(action_space, "low") else action_space
+        dev = torch.device(device)
+        f = lambda ts: [torch.as_tensor(t, dtype=torch.float32).to(dev) for t in ts]  # noqa: E731
+        return cls(f(aw), f(ab), f(cw), f(cb), f([log_std])[0], activation, low, high,
+                   obs_mean, obs_var, clip_obs, eps, seed, dev)
+
+    # ---- parameters
+    def _set_params(self, aw, ab, cw, cb, log_std):
+        A = self.shape.act_dim
+        log_std = torch.as_tensor(log_std)
+        if log_std.numel() != A:
+            raise ValueError(f"log_std needs {A} values")
+        params = []
+        for w, b in zip(list(aw) + list(cw), list(ab) + list(cb)):
+            params += [w, b]
+        params.append(log_std)
+        if self._params is not None and [tuple(p.shape) for p in params[:-1]] != [tuple(p.shape) for p in self._params[:-1]]:
+            raise ValueError("update_from: the networks' shapes changed (build a new policy)")
+        self._params = params
+
+    def sources(self):
+        """The tensors the packed buffer is gathered from, in `pack_index` order: obs_mean, obs_std, action_low,
+        action_high, log_std, then (weight, bias) per layer of the actor (head last) and of the critic."""
+        p = self._params
+        return self._fixed + [p[-1]] + p[:-1]
+
+    def update_from(self, actor=None, critic=None, log_std=None) -> None:
+        """Re-pack the weights -- of the given modules, or of the ones the policy was built from (`from_modules`),
+        after an optimiser step on them -- with torch ops on the device: one gather into the packed buffer in place
+        (captured graphs keep reading it), no host synchronisation."""
+        if actor is not None or critic is not None or log_std is not None:
+            mods = getattr(self, "_modules", (None, None, None))
+            actor = actor if actor is not None else mods[0]
+            critic = critic if critic is not None else mods[1]
+            log_std = log_std if log_std is not None else mods[2]
+            if actor is None or log_std is None:
+                raise ValueError("update_from needs the actor and log_std (the policy was not built from modules)")
+            aw, ab, _ = _linear_stack(actor, "actor")
+            cw, cb, _ = ([], [], None) if critic is None else _linear_stack(critic, "critic")
+            self._set_params(aw, ab, cw, cb, log_std)
+            self._modules = (actor, critic, log_std)
+        flat = [t.detach().reshape(-1).to(device=self.device, dtype=torch.float32) for t in self.sources()]
+        torch.index_select(torch.cat(flat + [self._zero]), 0, self._index, out=self.packed)
+
+    def unpack(self):
+        """The source tensors (`sources()` order, flattened) read back from the packed buffer."""
+        sizes = [t.numel() for t in self.sources()]
+        flat = torch.zeros(sum(sizes) + 1, dtype=torch.float32, device=self.device)
+        flat[self._index] = self.packed
+        return list(torch.split(flat[:-1], sizes))
+
+    def reseed(self, seed: Optional[int] = None) -> None:
+        """Reset every env's call counter (and set a new seed): the draws start over."""
+        if seed is not None:
+            self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if self.calls is not None:
+            self.calls.zero_()
+
+    # ---- calls
+    def _obs(self, obs: torch.Tensor) -> torch.Tensor:
+        if not isinstance(obs, torch.Tensor) or not obs.is_cuda:
+            raise UpkieRuntimeError("MlpActorCritic runs on the HIP device only (there is no CPU fallback): observations must be device tensors")
+        if obs.device != self.device:
+            raise ValueError(f"observations on {obs.device}, policy on {self.device}")
+        if obs.dim() < 1 or obs.shape[0] < 1 or obs[0].numel() != self.shape.obs_dim:
+            raise ValueError(f"observations must be [N, ...] with {self.shape.obs_dim} words per env, got {tuple(obs.shape)}")
+        if obs.dtype is not torch.float32 or not obs.is_contiguous():
+            obs = obs.to(torch.float32).contiguous()
+        return obs
+
+    def _buffers(self, n: int):
+        """The persistent outputs and per-env call counters, allocated by the first call: a policy serves ONE batch
+        size, so that they are never reallocated under a captured graph and the random stream never restarts behind
+        the caller's back (another N: build another policy)."""
+        if self._out.get("n") != n:
+            if self._out:
+                raise ValueError(f"this policy serves batches of {self._out['n']} envs (its outputs and call counters are sized by "
+                                 f"the first call); build another policy for {n}")
+            f32 = dict(dtype=torch.float32, device=self.device)
+            A = self.shape.act_dim
+            self._out = {"n": n, "env_action": torch.empty((n, A), **f32), "action": torch.empty((n, A), **f32),
+                         "value": torch.empty(n, **f32), "log_prob": torch.empty(n, **f32)}
+            self.calls = torch.zeros(n, dtype=torch.int32, device=self.device)
+        return self._out
+
+    def _check_out(self, name: str, t: torch.Tensor, n: int) -> torch.Tensor:
+        words = {"norm_obs": self.shape.obs_dim, "value": 1, "log_prob": 1}.get(name, self.shape.act_dim) * n
+        if name not in OUTPUT_NAMES:
+            raise ValueError(f"unknown output {name!r} (one of {OUTPUT_NAMES})")
+        if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype is not torch.float32 or not t.is_contiguous() or t.numel() != words:
+            raise ValueError(f"out[{name!r}] must be a contiguous float32 tensor of {words} words on {self.device}")
+        return t
+
+    def _launch(self, obs, deterministic: bool, outs: dict) -> None:
+        n = obs.shape[0]
+        ptr = lambda name: outs[name].data_ptr() if outs.get(name) is not None else None  # noqa: E731
+        with torch.cuda.device(self.device):
+            status = self._lib.upkie_mlp_actor_critic(
+                n, C.byref(self.shape), self.packed.data_ptr(), obs.data_ptr(), self.calls.data_ptr(), self.seed, int(bool(deterministic)),
+                *[ptr(name) for name in OUTPUT_NAMES], torch.cuda.current_stream(self.device).cuda_stream)
+        if status < 0:
+            lib.check(status, None)
+
+    def act(self, obs: torch.Tensor, deterministic: bool = False, out: Optional[dict] = None):
+        """(env_action, action, value, log_prob) of a batch of observations ``[N, ...]``; value is None without a
+        critic. ``out``: tensors to write instead of the persistent buffers (any of `OUTPUT_NAMES`; "norm_obs" and
+        "mean" are written only when given)."""
+        obs = self._obs(obs)
+        n = obs.shape[0]
+        outs = dict(self._buffers(n))
+        del outs["n"]
+        if self.shape.critic_layers == 0:
+            outs["value"] = None
+        for name, t in (out or {}).items():
+            outs[name] = self._check_out(name, t, n)
+        self._launch(obs, deterministic, outs)
+        return outs["env_action"], outs["action"], outs["value"], outs["log_prob"]
+
+    def value(self, obs: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The critic alone (e.g. the bootstrap values of the observations after a rollout's last step)."""
+        if self.shape.critic_layers == 0:
+            raise UpkieRuntimeError("this policy has no critic")
+        obs = self._obs(obs)
+        n = obs.shape[0]
+        v = self._buffers(n)["value"] if out is None else self._check_out("value", out, n)
+        self._launch(obs, True, {"value": v})
+        return v
+
+
+class MlpPolicy(MlpActorCritic):
+    """The actor of `MlpActorCritic` alone, deterministic (the Gaussian's mean, clamped to the action bounds):
+    ``policy(obs)`` returns the ``[N, act_dim]`` env action, like `LinearPolicy`, for ``env.step(policy(obs))``."""
+
+    @classmethod
+    def from_modules(cls, actor, action_low=None, action_high=None, obs_mean=None, obs_var=None, clip_obs: float = 10.0, eps: float = 1e-8,
+                     device=None):
+        aw = _linear_stack(actor, "actor")[0]
+        log_std = torch.zeros(aw[-1].shape[0], device=aw[-1].device)
+        return super().from_modules(actor, None, log_std, action_low, action_high, obs_mean, obs_var, clip_obs, eps, 0, device)
+
+    def __call__(self, obs: torch.Tensor) -> torch.Tensor:
+        obs = self._obs(obs)
+        env_action = self._buffers(obs.shape[0])["env_action"]
+        self._launch(obs, True, {"env_action": env_action})
+        return env_action

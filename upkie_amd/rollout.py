@@ -87,6 +87,25 @@ class RolloutBuffer:
         self.pos += 1
         self.full = self.pos == self.buffer_size
 
+    def add_policy_step(self, obs, reward, episode_start, policy_outputs) -> None:
+        """`add` for a step whose policy outputs come from `MlpActorCritic.act` (``policy_outputs``: its ``(env_action,
+        action, value, log_prob)``), called with ``out=`` slices of this buffer at `pos` or not: only what the kernel
+        did not already write into the slot is copied. ``obs`` None: the observation slot was written by the kernel
+        (``out={"norm_obs": buffer.observations[buffer.pos]}``)."""
+        if self.full:
+            raise UpkieRuntimeError("rollout buffer is full")
+        t = self.pos
+        _, action, value, log_prob = policy_outputs
+        if value is None:
+            raise UpkieRuntimeError("the policy has no critic: PPO's buffer needs values")
+        for dst, src in ((self.observations[t], obs), (self.actions[t], action), (self.values[t], value), (self.log_probs[t], log_prob)):
+            if src is not None and src.data_ptr() != dst.data_ptr():
+                dst.copy_(src.reshape(dst.shape))
+        self.rewards[t].copy_(reward.reshape(self.n_envs))
+        self.episode_starts[t].copy_(episode_start.reshape(self.n_envs))
+        self.pos += 1
+        self.full = self.pos == self.buffer_size
+
     def compute_returns_and_advantage(self, last_values: torch.Tensor, dones: torch.Tensor) -> None:
         """`last_values` [N]: value estimates of the observations after the last
         stored step; `dones` [N]: whether that step ended an episode."""
