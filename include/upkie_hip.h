@@ -808,7 +808,8 @@ int upkie_linear_policy(int32_t num_envs, int32_t obs_dim, int32_t act_dim, cons
  * The policy side of a rollout step as one launch: what Stable-Baselines3's
  * MlpPolicy evaluates between two env steps (separate actor and critic towers,
  * one activation, a diagonal Gaussian with a state-independent log_std,
- * optionally frozen VecNormalize statistics), computed on fp32 MFMA
+ * optionally VecNormalize statistics: frozen, or kept live in the packed
+ * buffer by upkie_vecnorm_step's packed_stats), computed on fp32 MFMA
  * (csrc/policy_mlp.hpp). For each env n < num_envs:
  *   x        = clamp((obs - obs_mean) / obs_std, -clip_obs, clip_obs)
  *              (obs_std = sqrt(var + eps); x = obs when normalize == 0)
@@ -864,6 +865,67 @@ int64_t upkie_mlp_packed_words(const UpkieMlpShape* shape);
 int upkie_mlp_actor_critic(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* obs,
                            uint32_t* calls, uint64_t seed, int32_t deterministic, float* norm_obs, float* mean,
                            float* action, float* env_action, float* value, float* log_prob, void* stream);
+
+/* ---- Running observation / reward normalisation (VecNormalize) ----------
+ * Stable-Baselines3's VecNormalize in training mode, on the device
+ * (csrc/vecnorm.hpp): running statistics of the observations and of the
+ * discounted returns, the reward scaled by the returns' running std. N =
+ * num_envs, D = obs_dim (1-256). State, all fp64 device buffers:
+ *   obs_stats [2 D + 1]: mean[D], var[D], count     (RunningMeanStd of obs)
+ *   ret_stats [3]:       mean, var, count           (RunningMeanStd of returns)
+ *   returns   [N]:       discounted return of every env
+ * (RunningMeanStd(epsilon = 1e-4) starts at mean 0, var 1, count 1e-4.)
+ * A batch x [N][D] updates (mean, var, count) with its fp64 mean bm and
+ * population variance bv over the N rows:
+ *   delta = bm - mean, tot = count + N
+ *   mean += delta N / tot
+ *   var   = (var count + bv N + delta^2 count N / tot) / tot,  count = tot
+ * (bm and bv N come from per-lane Welford sums merged by Chan's formula in a
+ * fixed order: the result is the same bits every call.)
+ * One call, flags a set of UpkieVecNormFlag; done = terminated | truncated
+ * (bytes, NULL: none); obs as the env returned it (with same-step autoreset,
+ * the reset observation of the envs that ended):
+ *   RESET:  returns[:] = 0; with TRAINING and NORM_OBS, obs updates obs_stats.
+ *   else:   with TRAINING and NORM_OBS, obs updates obs_stats;
+ *           with TRAINING, returns = returns gamma + reward and the N returns
+ *           update ret_stats (whether or not NORM_REWARD is set);
+ *           then returns[done] = 0.
+ * Outputs (each may be NULL), computed with the statistics after the update:
+ *   norm_reward[n]    = NORM_REWARD ? (float)clip(reward[n] / sqrt(ret_var + epsilon), +-clip_reward)
+ *                       (in fp64, rounded once) : reward[n]
+ *   norm_obs[n][d]    = NORM_OBS ? clip((obs[n][d] - mean_f32[d]) / std_f32[d], +-(float)clip_obs)
+ *                       (in fp32: the MLP policy's expression, the same bits) : obs[n][d]
+ *   episode_starts[n] = done[n] (uint8)
+ * Whenever obs_stats move, the fp32 mirrors are rewritten: mean_f32[d] =
+ * (float)mean[d], std_f32[d] = (float)sqrt(var[d] + epsilon), and, with a
+ * policy's packed weight buffer in packed_stats (NULL: none), its obs_mean and
+ * obs_std words: packed_stats[d] = mean_f32[d], packed_stats[Dp + d] =
+ * std_f32[d], Dp = D rounded up to 4 (csrc/policy_mlp.hpp).
+ * Launches: with TRAINING, one that reduces the moments (its last block
+ * updates the statistics in place); a second one when a normalised reward or
+ * normalised observations are asked for; without TRAINING, only the second.
+ * No block waits on another, no float atomics, no allocation, no host
+ * synchronisation: the call can be captured in a hipGraph and replayed.
+ * workspace: upkie_vecnorm_workspace_bytes(N, D) bytes, zeroed once before
+ * the first call (every call leaves its counter at zero again); needed with
+ * TRAINING. No CPU fallback: UPKIE_ERR_NO_DEVICE without a HIP device. Errors
+ * are reported through upkie_sim_last_error(NULL). */
+enum UpkieVecNormFlag {
+  UPKIE_VECNORM_TRAINING = 1,
+  UPKIE_VECNORM_NORM_OBS = 2,
+  UPKIE_VECNORM_NORM_REWARD = 4,
+  UPKIE_VECNORM_RESET = 8
+};
+
+/* Bytes of the workspace for num_envs envs of obs_dim words, or -1 (with the
+ * reason in upkie_sim_last_error(NULL)) out of range. Needs no device. */
+int64_t upkie_vecnorm_workspace_bytes(int32_t num_envs, int32_t obs_dim);
+
+int upkie_vecnorm_step(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
+                       const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace,
+                       int32_t flags, double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32,
+                       float* std_f32, float* packed_stats, float* norm_obs, float* norm_reward, uint8_t* episode_starts,
+                       void* stream);
 
 /* ---- Rollout consumer (BASELINE.json configs[3]) ---
  * Generalized advantage estimation over a rollout resident in HBM: rewards,

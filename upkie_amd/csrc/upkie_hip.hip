@@ -8,6 +8,8 @@
 // constants are kernel arguments (scalar loads, SGPR-resident).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -18,6 +20,7 @@
 
 #include "policy_mlp.hpp"
 #include "rollout.hpp"
+#include "vecnorm.hpp"
 
 #include "step_kernels.hpp"
 #include "step_instances.hpp"  // (the step kernels this unit launches are compiled elsewhere, by groups: declarations only)
@@ -1276,6 +1279,90 @@ extern "C" int upkie_mlp_actor_critic(int32_t num_envs, const UpkieMlpShape* sha
     case 64: launch_mlp<64>(shape->activation, grid, s, P, packed, obs, calls, out); break;
     case 128: launch_mlp<128>(shape->activation, grid, s, P, packed, obs, calls, out); break;
     default: launch_mlp<256>(shape->activation, grid, s, P, packed, obs, calls, out); break;
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) {
+    g_create_error = hipGetErrorString(err);
+    return UPKIE_ERR_HIP;
+  }
+  return UPKIE_OK;
+}
+
+// ============================================================ running normalisation (VecNormalize)
+static bool vecnorm_shape_ok(int32_t num_envs, int32_t obs_dim) {
+  if (num_envs <= 0 || obs_dim < 1 || obs_dim > 256 || (int64_t)num_envs * obs_dim > INT_MAX) {
+    g_create_error = "num_envs must be positive and obs_dim in 1-256 (num_envs * obs_dim below 2^31)";
+    return false;
+  }
+  return true;
+}
+
+extern "C" int64_t upkie_vecnorm_workspace_bytes(int32_t num_envs, int32_t obs_dim) {
+  if (!vecnorm_shape_ok(num_envs, obs_dim)) return UPKIE_ERR_INVALID_ARGUMENT;
+  const int blocks = upkie::vecnorm_blocks(num_envs, obs_dim, nullptr);
+  return upkie::VECNORM_PARTIALS_OFFSET + (int64_t)blocks * 2 * (obs_dim + 1) * (int64_t)sizeof(double);
+}
+
+extern "C" int upkie_vecnorm_step(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
+                                  const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace, int32_t flags,
+                                  double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32, float* std_f32,
+                                  float* packed_stats, float* norm_obs, float* norm_reward, uint8_t* episode_starts, void* stream) {
+  if (!vecnorm_shape_ok(num_envs, obs_dim)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (flags & ~(UPKIE_VECNORM_TRAINING | UPKIE_VECNORM_NORM_OBS | UPKIE_VECNORM_NORM_REWARD | UPKIE_VECNORM_RESET)) {
+    g_create_error = "unknown vecnorm flags";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (!(gamma >= 0.0 && gamma <= 1.0) || !(epsilon > 0.0) || !(clip_obs > 0.0) || !(clip_reward > 0.0)) {
+    g_create_error = "gamma must be in [0, 1], epsilon, clip_obs and clip_reward positive";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  const bool training = flags & UPKIE_VECNORM_TRAINING, reset = flags & UPKIE_VECNORM_RESET;
+  upkie::VecNormDev P{};
+  P.num_envs = num_envs;
+  P.obs_dim = obs_dim;
+  P.packed_dp = (obs_dim + 3) / 4 * 4;
+  P.obs_cols = training && (flags & UPKIE_VECNORM_NORM_OBS) ? obs_dim : 0;
+  P.ret_col = training && !reset ? 1 : 0;
+  P.reset = reset;
+  P.norm_obs = (flags & UPKIE_VECNORM_NORM_OBS) != 0;
+  P.norm_reward = (flags & UPKIE_VECNORM_NORM_REWARD) != 0;
+  const bool moments = P.obs_cols + P.ret_col > 0;
+  const bool apply = !moments || norm_obs || (norm_reward && P.norm_reward);
+  P.outputs_in_moments = moments && !apply;
+  if (!obs_stats || !ret_stats || !returns || !mean_f32 || !std_f32) {
+    g_create_error = "null statistics, returns or fp32 mirror buffer";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if ((P.obs_cols || norm_obs) && !obs) {
+    g_create_error = "updating or normalising observations needs obs";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if ((P.ret_col || norm_reward) && !reward) {
+    g_create_error = "updating the returns or writing norm_reward needs reward";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (moments && !workspace) {
+    g_create_error = "training needs the workspace";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (upkie_hip_device_count() <= 0) {
+    g_create_error = "no HIP device visible";
+    return UPKIE_ERR_NO_DEVICE;
+  }
+  P.blocks = upkie::vecnorm_blocks(num_envs, obs_dim, &P.rows);
+  P.gamma = gamma, P.eps = epsilon, P.clip_obs = clip_obs, P.clip_reward = clip_reward;
+  P.obs = obs, P.reward = reward, P.terminated = terminated, P.truncated = truncated;
+  P.obs_stats = obs_stats, P.ret_stats = ret_stats, P.returns = returns;
+  P.ticket = (unsigned*)workspace;
+  P.partials = workspace ? (double*)((char*)workspace + upkie::VECNORM_PARTIALS_OFFSET) : nullptr;
+  P.mean_f32 = mean_f32, P.std_f32 = std_f32, P.packed = packed_stats;
+  P.norm_obs_out = norm_obs, P.reward_out = norm_reward, P.starts_out = episode_starts;
+  const hipStream_t s = (hipStream_t)stream;
+  if (moments) hipLaunchKernelGGL(upkie::vecnorm_moments_kernel, dim3((unsigned)P.blocks), dim3(upkie::VECNORM_THREADS), 0, s, P);
+  if (apply) {
+    const int64_t work = norm_obs ? (int64_t)num_envs * obs_dim : num_envs;
+    const int64_t grid = std::min<int64_t>((work + upkie::VECNORM_THREADS - 1) / upkie::VECNORM_THREADS, 1024);
+    hipLaunchKernelGGL(upkie::vecnorm_apply_kernel, dim3((unsigned)grid), dim3(upkie::VECNORM_THREADS), 0, s, P);
   }
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) {

@@ -30,6 +30,7 @@ SOURCES = [
     os.path.join(_HERE, "csrc", "observers.hpp"),
     os.path.join(_HERE, "csrc", "rollout.hpp"),
     os.path.join(_HERE, "csrc", "policy_mlp.hpp"),
+    os.path.join(_HERE, "csrc", "vecnorm.hpp"),
     os.path.join(_HERE, "csrc", "wave_io.hpp"),
     os.path.join(_HERE, "..", "include", "upkie_hip.h"),
 ]
@@ -93,6 +94,8 @@ EXPORTED_SYMBOLS = (
     "upkie_linear_policy",
     "upkie_mlp_packed_words",
     "upkie_mlp_actor_critic",
+    "upkie_vecnorm_workspace_bytes",
+    "upkie_vecnorm_step",
 )
 
 
@@ -356,6 +359,11 @@ def load() -> C.CDLL:
         lib.upkie_mlp_packed_words.argtypes = [C.POINTER(abi.UpkieMlpShape)]
         lib.upkie_mlp_actor_critic.restype = C.c_int
         lib.upkie_mlp_actor_critic.argtypes = [C.c_int32, C.POINTER(abi.UpkieMlpShape), vp, vp, vp, C.c_uint64, C.c_int32] + [vp] * 7
+    if hasattr(lib, "upkie_vecnorm_step"):  # (newer entry points: an older build loaded for an A/B run lacks them)
+        lib.upkie_vecnorm_workspace_bytes.restype = C.c_int64
+        lib.upkie_vecnorm_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+        lib.upkie_vecnorm_step.restype = C.c_int
+        lib.upkie_vecnorm_step.argtypes = ([C.c_int32, C.c_int32] + [vp] * 8 + [C.c_int32] + [C.c_double] * 4 + [vp] * 7)
     lib.upkie_rollout_gae.restype = C.c_int
     lib.upkie_rollout_gae.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
     _lib = lib

@@ -1,0 +1,306 @@
+"""Stable-Baselines3's ``VecNormalize`` in training mode on the device: running statistics of the observations and of
+the discounted returns, updated every env step, and the reward scaled by the returns' running std.
+
+As torch ops the obs moments, the fp64 merges, the returns update and its moments, the reward scaling, zeroing the
+returns of finished envs and re-packing a policy's mean / std come to some 20-30 small launches per step.
+`RunningNormalizer` does a step in one launch, or two when a normalised reward or normalised observations are asked
+for (`upkie_vecnorm_step`, csrc/vecnorm.hpp; include/upkie_hip.h states the arithmetic), and writes straight into a
+rollout buffer's slots and into an attached `MlpActorCritic`'s packed statistics."""
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import lib
+from .exceptions import UpkieRuntimeError
+
+# enum UpkieVecNormFlag
+TRAINING, NORM_OBS, NORM_REWARD, RESET = 1, 2, 4, 8
+OUTPUT_NAMES = ("reward", "norm_obs", "episode_starts")
+_SB3_SCALARS = ("gamma", "epsilon", "clip_obs", "clip_reward", "norm_obs", "norm_reward", "training")
+
+
+def packed_offsets(obs_dim: int):
+    """Words of obs_mean and obs_std in an MLP policy's packed buffer (csrc/policy_mlp.hpp): 0 and obs_dim rounded up
+    to 4, where the kernel writes the live statistics (``packed_stats`` of ``upkie_vecnorm_step``)."""
+    return 0, (int(obs_dim) + 3) // 4 * 4
+
+
+class RunningNormalizer:
+    """SB3's ``VecNormalize`` (``RunningMeanStd(epsilon=1e-4)`` for the observations and the returns, fp64) for
+    ``num_envs`` envs with ``[num_envs, obs_dim]`` float32 observations, on the device.
+
+    ``step(obs, reward, terminated, truncated)`` is what SB3's ``step_wait`` does to the env's outputs: it updates the
+    observation statistics (training and norm_obs), the per-env returns and their statistics (training), and returns
+    the normalised reward; ``out=`` may also ask for the normalised observations and the episode starts, written into
+    given tensors (e.g. a rollout buffer's slots). ``reset(obs)`` zeroes the returns and updates the observation
+    statistics. ``normalize_obs`` / ``normalize_reward`` use the current statistics without updating them.
+
+    State, outputs and the workspace are allocated once: a step allocates nothing and has no host argument that changes
+    between steps, so it can be captured in a hipGraph (`GraphedLoop`). ``training`` may be switched between steps
+    (a captured graph keeps the value it was captured with); ``obs_mean_f32`` / ``obs_std_f32`` are the fp32 mirrors
+    ``(float)mean`` and ``(float)sqrt(var + epsilon)`` that `attach`-ed policies read. One difference from SB3: the
+    batch moments are computed in fp64 (SB3: numpy on the float32 batch)."""
+
+    def __init__(self, num_envs: int, obs_dim: int, gamma: float = 0.99, epsilon: float = 1e-8, clip_obs: float = 10.0,
+                 clip_reward: float = 10.0, norm_obs: bool = True, norm_reward: bool = True, training: bool = True, device="cuda:0"):
+        self.num_envs, self.obs_dim = int(num_envs), int(obs_dim)
+        if self.num_envs < 1 or not 1 <= self.obs_dim <= 256:
+            raise ValueError("num_envs must be positive and obs_dim in 1-256")
+        if not 0.0 <= float(gamma) <= 1.0 or not float(epsilon) > 0.0 or not float(clip_obs) > 0.0 or not float(clip_reward) > 0.0:
+            raise ValueError("gamma must be in [0, 1], epsilon, clip_obs and clip_reward positive")
+        self.device = torch.device(device)  # (a CPU device holds statistics for saving and loading only: every call is refused)
+        self.gamma, self.epsilon, self.clip_obs, self.clip_reward = float(gamma), float(epsilon), float(clip_obs), float(clip_reward)
+        self.norm_obs, self.norm_reward, self.training = bool(norm_obs), bool(norm_reward), bool(training)
+        self._lib = lib.load()
+        if not hasattr(self._lib, "upkie_vecnorm_step"):
+            raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_vecnorm_step")
+        nbytes = int(self._lib.upkie_vecnorm_workspace_bytes(self.num_envs, self.obs_dim))
+        if nbytes < 0:
+            lib.check(nbytes, None)
+        N, D = self.num_envs, self.obs_dim
+        f64 = dict(dtype=torch.float64, device=self.device)
+        self.obs_stats = torch.zeros(2 * D + 1, **f64)  # mean[D], var[D], count
+        self.ret_stats = torch.zeros(3, **f64)  # mean, var, count
+        self.returns = torch.zeros(N, **f64)
+        self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)  # (its ticket starts, and stays, at zero)
+        self.obs_mean_f32 = torch.zeros(D, dtype=torch.float32, device=self.device)
+        self.obs_std_f32 = torch.ones(D, dtype=torch.float32, device=self.device)
+        self._reward = torch.empty(N, dtype=torch.float32, device=self.device)
+        self._norm_obs = torch.empty((N, D), dtype=torch.float32, device=self.device)
+        self._policy = None
+        self.obs_stats[D:2 * D] = 1.0
+        self.obs_stats[2 * D] = 1e-4
+        self.ret_stats[1], self.ret_stats[2] = 1.0, 1e-4
+        self._refresh_mirrors()
+
+    @classmethod
+    def for_env(cls, env, **kwargs):
+        """A normalizer sized by a batched env (``num_envs``, a ``[num_envs, obs_dim]`` observation, its device).
+        Statistics shared across the ranks of a `ShardedVecEnv` are not supported: each rank's envs would need an
+        all-reduce of the moments."""
+        if getattr(env, "world_size", 1) > 1:
+            raise UpkieRuntimeError("RunningNormalizer does not share statistics across ShardedVecEnv ranks (not supported yet)")
+        shape = tuple(getattr(env, "single_observation_space").shape) if hasattr(env, "single_observation_space") else None
+        if shape is None or len(shape) != 1:
+            raise UpkieRuntimeError(f"RunningNormalizer needs one [num_envs, obs_dim] float32 observation block, the env has {shape}")
+        kwargs.setdefault("device", getattr(env, "device", "cuda:0"))
+        return cls(env.num_envs, shape[0], **kwargs)
+
+    # ---- views of the state
+    @property
+    def obs_mean(self) -> torch.Tensor:
+        return self.obs_stats[: self.obs_dim]
+
+    @property
+    def obs_var(self) -> torch.Tensor:
+        return self.obs_stats[self.obs_dim: 2 * self.obs_dim]
+
+    @property
+    def obs_count(self) -> torch.Tensor:
+        return self.obs_stats[2 * self.obs_dim]
+
+    @property
+    def ret_mean(self) -> torch.Tensor:
+        return self.ret_stats[0]
+
+    @property
+    def ret_var(self) -> torch.Tensor:
+        return self.ret_stats[1]
+
+    @property
+    def ret_count(self) -> torch.Tensor:
+        return self.ret_stats[2]
+
+    # ---- arguments
+    def _block(self, obs, what="observations") -> torch.Tensor:
+        if not isinstance(obs, torch.Tensor):
+            raise UpkieRuntimeError(f"{what} must be one [num_envs, obs_dim] float32 device tensor (dict or tuple observations are not supported)")
+        if not obs.is_cuda:
+            raise UpkieRuntimeError("RunningNormalizer runs on the HIP device only (there is no CPU fallback): observations must be device tensors")
+        if (obs.device != self.device or obs.dtype is not torch.float32 or not obs.is_contiguous()
+                or tuple(obs.shape) != (self.num_envs, self.obs_dim)):
+            raise ValueError(f"{what} must be one contiguous [{self.num_envs}, {self.obs_dim}] float32 block on {self.device}, got "
+                             f"{tuple(obs.shape)} {obs.dtype} on {obs.device}")
+        return obs
+
+    def _vector(self, t, what, dtypes):
+        if t is None:
+            return None
+        if (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype not in dtypes or not t.is_contiguous()
+                or t.numel() != self.num_envs):
+            raise ValueError(f"{what} must be a contiguous tensor of {self.num_envs} {' or '.join(map(str, dtypes))} on {self.device}")
+        return t
+
+    def _outputs(self, out: Optional[dict]) -> dict:
+        outs = {"reward": self._reward}
+        for name, t in (out or {}).items():
+            if name not in OUTPUT_NAMES:
+                raise ValueError(f"unknown output {name!r} (one of {OUTPUT_NAMES})")
+            if name == "norm_obs":
+                outs[name] = self._block(t, "out['norm_obs']")
+            else:
+                dt = (torch.float32,) if name == "reward" else (torch.uint8, torch.bool)
+                outs[name] = self._vector(t, f"out[{name!r}]", dt)
+        return outs
+
+    def _flags(self, training: bool) -> int:
+        return (TRAINING if training else 0) | (NORM_OBS if self.norm_obs else 0) | (NORM_REWARD if self.norm_reward else 0)
+
+    def _launch(self, flags, obs=None, reward=None, terminated=None, truncated=None, norm_obs=None, norm_reward=None, starts=None) -> None:
+        if self.device.type != "cuda":
+            raise UpkieRuntimeError("RunningNormalizer runs on the HIP device only (there is no CPU fallback): build it with device='cuda:0'")
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        packed = None if self._policy is None else self._policy.packed
+        with torch.cuda.device(self.device):
+            status = self._lib.upkie_vecnorm_step(
+                self.num_envs, self.obs_dim, ptr(obs), ptr(reward), ptr(terminated), ptr(truncated), self.obs_stats.data_ptr(),
+                self.ret_stats.data_ptr(), self.returns.data_ptr(), self.workspace.data_ptr(), flags, self.gamma, self.epsilon, self.clip_obs,
+                self.clip_reward, self.obs_mean_f32.data_ptr(), self.obs_std_f32.data_ptr(), ptr(packed), ptr(norm_obs), ptr(norm_reward),
+                ptr(starts), torch.cuda.current_stream(self.device).cuda_stream)
+        if status < 0:
+            lib.check(status, None)
+
+    # ---- calls
+    def reset(self, obs: torch.Tensor) -> None:
+        """``returns[:] = 0``; with training and norm_obs, ``obs`` (the envs' first observations) updates the observation
+        statistics."""
+        self._launch(self._flags(self.training) | RESET, obs=self._block(obs))
+
+    def step(self, obs: torch.Tensor, reward: torch.Tensor, terminated=None, truncated=None, out: Optional[dict] = None) -> torch.Tensor:
+        """One env step: ``obs`` as the env returned it (with same-step autoreset, the reset observation of the envs that
+        ended), ``reward`` [N] float32, ``terminated`` / ``truncated`` [N] bool or uint8 (None: none ended). Returns the
+        normalised reward: the normalizer's own buffer, rewritten by every step, or ``out["reward"]``. ``out`` may also
+        name ``"norm_obs"`` ([N, D] float32) and ``"episode_starts"`` ([N] uint8 or bool: terminated | truncated),
+        which are written only when given."""
+        obs = self._block(obs)
+        reward = self._vector(reward, "reward", (torch.float32,))
+        if reward is None:
+            raise ValueError("step needs the reward")
+        terminated = self._vector(terminated, "terminated", (torch.bool, torch.uint8))
+        truncated = self._vector(truncated, "truncated", (torch.bool, torch.uint8))
+        outs = self._outputs(out)
+        self._launch(self._flags(self.training), obs, reward, terminated, truncated, outs.get("norm_obs"), outs["reward"], outs.get("episode_starts"))
+        return outs["reward"]
+
+    def normalize_obs(self, obs: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``clip((obs - mean) / std, +-clip_obs)`` with the fp32 mirrors (``obs`` itself, copied, without norm_obs); the
+        statistics do not move. Returns the normalizer's own buffer or ``out``."""
+        dst = self._norm_obs if out is None else self._block(out, "out")
+        self._launch(self._flags(False), obs=self._block(obs), norm_obs=dst)
+        return dst
+
+    def normalize_reward(self, reward: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``clip(reward / sqrt(ret_var + epsilon), +-clip_reward)`` (``reward`` itself without norm_reward); the
+        statistics do not move."""
+        reward = self._vector(reward, "reward", (torch.float32,))
+        dst = self._reward if out is None else self._vector(out, "out", (torch.float32,))
+        self._launch(self._flags(False), reward=reward, norm_reward=dst)
+        return dst
+
+    # ---- a policy reading the live statistics
+    def attach(self, policy) -> None:
+        """Make an `MlpActorCritic` / `MlpPolicy` normalise its observations with these statistics: every step that moves
+        them also rewrites the policy's packed obs_mean / obs_std words, the fp32 mirrors become the tensors its
+        `update_from` gathers them from (an optimiser step does not revert them), and its normalisation flag and
+        clip_obs follow the normalizer. Attach before the policy's first call (and before any capture)."""
+        from .policies import MlpActorCritic
+
+        if not isinstance(policy, MlpActorCritic):
+            raise TypeError("attach takes an MlpActorCritic or MlpPolicy")
+        if int(policy.shape.obs_dim) != self.obs_dim:
+            raise ValueError(f"the policy takes {policy.shape.obs_dim} observation words, the normalizer {self.obs_dim}")
+        if policy.device != self.device:
+            raise ValueError(f"the policy is on {policy.device}, the normalizer on {self.device}")
+        if policy._out:
+            raise UpkieRuntimeError("attach the normalizer before the policy's first call: it has already been called (or captured), "
+                                    "and its launches keep the normalisation settings they were made with")
+        if self._policy is not None and self._policy is not policy:
+            raise UpkieRuntimeError("this normalizer already feeds another policy")
+        policy._fixed[0], policy._fixed[1] = self.obs_mean_f32, self.obs_std_f32
+        self._policy = policy
+        self._sync_policy()
+        policy.update_from()
+
+    def _sync_policy(self) -> None:
+        p = self._policy
+        if p is None:
+            return
+        p.shape.normalize = int(self.norm_obs)
+        p.shape.clip_obs = self.clip_obs
+        p.clip_obs, p.eps = self.clip_obs, self.epsilon
+        D, (mean_at, std_at) = self.obs_dim, packed_offsets(self.obs_dim)
+        p.packed[mean_at: mean_at + D].copy_(self.obs_mean_f32)
+        p.packed[std_at: std_at + D].copy_(self.obs_std_f32)
+
+    def _refresh_mirrors(self) -> None:
+        mean = self.obs_mean.cpu().numpy()
+        var = self.obs_var.cpu().numpy()
+        self.obs_mean_f32.copy_(torch.from_numpy(mean.astype(np.float32)))
+        self.obs_std_f32.copy_(torch.from_numpy(np.sqrt(var + self.epsilon).astype(np.float32)))
+        self._sync_policy()
+
+    # ---- saving and loading
+    def state_dict(self) -> dict:
+        """Statistics, returns and settings (host copies; `load_state_dict` restores them bit for bit)."""
+        sd = {"obs_mean": self.obs_mean.cpu().clone(), "obs_var": self.obs_var.cpu().clone(), "obs_count": self.obs_count.cpu().clone(),
+              "ret_mean": self.ret_mean.cpu().clone(), "ret_var": self.ret_var.cpu().clone(), "ret_count": self.ret_count.cpu().clone(),
+              "returns": self.returns.cpu().clone()}
+        sd.update({k: getattr(self, k) for k in _SB3_SCALARS})
+        return sd
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Restores `state_dict`'s statistics in place (captured graphs keep reading the same buffers) and the settings;
+        a captured graph keeps the settings it was captured with."""
+        D = self.obs_dim
+        for key, n in (("obs_mean", D), ("obs_var", D), ("returns", self.num_envs)):
+            if torch.as_tensor(sd[key]).numel() != n:
+                raise ValueError(f"{key} holds {torch.as_tensor(sd[key]).numel()} values, this normalizer {n}")
+        f64 = lambda k: torch.as_tensor(sd[k], dtype=torch.float64).reshape(-1)  # noqa: E731
+        host = torch.cat([f64("obs_mean"), f64("obs_var"), f64("obs_count"), f64("ret_mean"), f64("ret_var"), f64("ret_count")])
+        if host.numel() != 2 * D + 4:
+            raise ValueError("obs_count, ret_mean, ret_var and ret_count must be scalars")
+        for key in _SB3_SCALARS:
+            if key in sd:
+                setattr(self, key, bool(sd[key]) if key in ("norm_obs", "norm_reward", "training") else float(sd[key]))
+        self.obs_stats.copy_(host[: 2 * D + 1])
+        self.ret_stats.copy_(host[2 * D + 1:])
+        self.returns.copy_(f64("returns"))
+        self._refresh_mirrors()
+
+    @classmethod
+    def from_sb3(cls, vec_normalize, device="cuda:0"):
+        """A normalizer with the statistics, returns and settings of a Stable-Baselines3 ``VecNormalize`` (duck-typed on
+        its attribute names; SB3 is not imported). Dict observation spaces are not supported."""
+        rms = vec_normalize.obs_rms
+        if isinstance(rms, dict) or not hasattr(rms, "mean"):
+            raise UpkieRuntimeError("RunningNormalizer needs one [num_envs, obs_dim] observation block (dict observations are not supported)")
+        mean = np.asarray(rms.mean)
+        if mean.ndim != 1:
+            raise UpkieRuntimeError(f"RunningNormalizer needs one [num_envs, obs_dim] observation block, the statistics have shape {mean.shape}")
+        returns = np.asarray(vec_normalize.returns)
+        self = cls(returns.size, mean.size, **{k: getattr(vec_normalize, k) for k in _SB3_SCALARS}, device=device)
+        self.load_state_dict(_sb3_state(vec_normalize))
+        return self
+
+    def to_sb3(self, vec_normalize) -> None:
+        """Writes the statistics, returns and settings into a Stable-Baselines3 ``VecNormalize`` (duck-typed), as fp64
+        numpy arrays and Python scalars."""
+        sd = self.state_dict()
+        rms, ret = vec_normalize.obs_rms, vec_normalize.ret_rms
+        if np.asarray(rms.mean).shape != (self.obs_dim,) or np.asarray(vec_normalize.returns).shape != (self.num_envs,):
+            raise ValueError("the VecNormalize has another number of envs or observation words")
+        rms.mean, rms.var, rms.count = sd["obs_mean"].numpy().copy(), sd["obs_var"].numpy().copy(), float(sd["obs_count"])
+        ret.mean, ret.var, ret.count = np.float64(sd["ret_mean"]), np.float64(sd["ret_var"]), float(sd["ret_count"])
+        vec_normalize.returns = sd["returns"].numpy().copy()
+        for key in _SB3_SCALARS:
+            setattr(vec_normalize, key, sd[key])
+
+
+def _sb3_state(v) -> dict:
+    sd = {"obs_mean": v.obs_rms.mean, "obs_var": v.obs_rms.var, "obs_count": v.obs_rms.count, "ret_mean": v.ret_rms.mean,
+          "ret_var": v.ret_rms.var, "ret_count": v.ret_rms.count, "returns": v.returns}
+    sd = {k: torch.as_tensor(np.asarray(x, dtype=np.float64)) for k, x in sd.items()}
+    sd.update({k: getattr(v, k) for k in _SB3_SCALARS})
+    return sd

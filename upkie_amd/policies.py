@@ -245,7 +245,8 @@ class MlpActorCritic:
     upkie_hip.h documents the mapping), so a call has no host argument that changes between calls and can be replayed
     from a hipGraph. ``reseed(seed)`` resets the counters (a new seed value is a new launch argument: re-capture).
     The first call fixes the batch size N (outputs and counters are allocated once; a call with another N raises).
-    Observation normalisation uses frozen VecNormalize statistics. Build with `from_modules` or
+    Observation normalisation uses VecNormalize statistics: frozen ones given here, or live ones kept by a
+    `upkie_amd.normalize.RunningNormalizer` it is attached to (`attach`). Build with `from_modules` or
     `from_sb3_state_dict`; after an optimiser step on those modules, `update_from` re-packs on the device."""
 
     def __init__(self, actor_weights, actor_biases, critic_weights, critic_biases, log_std, activation: str, action_low=None,
