@@ -205,7 +205,8 @@ enum UpkieStructId {
   UPKIE_STRUCT_OBSERVER_INPUT = 7,
   UPKIE_STRUCT_OBSERVER_OUTPUT = 8,
   UPKIE_STRUCT_MLP_SHAPE = 9,
-  UPKIE_STRUCT_COUNT = 10
+  UPKIE_STRUCT_PPO_CONFIG = 10,
+  UPKIE_STRUCT_COUNT = 11
 };
 int64_t upkie_hip_struct_bytes(int which);
 
@@ -926,6 +927,87 @@ int upkie_vecnorm_step(int32_t num_envs, int32_t obs_dim, const float* obs, cons
                        int32_t flags, double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32,
                        float* std_f32, float* packed_stats, float* norm_obs, float* norm_reward, uint8_t* episode_starts,
                        void* stream);
+
+/* ---- PPO update of the MLP actor-critic --------------------------------
+ * One minibatch of Stable-Baselines3's PPO.train for a MlpPolicy with separate
+ * actor and critic towers (no gSDE), on the device (csrc/ppo.hpp), applied in
+ * place to the packed weight buffer the rollout kernel reads. B = the
+ * minibatch's samples, s = perm[minibatch_start + j], j < minibatch_size, of
+ * the flattened [T N] rollout (obs [T N][obs_dim], actions [T N][act_dim]:
+ * the raw Gaussian samples, old_values, old_log_prob, advantages, returns
+ * [T N]); x = the observation normalised as upkie_mlp_actor_critic does
+ * (unless config->obs_normalized: the buffer holds normalised observations).
+ *   mu, value = the towers on x;  sigma_a = exp(log_std_a)
+ *   log_prob  = sum_a -(act_a - mu_a)^2 / (2 sigma_a^2) - log_std_a - ln(2 pi) / 2
+ *   adv       = (advantage - mean) / (std + 1e-8) over the minibatch (std
+ *               unbiased; upkie_ppo_advantage_stats), or unchanged when
+ *               normalize_advantage is off or B = 1
+ *   ratio     = exp(log_prob - old_log_prob)
+ *   policy_loss  = -mean(min(adv ratio, adv clamp(ratio, 1 - clip_range, 1 + clip_range)))
+ *   values_pred  = clip_range_vf <= 0 ? value
+ *                  : old_values + clamp(value - old_values, -clip_range_vf, clip_range_vf)
+ *   value_loss   = mean((returns - values_pred)^2)
+ *   entropy_loss = -sum_a (0.5 + ln(2 pi) / 2 + log_std_a)
+ *   loss = policy_loss + ent_coef entropy_loss + vf_coef value_loss
+ * g = d loss / d params, the gradient torch autograd gives for these
+ * expressions (a tie of the minimum splits half / half, the clamps pass their
+ * bounds); the parameters are every weight and bias of both towers (heads
+ * included) and log_std -- the packed words from log_std's on; obs_mean /
+ * obs_std and the action bounds are never written. Then clip_grad_norm_ and
+ * torch.optim.Adam (m, v: [packed words] fp32 in the packed layout, zero
+ * before the first step; adam_scalars[0] = lr, adam_scalars[1] = t, fp64):
+ *   coef = min(1, max_grad_norm / (||g||_2 + 1e-6)),  g = coef g
+ *   t += 1;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2
+ *   p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + adam_eps)
+ * Padding words of the packed layout have a zero gradient and stay zero.
+ * stats[7] = policy_loss, value_loss, entropy_loss, loss, approx_kl =
+ * mean((ratio - 1) - ln ratio), clip_fraction = mean(|ratio - 1| >
+ * clip_range), ||g||_2 before the clip. Three launches (gradient partials per
+ * block; their fold in a fixed order, whose last block forms ||g||, the clip
+ * coefficient, the statistics and t; Adam), no float atomics: the result is
+ * the same bits every call. No allocation, no host synchronisation, every
+ * argument constant across training iterations: a sequence of calls can be
+ * captured in a hipGraph and replayed. SB3's defaults: clip_range 0.2,
+ * clip_range_vf None, ent_coef 0, vf_coef 0.5, max_grad_norm 0.5, Adam
+ * betas (0.9, 0.999), eps 1e-5, lr 3e-4, normalize_advantage on. */
+typedef struct {
+  float clip_range;     /* > 0 */
+  float clip_range_vf;  /* > 0, or <= 0 for None (no value clipping) */
+  float ent_coef;
+  float vf_coef;
+  float max_grad_norm;  /* > 0 */
+  float adam_beta1;     /* in [0, 1) */
+  float adam_beta2;     /* in [0, 1) */
+  float adam_eps;       /* > 0 */
+  int32_t obs_normalized; /* 1: obs holds normalised observations (no transform) */
+  int32_t reserved;       /* 0 */
+} UpkiePpoConfig;
+
+/* Bytes of the workspace of upkie_ppo_minibatch_update for `shape` (which
+ * needs a critic) and minibatches of at most max_minibatch samples (<= 64 MiB
+ * for every valid shape), or UPKIE_ERR_INVALID_ARGUMENT (the reason in
+ * upkie_sim_last_error(NULL)). Needs no device. The workspace is zeroed once
+ * before the first call; every call leaves its counter at zero again. */
+int64_t upkie_ppo_workspace_bytes(const UpkieMlpShape* shape, int32_t max_minibatch);
+
+/* For every minibatch j of an epoch (samples perm[j batch_size ..] of the
+ * `total`, the last one short): adv_stats[j] = (mean, std + 1e-8) of its
+ * advantages (fp64, std unbiased, a fixed order), or (0, 1) when normalize is
+ * 0 or the minibatch has one sample. One launch. */
+int upkie_ppo_advantage_stats(int32_t total, int32_t batch_size, const int32_t* perm, const float* advantages,
+                              int32_t normalize, double* adv_stats, void* stream);
+
+/* One minibatch (above): gradient, clip and Adam, and its stats row.
+ * adv_stats: this minibatch's (mean, std + 1e-8) pair. Argument and shape
+ * errors return UPKIE_ERR_INVALID_ARGUMENT before any device use; no CPU
+ * fallback: UPKIE_ERR_NO_DEVICE without a HIP device. Errors are reported
+ * through upkie_sim_last_error(NULL). */
+int upkie_ppo_minibatch_update(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total,
+                               int32_t minibatch_start, int32_t minibatch_size, int32_t max_minibatch,
+                               const int32_t* perm, const float* obs, const float* actions, const float* old_values,
+                               const float* old_log_prob, const float* advantages, const float* returns,
+                               const double* adv_stats, float* packed, float* adam_m, float* adam_v,
+                               double* adam_scalars, void* workspace, float* stats, void* stream);
 
 /* ---- Rollout consumer (BASELINE.json configs[3]) ---
  * Generalized advantage estimation over a rollout resident in HBM: rewards,

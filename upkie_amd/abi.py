@@ -299,6 +299,21 @@ class UpkieMlpShape(C.Structure):
     ]
 
 
+class UpkiePpoConfig(C.Structure):
+    _fields_ = [
+        ("clip_range", C.c_float),
+        ("clip_range_vf", C.c_float),
+        ("ent_coef", C.c_float),
+        ("vf_coef", C.c_float),
+        ("max_grad_norm", C.c_float),
+        ("adam_beta1", C.c_float),
+        ("adam_beta2", C.c_float),
+        ("adam_eps", C.c_float),
+        ("obs_normalized", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 # enum UpkieStructId -> the mirror of that struct here (`upkie_hip_struct_bytes`: lib.load() compares sizes)
 STRUCT_IDS = {
     0: UpkieModel,
@@ -311,10 +326,11 @@ STRUCT_IDS = {
     7: UpkieObserverInput,
     8: UpkieObserverOutput,
     9: UpkieMlpShape,
+    10: UpkiePpoConfig,
 }
 # structs that only newer, optional entry points read: a build without that entry point (an older library loaded through
 # UPKIE_HIP_LIBRARY for an A/B run) answers -1 for them, and lib.load() still accepts it
-OPTIONAL_STRUCTS = {9: "upkie_mlp_actor_critic"}
+OPTIONAL_STRUCTS = {9: "upkie_mlp_actor_critic", 10: "upkie_ppo_minibatch_update"}
 MAX_GRAPH_CAPTURES = 8  # UPKIE_MAX_GRAPH_CAPTURES
 
 # observer memory words (enum UpkieObserverStateWord)

@@ -1,0 +1,604 @@
+// ppo.hpp -- the learner half of PPO on the device: one minibatch of Stable-Baselines3's PPO.train (clipped surrogate,
+// value loss, entropy bonus, their gradient through both MLP towers, clip_grad_norm_, Adam) on the packed weight buffer
+// the rollout kernel reads (csrc/policy_mlp.hpp), in three launches per minibatch plus one per epoch. include/upkie_hip.h
+// states the arithmetic; Python: upkie_amd/ppo.py.
+//
+// Launch 0, advantage statistics (once per epoch): block j reduces the advantages of minibatch j of the epoch's
+// permutation in fp64 (two passes, a fixed LDS tree) into (mean, std + 1e-8), or (0, 1) without normalisation.
+//
+// Launch A, gradient. A block of NW waves (1-4, as many 16-sample tiles as fit the LDS budget) takes chunks of NW tiles
+// of the minibatch in turn (chunk blockIdx.x, + gridDim.x, ...); wave w owns tile w of a chunk, lane l its sample l & 15,
+// gathered through the permutation straight from the buffer's [T, N, ...] tensors. Per tower (actor, then critic):
+//   forward: policy_mlp.hpp's mlp_dense / mlp_dot (transposed layers on v_mfma_f32_16x16x4_f32, lane = sample,
+//     accumulators feeding the next layer), each layer's output also stored to the wave's LDS stage as [unit][sample];
+//   loss: the sample's log-probability, ratio, clipped surrogate (or value loss) and their derivative dZ of the head;
+//   backward, layer by layer from the head: dX = W^T dZ sums over the accumulator's row index, so it is one MFMA chain
+//     with no lane movement (A = a W^T fragment gathered from the packed weights, B = the lane's own dZ accumulators);
+//     dZ of the layer below = dX * act'(H), written over H in the stage. dW = dZ X^T sums over samples (the lane index):
+//     after a barrier every wave reads the whole chunk's [unit][sample] stage transposed -- that is the one transpose
+//     per layer -- and each 16 x 16 fragment of dW (owned by wave f % NW) is a chain of 4 NW MFMAs whose result lands in
+//     the packed layout directly. Biases, dot heads and log_std are VALU sums over the stage's samples.
+// The block's partial gradient (fp32, the packed layout from log_std_off on) lives in the workspace: its first chunk
+// writes it, later chunks add to it (every word has one owning thread, so no atomics and no race). Loss sums (fp64,
+// per lane, then a fixed shuffle tree and wave order) go to a per-block stats partial.
+//
+// Launch B, fold: thread i sums word i of the G partials in block order (+ the entropy term of log_std), writes the
+// minibatch gradient and its square; a fixed LDS tree gives one sum of squares per block; the vecnorm ticket
+// (agent-scope release / acquire, last arriver, counter reset in-kernel) lets the last block form ||g||, the clip
+// coefficient, the statistics row, t += 1 and Adam's bias corrections, all in a fixed order.
+//
+// Launch C, Adam: element-wise over the trainable words (log_std_off on; the fixed obs_mean / obs_std / action bounds
+// before it are never written; padding words have a zero gradient, so m, v and the word stay 0).
+//
+// Every launch argument is constant for a given (epoch, minibatch) position: counters, t, lr and the permutation live
+// in device memory, so the whole sequence can be captured in a hipGraph and replayed.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/upkie_hip.h"
+#include "policy_mlp.hpp"
+
+namespace upkie {
+
+enum {
+  PPO_THREADS = 256,           // launches B, C
+  PPO_ADV_THREADS = 1024,      // launch 0
+  PPO_HEADER_BYTES = 256,      // ticket (u32 at 0), then coef, step size, sqrt(1 - beta2^t) as fp32 at words 4-6
+  PPO_LDS_BUDGET = 65280,      // dynamic LDS of launch A when the stage of one tile fits (64 KiB less the static part)
+  // the largest one-tile stage of any valid shape (obs 256, four 256-unit layers, act 64: 16 (256 + 4 * 256 + 64 + 64) floats)
+  PPO_LDS_MAX = 4 * 16 * (256 + 4 * 256 + 64 + 64),
+  PPO_MAX_GRID = 512,          // blocks of launch A
+  PPO_STATS = 4,               // per-block loss sums: min(surrogates), (R - v_pred)^2, approx_kl terms, clipped count
+};
+static const int64_t PPO_PARTIAL_CAP_BYTES = 48ll << 20;  // partial gradients (the grid shrinks for large networks)
+
+// LDS stage of one 16-sample tile for one tower, in rows of 16 floats: the input x (tiles(obs) rows of 16), each hidden
+// layer's output H_l (later its dZ), the head's dZ (1 row for a dot head) and, for the actor, the per-sample log_std
+// terms.
+struct PpoStage {
+  int h_off[UPKIE_MLP_MAX_LAYERS];  // float offsets (x at 0)
+  int head_off, ls_off, floats;
+};
+
+struct PpoDev {
+  MlpDev net;
+  PpoStage stage[2];  // actor, critic
+  int train_off, train_words;
+  int mb_start, mb_size, nw, tile_floats, grid, fold_blocks;
+  int obs_normalized, vf_clip;
+  float clip_lo, clip_hi, clip_range, clip_vf, ent_coef, vf_coef, max_grad_norm, beta1, beta2, adam_eps;
+  const int32_t* perm;
+  const float* obs;
+  const float* actions;
+  const float* old_values;
+  const float* old_log_prob;
+  const float* advantages;
+  const float* returns;
+  const double* adv_stats;  // this minibatch's (mean, denominator)
+  float* packed;
+  float* m;
+  float* v;
+  double* scalars;  // lr, t
+  float* stats;     // [7]
+  unsigned* ticket;
+  float* header;
+  float* partials;        // [grid][train_words]
+  double* stat_partials;  // [grid][PPO_STATS]
+  float* grad;            // [train_words]
+  double* sq_partials;    // [fold_blocks]
+};
+
+struct PpoPlan {
+  PpoStage stage[2];
+  int train_off, train_words, nw, tile_floats, lds_bytes, grid_cap, fold_blocks;
+};
+
+__host__ __device__ inline int ppo_tiles(int n) { return (int)(((int64_t)n + 15) / 16); }  // (no overflow up to INT_MAX)
+
+// Stage layout, waves per block, grid cap and workspace sizes of a shape; false for a shape out of range or without a
+// critic.
+inline bool ppo_plan(const UpkieMlpShape& s, PpoPlan* plan) {
+  MlpDev d;
+  const int64_t words = mlp_layout(s, &d);
+  if (words < 0 || s.critic_layers < 1) return false;
+  PpoPlan p{};
+  auto stage = [&](const MlpTowerDev& T, bool actor) {
+    PpoStage st{};
+    int off = 16 * 16 * ppo_tiles(s.obs_dim);
+    for (int l = 0; l < T.layers; ++l) st.h_off[l] = off, off += 16 * 16 * T.hidden[l].out_tiles;
+    st.head_off = off, off += T.head_dot ? 16 : 16 * 16 * T.head.out_tiles;
+    st.ls_off = off;
+    if (actor) off += 16 * 16 * d.act_tiles;
+    st.floats = off;
+    return st;
+  };
+  p.stage[0] = stage(d.actor, true);
+  p.stage[1] = stage(d.critic, false);
+  p.tile_floats = p.stage[0].floats > p.stage[1].floats ? p.stage[0].floats : p.stage[1].floats;
+  const int tile_bytes = 4 * p.tile_floats;
+  p.nw = PPO_LDS_BUDGET / tile_bytes;
+  p.nw = p.nw < 1 ? 1 : p.nw > 4 ? 4 : p.nw;
+  p.lds_bytes = p.nw * tile_bytes;  // (<= PPO_LDS_MAX: a larger one tile is not possible)
+  if (p.lds_bytes > PPO_LDS_MAX) return false;
+  p.train_off = d.log_std_off;
+  p.train_words = (int)(words - d.log_std_off);
+  int64_t cap = PPO_PARTIAL_CAP_BYTES / (4 * (int64_t)p.train_words);
+  p.grid_cap = cap < 1 ? 1 : cap > PPO_MAX_GRID ? PPO_MAX_GRID : (int)cap;
+  p.fold_blocks = (p.train_words + PPO_THREADS - 1) / PPO_THREADS;
+  if (plan) *plan = p;
+  return true;
+}
+
+// Blocks of launch A for a minibatch of n samples.
+inline int ppo_grid(const PpoPlan& p, int n) {
+  const int chunks = (ppo_tiles(n) + p.nw - 1) / p.nw;
+  return chunks < p.grid_cap ? chunks : p.grid_cap;
+}
+
+// Workspace offsets (bytes) for a grid of g blocks.
+inline int64_t ppo_stat_partials_at(const PpoPlan& p, int g) { return PPO_HEADER_BYTES + 4 * (int64_t)g * p.train_words; }
+inline int64_t ppo_grad_at(const PpoPlan& p, int g) { return ppo_stat_partials_at(p, g) + 8 * (int64_t)g * PPO_STATS; }
+inline int64_t ppo_sq_at(const PpoPlan& p, int g) { return ppo_grad_at(p, g) + 4 * (int64_t)p.train_words; }
+inline int64_t ppo_workspace_bytes(const PpoPlan& p, int g) { return ppo_sq_at(p, g) + 8 * (int64_t)p.fold_blocks; }
+
+#if defined(__HIPCC__)
+
+template <int ACT>
+__device__ __forceinline__ float ppo_dact(float h) {  // the activation's derivative from its output
+  if constexpr (ACT == UPKIE_MLP_TANH) return 1.f - h * h;
+  else return h > 0.f ? 1.f : 0.f;
+}
+
+// dx = W^T dz for a layer in hidden (accumulator) k order: A = the W^T fragment W[16o + 4q + s][16t + r], gathered from
+// packed word (o, t, lane 16 (r >> 2) + 4q + s, step r & 3); B = the lane's own accumulator s of dz tile o. dx tile t
+// comes out in the accumulator layout of the layer's input (units 16t + 4q + i of sample r).
+template <int WT>
+__device__ __forceinline__ void ppo_dx(const float* __restrict__ packed, const MlpLayerDev& L, const float (&dz)[WT][4], float (&dx)[WT][4],
+                                       int lane) {
+  const int q = lane >> 4, r = lane & 15;
+#pragma unroll
+  for (int t = 0; t < WT; ++t) {
+    mlp_f4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (t < L.in_tiles) {
+#pragma unroll
+      for (int o = 0; o < WT; ++o) {
+        if (o < L.out_tiles) {
+          const float* w = packed + L.w_off + ((o * L.in_tiles + t) * 64 + 16 * (r >> 2) + 4 * q) * 4 + (r & 3);
+          float a[4];
+#pragma unroll
+          for (int s = 0; s < 4; ++s) a[s] = w[4 * s];
+#pragma unroll
+          for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], dz[o][s], acc, 0, 0, 0);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) dx[t][i] = acc[i];
+  }
+}
+
+// Partial-gradient word: the first chunk of a block writes it, later chunks add to it (same owning thread every chunk).
+__device__ __forceinline__ void ppo_acc(float* part, int i, float x, bool first) { part[i] = first ? x : part[i] + x; }
+
+// dW of an MFMA layer over the chunk's samples: fragment (o, t) = sum over samples of X[16t + r][k] dZ[16o + r'][k],
+// read transposed from every wave's stage ([unit][sample] rows); A = X^T, B = dZ^T, k = 4 samples per step, so lane
+// (q, r) ends with W[16o + r][16t + 4q + i], packed word (o, t, lane, i) -- or, for the first layer (natural k order),
+// (o, t, lane 16i + r, step q). Then the bias: the sum of dZ's rows.
+__device__ __forceinline__ void ppo_dw_mfma(const PpoDev& P, const float* stage, const MlpLayerDev& L, bool first_layer, int x_off, int z_off,
+                                            float* part, bool first, int wave, int lane) {
+  const int q = lane >> 4, r = lane & 15;
+  const int frags = L.out_tiles * L.in_tiles;
+  for (int f = wave; f < frags; f += P.nw) {
+    const int o = f / L.in_tiles, t = f - o * L.in_tiles;
+    mlp_f4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int w = 0; w < P.nw; ++w) {
+      const float* tb = stage + w * P.tile_floats;
+      const float* xa = tb + x_off + (16 * t + r) * 16 + q;
+      const float* zb = tb + z_off + (16 * o + r) * 16 + q;
+      float a[4], b[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) a[s] = xa[4 * s], b[s] = zb[4 * s];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b[s], acc, 0, 0, 0);
+    }
+    const int base = L.w_off - P.train_off + (o * L.in_tiles + t) * 256;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ppo_acc(part, base + (first_layer ? (16 * i + r) * 4 + q : lane * 4 + i), acc[i], first);
+  }
+  const int tid = wave * 64 + lane;
+  for (int u = tid; u < 16 * L.out_tiles; u += 64 * P.nw) {
+    float s = 0.f;
+    for (int w = 0; w < P.nw; ++w) {
+      const float* z = stage + w * P.tile_floats + z_off + u * 16;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) s += z[k];
+    }
+    ppo_acc(part, L.b_off - P.train_off + u, s, first);
+  }
+}
+
+// dW of a dot head (one row dz at z_off): word k = sum over samples of dz X[k]; bias word = sum of dz (its 3 padding
+// words 0).
+__device__ __forceinline__ void ppo_dw_dot(const PpoDev& P, const float* stage, const MlpLayerDev& L, int x_off, int z_off, float* part, bool first,
+                                           int tid) {
+  for (int k = tid; k < 16 * L.in_tiles + 4; k += 64 * P.nw) {
+    float s = 0.f;
+    if (k < 16 * L.in_tiles) {
+      for (int w = 0; w < P.nw; ++w) {
+        const float* tb = stage + w * P.tile_floats;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) s = fmaf(tb[z_off + j], tb[x_off + k * 16 + j], s);
+      }
+      ppo_acc(part, L.w_off - P.train_off + k, s, first);
+    } else {
+      if (k == 16 * L.in_tiles)
+        for (int w = 0; w < P.nw; ++w) {
+          const float* tb = stage + w * P.tile_floats;
+#pragma unroll
+          for (int j = 0; j < 16; ++j) s += tb[z_off + j];
+        }
+      ppo_acc(part, L.b_off - P.train_off + (k - 16 * L.in_tiles), s, first);
+    }
+  }
+}
+
+// Sum over the chunk's samples of `rows` stage rows at `off` into partial words [at, at + rows).
+__device__ __forceinline__ void ppo_row_sums(const PpoDev& P, const float* stage, int off, int rows, int at, float* part, bool first, int tid) {
+  for (int u = tid; u < rows; u += 64 * P.nw) {
+    float s = 0.f;
+    for (int w = 0; w < P.nw; ++w) {
+      const float* z = stage + w * P.tile_floats + off + u * 16;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) s += z[k];
+    }
+    ppo_acc(part, at + u, s, first);
+  }
+}
+
+// Writes accumulator tiles [0, tiles) of `h` as [unit][sample] rows at `off` of the wave's stage.
+template <int WT>
+__device__ __forceinline__ void ppo_store(float* my, int off, int tiles, const float (&h)[WT][4], int lane) {
+  const int q = lane >> 4, r = lane & 15;
+#pragma unroll
+  for (int t = 0; t < WT; ++t)
+    if (t < tiles)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) my[off + (16 * t + 4 * q + i) * 16 + r] = h[t][i];
+}
+
+// One tower of one chunk: forward, loss, backward, dW. ACTOR: the policy loss through the Gaussian head (and log_std);
+// otherwise the value loss through the critic's dot head. `st` collects the loss sums of the lane's sample (lanes of
+// group 0 only).
+template <int WT, int ACT, bool ACTOR>
+__device__ __forceinline__ void ppo_tower(const PpoDev& P, float* stage, int sample, bool valid, float* part, bool first, double (&st)[PPO_STATS],
+                                          int wave, int lane) {
+  const int q = lane >> 4, r = lane & 15, tid = wave * 64 + lane;
+  const MlpTowerDev& T = ACTOR ? P.net.actor : P.net.critic;
+  const PpoStage& S = P.stage[ACTOR ? 0 : 1];
+  const float* __restrict__ packed = P.packed;
+  float* my = stage + wave * P.tile_floats;
+  const float inv_b = 1.f / (float)P.mb_size;
+  float cur[WT][4] = {};  // dZ of the current layer (accumulator layout)
+  float dz_dot = 0.f;     // dZ of a dot head (every lane of the sample)
+  {
+    float x[WT][4] = {}, h[WT][4] = {};
+    __syncthreads();  // (every wave is done reading the previous tower's stage)
+#pragma unroll
+    for (int t = 0; t < WT; ++t)
+      if (16 * t < P.net.obs_dim)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) x[t][s] = my[(16 * t + 4 * s + q) * 16 + r];
+    mlp_dense<WT, ACT, true, true>(packed, T.hidden[0], P.net.obs_dim, x, h, lane);
+    ppo_store<WT>(my, S.h_off[0], T.hidden[0].out_tiles, h, lane);
+#pragma unroll 1
+    for (int l = 1; l < T.layers; ++l) {
+      mlp_dense<WT, ACT, false, true>(packed, T.hidden[l], P.net.obs_dim, h, x, lane);
+#pragma unroll
+      for (int t = 0; t < WT; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) h[t][i] = x[t][i];
+      ppo_store<WT>(my, S.h_off[l], T.hidden[l].out_tiles, h, lane);
+    }
+    if constexpr (ACTOR) {
+      float head[WT][4] = {};
+      float m1 = 0.f;
+      if (T.head_dot) m1 = mlp_dot<WT>(packed, T.head, h, lane);
+      else mlp_dense<WT, ACT, false, false>(packed, T.head, P.net.obs_dim, h, head, lane);
+      if (T.head_dot) head[0][0] = m1;
+      constexpr float HALF_LOG_2PI = 0.91893853320467274f;
+      float lp = 0.f, d[4][4] = {}, sig2[4][4] = {};
+#pragma unroll
+      for (int o = 0; o < (WT < 4 ? WT : 4); ++o) {
+        const int a0 = 16 * o + 4 * q;
+        if (o < P.net.act_tiles && a0 < P.net.act_dim) {
+          const mlp_f4 log_std = mlp_load4(packed + P.net.log_std_off + a0);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int a = a0 + i;
+            if (a < P.net.act_dim) {
+              const float sigma = expf(log_std[i]);
+              const float dd = P.actions[(size_t)sample * P.net.act_dim + a] - head[o][i];
+              d[o][i] = dd, sig2[o][i] = sigma * sigma;
+              lp += -(dd * dd) / (2.f * sigma * sigma) - log_std[i] - HALF_LOG_2PI;
+            }
+          }
+        }
+      }
+      lp += __shfl_xor(lp, 16);
+      lp += __shfl_xor(lp, 32);
+      // clipped surrogate: d loss / d log_prob (torch.minimum splits a tie half / half; clamp passes at its bounds)
+      const double* as = P.adv_stats;
+      const float adv = (float)(((double)P.advantages[sample] - as[0]) / as[1]);
+      const float log_ratio = lp - P.old_log_prob[sample];
+      const float ratio = expf(log_ratio);
+      const float a1 = adv * ratio, a2 = adv * fminf(fmaxf(ratio, P.clip_lo), P.clip_hi);
+      const float w1 = a1 < a2 ? 1.f : a1 == a2 ? 0.5f : 0.f, w2 = 1.f - w1;
+      const float pass = ratio >= P.clip_lo && ratio <= P.clip_hi ? 1.f : 0.f;
+      const float g_lp = valid ? -inv_b * (w1 * adv + w2 * adv * pass) * ratio : 0.f;
+      if (valid && q == 0) {
+        st[0] += (double)fminf(a1, a2);
+        st[2] += (double)((ratio - 1.f) - log_ratio);
+        st[3] += fabsf(ratio - 1.f) > P.clip_range ? 1.0 : 0.0;
+      }
+      // head dZ = d loss / d mean, and the per-sample log_std terms, into the stage
+#pragma unroll
+      for (int o = 0; o < (WT < 4 ? WT : 4); ++o) {
+        if (o < P.net.act_tiles) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const bool on = 16 * o + 4 * q + i < P.net.act_dim;
+            const float dmu = on ? g_lp * d[o][i] / sig2[o][i] : 0.f;
+            cur[o][i] = dmu;
+            my[S.ls_off + (16 * o + 4 * q + i) * 16 + r] = on ? g_lp * (d[o][i] * d[o][i] / sig2[o][i] - 1.f) : 0.f;
+          }
+        }
+      }
+      if (T.head_dot) {
+        dz_dot = __shfl(cur[0][0], r);  // (action 0: lane group 0, accumulator 0)
+        if (q == 0) my[S.head_off + r] = dz_dot;
+      } else {
+        ppo_store<WT>(my, S.head_off, T.head.out_tiles, cur, lane);  // (tiles past act_tiles: zeros)
+      }
+    } else {
+      const float v = mlp_dot<WT>(packed, T.head, h, lane);
+      const float old_v = P.old_values[sample], ret = P.returns[sample];
+      float vp = v, pass = 1.f;
+      if (P.vf_clip) {
+        const float dv = v - old_v;
+        vp = old_v + fminf(fmaxf(dv, -P.clip_vf), P.clip_vf);
+        pass = dv >= -P.clip_vf && dv <= P.clip_vf ? 1.f : 0.f;
+      }
+      const float e = ret - vp;
+      dz_dot = valid ? P.vf_coef * 2.f * (vp - ret) * inv_b * pass : 0.f;
+      if (valid && q == 0) st[1] += (double)e * (double)e;
+      if (q == 0) my[S.head_off + r] = dz_dot;
+    }
+  }
+
+  // backward: layer l + 1 (the head when l = layers - 1) -> dZ of hidden layer l, over H_l in the stage
+#pragma unroll 1
+  for (int l = T.layers - 1; l >= 0; --l) {
+    const bool head = l == T.layers - 1;
+    const MlpLayerDev& U = head ? T.head : T.hidden[l + 1];
+    const int z_off = head ? S.head_off : S.h_off[l + 1];
+    __syncthreads();  // (dZ of layer l + 1 and H_l of every wave are in the stage)
+    if (head && T.head_dot) ppo_dw_dot(P, stage, U, S.h_off[l], z_off, part, first, tid);
+    else ppo_dw_mfma(P, stage, U, false, S.h_off[l], z_off, part, first, wave, lane);
+    __syncthreads();  // (H_l read: it may be overwritten)
+    float dx[WT][4] = {};
+    if (head && T.head_dot) {
+#pragma unroll
+      for (int t = 0; t < WT; ++t)
+        if (t < U.in_tiles) {
+          const mlp_f4 w = mlp_load4(packed + U.w_off + 16 * t + 4 * q);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) dx[t][i] = w[i] * dz_dot;
+        }
+    } else {
+      ppo_dx<WT>(packed, U, cur, dx, lane);
+    }
+    const int tiles = T.hidden[l].out_tiles, off = S.h_off[l];
+#pragma unroll
+    for (int t = 0; t < WT; ++t) {
+      if (t < tiles) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int at = off + (16 * t + 4 * q + i) * 16 + r;
+          const float dz = t < U.in_tiles ? dx[t][i] * ppo_dact<ACT>(my[at]) : 0.f;
+          cur[t][i] = dz;
+          my[at] = dz;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  ppo_dw_mfma(P, stage, T.hidden[0], true, 0, S.h_off[0], part, first, wave, lane);
+  if constexpr (ACTOR) ppo_row_sums(P, stage, S.ls_off, 16 * P.net.act_tiles, P.net.log_std_off - P.train_off, part, first, tid);
+}
+
+template <int W, int ACT>
+__global__ __launch_bounds__(256) void ppo_grad_kernel(const PpoDev P) {
+  extern __shared__ float stage[];
+  __shared__ double red[4][PPO_STATS];
+  constexpr int WT = W / 16;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15;
+  float* part = P.partials + (size_t)blockIdx.x * P.train_words;
+  float* my = stage + wave * P.tile_floats;
+  double st[PPO_STATS] = {0.0, 0.0, 0.0, 0.0};
+  const int chunks = (ppo_tiles(P.mb_size) + P.nw - 1) / P.nw;
+  for (int c = blockIdx.x; c < chunks; c += gridDim.x) {
+    const bool first = c == (int)blockIdx.x;
+    const int64_t j = ((int64_t)c * P.nw + wave) * 16 + r;  // position in the minibatch (64-bit: no overflow near INT_MAX)
+    const bool valid = j < P.mb_size;
+    const int sample = P.perm[(int64_t)P.mb_start + (valid ? j : 0)];
+    __syncthreads();  // (the previous chunk's critic is done reading x)
+    // x rows: element k of the sample, normalised as act() does unless the buffer holds normalised observations
+#pragma unroll
+    for (int t = 0; t < WT; ++t) {
+      if (16 * t < P.net.obs_dim) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int k = 16 * t + 4 * s + q;
+          float u = 0.f;
+          if (k < P.net.obs_dim) {
+            u = P.obs[(size_t)sample * P.net.obs_dim + k];
+            if (P.net.normalize && !P.obs_normalized)
+              u = fminf(fmaxf((u - P.packed[P.net.mean_off + k]) / P.packed[P.net.std_off + k], -P.net.clip_obs), P.net.clip_obs);
+          }
+          my[k * 16 + r] = u;
+        }
+      }
+    }
+    ppo_tower<WT, ACT, true>(P, stage, sample, valid, part, first, st, wave, lane);
+    ppo_tower<WT, ACT, false>(P, stage, sample, valid, part, first, st, wave, lane);
+  }
+  // loss sums: a fixed shuffle tree per wave, then the waves in order
+#pragma unroll
+  for (int k = 0; k < PPO_STATS; ++k) {
+    double x = st[k];
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) x += __shfl_xor(x, m);
+    if (lane == 0) red[wave][k] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < PPO_STATS) {
+    double s = 0.0;
+    for (int w = 0; w < P.nw; ++w) s += red[w][threadIdx.x];
+    P.stat_partials[blockIdx.x * PPO_STATS + threadIdx.x] = s;
+  }
+}
+
+// Launch B: fold the partials, ||g||^2 per block, and the last block's scalars (see the top of the file).
+__global__ __launch_bounds__(PPO_THREADS) void ppo_fold_kernel(const PpoDev P) {
+  __shared__ double lds[PPO_THREADS + 1];
+  const int tid = threadIdx.x, i = blockIdx.x * PPO_THREADS + tid;
+  double sq = 0.0;
+  if (i < P.train_words) {
+    float s = 0.f;
+    const float* p = P.partials + i;
+    int b = 0;
+    for (; b + 32 <= P.grid; b += 32) {  // (32 loads in flight, added in block order)
+      float x[32];
+#pragma unroll
+      for (int k = 0; k < 32; ++k) x[k] = p[(size_t)(b + k) * P.train_words];
+#pragma unroll
+      for (int k = 0; k < 32; ++k) s += x[k];
+    }
+    for (; b < P.grid; ++b) s += p[(size_t)b * P.train_words];
+    if (i < P.net.act_dim) s -= P.ent_coef;  // d(ent_coef * entropy_loss) / d log_std_a
+    P.grad[i] = s;
+    sq = (double)s * (double)s;
+  }
+  lds[tid] = sq;
+  for (int h = PPO_THREADS / 2; h > 0; h >>= 1) {
+    __syncthreads();
+    if (tid < h) lds[tid] += lds[tid + h];
+  }
+  __syncthreads();
+  if (tid == 0) P.sq_partials[blockIdx.x] = lds[0];
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid != 0) return;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const unsigned ticket = __hip_atomic_fetch_add(P.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (ticket != (unsigned)(P.fold_blocks - 1)) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __hip_atomic_store(P.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  double total = 0.0;
+  for (int b = 0; b < P.fold_blocks; ++b) total += P.sq_partials[b];
+  const double norm = sqrt(total);
+  const double coef = fmin(1.0, (double)P.max_grad_norm / (norm + 1e-6));
+  double sums[PPO_STATS] = {0.0, 0.0, 0.0, 0.0};
+  for (int b = 0; b < P.grid; ++b)
+#pragma unroll
+    for (int k = 0; k < PPO_STATS; ++k) sums[k] += P.stat_partials[b * PPO_STATS + k];
+  const double n = (double)P.mb_size;
+  double entropy = 0.0;
+  for (int a = 0; a < P.net.act_dim; ++a) entropy += 0.5 + 0.91893853320467274 + (double)P.packed[P.net.log_std_off + a];
+  const double pg = -sums[0] / n, vl = sums[1] / n, ent_loss = -entropy;
+  P.stats[0] = (float)pg;
+  P.stats[1] = (float)vl;
+  P.stats[2] = (float)ent_loss;
+  P.stats[3] = (float)(pg + (double)P.ent_coef * ent_loss + (double)P.vf_coef * vl);
+  P.stats[4] = (float)(sums[2] / n);
+  P.stats[5] = (float)(sums[3] / n);
+  P.stats[6] = (float)norm;
+  const double t = P.scalars[1] + 1.0;
+  P.scalars[1] = t;
+  P.header[4] = (float)coef;
+  P.header[5] = (float)(P.scalars[0] / (1.0 - pow((double)P.beta1, t)));
+  P.header[6] = (float)sqrt(1.0 - pow((double)P.beta2, t));
+}
+
+// Launch C: clip + Adam on the trainable words, in place.
+__global__ __launch_bounds__(PPO_THREADS) void ppo_adam_kernel(const PpoDev P) {
+  const int i = blockIdx.x * PPO_THREADS + threadIdx.x;
+  if (i >= P.train_words) return;
+  const float coef = P.header[4], step = P.header[5], bc2 = P.header[6];
+  const int w = P.train_off + i;
+  const float g = P.grad[i] * coef;
+  const float m = P.beta1 * P.m[w] + (1.f - P.beta1) * g;
+  const float v = P.beta2 * P.v[w] + (1.f - P.beta2) * g * g;
+  P.m[w] = m;
+  P.v[w] = v;
+  P.packed[w] -= step * (m / (sqrtf(v) / bc2 + P.adam_eps));
+}
+
+// Launch 0: (mean, std + 1e-8) of the advantages of every minibatch of an epoch, fp64, two passes in a fixed order (each
+// thread 8 gathers in flight at a time, then a fixed LDS tree).
+__global__ __launch_bounds__(PPO_ADV_THREADS) void ppo_adv_stats_kernel(int total, int batch, const int32_t* __restrict__ perm,
+                                                                       const float* __restrict__ adv, int normalize, double* __restrict__ out) {
+  __shared__ double lds[PPO_ADV_THREADS];
+  const int tid = threadIdx.x, start = blockIdx.x * batch;
+  const int n = total - start < batch ? total - start : batch;
+  auto tree = [&](double x) {
+    lds[tid] = x;
+    for (int h = PPO_ADV_THREADS / 2; h > 0; h >>= 1) {
+      __syncthreads();
+      if (tid < h) lds[tid] += lds[tid + h];
+    }
+    __syncthreads();
+    const double s = lds[0];
+    __syncthreads();
+    return s;
+  };
+  if (!normalize || n < 2) {
+    if (tid == 0) out[2 * blockIdx.x] = 0.0, out[2 * blockIdx.x + 1] = 1.0;
+    return;
+  }
+  double s = 0.0;
+  for (int64_t i0 = tid; i0 < n; i0 += 8 * PPO_ADV_THREADS) {  // (64-bit: no overflow near INT_MAX)
+    double x[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int64_t i = i0 + k * PPO_ADV_THREADS;
+      x[k] = i < n ? (double)adv[perm[start + i]] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += x[k];
+  }
+  const double mean = tree(s) / n;
+  s = 0.0;
+  for (int64_t i0 = tid; i0 < n; i0 += 8 * PPO_ADV_THREADS) {
+    double x[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int64_t i = i0 + k * PPO_ADV_THREADS;
+      x[k] = i < n ? (double)adv[perm[start + i]] - mean : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += x[k] * x[k];
+  }
+  const double var = tree(s) / (n - 1);
+  if (tid == 0) out[2 * blockIdx.x] = mean, out[2 * blockIdx.x + 1] = sqrt(var) + 1e-8;
+}
+
+#endif  // __HIPCC__
+
+}  // namespace upkie

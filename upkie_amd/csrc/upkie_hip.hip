@@ -21,6 +21,7 @@
 #include "policy_mlp.hpp"
 #include "rollout.hpp"
 #include "vecnorm.hpp"
+#include "ppo.hpp"
 
 #include "step_kernels.hpp"
 #include "step_instances.hpp"  // (the step kernels this unit launches are compiled elsewhere, by groups: declarations only)
@@ -337,6 +338,7 @@ extern "C" int64_t upkie_hip_struct_bytes(int which) {
     case UPKIE_STRUCT_OBSERVER_INPUT: return (int64_t)sizeof(UpkieObserverInput);
     case UPKIE_STRUCT_OBSERVER_OUTPUT: return (int64_t)sizeof(UpkieObserverOutput);
     case UPKIE_STRUCT_MLP_SHAPE: return (int64_t)sizeof(UpkieMlpShape);
+    case UPKIE_STRUCT_PPO_CONFIG: return (int64_t)sizeof(UpkiePpoConfig);
     default: return -1;
   }
 }
@@ -1365,6 +1367,157 @@ extern "C" int upkie_vecnorm_step(int32_t num_envs, int32_t obs_dim, const float
     hipLaunchKernelGGL(upkie::vecnorm_apply_kernel, dim3((unsigned)grid), dim3(upkie::VECNORM_THREADS), 0, s, P);
   }
   hipError_t err = hipGetLastError();
+  if (err != hipSuccess) {
+    g_create_error = hipGetErrorString(err);
+    return UPKIE_ERR_HIP;
+  }
+  return UPKIE_OK;
+}
+
+// ============================================================ PPO update (csrc/ppo.hpp)
+static bool ppo_shape_ok(const UpkieMlpShape* shape, upkie::PpoPlan* plan) {
+  if (!shape) {
+    g_create_error = "null shape";
+    return false;
+  }
+  if (upkie::mlp_layout(*shape, nullptr) < 0) {
+    upkie_mlp_packed_words(shape);  // (sets the message)
+    return false;
+  }
+  if (!upkie::ppo_plan(*shape, plan)) {
+    g_create_error = "PPO needs a critic (critic_layers > 0)";
+    return false;
+  }
+  return true;
+}
+
+extern "C" int64_t upkie_ppo_workspace_bytes(const UpkieMlpShape* shape, int32_t max_minibatch) {
+  upkie::PpoPlan plan;
+  if (!ppo_shape_ok(shape, &plan)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (max_minibatch < 1) {
+    g_create_error = "max_minibatch must be positive";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  return upkie::ppo_workspace_bytes(plan, upkie::ppo_grid(plan, max_minibatch));
+}
+
+extern "C" int upkie_ppo_advantage_stats(int32_t total, int32_t batch_size, const int32_t* perm, const float* advantages, int32_t normalize,
+                                         double* adv_stats, void* stream) {
+  if (total < 1 || batch_size < 1) {
+    g_create_error = "total and batch_size must be positive";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (!perm || !advantages || !adv_stats) {
+    g_create_error = "null argument";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (upkie_hip_device_count() <= 0) {
+    g_create_error = "no HIP device visible";
+    return UPKIE_ERR_NO_DEVICE;
+  }
+  const unsigned blocks = (unsigned)((total + (int64_t)batch_size - 1) / batch_size);
+  hipLaunchKernelGGL(upkie::ppo_adv_stats_kernel, dim3(blocks), dim3(upkie::PPO_ADV_THREADS), 0, (hipStream_t)stream, total, batch_size, perm,
+                     advantages, normalize ? 1 : 0, adv_stats);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) {
+    g_create_error = hipGetErrorString(err);
+    return UPKIE_ERR_HIP;
+  }
+  return UPKIE_OK;
+}
+
+template <int W, int ACT>
+static hipError_t launch_ppo_grad(const upkie::PpoDev& P, int lds_bytes, hipStream_t s) {
+  auto kernel = upkie::ppo_grad_kernel<W, ACT>;
+  if (lds_bytes > upkie::PPO_LDS_BUDGET) {
+    // (one tile of the widest shapes needs more than 64 KiB; MI355X has 160 KiB per CU). Raised once per instantiation, to
+    // what any valid shape of it can need, so that a later shape with a larger stage is covered too.
+    static const hipError_t raised = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, upkie::PPO_LDS_MAX);
+    if (raised != hipSuccess) return raised;
+  }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)P.grid), dim3(64 * P.nw), (size_t)lds_bytes, s, P);
+  return hipGetLastError();
+}
+
+template <int W>
+static hipError_t launch_ppo_grad_w(int activation, const upkie::PpoDev& P, int lds_bytes, hipStream_t s) {
+  return activation == UPKIE_MLP_TANH ? launch_ppo_grad<W, UPKIE_MLP_TANH>(P, lds_bytes, s) : launch_ppo_grad<W, UPKIE_MLP_RELU>(P, lds_bytes, s);
+}
+
+extern "C" int upkie_ppo_minibatch_update(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
+                                          int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm, const float* obs,
+                                          const float* actions, const float* old_values, const float* old_log_prob, const float* advantages,
+                                          const float* returns, const double* adv_stats, float* packed, float* adam_m, float* adam_v,
+                                          double* adam_scalars, void* workspace, float* stats, void* stream) {
+  upkie::PpoPlan plan;
+  if (!ppo_shape_ok(shape, &plan)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!config) {
+    g_create_error = "null config";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  const UpkiePpoConfig& c = *config;
+  if (!(c.clip_range > 0.f) || !(c.max_grad_norm > 0.f) || !(c.adam_eps > 0.f) || !(c.adam_beta1 >= 0.f && c.adam_beta1 < 1.f) ||
+      !(c.adam_beta2 >= 0.f && c.adam_beta2 < 1.f) || !std::isfinite(c.ent_coef) || !std::isfinite(c.vf_coef) || !(c.clip_range_vf == c.clip_range_vf)) {
+    g_create_error = "config: clip_range, max_grad_norm and adam_eps must be positive, adam betas in [0, 1), coefficients finite";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (total < 1 || minibatch_size < 1 || max_minibatch < 1 || minibatch_start < 0 || minibatch_size > max_minibatch ||
+      (int64_t)minibatch_start + minibatch_size > total) {
+    g_create_error = "minibatch out of range: 0 <= minibatch_start, 1 <= minibatch_size <= max_minibatch, start + size <= total";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if ((int64_t)total * (shape->obs_dim > shape->act_dim ? shape->obs_dim : shape->act_dim) > INT_MAX) {
+    g_create_error = "total * obs_dim (or act_dim) must stay below 2^31";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (!perm || !obs || !actions || !old_values || !old_log_prob || !advantages || !returns || !adv_stats || !packed || !adam_m || !adam_v ||
+      !adam_scalars || !workspace || !stats) {
+    g_create_error = "null argument";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (upkie_hip_device_count() <= 0) {
+    g_create_error = "no HIP device visible";
+    return UPKIE_ERR_NO_DEVICE;
+  }
+  upkie::PpoDev P{};
+  upkie::mlp_layout(*shape, &P.net);
+  P.stage[0] = plan.stage[0], P.stage[1] = plan.stage[1];
+  P.train_off = plan.train_off, P.train_words = plan.train_words;
+  P.mb_start = minibatch_start, P.mb_size = minibatch_size;
+  P.nw = plan.nw, P.tile_floats = plan.tile_floats;
+  P.grid = upkie::ppo_grid(plan, minibatch_size);
+  const int ws_grid = upkie::ppo_grid(plan, max_minibatch);  // (the workspace's layout)
+  P.fold_blocks = plan.fold_blocks;
+  P.obs_normalized = c.obs_normalized ? 1 : 0;
+  P.vf_clip = c.clip_range_vf > 0.f;
+  P.clip_range = c.clip_range;
+  P.clip_lo = (float)(1.0 - (double)c.clip_range), P.clip_hi = (float)(1.0 + (double)c.clip_range);
+  P.clip_vf = c.clip_range_vf, P.ent_coef = c.ent_coef, P.vf_coef = c.vf_coef, P.max_grad_norm = c.max_grad_norm;
+  P.beta1 = c.adam_beta1, P.beta2 = c.adam_beta2, P.adam_eps = c.adam_eps;
+  P.perm = perm, P.obs = obs, P.actions = actions, P.old_values = old_values, P.old_log_prob = old_log_prob;
+  P.advantages = advantages, P.returns = returns, P.adv_stats = adv_stats;
+  P.packed = packed, P.m = adam_m, P.v = adam_v, P.scalars = adam_scalars, P.stats = stats;
+  char* ws = (char*)workspace;
+  P.ticket = (unsigned*)ws;
+  P.header = (float*)ws;
+  P.partials = (float*)(ws + upkie::PPO_HEADER_BYTES);
+  P.stat_partials = (double*)(ws + upkie::ppo_stat_partials_at(plan, ws_grid));
+  P.grad = (float*)(ws + upkie::ppo_grad_at(plan, ws_grid));
+  P.sq_partials = (double*)(ws + upkie::ppo_sq_at(plan, ws_grid));
+  const hipStream_t s = (hipStream_t)stream;
+  hipError_t err = hipSuccess;
+  switch (upkie::mlp_width_class(*shape)) {
+    case 16: err = launch_ppo_grad_w<16>(shape->activation, P, plan.lds_bytes, s); break;
+    case 32: err = launch_ppo_grad_w<32>(shape->activation, P, plan.lds_bytes, s); break;
+    case 64: err = launch_ppo_grad_w<64>(shape->activation, P, plan.lds_bytes, s); break;
+    case 128: err = launch_ppo_grad_w<128>(shape->activation, P, plan.lds_bytes, s); break;
+    default: err = launch_ppo_grad_w<256>(shape->activation, P, plan.lds_bytes, s); break;
+  }
+  if (err == hipSuccess) {
+    hipLaunchKernelGGL(upkie::ppo_fold_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
+    hipLaunchKernelGGL(upkie::ppo_adam_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
+    err = hipGetLastError();
+  }
   if (err != hipSuccess) {
     g_create_error = hipGetErrorString(err);
     return UPKIE_ERR_HIP;

@@ -31,6 +31,7 @@ SOURCES = [
     os.path.join(_HERE, "csrc", "rollout.hpp"),
     os.path.join(_HERE, "csrc", "policy_mlp.hpp"),
     os.path.join(_HERE, "csrc", "vecnorm.hpp"),
+    os.path.join(_HERE, "csrc", "ppo.hpp"),
     os.path.join(_HERE, "csrc", "wave_io.hpp"),
     os.path.join(_HERE, "..", "include", "upkie_hip.h"),
 ]
@@ -96,6 +97,9 @@ EXPORTED_SYMBOLS = (
     "upkie_mlp_actor_critic",
     "upkie_vecnorm_workspace_bytes",
     "upkie_vecnorm_step",
+    "upkie_ppo_workspace_bytes",
+    "upkie_ppo_advantage_stats",
+    "upkie_ppo_minibatch_update",
 )
 
 
@@ -364,6 +368,13 @@ def load() -> C.CDLL:
         lib.upkie_vecnorm_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
         lib.upkie_vecnorm_step.restype = C.c_int
         lib.upkie_vecnorm_step.argtypes = ([C.c_int32, C.c_int32] + [vp] * 8 + [C.c_int32] + [C.c_double] * 4 + [vp] * 7)
+    if hasattr(lib, "upkie_ppo_minibatch_update"):  # (newer entry points: an older build loaded for an A/B run lacks them)
+        lib.upkie_ppo_workspace_bytes.restype = C.c_int64
+        lib.upkie_ppo_workspace_bytes.argtypes = [C.POINTER(abi.UpkieMlpShape), C.c_int32]
+        lib.upkie_ppo_advantage_stats.restype = C.c_int
+        lib.upkie_ppo_advantage_stats.argtypes = [C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp]
+        lib.upkie_ppo_minibatch_update.restype = C.c_int
+        lib.upkie_ppo_minibatch_update.argtypes = ([C.POINTER(abi.UpkieMlpShape), C.POINTER(abi.UpkiePpoConfig)] + [C.c_int32] * 4 + [vp] * 15)
     lib.upkie_rollout_gae.restype = C.c_int
     lib.upkie_rollout_gae.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
     _lib = lib

@@ -220,6 +220,7 @@ class RunningNormalizer:
             raise UpkieRuntimeError("this normalizer already feeds another policy")
         policy._fixed[0], policy._fixed[1] = self.obs_mean_f32, self.obs_std_f32
         self._policy = policy
+        policy._normalizer = self  # (upkie_amd.ppo refuses raw observations for a policy reading live statistics)
         self._sync_policy()
         policy.update_from()
 
