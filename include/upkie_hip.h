@@ -928,6 +928,43 @@ int upkie_vecnorm_step(int32_t num_envs, int32_t obs_dim, const float* obs, cons
                        float* std_f32, float* packed_stats, float* norm_obs, float* norm_reward, uint8_t* episode_starts,
                        void* stream);
 
+/* Data-parallel form: W ranks (W >= 1), each with its own N_r envs, keep
+ * one set of statistics, those of one normaliser over all sum_r N_r envs. A
+ * step that moves a statistic (TRAINING, and NORM_OBS or not RESET) becomes
+ *   upkie_vecnorm_moments_local(..., slot):  the returns update as in
+ *     upkie_vecnorm_step; the batch moments of this rank's envs, per
+ *     observation column d and for the returns (column D), go to slot:
+ *       slot[c] = count, slot[D + 1 + c] = mean, slot[2 (D + 1) + c] = M2
+ *     (c < D + 1; the columns the step does not reduce are not written); the
+ *     statistics do not move. Launch A of upkie_vecnorm_step, and its per-env
+ *     outputs when that step is one launch.
+ *   the caller makes every rank's slot visible to every rank, unchanged:
+ *     slots[r] = rank r's slot (slots[r] at slots + r * slot doubles);
+ *   upkie_vecnorm_merge(..., slots, W): per column, (n, mean, M2) = slots[0],
+ *     then Chan's merge of slots[1], ..., slots[W - 1] in rank order:
+ *       delta = mean_r - mean, tot = n + n_r
+ *       mean += delta n_r / tot,  M2 += M2_r + delta^2 n n_r / tot,  n = tot
+ *     then the update above with bm = mean, bv N = M2 and N = n, the fp32
+ *     mirrors and packed words as above, count += n; then the second launch
+ *     of upkie_vecnorm_step when it has one.
+ * Both take upkie_vecnorm_step's arguments, the same on both calls. Every
+ * rank computes the same merge on the same bits: the statistics are the same
+ * bits on every rank, and with W = 1 the same bits as upkie_vecnorm_step's.
+ * slot: upkie_vecnorm_slot_bytes(D) bytes (8-byte aligned). */
+int64_t upkie_vecnorm_slot_bytes(int32_t obs_dim);
+
+int upkie_vecnorm_moments_local(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward,
+                                const uint8_t* terminated, const uint8_t* truncated, double* obs_stats, double* ret_stats,
+                                double* returns, void* workspace, int32_t flags, double gamma, double epsilon,
+                                double clip_obs, double clip_reward, float* mean_f32, float* std_f32, float* packed_stats,
+                                float* norm_obs, float* norm_reward, uint8_t* episode_starts, double* slot, void* stream);
+
+int upkie_vecnorm_merge(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
+                        const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace,
+                        int32_t flags, double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32,
+                        float* std_f32, float* packed_stats, float* norm_obs, float* norm_reward, uint8_t* episode_starts,
+                        const double* slots, int32_t world, void* stream);
+
 /* ---- PPO update of the MLP actor-critic --------------------------------
  * One minibatch of Stable-Baselines3's PPO.train for a MlpPolicy with separate
  * actor and critic towers (no gSDE), on the device (csrc/ppo.hpp), applied in
@@ -1008,6 +1045,61 @@ int upkie_ppo_minibatch_update(const UpkieMlpShape* shape, const UpkiePpoConfig*
                                const float* old_log_prob, const float* advantages, const float* returns,
                                const double* adv_stats, float* packed, float* adam_m, float* adam_v,
                                double* adam_scalars, void* workspace, float* stats, void* stream);
+
+/* Data-parallel form: W ranks (W >= 1), each with its own rollout of the
+ * same T N samples, the same minibatch size and a replica of the same
+ * weights, train as one learner on the union: minibatch j of the union is
+ * the union of the ranks' minibatches j, B_g = W B samples. Every exchange:
+ * each rank writes its slot, the caller makes every rank's slot visible to
+ * every rank unchanged (slots[r] = rank r's, contiguous), and every rank
+ * folds them in rank order, so every rank computes the same bits.
+ * Advantage statistics of an epoch (M minibatches; slot: 2 M doubles,
+ * upkie_ppo_advantage_slot_bytes):
+ *   upkie_ppo_advantage_partials(phase 0): slot[j] = sum of the minibatch's
+ *     advantages (fp64, upkie_ppo_advantage_stats' order);
+ *   exchange;
+ *   upkie_ppo_advantage_partials(phase 1, slots, W): mean_j = sum_r
+ *     slots[r][j] / (W B_j); slot[M + j] = sum of (advantage - mean_j)^2;
+ *   exchange;
+ *   upkie_ppo_advantage_finish(slots, W): adv_stats[j] = (mean_j,
+ *     sqrt(sum_r slots[r][M + j] / (W B_j - 1)) + 1e-8), or (0, 1) when
+ *     normalize is 0 or W B_j = 1.
+ * A minibatch (slot: upkie_ppo_slot_bytes(shape)):
+ *   upkie_ppo_minibatch_gradient(..., global_minibatch_size = W B, slot):
+ *     the gradient of upkie_ppo_minibatch_update with the loss means over
+ *     global_minibatch_size samples, summed over this rank's samples, without
+ *     the entropy term: slot = g_r (fp32, packed words from log_std's on,
+ *     padded to an even count), then the fp64 loss sums of the stats row
+ *     (sum of min(surrogates), of (returns - values_pred)^2, of the
+ *     approx_kl terms, the clipped count). The weights do not move;
+ *   exchange;
+ *   upkie_ppo_minibatch_apply(slots, W): g = g_0 + g_1 + ... + g_{W-1} in
+ *     fp32 in rank order, minus ent_coef on the log_std words; then clip,
+ *     Adam, t and the stats row (means over global_minibatch_size) exactly as
+ *     upkie_ppo_minibatch_update.
+ * With W = 1 (global_minibatch_size = minibatch_size) every output is the
+ * same bits as upkie_ppo_advantage_stats' and upkie_ppo_minibatch_update's.
+ * Same workspace as upkie_ppo_minibatch_update; slots 8-byte aligned. */
+int64_t upkie_ppo_slot_bytes(const UpkieMlpShape* shape);
+
+int64_t upkie_ppo_advantage_slot_bytes(int32_t total, int32_t batch_size);
+
+int upkie_ppo_advantage_partials(int32_t total, int32_t batch_size, const int32_t* perm, const float* advantages,
+                                 int32_t phase, const double* slots, int32_t world, double* slot, void* stream);
+
+int upkie_ppo_advantage_finish(int32_t total, int32_t batch_size, int32_t normalize, const double* slots, int32_t world,
+                               double* adv_stats, void* stream);
+
+int upkie_ppo_minibatch_gradient(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total,
+                                 int32_t minibatch_start, int32_t minibatch_size, int32_t global_minibatch_size,
+                                 int32_t max_minibatch, const int32_t* perm, const float* obs, const float* actions,
+                                 const float* old_values, const float* old_log_prob, const float* advantages,
+                                 const float* returns, const double* adv_stats, float* packed, void* workspace,
+                                 void* slot, void* stream);
+
+int upkie_ppo_minibatch_apply(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t global_minibatch_size,
+                              int32_t max_minibatch, const void* slots, int32_t world, float* packed, float* adam_m,
+                              float* adam_v, double* adam_scalars, void* workspace, float* stats, void* stream);
 
 /* ---- Rollout consumer (BASELINE.json configs[3]) ---
  * Generalized advantage estimation over a rollout resident in HBM: rewards,

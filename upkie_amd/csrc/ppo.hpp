@@ -30,6 +30,15 @@
 // Launch C, Adam: element-wise over the trainable words (log_std_off on; the fixed obs_mean / obs_std / action bounds
 // before it are never written; padding words have a zero gradient, so m, v and the word stay 0).
 //
+// Data-parallel form (several ranks, each with its own samples; the result is one learner on the union): launch A
+// scales by the global minibatch size (`count`, = mb_size in the fused form); launch B' (local fold) sums the G partials
+// in block order into this rank's slot (train_words fp32 words, then PPO_STATS fp64 loss sums; no entropy term); the
+// caller exchanges the slots so that every rank holds every rank's row, bit for bit; launch B then runs on the slots as
+// its partials (W of them, in rank order) and adds the entropy term once; launch C is unchanged. The advantage
+// statistics split the same way: per-minibatch sums (launch 0a, phase 0), exchange, squared deviations about the
+// global mean (launch 0a, phase 1), exchange, (mean, std + 1e-8) over the global count (launch 0b). With one rank every
+// output is the same bits as the fused form's.
+//
 // Every launch argument is constant for a given (epoch, minibatch) position: counters, t, lr and the permutation live
 // in device memory, so the whole sequence can be captured in a hipGraph and replayed.
 #pragma once
@@ -69,6 +78,8 @@ struct PpoDev {
   PpoStage stage[2];  // actor, critic
   int train_off, train_words;
   int mb_start, mb_size, nw, tile_floats, grid, fold_blocks;
+  int count;                      // samples the loss means run over: mb_size, or the global minibatch size (all ranks)
+  int part_stride, stat_stride;   // launch B: floats between two gradient partials, doubles between two loss-sum partials
   int obs_normalized, vf_clip;
   float clip_lo, clip_hi, clip_range, clip_vf, ent_coef, vf_coef, max_grad_norm, beta1, beta2, adam_eps;
   const int32_t* perm;
@@ -87,9 +98,10 @@ struct PpoDev {
   unsigned* ticket;
   float* header;
   float* partials;        // [grid][train_words]
-  double* stat_partials;  // [grid][PPO_STATS]
+  double* stat_partials;  // [grid][stat_stride]
   float* grad;            // [train_words]
   double* sq_partials;    // [fold_blocks]
+  float* slot;            // launch B': this rank's slot (ppo_slot_words floats)
 };
 
 struct PpoPlan {
@@ -144,6 +156,11 @@ inline int64_t ppo_stat_partials_at(const PpoPlan& p, int g) { return PPO_HEADER
 inline int64_t ppo_grad_at(const PpoPlan& p, int g) { return ppo_stat_partials_at(p, g) + 8 * (int64_t)g * PPO_STATS; }
 inline int64_t ppo_sq_at(const PpoPlan& p, int g) { return ppo_grad_at(p, g) + 4 * (int64_t)p.train_words; }
 inline int64_t ppo_workspace_bytes(const PpoPlan& p, int g) { return ppo_sq_at(p, g) + 8 * (int64_t)p.fold_blocks; }
+
+// A rank's slot of the data-parallel form: the gradient (train_words fp32, padded to an even count), then the PPO_STATS
+// fp64 loss sums, in fp32 words (an even count: every slot of a [world][words] array stays 8-byte aligned).
+inline int ppo_slot_stats_at(const PpoPlan& p) { return (p.train_words + 1) & ~1; }
+inline int ppo_slot_words(const PpoPlan& p) { return ppo_slot_stats_at(p) + 2 * PPO_STATS; }
 
 #if defined(__HIPCC__)
 
@@ -281,7 +298,7 @@ __device__ __forceinline__ void ppo_tower(const PpoDev& P, float* stage, int sam
   const PpoStage& S = P.stage[ACTOR ? 0 : 1];
   const float* __restrict__ packed = P.packed;
   float* my = stage + wave * P.tile_floats;
-  const float inv_b = 1.f / (float)P.mb_size;
+  const float inv_b = 1.f / (float)P.count;
   float cur[WT][4] = {};  // dZ of the current layer (accumulator layout)
   float dz_dot = 0.f;     // dZ of a dot head (every lane of the sample)
   {
@@ -484,11 +501,11 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fold_kernel(const PpoDev P) {
     for (; b + 32 <= P.grid; b += 32) {  // (32 loads in flight, added in block order)
       float x[32];
 #pragma unroll
-      for (int k = 0; k < 32; ++k) x[k] = p[(size_t)(b + k) * P.train_words];
+      for (int k = 0; k < 32; ++k) x[k] = p[(size_t)(b + k) * P.part_stride];
 #pragma unroll
       for (int k = 0; k < 32; ++k) s += x[k];
     }
-    for (; b < P.grid; ++b) s += p[(size_t)b * P.train_words];
+    for (; b < P.grid; ++b) s += p[(size_t)b * P.part_stride];
     if (i < P.net.act_dim) s -= P.ent_coef;  // d(ent_coef * entropy_loss) / d log_std_a
     P.grad[i] = s;
     sq = (double)s * (double)s;
@@ -517,8 +534,8 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fold_kernel(const PpoDev P) {
   double sums[PPO_STATS] = {0.0, 0.0, 0.0, 0.0};
   for (int b = 0; b < P.grid; ++b)
 #pragma unroll
-    for (int k = 0; k < PPO_STATS; ++k) sums[k] += P.stat_partials[b * PPO_STATS + k];
-  const double n = (double)P.mb_size;
+    for (int k = 0; k < PPO_STATS; ++k) sums[k] += P.stat_partials[(size_t)b * P.stat_stride + k];
+  const double n = (double)P.count;
   double entropy = 0.0;
   for (int a = 0; a < P.net.act_dim; ++a) entropy += 0.5 + 0.91893853320467274 + (double)P.packed[P.net.log_std_off + a];
   const double pg = -sums[0] / n, vl = sums[1] / n, ent_loss = -entropy;
@@ -536,6 +553,35 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fold_kernel(const PpoDev P) {
   P.header[6] = (float)sqrt(1.0 - pow((double)P.beta2, t));
 }
 
+// Launch B' (data-parallel form): word i of this rank's slot = the sum of word i of the G partials in block order, as
+// launch B sums them but without the entropy term; block 0 also sums the loss-sum partials in block order and zeroes the
+// padding word. No ticket: launch B runs on the exchanged slots.
+__global__ __launch_bounds__(PPO_THREADS) void ppo_local_fold_kernel(const PpoDev P) {
+  const int tid = threadIdx.x, i = blockIdx.x * PPO_THREADS + tid;
+  if (i < P.train_words) {
+    float s = 0.f;
+    const float* p = P.partials + i;
+    int b = 0;
+    for (; b + 32 <= P.grid; b += 32) {
+      float x[32];
+#pragma unroll
+      for (int k = 0; k < 32; ++k) x[k] = p[(size_t)(b + k) * P.part_stride];
+#pragma unroll
+      for (int k = 0; k < 32; ++k) s += x[k];
+    }
+    for (; b < P.grid; ++b) s += p[(size_t)b * P.part_stride];
+    P.slot[i] = s;
+  }
+  if (blockIdx.x != 0) return;
+  const int at = (P.train_words + 1) & ~1;
+  if (tid < PPO_STATS) {
+    double s = 0.0;
+    for (int b = 0; b < P.grid; ++b) s += P.stat_partials[(size_t)b * P.stat_stride + tid];
+    ((double*)(P.slot + at))[tid] = s;
+  }
+  if (tid == PPO_STATS && at != P.train_words) P.slot[P.train_words] = 0.f;
+}
+
 // Launch C: clip + Adam on the trainable words, in place.
 __global__ __launch_bounds__(PPO_THREADS) void ppo_adam_kernel(const PpoDev P) {
   const int i = blockIdx.x * PPO_THREADS + threadIdx.x;
@@ -550,53 +596,86 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_adam_kernel(const PpoDev P) {
   P.packed[w] -= step * (m / (sqrtf(v) / bc2 + P.adam_eps));
 }
 
-// Launch 0: (mean, std + 1e-8) of the advantages of every minibatch of an epoch, fp64, two passes in a fixed order (each
-// thread 8 gathers in flight at a time, then a fixed LDS tree).
-__global__ __launch_bounds__(PPO_ADV_THREADS) void ppo_adv_stats_kernel(int total, int batch, const int32_t* __restrict__ perm,
-                                                                       const float* __restrict__ adv, int normalize, double* __restrict__ out) {
-  __shared__ double lds[PPO_ADV_THREADS];
-  const int tid = threadIdx.x, start = blockIdx.x * batch;
-  const int n = total - start < batch ? total - start : batch;
-  auto tree = [&](double x) {
-    lds[tid] = x;
-    for (int h = PPO_ADV_THREADS / 2; h > 0; h >>= 1) {
-      __syncthreads();
-      if (tid < h) lds[tid] += lds[tid + h];
-    }
-    __syncthreads();
-    const double s = lds[0];
-    __syncthreads();
-    return s;
-  };
-  if (!normalize || n < 2) {
-    if (tid == 0) out[2 * blockIdx.x] = 0.0, out[2 * blockIdx.x + 1] = 1.0;
-    return;
-  }
+// One pass of launch 0 over minibatch `start`'s n advantages: the sum of x (or of (x - mean)^2 when `square`), each
+// thread 8 gathers in flight at a time, then a fixed LDS tree. Every thread of the block calls it and gets the sum.
+__device__ __forceinline__ double ppo_adv_pass(double* lds, int n, int start, const int32_t* __restrict__ perm, const float* __restrict__ adv,
+                                               bool square, double mean) {
+  const int tid = threadIdx.x;
   double s = 0.0;
   for (int64_t i0 = tid; i0 < n; i0 += 8 * PPO_ADV_THREADS) {  // (64-bit: no overflow near INT_MAX)
     double x[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int64_t i = i0 + k * PPO_ADV_THREADS;
-      x[k] = i < n ? (double)adv[perm[start + i]] : 0.0;
+      x[k] = i < n ? (double)adv[perm[start + i]] - (square ? mean : 0.0) : 0.0;
     }
 #pragma unroll
-    for (int k = 0; k < 8; ++k) s += x[k];
+    for (int k = 0; k < 8; ++k) s += square ? x[k] * x[k] : x[k];
   }
-  const double mean = tree(s) / n;
-  s = 0.0;
-  for (int64_t i0 = tid; i0 < n; i0 += 8 * PPO_ADV_THREADS) {
-    double x[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int64_t i = i0 + k * PPO_ADV_THREADS;
-      x[k] = i < n ? (double)adv[perm[start + i]] - mean : 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += x[k] * x[k];
+  lds[tid] = s;
+  for (int h = PPO_ADV_THREADS / 2; h > 0; h >>= 1) {
+    __syncthreads();
+    if (tid < h) lds[tid] += lds[tid + h];
   }
-  const double var = tree(s) / (n - 1);
-  if (tid == 0) out[2 * blockIdx.x] = mean, out[2 * blockIdx.x + 1] = sqrt(var) + 1e-8;
+  __syncthreads();
+  const double r = lds[0];
+  __syncthreads();
+  return r;
+}
+
+// Launch 0: (mean, std + 1e-8) of the advantages of every minibatch of an epoch, fp64, two passes in a fixed order.
+__global__ __launch_bounds__(PPO_ADV_THREADS) void ppo_adv_stats_kernel(int total, int batch, const int32_t* __restrict__ perm,
+                                                                       const float* __restrict__ adv, int normalize, double* __restrict__ out) {
+  __shared__ double lds[PPO_ADV_THREADS];
+  const int start = blockIdx.x * batch;
+  const int n = total - start < batch ? total - start : batch;
+  if (!normalize || n < 2) {
+    if (threadIdx.x == 0) out[2 * blockIdx.x] = 0.0, out[2 * blockIdx.x + 1] = 1.0;
+    return;
+  }
+  const double mean = ppo_adv_pass(lds, n, start, perm, adv, false, 0.0) / n;
+  const double var = ppo_adv_pass(lds, n, start, perm, adv, true, mean) / (n - 1);
+  if (threadIdx.x == 0) out[2 * blockIdx.x] = mean, out[2 * blockIdx.x + 1] = sqrt(var) + 1e-8;
+}
+
+// Launch 0a (data-parallel form), block j = minibatch j of M: phase 0 writes its local sum to mine[j]; phase 1 (after
+// the exchange) forms the global mean from slots[r][j], r in rank order, over world * n samples (every rank holds n),
+// and writes the local sum of squared deviations about it to mine[M + j]. mine / slots[r]: 2 M doubles.
+__global__ __launch_bounds__(PPO_ADV_THREADS) void ppo_adv_partials_kernel(int total, int batch, const int32_t* __restrict__ perm,
+                                                                          const float* __restrict__ adv, int phase, const double* __restrict__ slots,
+                                                                          int world, double* __restrict__ mine) {
+  __shared__ double lds[PPO_ADV_THREADS];
+  const int j = blockIdx.x, M = gridDim.x, start = j * batch;
+  const int n = total - start < batch ? total - start : batch;
+  if (phase == 0) {
+    const double s = ppo_adv_pass(lds, n, start, perm, adv, false, 0.0);
+    if (threadIdx.x == 0) mine[j] = s;
+    return;
+  }
+  double g = slots[j];
+  for (int r = 1; r < world; ++r) g += slots[(size_t)r * 2 * M + j];
+  const double mean = g / ((double)world * n);
+  const double q = ppo_adv_pass(lds, n, start, perm, adv, true, mean);
+  if (threadIdx.x == 0) mine[M + j] = q;
+}
+
+// Launch 0b (data-parallel form): out[j] = (mean, std + 1e-8) over the world * n samples of minibatch j from the
+// exchanged slots (sums in rank order; std unbiased), or (0, 1) when normalize is 0 or there is one sample.
+__global__ __launch_bounds__(PPO_THREADS) void ppo_adv_finish_kernel(int total, int batch, int minibatches, int normalize, const double* __restrict__ slots,
+                                                                    int world, double* __restrict__ out) {
+  const int j = blockIdx.x * PPO_THREADS + threadIdx.x, M = minibatches;
+  if (j >= M) return;
+  const int start = j * batch;
+  const int n = total - start < batch ? total - start : batch;
+  const double cnt = (double)world * n;
+  if (!normalize || cnt < 2.0) {
+    out[2 * j] = 0.0, out[2 * j + 1] = 1.0;
+    return;
+  }
+  double g = slots[j], q = slots[M + j];
+  for (int r = 1; r < world; ++r) g += slots[(size_t)r * 2 * M + j], q += slots[(size_t)r * 2 * M + M + j];
+  const double mean = g / cnt;
+  out[2 * j] = mean, out[2 * j + 1] = sqrt(q / (cnt - 1.0)) + 1e-8;
 }
 
 #endif  // __HIPCC__

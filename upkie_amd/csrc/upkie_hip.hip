@@ -1305,10 +1305,12 @@ extern "C" int64_t upkie_vecnorm_workspace_bytes(int32_t num_envs, int32_t obs_d
   return upkie::VECNORM_PARTIALS_OFFSET + (int64_t)blocks * 2 * (obs_dim + 1) * (int64_t)sizeof(double);
 }
 
-extern "C" int upkie_vecnorm_step(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
-                                  const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace, int32_t flags,
-                                  double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32, float* std_f32,
-                                  float* packed_stats, float* norm_obs, float* norm_reward, uint8_t* episode_starts, void* stream) {
+// The launch arguments of upkie_vecnorm_step (and of its data-parallel halves) after the argument checks; returns
+// UPKIE_OK or the error status. *moments / *apply: whether launch A / launch B runs.
+static int vecnorm_setup(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
+                         const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace, int32_t flags,
+                         double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32, float* std_f32, float* packed_stats,
+                         float* norm_obs, float* norm_reward, uint8_t* episode_starts, upkie::VecNormDev* out, bool* moments_out, bool* apply_out) {
   if (!vecnorm_shape_ok(num_envs, obs_dim)) return UPKIE_ERR_INVALID_ARGUMENT;
   if (flags & ~(UPKIE_VECNORM_TRAINING | UPKIE_VECNORM_NORM_OBS | UPKIE_VECNORM_NORM_REWARD | UPKIE_VECNORM_RESET)) {
     g_create_error = "unknown vecnorm flags";
@@ -1359,19 +1361,96 @@ extern "C" int upkie_vecnorm_step(int32_t num_envs, int32_t obs_dim, const float
   P.partials = workspace ? (double*)((char*)workspace + upkie::VECNORM_PARTIALS_OFFSET) : nullptr;
   P.mean_f32 = mean_f32, P.std_f32 = std_f32, P.packed = packed_stats;
   P.norm_obs_out = norm_obs, P.reward_out = norm_reward, P.starts_out = episode_starts;
-  const hipStream_t s = (hipStream_t)stream;
-  if (moments) hipLaunchKernelGGL(upkie::vecnorm_moments_kernel, dim3((unsigned)P.blocks), dim3(upkie::VECNORM_THREADS), 0, s, P);
-  if (apply) {
-    const int64_t work = norm_obs ? (int64_t)num_envs * obs_dim : num_envs;
-    const int64_t grid = std::min<int64_t>((work + upkie::VECNORM_THREADS - 1) / upkie::VECNORM_THREADS, 1024);
-    hipLaunchKernelGGL(upkie::vecnorm_apply_kernel, dim3((unsigned)grid), dim3(upkie::VECNORM_THREADS), 0, s, P);
-  }
+  *out = P;
+  *moments_out = moments;
+  *apply_out = apply;
+  return UPKIE_OK;
+}
+
+static void vecnorm_launch_apply(const upkie::VecNormDev& P, hipStream_t s) {
+  const int64_t work = P.norm_obs_out ? (int64_t)P.num_envs * P.obs_dim : P.num_envs;
+  const int64_t grid = std::min<int64_t>((work + upkie::VECNORM_THREADS - 1) / upkie::VECNORM_THREADS, 1024);
+  hipLaunchKernelGGL(upkie::vecnorm_apply_kernel, dim3((unsigned)grid), dim3(upkie::VECNORM_THREADS), 0, s, P);
+}
+
+static int launch_status() {
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) {
     g_create_error = hipGetErrorString(err);
     return UPKIE_ERR_HIP;
   }
   return UPKIE_OK;
+}
+
+extern "C" int upkie_vecnorm_step(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
+                                  const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace, int32_t flags,
+                                  double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32, float* std_f32,
+                                  float* packed_stats, float* norm_obs, float* norm_reward, uint8_t* episode_starts, void* stream) {
+  upkie::VecNormDev P;
+  bool moments, apply;
+  const int status = vecnorm_setup(num_envs, obs_dim, obs, reward, terminated, truncated, obs_stats, ret_stats, returns, workspace, flags, gamma,
+                                   epsilon, clip_obs, clip_reward, mean_f32, std_f32, packed_stats, norm_obs, norm_reward, episode_starts, &P,
+                                   &moments, &apply);
+  if (status != UPKIE_OK) return status;
+  const hipStream_t s = (hipStream_t)stream;
+  if (moments) hipLaunchKernelGGL(upkie::vecnorm_moments_kernel, dim3((unsigned)P.blocks), dim3(upkie::VECNORM_THREADS), 0, s, P);
+  if (apply) vecnorm_launch_apply(P, s);
+  return launch_status();
+}
+
+// Whether a step with these flags moves a statistic (launch A runs): the steps of the data-parallel form.
+static bool vecnorm_moves(int32_t flags) {
+  return (flags & UPKIE_VECNORM_TRAINING) && ((flags & UPKIE_VECNORM_NORM_OBS) || !(flags & UPKIE_VECNORM_RESET));
+}
+
+extern "C" int64_t upkie_vecnorm_slot_bytes(int32_t obs_dim) {
+  if (obs_dim < 1 || obs_dim > 256) {
+    g_create_error = "obs_dim must be in 1-256";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  return 8 * (int64_t)upkie::vecnorm_slot_doubles(obs_dim);
+}
+
+extern "C" int upkie_vecnorm_moments_local(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
+                                           const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace,
+                                           int32_t flags, double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32,
+                                           float* std_f32, float* packed_stats, float* norm_obs, float* norm_reward, uint8_t* episode_starts,
+                                           double* slot, void* stream) {
+  if (!vecnorm_moves(flags) || !slot) {
+    g_create_error = "upkie_vecnorm_moments_local needs a step that moves a statistic (TRAINING, and NORM_OBS or not RESET) and a slot";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  upkie::VecNormDev P;
+  bool moments, apply;
+  const int status = vecnorm_setup(num_envs, obs_dim, obs, reward, terminated, truncated, obs_stats, ret_stats, returns, workspace, flags, gamma,
+                                   epsilon, clip_obs, clip_reward, mean_f32, std_f32, packed_stats, norm_obs, norm_reward, episode_starts, &P,
+                                   &moments, &apply);
+  if (status != UPKIE_OK) return status;
+  P.slot = slot;
+  hipLaunchKernelGGL(upkie::vecnorm_moments_kernel, dim3((unsigned)P.blocks), dim3(upkie::VECNORM_THREADS), 0, (hipStream_t)stream, P);
+  return launch_status();
+}
+
+extern "C" int upkie_vecnorm_merge(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
+                                   const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace, int32_t flags,
+                                   double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32, float* std_f32,
+                                   float* packed_stats, float* norm_obs, float* norm_reward, uint8_t* episode_starts, const double* slots,
+                                   int32_t world, void* stream) {
+  if (!vecnorm_moves(flags) || !slots || world < 1) {
+    g_create_error = "upkie_vecnorm_merge needs a step that moves a statistic, the exchanged slots and world >= 1";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  upkie::VecNormDev P;
+  bool moments, apply;
+  const int status = vecnorm_setup(num_envs, obs_dim, obs, reward, terminated, truncated, obs_stats, ret_stats, returns, workspace, flags, gamma,
+                                   epsilon, clip_obs, clip_reward, mean_f32, std_f32, packed_stats, norm_obs, norm_reward, episode_starts, &P,
+                                   &moments, &apply);
+  if (status != UPKIE_OK) return status;
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(upkie::vecnorm_merge_kernel, dim3(1), dim3(upkie::VECNORM_THREADS), 0, s, P, slots, (int)world,
+                     upkie::vecnorm_slot_doubles(obs_dim));
+  if (apply) vecnorm_launch_apply(P, s);
+  return launch_status();
 }
 
 // ============================================================ PPO update (csrc/ppo.hpp)
@@ -1444,34 +1523,65 @@ static hipError_t launch_ppo_grad_w(int activation, const upkie::PpoDev& P, int 
   return activation == UPKIE_MLP_TANH ? launch_ppo_grad<W, UPKIE_MLP_TANH>(P, lds_bytes, s) : launch_ppo_grad<W, UPKIE_MLP_RELU>(P, lds_bytes, s);
 }
 
-extern "C" int upkie_ppo_minibatch_update(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
-                                          int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm, const float* obs,
-                                          const float* actions, const float* old_values, const float* old_log_prob, const float* advantages,
-                                          const float* returns, const double* adv_stats, float* packed, float* adam_m, float* adam_v,
-                                          double* adam_scalars, void* workspace, float* stats, void* stream) {
-  upkie::PpoPlan plan;
-  if (!ppo_shape_ok(shape, &plan)) return UPKIE_ERR_INVALID_ARGUMENT;
+static bool ppo_config_ok(const UpkiePpoConfig* config) {
   if (!config) {
     g_create_error = "null config";
-    return UPKIE_ERR_INVALID_ARGUMENT;
+    return false;
   }
   const UpkiePpoConfig& c = *config;
   if (!(c.clip_range > 0.f) || !(c.max_grad_norm > 0.f) || !(c.adam_eps > 0.f) || !(c.adam_beta1 >= 0.f && c.adam_beta1 < 1.f) ||
       !(c.adam_beta2 >= 0.f && c.adam_beta2 < 1.f) || !std::isfinite(c.ent_coef) || !std::isfinite(c.vf_coef) || !(c.clip_range_vf == c.clip_range_vf)) {
     g_create_error = "config: clip_range, max_grad_norm and adam_eps must be positive, adam betas in [0, 1), coefficients finite";
-    return UPKIE_ERR_INVALID_ARGUMENT;
+    return false;
   }
+  return true;
+}
+
+// The fields of every launch of a minibatch but the gradient launch's inputs, and the workspace layout for minibatches
+// of at most max_minibatch samples.
+static void ppo_fill(upkie::PpoDev& P, const UpkieMlpShape& shape, const upkie::PpoPlan& plan, const UpkiePpoConfig& c, int max_minibatch,
+                     void* workspace) {
+  upkie::mlp_layout(shape, &P.net);
+  P.stage[0] = plan.stage[0], P.stage[1] = plan.stage[1];
+  P.train_off = plan.train_off, P.train_words = plan.train_words;
+  P.nw = plan.nw, P.tile_floats = plan.tile_floats;
+  const int ws_grid = upkie::ppo_grid(plan, max_minibatch);  // (the workspace's layout)
+  P.fold_blocks = plan.fold_blocks;
+  P.part_stride = plan.train_words, P.stat_stride = upkie::PPO_STATS;
+  P.obs_normalized = c.obs_normalized ? 1 : 0;
+  P.vf_clip = c.clip_range_vf > 0.f;
+  P.clip_range = c.clip_range;
+  P.clip_lo = (float)(1.0 - (double)c.clip_range), P.clip_hi = (float)(1.0 + (double)c.clip_range);
+  P.clip_vf = c.clip_range_vf, P.ent_coef = c.ent_coef, P.vf_coef = c.vf_coef, P.max_grad_norm = c.max_grad_norm;
+  P.beta1 = c.adam_beta1, P.beta2 = c.adam_beta2, P.adam_eps = c.adam_eps;
+  char* ws = (char*)workspace;
+  P.ticket = (unsigned*)ws;
+  P.header = (float*)ws;
+  P.partials = (float*)(ws + upkie::PPO_HEADER_BYTES);
+  P.stat_partials = (double*)(ws + upkie::ppo_stat_partials_at(plan, ws_grid));
+  P.grad = (float*)(ws + upkie::ppo_grad_at(plan, ws_grid));
+  P.sq_partials = (double*)(ws + upkie::ppo_sq_at(plan, ws_grid));
+}
+
+// Checks and fields of the gradient launch (launch A) of minibatch [minibatch_start, + minibatch_size).
+static int ppo_gradient_setup(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
+                              int32_t minibatch_size, int32_t count, int32_t max_minibatch, const int32_t* perm, const float* obs,
+                              const float* actions, const float* old_values, const float* old_log_prob, const float* advantages,
+                              const float* returns, const double* adv_stats, float* packed, void* workspace, upkie::PpoDev* out,
+                              upkie::PpoPlan* plan) {
+  if (!ppo_shape_ok(shape, plan)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!ppo_config_ok(config)) return UPKIE_ERR_INVALID_ARGUMENT;
   if (total < 1 || minibatch_size < 1 || max_minibatch < 1 || minibatch_start < 0 || minibatch_size > max_minibatch ||
-      (int64_t)minibatch_start + minibatch_size > total) {
-    g_create_error = "minibatch out of range: 0 <= minibatch_start, 1 <= minibatch_size <= max_minibatch, start + size <= total";
+      (int64_t)minibatch_start + minibatch_size > total || count < minibatch_size) {
+    g_create_error =
+        "minibatch out of range: 0 <= minibatch_start, 1 <= minibatch_size <= max_minibatch, start + size <= total, global size >= size";
     return UPKIE_ERR_INVALID_ARGUMENT;
   }
   if ((int64_t)total * (shape->obs_dim > shape->act_dim ? shape->obs_dim : shape->act_dim) > INT_MAX) {
     g_create_error = "total * obs_dim (or act_dim) must stay below 2^31";
     return UPKIE_ERR_INVALID_ARGUMENT;
   }
-  if (!perm || !obs || !actions || !old_values || !old_log_prob || !advantages || !returns || !adv_stats || !packed || !adam_m || !adam_v ||
-      !adam_scalars || !workspace || !stats) {
+  if (!perm || !obs || !actions || !old_values || !old_log_prob || !advantages || !returns || !adv_stats || !packed || !workspace) {
     g_create_error = "null argument";
     return UPKIE_ERR_INVALID_ARGUMENT;
   }
@@ -1480,49 +1590,170 @@ extern "C" int upkie_ppo_minibatch_update(const UpkieMlpShape* shape, const Upki
     return UPKIE_ERR_NO_DEVICE;
   }
   upkie::PpoDev P{};
-  upkie::mlp_layout(*shape, &P.net);
-  P.stage[0] = plan.stage[0], P.stage[1] = plan.stage[1];
-  P.train_off = plan.train_off, P.train_words = plan.train_words;
-  P.mb_start = minibatch_start, P.mb_size = minibatch_size;
-  P.nw = plan.nw, P.tile_floats = plan.tile_floats;
-  P.grid = upkie::ppo_grid(plan, minibatch_size);
-  const int ws_grid = upkie::ppo_grid(plan, max_minibatch);  // (the workspace's layout)
-  P.fold_blocks = plan.fold_blocks;
-  P.obs_normalized = c.obs_normalized ? 1 : 0;
-  P.vf_clip = c.clip_range_vf > 0.f;
-  P.clip_range = c.clip_range;
-  P.clip_lo = (float)(1.0 - (double)c.clip_range), P.clip_hi = (float)(1.0 + (double)c.clip_range);
-  P.clip_vf = c.clip_range_vf, P.ent_coef = c.ent_coef, P.vf_coef = c.vf_coef, P.max_grad_norm = c.max_grad_norm;
-  P.beta1 = c.adam_beta1, P.beta2 = c.adam_beta2, P.adam_eps = c.adam_eps;
+  ppo_fill(P, *shape, *plan, *config, max_minibatch, workspace);
+  P.mb_start = minibatch_start, P.mb_size = minibatch_size, P.count = count;
+  P.grid = upkie::ppo_grid(*plan, minibatch_size);
   P.perm = perm, P.obs = obs, P.actions = actions, P.old_values = old_values, P.old_log_prob = old_log_prob;
   P.advantages = advantages, P.returns = returns, P.adv_stats = adv_stats;
-  P.packed = packed, P.m = adam_m, P.v = adam_v, P.scalars = adam_scalars, P.stats = stats;
-  char* ws = (char*)workspace;
-  P.ticket = (unsigned*)ws;
-  P.header = (float*)ws;
-  P.partials = (float*)(ws + upkie::PPO_HEADER_BYTES);
-  P.stat_partials = (double*)(ws + upkie::ppo_stat_partials_at(plan, ws_grid));
-  P.grad = (float*)(ws + upkie::ppo_grad_at(plan, ws_grid));
-  P.sq_partials = (double*)(ws + upkie::ppo_sq_at(plan, ws_grid));
-  const hipStream_t s = (hipStream_t)stream;
-  hipError_t err = hipSuccess;
-  switch (upkie::mlp_width_class(*shape)) {
-    case 16: err = launch_ppo_grad_w<16>(shape->activation, P, plan.lds_bytes, s); break;
-    case 32: err = launch_ppo_grad_w<32>(shape->activation, P, plan.lds_bytes, s); break;
-    case 64: err = launch_ppo_grad_w<64>(shape->activation, P, plan.lds_bytes, s); break;
-    case 128: err = launch_ppo_grad_w<128>(shape->activation, P, plan.lds_bytes, s); break;
-    default: err = launch_ppo_grad_w<256>(shape->activation, P, plan.lds_bytes, s); break;
+  P.packed = packed;
+  *out = P;
+  return UPKIE_OK;
+}
+
+static hipError_t ppo_launch_gradient(const UpkieMlpShape& shape, const upkie::PpoDev& P, const upkie::PpoPlan& plan, hipStream_t s) {
+  switch (upkie::mlp_width_class(shape)) {
+    case 16: return launch_ppo_grad_w<16>(shape.activation, P, plan.lds_bytes, s);
+    case 32: return launch_ppo_grad_w<32>(shape.activation, P, plan.lds_bytes, s);
+    case 64: return launch_ppo_grad_w<64>(shape.activation, P, plan.lds_bytes, s);
+    case 128: return launch_ppo_grad_w<128>(shape.activation, P, plan.lds_bytes, s);
+    default: return launch_ppo_grad_w<256>(shape.activation, P, plan.lds_bytes, s);
   }
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(upkie::ppo_fold_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
-    hipLaunchKernelGGL(upkie::ppo_adam_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
-    err = hipGetLastError();
-  }
+}
+
+static int hip_status(hipError_t err) {
   if (err != hipSuccess) {
     g_create_error = hipGetErrorString(err);
     return UPKIE_ERR_HIP;
   }
   return UPKIE_OK;
+}
+
+extern "C" int upkie_ppo_minibatch_update(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
+                                          int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm, const float* obs,
+                                          const float* actions, const float* old_values, const float* old_log_prob, const float* advantages,
+                                          const float* returns, const double* adv_stats, float* packed, float* adam_m, float* adam_v,
+                                          double* adam_scalars, void* workspace, float* stats, void* stream) {
+  upkie::PpoPlan plan;
+  upkie::PpoDev P;
+  if (!adam_m || !adam_v || !adam_scalars || !stats) {
+    g_create_error = "null argument";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  const int status = ppo_gradient_setup(shape, config, total, minibatch_start, minibatch_size, minibatch_size, max_minibatch, perm, obs, actions,
+                                        old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, &P, &plan);
+  if (status != UPKIE_OK) return status;
+  P.m = adam_m, P.v = adam_v, P.scalars = adam_scalars, P.stats = stats;
+  const hipStream_t s = (hipStream_t)stream;
+  hipError_t err = ppo_launch_gradient(*shape, P, plan, s);
+  if (err == hipSuccess) {
+    hipLaunchKernelGGL(upkie::ppo_fold_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
+    hipLaunchKernelGGL(upkie::ppo_adam_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
+    err = hipGetLastError();
+  }
+  return hip_status(err);
+}
+
+// ---- data-parallel form (several ranks; include/upkie_hip.h)
+extern "C" int64_t upkie_ppo_slot_bytes(const UpkieMlpShape* shape) {
+  upkie::PpoPlan plan;
+  if (!ppo_shape_ok(shape, &plan)) return UPKIE_ERR_INVALID_ARGUMENT;
+  return 4 * (int64_t)upkie::ppo_slot_words(plan);
+}
+
+extern "C" int upkie_ppo_minibatch_gradient(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
+                                            int32_t minibatch_size, int32_t global_minibatch_size, int32_t max_minibatch, const int32_t* perm,
+                                            const float* obs, const float* actions, const float* old_values, const float* old_log_prob,
+                                            const float* advantages, const float* returns, const double* adv_stats, float* packed, void* workspace,
+                                            void* slot, void* stream) {
+  upkie::PpoPlan plan;
+  upkie::PpoDev P;
+  if (!slot) {
+    g_create_error = "null slot";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  const int status = ppo_gradient_setup(shape, config, total, minibatch_start, minibatch_size, global_minibatch_size, max_minibatch, perm, obs,
+                                        actions, old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, &P, &plan);
+  if (status != UPKIE_OK) return status;
+  P.slot = (float*)slot;
+  const hipStream_t s = (hipStream_t)stream;
+  hipError_t err = ppo_launch_gradient(*shape, P, plan, s);
+  if (err == hipSuccess) {
+    hipLaunchKernelGGL(upkie::ppo_local_fold_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
+    err = hipGetLastError();
+  }
+  return hip_status(err);
+}
+
+extern "C" int upkie_ppo_minibatch_apply(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t global_minibatch_size,
+                                         int32_t max_minibatch, const void* slots, int32_t world, float* packed, float* adam_m, float* adam_v,
+                                         double* adam_scalars, void* workspace, float* stats, void* stream) {
+  upkie::PpoPlan plan;
+  if (!ppo_shape_ok(shape, &plan)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!ppo_config_ok(config)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (global_minibatch_size < 1 || max_minibatch < 1 || world < 1) {
+    g_create_error = "global_minibatch_size, max_minibatch and world must be positive";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (!slots || !packed || !adam_m || !adam_v || !adam_scalars || !workspace || !stats) {
+    g_create_error = "null argument";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (upkie_hip_device_count() <= 0) {
+    g_create_error = "no HIP device visible";
+    return UPKIE_ERR_NO_DEVICE;
+  }
+  upkie::PpoDev P{};
+  ppo_fill(P, *shape, plan, *config, max_minibatch, workspace);
+  P.count = global_minibatch_size;
+  P.grid = world;  // (launch B's partials: the slots, in rank order)
+  const int words = upkie::ppo_slot_words(plan);
+  P.partials = (float*)slots;
+  P.part_stride = words;
+  P.stat_partials = (double*)((float*)slots + upkie::ppo_slot_stats_at(plan));
+  P.stat_stride = words / 2;
+  P.packed = packed, P.m = adam_m, P.v = adam_v, P.scalars = adam_scalars, P.stats = stats;
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(upkie::ppo_fold_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
+  hipLaunchKernelGGL(upkie::ppo_adam_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
+  return hip_status(hipGetLastError());
+}
+
+extern "C" int64_t upkie_ppo_advantage_slot_bytes(int32_t total, int32_t batch_size) {
+  if (total < 1 || batch_size < 1) {
+    g_create_error = "total and batch_size must be positive";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  return 16 * ((total + (int64_t)batch_size - 1) / batch_size);
+}
+
+extern "C" int upkie_ppo_advantage_partials(int32_t total, int32_t batch_size, const int32_t* perm, const float* advantages, int32_t phase,
+                                            const double* slots, int32_t world, double* slot, void* stream) {
+  if (total < 1 || batch_size < 1 || (phase != 0 && phase != 1) || world < 1) {
+    g_create_error = "total, batch_size and world must be positive, phase 0 or 1";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (!perm || !advantages || !slot || (phase == 1 && !slots)) {
+    g_create_error = "null argument";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (upkie_hip_device_count() <= 0) {
+    g_create_error = "no HIP device visible";
+    return UPKIE_ERR_NO_DEVICE;
+  }
+  const unsigned blocks = (unsigned)((total + (int64_t)batch_size - 1) / batch_size);
+  hipLaunchKernelGGL(upkie::ppo_adv_partials_kernel, dim3(blocks), dim3(upkie::PPO_ADV_THREADS), 0, (hipStream_t)stream, total, batch_size, perm,
+                     advantages, phase, slots, world, slot);
+  return hip_status(hipGetLastError());
+}
+
+extern "C" int upkie_ppo_advantage_finish(int32_t total, int32_t batch_size, int32_t normalize, const double* slots, int32_t world,
+                                          double* adv_stats, void* stream) {
+  if (total < 1 || batch_size < 1 || world < 1) {
+    g_create_error = "total, batch_size and world must be positive";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (!slots || !adv_stats) {
+    g_create_error = "null argument";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (upkie_hip_device_count() <= 0) {
+    g_create_error = "no HIP device visible";
+    return UPKIE_ERR_NO_DEVICE;
+  }
+  const int M = (int)((total + (int64_t)batch_size - 1) / batch_size);
+  hipLaunchKernelGGL(upkie::ppo_adv_finish_kernel, dim3((unsigned)((M + upkie::PPO_THREADS - 1) / upkie::PPO_THREADS)), dim3(upkie::PPO_THREADS), 0,
+                     (hipStream_t)stream, total, batch_size, M, normalize ? 1 : 0, slots, world, adv_stats);
+  return hip_status(hipGetLastError());
 }
 
 // ============================================================ rollout consumer

@@ -25,6 +25,13 @@
 // Without them (norm_reward off, no normalised observations wanted) launch A writes the per-env outputs itself and the
 // step is one launch.
 //
+// Data-parallel form (several ranks, each with its own envs; the statistics are those of one normaliser over the union):
+// launch A's last block writes this rank's batch (count, mean, M2) per column to its slot instead of folding it in; the
+// caller exchanges the slots so that every rank holds every rank's row, bit for bit; launch M (merge, one block) merges
+// the slots by Chan's formula in rank order, starting from slot 0 (one slot passes through unchanged), and applies the
+// same RunningMeanStd update, mirrors and packed words as launch A's last block, then adds the global env count. Launch B
+// follows as before. The per-env returns stay local. With one rank every output is the same bits as the fused form's.
+//
 // Grid of launch A: one block per 256 envs, at most 256 blocks, and at most 8192 / (2 (obs_dim + 1)) blocks so that the
 // partials the last block reads stay <= 64 KB (1.4 KB at 4096 envs x 4 columns).
 #pragma once
@@ -52,6 +59,7 @@ struct VecNormDev {
   double* ret_stats;  // mean, var, count
   double* returns;    // [num_envs]
   double* partials;   // [blocks][2 (obs_cols + ret_col)]
+  double* slot;       // data-parallel form: this rank's slot (vecnorm_slot_doubles), or null (fused)
   unsigned* ticket;
   float* mean_f32;
   float* std_f32;
@@ -60,6 +68,9 @@ struct VecNormDev {
   float* reward_out;
   uint8_t* starts_out;
 };
+
+// A rank's slot: n[obs_dim + 1], mean[obs_dim + 1], M2[obs_dim + 1]; column obs_dim is the returns'.
+inline int vecnorm_slot_doubles(int obs_dim) { return 3 * (obs_dim + 1); }
 
 // Grid of launch A for (num_envs, obs_dim) and its envs per block (every block owns at least one env).
 inline int vecnorm_blocks(int num_envs, int obs_dim, int* rows) {
@@ -152,6 +163,29 @@ __device__ __forceinline__ void vecnorm_lane_moments(int first, int end, int ste
   }
 }
 
+// RunningMeanStd.update_from_moments of column `col` (an observation column below obs_cols, else the returns) with the
+// batch (count bn, mean bm, M2 = var * count bm2), in place, with the fp32 mirrors and a policy's packed words. The
+// counts themselves move after every column has read them.
+__device__ __forceinline__ void vecnorm_update_column(const VecNormDev& P, int col, double bn, double bm, double bm2) {
+  const int D = P.obs_dim;
+  const bool is_obs = col < P.obs_cols;
+  double* mean_p = is_obs ? P.obs_stats + col : P.ret_stats;
+  double* var_p = is_obs ? P.obs_stats + D + col : P.ret_stats + 1;
+  const double count = is_obs ? P.obs_stats[2 * D] : P.ret_stats[2];
+  const double old_mean = *mean_p, old_var = *var_p;
+  const double delta = bm - old_mean, tot = count + bn;
+  const double new_mean = old_mean + delta * bn / tot;
+  const double new_var = (old_var * count + bm2 + delta * delta * count * bn / tot) / tot;
+  *mean_p = new_mean;
+  *var_p = new_var;
+  if (is_obs) {
+    const float m32 = (float)new_mean, s32 = (float)sqrt(new_var + P.eps);
+    P.mean_f32[col] = m32;
+    P.std_f32[col] = s32;
+    if (P.packed) P.packed[col] = m32, P.packed[P.packed_dp + col] = s32;
+  }
+}
+
 __global__ __launch_bounds__(VECNORM_THREADS) void vecnorm_moments_kernel(const VecNormDev P) {
   __shared__ double lds[3 * VECNORM_THREADS + 1];  // n, mean, M2 per thread; [3 * 256]: "last block" flag
   const int tid = threadIdx.x;
@@ -223,31 +257,47 @@ __global__ __launch_bounds__(VECNORM_THREADS) void vecnorm_moments_kernel(const 
     }
     vecnorm_lds_tree(lds, g, slots, tid % g, p, active);
     if (tid < g) {
-      // RunningMeanStd.update_from_moments with batch (mean bm, M2 = var * count bm2, count bn)
       const int col = c0 + tid;
-      const bool is_obs = col < P.obs_cols;
-      double* mean_p = is_obs ? P.obs_stats + col : P.ret_stats;
-      double* var_p = is_obs ? P.obs_stats + D + col : P.ret_stats + 1;
-      const double count = is_obs ? P.obs_stats[2 * D] : P.ret_stats[2];
       const double bn = lds[tid], bm = lds[VECNORM_THREADS + tid], bm2 = lds[2 * VECNORM_THREADS + tid];
-      const double old_mean = *mean_p, old_var = *var_p;
-      const double delta = bm - old_mean, tot = count + bn;
-      const double new_mean = old_mean + delta * bn / tot;
-      const double new_var = (old_var * count + bm2 + delta * delta * count * bn / tot) / tot;
-      *mean_p = new_mean;
-      *var_p = new_var;
-      if (is_obs) {
-        const float m32 = (float)new_mean, s32 = (float)sqrt(new_var + P.eps);
-        P.mean_f32[col] = m32;
-        P.std_f32[col] = s32;
-        if (P.packed) P.packed[col] = m32, P.packed[P.packed_dp + col] = s32;
+      if (P.slot) {
+        const int sc = col < P.obs_cols ? col : D;
+        P.slot[sc] = bn, P.slot[D + 1 + sc] = bm, P.slot[2 * (D + 1) + sc] = bm2;
+      } else {
+        vecnorm_update_column(P, col, bn, bm, bm2);
       }
     }
     __syncthreads();
   }
+  if (P.slot) return;
   if (tid == 0) {  // (after every column read the old counts)
     if (P.obs_cols) P.obs_stats[2 * D] += (double)P.num_envs;
     if (P.ret_col) P.ret_stats[2] += (double)P.num_envs;
+  }
+}
+
+// Launch M (data-parallel form, one block): Chan's merge of the `world` exchanged slots (stride doubles apart) in rank
+// order from slot 0, per column launch A reduces, then the update of launch A's last block; the counts grow by the
+// merged env count.
+__global__ __launch_bounds__(VECNORM_THREADS) void vecnorm_merge_kernel(const VecNormDev P, const double* __restrict__ slots, int world, int stride) {
+  const int D = P.obs_dim, tid = threadIdx.x;
+  const int cols = P.obs_cols + P.ret_col;
+  auto merged = [&](int sc, double& n, double& mean, double& m2) {
+    n = slots[sc], mean = slots[D + 1 + sc], m2 = slots[2 * (D + 1) + sc];
+    for (int r = 1; r < world; ++r) {
+      const double* q = slots + (size_t)r * stride;
+      chan_merge(n, mean, m2, q[sc], q[D + 1 + sc], q[2 * (D + 1) + sc]);
+    }
+  };
+  for (int col = tid; col < cols; col += VECNORM_THREADS) {
+    double n, mean, m2;
+    merged(col < P.obs_cols ? col : D, n, mean, m2);
+    vecnorm_update_column(P, col, n, mean, m2);
+  }
+  __syncthreads();
+  if (tid == 0) {  // (after every column read the old counts)
+    double n, mean, m2;
+    if (P.obs_cols) merged(0, n, mean, m2), P.obs_stats[2 * D] += n;
+    if (P.ret_col) merged(D, n, mean, m2), P.ret_stats[2] += n;
   }
 }
 

@@ -653,3 +653,70 @@ class ShardedVecEnv:
             self.sim.close()
         if destroy_group and self._collectives and dist.is_initialized():
             dist.destroy_process_group()
+
+
+class SlotExchange:
+    """Every rank's slot, visible on every rank, bit for bit: the exchange behind the data-parallel learner
+    (`upkie_amd.ppo.PpoTrainer`) and normaliser (`upkie_amd.normalize.RunningNormalizer`) with a process group.
+
+    Each rank's kernels write its contribution into `mine` (``words`` 32-bit words); `exchange` fills ``slots
+    [world, words]`` with every rank's `mine`, row r = rank r's, unchanged. The kernels then fold the rows in rank order,
+    so the result does not depend on the collective's algorithm and is the same bits on every rank (no sum all-reduce).
+    RCCL ("nccl"): one ``all_gather_into_tensor`` on the device, stream-ordered, no host synchronisation. gloo: staged
+    through host tensors and ``all_gather`` (gloo has no device all-gather; it lets two ranks share one GPU in tests).
+    Without a group: world 1, `mine` is row 0 of `slots` and `exchange` does nothing."""
+
+    def __init__(self, words: int, device, group=None):
+        self.group = group
+        self.words = int(words)
+        self.device = torch.device(device)
+        self.world = dist.get_world_size(group) if group is not None else 1
+        self.rank = dist.get_rank(group) if group is not None else 0
+        self.slots = torch.zeros((self.world, self.words), dtype=torch.int32, device=self.device)
+        self._gloo = group is not None and dist.get_backend(group) == "gloo"
+        if group is None:
+            self.mine = self.slots[0]
+        else:
+            self.mine = torch.zeros(self.words, dtype=torch.int32, device=self.device)
+        self._host = None
+        if self._gloo and self.device.type != "cpu":
+            self._host = (torch.zeros(self.words, dtype=torch.int32), torch.zeros((self.world, self.words), dtype=torch.int32))
+
+    def exchange(self) -> None:
+        if self.group is None:
+            return
+        if not self._gloo:
+            dist.all_gather_into_tensor(self.slots, self.mine, group=self.group)
+        elif self._host is None:
+            dist.all_gather(list(self.slots.unbind(0)), self.mine, group=self.group)
+        else:
+            mine, rows = self._host
+            mine.copy_(self.mine)
+            dist.all_gather(list(rows.unbind(0)), mine, group=self.group)
+            self.slots.copy_(rows)
+
+
+def _collective_device(group, device):
+    """Where a small collective of `group` runs: the device for RCCL, the host for gloo."""
+    return torch.device(device) if dist.get_backend(group) != "gloo" else torch.device("cpu")
+
+
+def all_gather_ints(values, group, device) -> List[List[int]]:
+    """Every rank's list of integers (the same length on every rank), in rank order. A collective: every rank of the group
+    calls it; with it, a check that fails on one rank can fail on all of them, and no rank is left waiting."""
+    dev = _collective_device(group, device)
+    t = torch.tensor([int(v) for v in values], dtype=torch.int64, device=dev)
+    out = torch.zeros((dist.get_world_size(group), t.numel()), dtype=torch.int64, device=dev)
+    dist.all_gather(list(out.unbind(0)), t, group=group)
+    return out.cpu().tolist()
+
+
+def broadcast_tensor_(tensor: torch.Tensor, src: int, group) -> None:
+    """`tensor` of group rank `src` into `tensor` on every rank, in place (staged through the host with gloo)."""
+    root = dist.get_global_rank(group, src) if group is not dist.group.WORLD else src
+    if _collective_device(group, tensor.device).type == tensor.device.type:
+        dist.broadcast(tensor, src=root, group=group)
+        return
+    host = tensor.detach().cpu()
+    dist.broadcast(host, src=root, group=group)
+    tensor.copy_(host)

@@ -100,6 +100,15 @@ EXPORTED_SYMBOLS = (
     "upkie_ppo_workspace_bytes",
     "upkie_ppo_advantage_stats",
     "upkie_ppo_minibatch_update",
+    "upkie_vecnorm_slot_bytes",
+    "upkie_vecnorm_moments_local",
+    "upkie_vecnorm_merge",
+    "upkie_ppo_slot_bytes",
+    "upkie_ppo_advantage_slot_bytes",
+    "upkie_ppo_advantage_partials",
+    "upkie_ppo_advantage_finish",
+    "upkie_ppo_minibatch_gradient",
+    "upkie_ppo_minibatch_apply",
 )
 
 
@@ -375,6 +384,27 @@ def load() -> C.CDLL:
         lib.upkie_ppo_advantage_stats.argtypes = [C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp]
         lib.upkie_ppo_minibatch_update.restype = C.c_int
         lib.upkie_ppo_minibatch_update.argtypes = ([C.POINTER(abi.UpkieMlpShape), C.POINTER(abi.UpkiePpoConfig)] + [C.c_int32] * 4 + [vp] * 15)
+    if hasattr(lib, "upkie_vecnorm_merge"):  # (the data-parallel halves: an older build lacks them, and still loads)
+        lib.upkie_vecnorm_slot_bytes.restype = C.c_int64
+        lib.upkie_vecnorm_slot_bytes.argtypes = [C.c_int32]
+        lib.upkie_vecnorm_moments_local.restype = C.c_int
+        lib.upkie_vecnorm_moments_local.argtypes = ([C.c_int32, C.c_int32] + [vp] * 8 + [C.c_int32] + [C.c_double] * 4 + [vp] * 8)
+        lib.upkie_vecnorm_merge.restype = C.c_int
+        lib.upkie_vecnorm_merge.argtypes = ([C.c_int32, C.c_int32] + [vp] * 8 + [C.c_int32] + [C.c_double] * 4 + [vp] * 6 + [vp, C.c_int32, vp])
+    if hasattr(lib, "upkie_ppo_minibatch_apply"):
+        shape_p, cfg_p = C.POINTER(abi.UpkieMlpShape), C.POINTER(abi.UpkiePpoConfig)
+        lib.upkie_ppo_slot_bytes.restype = C.c_int64
+        lib.upkie_ppo_slot_bytes.argtypes = [shape_p]
+        lib.upkie_ppo_advantage_slot_bytes.restype = C.c_int64
+        lib.upkie_ppo_advantage_slot_bytes.argtypes = [C.c_int32, C.c_int32]
+        lib.upkie_ppo_advantage_partials.restype = C.c_int
+        lib.upkie_ppo_advantage_partials.argtypes = [C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp]
+        lib.upkie_ppo_advantage_finish.restype = C.c_int
+        lib.upkie_ppo_advantage_finish.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp]
+        lib.upkie_ppo_minibatch_gradient.restype = C.c_int
+        lib.upkie_ppo_minibatch_gradient.argtypes = [shape_p, cfg_p] + [C.c_int32] * 5 + [vp] * 12
+        lib.upkie_ppo_minibatch_apply.restype = C.c_int
+        lib.upkie_ppo_minibatch_apply.argtypes = [shape_p, cfg_p, C.c_int32, C.c_int32, vp, C.c_int32] + [vp] * 7
     lib.upkie_rollout_gae.restype = C.c_int
     lib.upkie_rollout_gae.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
     _lib = lib

@@ -41,10 +41,18 @@ class RunningNormalizer:
     between steps, so it can be captured in a hipGraph (`GraphedLoop`). ``training`` may be switched between steps
     (a captured graph keeps the value it was captured with); ``obs_mean_f32`` / ``obs_std_f32`` are the fp32 mirrors
     ``(float)mean`` and ``(float)sqrt(var + epsilon)`` that `attach`-ed policies read. One difference from SB3: the
-    batch moments are computed in fp64 (SB3: numpy on the float32 batch)."""
+    batch moments are computed in fp64 (SB3: numpy on the float32 batch).
+
+    ``process_group``: data-parallel training, one normaliser per rank of a ``torch.distributed`` group, each over its
+    own shard of envs (a `ShardedVecEnv`). The statistics are those of one normaliser over the union of the shards, the
+    same bits on every rank after every step: a step that moves them writes this rank's batch moments to a slot, the
+    slots are exchanged (`upkie_amd.distributed.SlotExchange`: one collective) and merged in rank order on every rank
+    (``upkie_vecnorm_moments_local`` / ``upkie_vecnorm_merge``). The per-env returns stay local. With a group of one
+    rank the results are the same bits as without a group. A step with a group cannot be captured in a graph."""
 
     def __init__(self, num_envs: int, obs_dim: int, gamma: float = 0.99, epsilon: float = 1e-8, clip_obs: float = 10.0,
-                 clip_reward: float = 10.0, norm_obs: bool = True, norm_reward: bool = True, training: bool = True, device="cuda:0"):
+                 clip_reward: float = 10.0, norm_obs: bool = True, norm_reward: bool = True, training: bool = True, device="cuda:0",
+                 process_group=None):
         self.num_envs, self.obs_dim = int(num_envs), int(obs_dim)
         if self.num_envs < 1 or not 1 <= self.obs_dim <= 256:
             raise ValueError("num_envs must be positive and obs_dim in 1-256")
@@ -70,6 +78,15 @@ class RunningNormalizer:
         self._reward = torch.empty(N, dtype=torch.float32, device=self.device)
         self._norm_obs = torch.empty((N, D), dtype=torch.float32, device=self.device)
         self._policy = None
+        self.process_group = process_group
+        self._exchange = None
+        if process_group is not None:
+            from .distributed import SlotExchange
+
+            if not hasattr(self._lib, "upkie_vecnorm_merge"):
+                raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_vecnorm_merge: rebuild it for a process group")
+            words = int(self._lib.upkie_vecnorm_slot_bytes(D)) // 4
+            self._exchange = SlotExchange(words, self.device, process_group)
         self.obs_stats[D:2 * D] = 1.0
         self.obs_stats[2 * D] = 1e-4
         self.ret_stats[1], self.ret_stats[2] = 1.0, 1e-4
@@ -77,12 +94,20 @@ class RunningNormalizer:
 
     @classmethod
     def for_env(cls, env, **kwargs):
-        """A normalizer sized by a batched env (``num_envs``, a ``[num_envs, obs_dim]`` observation, its device).
-        Statistics shared across the ranks of a `ShardedVecEnv` are not supported: each rank's envs would need an
-        all-reduce of the moments."""
-        if getattr(env, "world_size", 1) > 1:
-            raise UpkieRuntimeError("RunningNormalizer does not share statistics across ShardedVecEnv ranks (not supported yet)")
-        shape = tuple(getattr(env, "single_observation_space").shape) if hasattr(env, "single_observation_space") else None
+        """A normalizer sized by a batched env (``num_envs``, a ``[num_envs, obs_dim]`` observation, its device). A shard
+        of a `ShardedVecEnv` with several ranks needs ``process_group=`` (the group its ranks train in): without one
+        each rank would keep statistics of its own shard only, and it is refused."""
+        group = kwargs.get("process_group")
+        if getattr(env, "world_size", 1) > 1 and group is None:
+            raise UpkieRuntimeError("RunningNormalizer does not share statistics across ShardedVecEnv ranks without a process group: "
+                                    "pass process_group=")
+        if hasattr(env, "single_observation_space"):
+            shape = tuple(getattr(env, "single_observation_space").shape)
+        elif group is not None and hasattr(env, "obs_shape"):  # (a ShardedVecEnv shard)
+            shape = tuple(env.obs_shape)
+            kwargs.setdefault("device", getattr(getattr(env, "sim", None), "device", "cuda:0"))
+        else:
+            shape = None
         if shape is None or len(shape) != 1:
             raise UpkieRuntimeError(f"RunningNormalizer needs one [num_envs, obs_dim] float32 observation block, the env has {shape}")
         kwargs.setdefault("device", getattr(env, "device", "cuda:0"))
@@ -153,14 +178,39 @@ class RunningNormalizer:
             raise UpkieRuntimeError("RunningNormalizer runs on the HIP device only (there is no CPU fallback): build it with device='cuda:0'")
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         packed = None if self._policy is None else self._policy.packed
+        training, reset = bool(flags & TRAINING), bool(flags & RESET)
+        shared = self._exchange is not None and training and (bool(flags & NORM_OBS) or not reset)  # (a statistic moves)
+        if shared and torch.cuda.is_current_stream_capturing():
+            raise UpkieRuntimeError("a RunningNormalizer with a process group cannot be captured in a graph (its step exchanges the "
+                                    "moments through a collective)")
         with torch.cuda.device(self.device):
-            status = self._lib.upkie_vecnorm_step(
-                self.num_envs, self.obs_dim, ptr(obs), ptr(reward), ptr(terminated), ptr(truncated), self.obs_stats.data_ptr(),
-                self.ret_stats.data_ptr(), self.returns.data_ptr(), self.workspace.data_ptr(), flags, self.gamma, self.epsilon, self.clip_obs,
-                self.clip_reward, self.obs_mean_f32.data_ptr(), self.obs_std_f32.data_ptr(), ptr(packed), ptr(norm_obs), ptr(norm_reward),
-                ptr(starts), torch.cuda.current_stream(self.device).cuda_stream)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            args = (self.num_envs, self.obs_dim, ptr(obs), ptr(reward), ptr(terminated), ptr(truncated), self.obs_stats.data_ptr(),
+                    self.ret_stats.data_ptr(), self.returns.data_ptr(), self.workspace.data_ptr(), flags, self.gamma, self.epsilon, self.clip_obs,
+                    self.clip_reward, self.obs_mean_f32.data_ptr(), self.obs_std_f32.data_ptr(), ptr(packed), ptr(norm_obs), ptr(norm_reward),
+                    ptr(starts))
+            if not shared:
+                status = self._lib.upkie_vecnorm_step(*args, stream)
+            else:
+                ex = self._exchange
+                status = self._lib.upkie_vecnorm_moments_local(*args, ex.mine.data_ptr(), stream)
+                if status >= 0:
+                    ex.exchange()
+                    status = self._lib.upkie_vecnorm_merge(*args, ex.slots.data_ptr(), ex.world, stream)
         if status < 0:
             lib.check(status, None)
+
+    def broadcast_statistics(self, src: int = 0) -> None:
+        """Copy the statistics of group rank `src` to every rank (with their fp32 mirrors and an attached policy's packed
+        words), so that the ranks start from the same statistics whatever they were built or loaded with. A collective:
+        every rank calls it. The per-env returns stay local."""
+        if self.process_group is None:
+            return
+        from .distributed import broadcast_tensor_
+
+        broadcast_tensor_(self.obs_stats, src, self.process_group)
+        broadcast_tensor_(self.ret_stats, src, self.process_group)
+        self._refresh_mirrors()
 
     # ---- calls
     def reset(self, obs: torch.Tensor) -> None:

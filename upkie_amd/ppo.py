@@ -47,11 +47,22 @@ class PpoTrainer:
     ``obs_normalized``: the buffer holds normalised observations (the rollout wrote ``norm_obs``); otherwise the
     training forward normalises them as ``act()`` does. With a live `RunningNormalizer` attached to the policy the
     statistics moved during the rollout, so raw observations are refused (SB3 trains on the normalised ones too).
-    Adam's ``m`` and ``v`` live in the packed layout; `state_dict` gives them in ``policy.sources()`` order."""
+    Adam's ``m`` and ``v`` live in the packed layout; `state_dict` gives them in ``policy.sources()`` order.
+
+    ``process_group``: data-parallel PPO over a ``torch.distributed`` group. Each rank holds a policy replica and a
+    `RolloutBuffer` of its own envs, all of the same size; together they train as ONE learner on the union of the
+    samples: minibatch j of the union is the union of the ranks' minibatches j, and every rank holds the same weights, m,
+    v and step count, bit for bit, after every minibatch. Per epoch the advantage statistics take two exchanges of
+    per-minibatch sums; per minibatch this rank's gradient and loss sums go to a slot, one collective makes every slot
+    visible on every rank (`upkie_amd.distributed.SlotExchange`), and every rank sums them in rank order, then clips
+    and steps Adam (``upkie_ppo_minibatch_gradient`` / ``upkie_ppo_minibatch_apply``). `prepare` checks, collectively,
+    that every rank has the same sample count; `broadcast_parameters` makes the replicas start identical. With a group
+    of one rank the results are the same bits as without a group. An update with a group cannot be captured in a graph.
+    Give each rank's policy its own seed (e.g. ``seed + rank``): its noise is keyed by the local env index."""
 
     def __init__(self, policy, lr: float = 3e-4, n_epochs: int = 10, batch_size: int = 64, clip_range: float = 0.2,
                  clip_range_vf: Optional[float] = None, normalize_advantage: bool = True, ent_coef: float = 0.0, vf_coef: float = 0.5,
-                 max_grad_norm: float = 0.5, obs_normalized: bool = False, seed: int = 0):
+                 max_grad_norm: float = 0.5, obs_normalized: bool = False, seed: int = 0, process_group=None):
         from .policies import MlpActorCritic
 
         if not isinstance(policy, MlpActorCritic):
@@ -90,6 +101,14 @@ class PpoTrainer:
         sizes = [t.numel() for t in policy.sources()]
         self._sizes = sizes
         self._flat = torch.zeros(sum(sizes) + 1, **f32)  # (sync_modules' scatter target)
+        self.process_group = process_group
+        self._grad_exchange = self._adv_exchange = None
+        if process_group is not None:
+            from .distributed import SlotExchange
+
+            if not hasattr(self._lib, "upkie_ppo_minibatch_apply"):
+                raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_ppo_minibatch_apply: rebuild it for a process group")
+            self._grad_exchange = SlotExchange(int(self._lib.upkie_ppo_slot_bytes(C.byref(policy.shape))) // 4, self.device, process_group)
 
     # ---- buffers, allocated by the first train() (one rollout size per trainer)
     def _allocate(self, total: int) -> None:
@@ -111,6 +130,10 @@ class PpoTrainer:
         self.returns = torch.zeros(total, dtype=torch.float32, device=self.device)
         self._mb = mb
         self._total = total
+        if self.process_group is not None:
+            from .distributed import SlotExchange
+
+            self._adv_exchange = SlotExchange(int(self._lib.upkie_ppo_advantage_slot_bytes(total, mb)) // 4, self.device, self.process_group)
 
     def _check_buffer(self, buffer):
         if buffer.advantages is None:
@@ -139,6 +162,8 @@ class PpoTrainer:
         """Outside any capture, after ``buffer.compute_returns_and_advantage``: copy the buffer's advantages and returns
         into the trainer's own tensors and draw this iteration's permutations (`shuffle`)."""
         total = self._check_buffer(buffer)
+        if self.process_group is not None:
+            self._check_ranks(total)
         self._allocate(total)
         if self._buffer is None:
             self._buffer = self._addresses(buffer)
@@ -147,6 +172,30 @@ class PpoTrainer:
         self.advantages.copy_(buffer.advantages.reshape(total))
         self.returns.copy_(buffer.returns.reshape(total))
         self.shuffle()
+
+    def _check_ranks(self, total: int) -> None:
+        """Every rank the same sample count and minibatch count (one learner on the union needs minibatches of the same
+        size on every rank). Collective: every rank sends its sizes and every rank raises when any differ."""
+        from .distributed import all_gather_ints
+
+        mb = min(self.batch_size, total)
+        sizes = all_gather_ints([total, (total + mb - 1) // mb], self.process_group, self.device)
+        if any(s != sizes[0] for s in sizes):
+            raise ValueError(f"every rank of the process group must hold the same number of samples and minibatches; (samples, minibatches) "
+                             f"by rank: {[tuple(s) for s in sizes]} (uneven shards are not supported)")
+
+    def broadcast_parameters(self, src: int = 0) -> None:
+        """Copy group rank `src`'s trainable packed words, Adam's m and v, lr and t to every rank, so that the replicas
+        start identical however they were built; then `sync_modules`. A collective: every rank calls it."""
+        if self.process_group is None:
+            return
+        from .distributed import broadcast_tensor_
+
+        off = trainable_offset(self.policy.shape)
+        trainable = self.policy.packed[off:]
+        for t in (trainable, self.m, self.v, self.scalars):
+            broadcast_tensor_(t, src, self.process_group)
+        self.sync_modules()
 
     def shuffle(self) -> None:
         """One ``randperm`` per epoch into the persistent index buffer (outside any capture)."""
@@ -167,6 +216,14 @@ class PpoTrainer:
         p = lambda t: t.data_ptr()  # noqa: E731
         obs, act = p(buffer.observations), p(buffer.actions)
         vals, logp, adv, ret = p(buffer.values), p(buffer.log_probs), p(self.advantages), p(self.returns)
+        if self.process_group is not None:
+            if torch.cuda.is_current_stream_capturing():
+                raise UpkieRuntimeError("a PpoTrainer with a process group cannot be captured in a graph (every minibatch exchanges the "
+                                        "gradients through a collective)")
+            self._update_shared(total, shape, cfg, obs, act, vals, logp, adv, ret)
+            if sync:
+                self.sync_modules()
+            return self.stats
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             for e in range(self.n_epochs):
@@ -185,6 +242,34 @@ class PpoTrainer:
         if sync:
             self.sync_modules()
         return self.stats
+
+    def _update_shared(self, total, shape, cfg, obs, act, vals, logp, adv, ret) -> None:
+        """`update`'s epochs and minibatches in the data-parallel form: the same launches split around the exchanges."""
+        lb, gx, ax = self._lib, self._grad_exchange, self._adv_exchange
+        p = lambda t: t.data_ptr()  # noqa: E731
+        W, mb = gx.world, self._mb
+
+        def ok(status):
+            if status < 0:
+                lib.check(status, None)
+
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            for e in range(self.n_epochs):
+                perm = p(self.perm[e])
+                ok(lb.upkie_ppo_advantage_partials(total, mb, perm, adv, 0, None, W, p(ax.mine), stream))
+                ax.exchange()
+                ok(lb.upkie_ppo_advantage_partials(total, mb, perm, adv, 1, p(ax.slots), W, p(ax.mine), stream))
+                ax.exchange()
+                ok(lb.upkie_ppo_advantage_finish(total, mb, int(self.normalize_advantage), p(ax.slots), W, p(self.adv_stats[e]), stream))
+                for j in range(self.n_minibatches):
+                    start = j * mb
+                    size = min(mb, total - start)
+                    ok(lb.upkie_ppo_minibatch_gradient(shape, cfg, total, start, size, W * size, mb, perm, obs, act, vals, logp, adv, ret,
+                                                       p(self.adv_stats[e, j]), p(self.policy.packed), p(self.workspace), p(gx.mine), stream))
+                    gx.exchange()
+                    ok(lb.upkie_ppo_minibatch_apply(shape, cfg, W * size, mb, p(gx.slots), W, p(self.policy.packed), p(self.m), p(self.v),
+                                                    p(self.scalars), p(self.workspace), p(self.stats[e, j]), stream))
 
     def train(self, buffer, sync: bool = True) -> torch.Tensor:
         """`prepare` then `update`: SB3's ``PPO.train`` on one full rollout buffer. Returns ``[n_epochs, n_minibatches, 7]``
