@@ -1101,6 +1101,69 @@ int upkie_ppo_minibatch_apply(const UpkieMlpShape* shape, const UpkiePpoConfig* 
                               int32_t max_minibatch, const void* slots, int32_t world, float* packed, float* adam_m,
                               float* adam_v, double* adam_scalars, void* workspace, float* stats, void* stream);
 
+/* ---- Time-limit bootstrap (SB3 collect_rollouts) ----------------------
+ * For every env n < num_envs with truncated[n] && !terminated[n] (bytes;
+ * terminated may be NULL: none terminated), in place:
+ *   reward[n] = fl32(reward[n] + fl32(fl32(gamma) * V(final_obs[n])))
+ * two roundings, no contraction: what Stable-Baselines3's float32
+ * `rewards[idx] += gamma * terminal_value` computes for an env that ended
+ * by its time limit. V is the critic of the MLP actor-critic of `shape` on
+ * the packed buffer, on final_obs [num_envs][obs_dim] normalised as
+ * upkie_mlp_actor_critic does (the same packed obs_mean / obs_std words,
+ * live when a normaliser writes them): bit for bit the value that
+ * upkie_mlp_actor_critic writes for the same observation. Every other
+ * reward keeps its bits. One launch, one wave per tile of 16 envs; a tile
+ * without such an env loads no weight. No allocation, no host argument that
+ * changes between steps: the call can be captured in a hipGraph. Needs a
+ * critic (critic_layers > 0) and gamma in [0, 1]. SB3's order within a
+ * rollout step: the Monitor statistics on the raw reward, VecNormalize, then
+ * this on the normalised reward with the statistics after that update; its
+ * semantics assume same-step autoreset (final_obs: the observation the
+ * ended episode stopped in). No CPU fallback: UPKIE_ERR_NO_DEVICE without a
+ * HIP device. Errors are reported through upkie_sim_last_error(NULL). */
+int upkie_mlp_bootstrap_time_limits(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* final_obs,
+                                    const uint8_t* terminated, const uint8_t* truncated, double gamma, float* reward,
+                                    void* stream);
+
+/* ---- Episode statistics (SB3 Monitor + ep_info_buffer) -----------------
+ * N = num_envs envs, a ring of `window` finished episodes (1-65536; SB3's
+ * stats_window_size, 100 by default), csrc/episodes.hpp. State, device
+ * buffers, zero before the first step:
+ *   ep_return [N] fp64, ep_length [N] int32: the running episode of each env
+ *   ring_return [window] fp64, ring_length [window] int32
+ *   counters [3] int64: episodes finished so far, ring head, ring fill
+ *   means [2] fp64: mean return, mean length over the ring (0 while empty)
+ * One step (one launch), done[n] = terminated[n] | truncated[n] (bytes, NULL:
+ * none):
+ *   ep_return[n] += (double)reward[n];  ep_length[n] += 1   (every env; the
+ *     fp64 sum in step order: Python's sum(Monitor.rewards), bit for bit)
+ *   the envs with done[n] finish their episode (return, length) and their
+ *   accumulators go back to 0; the step's K finished episodes, in increasing
+ *   n, are appended to the ring: with K > window only the last `window` of
+ *   them (a deque of maxlen window);
+ *   counters[0] += K;  head = (head + min(K, window)) mod window;
+ *   fill = min(fill + min(K, window), window);
+ *   means[0] = (r_0 + r_1 + ... + r_{fill-1}) / fill in fp64, summed
+ *     sequentially from the oldest entry to the newest;
+ *   means[1] = (l_0 + ... + l_{fill-1}) / fill (integer sum, one rounding).
+ * Monitor's round(r, 6) is not applied and there is no "t" (wall-clock)
+ * entry. The ring's oldest entry is at (head - fill) mod window.
+ * workspace: upkie_episodes_workspace_bytes(N) bytes, zeroed once before the
+ * first step (every step leaves its counter at zero again). No block waits
+ * on another, no float atomics, no allocation, no host synchronisation: the
+ * same bits every call, and the step can be captured in a hipGraph.
+ * upkie_episodes_reset: the accumulators of the envs with mask[n] != 0 (all
+ * when mask is NULL) back to 0, no episode recorded, the ring kept
+ * (Monitor.reset). No CPU fallback: UPKIE_ERR_NO_DEVICE without a HIP device.
+ * Errors are reported through upkie_sim_last_error(NULL). */
+int64_t upkie_episodes_workspace_bytes(int32_t num_envs);
+
+int upkie_episodes_step(int32_t num_envs, int32_t window, const float* reward, const uint8_t* terminated,
+                        const uint8_t* truncated, double* ep_return, int32_t* ep_length, double* ring_return,
+                        int32_t* ring_length, int64_t* counters, double* means, void* workspace, void* stream);
+
+int upkie_episodes_reset(int32_t num_envs, const uint8_t* mask, double* ep_return, int32_t* ep_length, void* stream);
+
 /* ---- Rollout consumer (BASELINE.json configs[3]) ---
  * Generalized advantage estimation over a rollout resident in HBM: rewards,
  * values, episode_starts, advantages, returns are [num_steps][num_envs]

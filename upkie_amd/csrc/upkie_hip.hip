@@ -22,6 +22,8 @@
 #include "rollout.hpp"
 #include "vecnorm.hpp"
 #include "ppo.hpp"
+#include "time_limits.hpp"
+#include "episodes.hpp"
 
 #include "step_kernels.hpp"
 #include "step_instances.hpp"  // (the step kernels this unit launches are compiled elsewhere, by groups: declarations only)
@@ -1282,6 +1284,130 @@ extern "C" int upkie_mlp_actor_critic(int32_t num_envs, const UpkieMlpShape* sha
     case 128: launch_mlp<128>(shape->activation, grid, s, P, packed, obs, calls, out); break;
     default: launch_mlp<256>(shape->activation, grid, s, P, packed, obs, calls, out); break;
   }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) {
+    g_create_error = hipGetErrorString(err);
+    return UPKIE_ERR_HIP;
+  }
+  return UPKIE_OK;
+}
+
+// ============================================================ time-limit bootstrap (SB3 collect_rollouts)
+template <int W>
+static void launch_bootstrap(int activation, dim3 grid, hipStream_t stream, const upkie::MlpDev& P, const float* packed, const float* final_obs,
+                             const uint8_t* terminated, const uint8_t* truncated, float gamma, float* reward) {
+  if (activation == UPKIE_MLP_TANH)
+    hipLaunchKernelGGL((upkie::mlp_bootstrap_time_limits_kernel<W, UPKIE_MLP_TANH>), grid, dim3(64), 0, stream, P, packed, final_obs, terminated,
+                       truncated, gamma, reward);
+  else
+    hipLaunchKernelGGL((upkie::mlp_bootstrap_time_limits_kernel<W, UPKIE_MLP_RELU>), grid, dim3(64), 0, stream, P, packed, final_obs, terminated,
+                       truncated, gamma, reward);
+}
+
+extern "C" int upkie_mlp_bootstrap_time_limits(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* final_obs,
+                                               const uint8_t* terminated, const uint8_t* truncated, double gamma, float* reward, void* stream) {
+  if (num_envs <= 0) {
+    g_create_error = "num_envs must be positive";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (!shape || !packed || !final_obs || !truncated || !reward) {
+    g_create_error = "null argument (shape, packed, final_obs, truncated and reward are required)";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  upkie::MlpDev P;
+  if (upkie::mlp_layout(*shape, &P) < 0)
+    return (int)upkie_mlp_packed_words(shape);  // (sets the message)
+  if (shape->critic_layers == 0) {
+    g_create_error = "the time-limit bootstrap needs a critic (critic_layers > 0)";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (!(gamma >= 0.0 && gamma <= 1.0)) {
+    g_create_error = "gamma must be in [0, 1]";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  P.num_envs = num_envs;
+  if (upkie_hip_device_count() <= 0) {
+    g_create_error = "no HIP device visible";
+    return UPKIE_ERR_NO_DEVICE;
+  }
+  const dim3 grid((unsigned)((num_envs + 15) / 16));
+  const hipStream_t s = (hipStream_t)stream;
+  const float g32 = (float)gamma;
+  switch (upkie::mlp_width_class(*shape)) {
+    case 16: launch_bootstrap<16>(shape->activation, grid, s, P, packed, final_obs, terminated, truncated, g32, reward); break;
+    case 32: launch_bootstrap<32>(shape->activation, grid, s, P, packed, final_obs, terminated, truncated, g32, reward); break;
+    case 64: launch_bootstrap<64>(shape->activation, grid, s, P, packed, final_obs, terminated, truncated, g32, reward); break;
+    case 128: launch_bootstrap<128>(shape->activation, grid, s, P, packed, final_obs, terminated, truncated, g32, reward); break;
+    default: launch_bootstrap<256>(shape->activation, grid, s, P, packed, final_obs, terminated, truncated, g32, reward); break;
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) {
+    g_create_error = hipGetErrorString(err);
+    return UPKIE_ERR_HIP;
+  }
+  return UPKIE_OK;
+}
+
+// ============================================================ episode statistics (SB3 Monitor + ep_info_buffer)
+static bool episodes_shape_ok(int32_t num_envs, int32_t window) {
+  if (num_envs <= 0 || window < 1 || window > upkie::EPISODES_MAX_WINDOW) {
+    g_create_error = "num_envs must be positive and window in 1-65536";
+    return false;
+  }
+  return true;
+}
+
+extern "C" int64_t upkie_episodes_workspace_bytes(int32_t num_envs) {
+  if (!episodes_shape_ok(num_envs, 1)) return UPKIE_ERR_INVALID_ARGUMENT;
+  return upkie::episodes_workspace_bytes(num_envs);
+}
+
+extern "C" int upkie_episodes_step(int32_t num_envs, int32_t window, const float* reward, const uint8_t* terminated, const uint8_t* truncated,
+                                   double* ep_return, int32_t* ep_length, double* ring_return, int32_t* ring_length, int64_t* counters,
+                                   double* means, void* workspace, void* stream) {
+  if (!episodes_shape_ok(num_envs, window)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!reward || !ep_return || !ep_length || !ring_return || !ring_length || !counters || !means || !workspace) {
+    g_create_error = "null argument (only terminated and truncated may be NULL)";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (upkie_hip_device_count() <= 0) {
+    g_create_error = "no HIP device visible";
+    return UPKIE_ERR_NO_DEVICE;
+  }
+  upkie::EpisodesDev P{};
+  P.num_envs = num_envs;
+  P.window = window;
+  P.blocks = upkie::episodes_blocks(num_envs, &P.rows);
+  P.reward = reward, P.terminated = terminated, P.truncated = truncated;
+  P.ep_return = ep_return, P.ep_length = ep_length, P.ring_return = ring_return, P.ring_length = ring_length;
+  P.counters = counters, P.means = means;
+  char* ws = (char*)workspace;
+  P.ticket = (unsigned*)ws;
+  P.counts = (int32_t*)(ws + upkie::EPISODES_COUNTS_OFFSET);
+  P.fin_return = (double*)(ws + upkie::EPISODES_COUNTS_OFFSET + upkie::EPISODES_MAX_BLOCKS * 4);
+  P.fin_length = (int32_t*)(ws + upkie::EPISODES_COUNTS_OFFSET + upkie::EPISODES_MAX_BLOCKS * 4 + (int64_t)num_envs * 8);
+  hipLaunchKernelGGL(upkie::episodes_step_kernel, dim3((unsigned)P.blocks), dim3(upkie::EPISODES_THREADS), 0, (hipStream_t)stream, P);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) {
+    g_create_error = hipGetErrorString(err);
+    return UPKIE_ERR_HIP;
+  }
+  return UPKIE_OK;
+}
+
+extern "C" int upkie_episodes_reset(int32_t num_envs, const uint8_t* mask, double* ep_return, int32_t* ep_length, void* stream) {
+  if (!episodes_shape_ok(num_envs, 1)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!ep_return || !ep_length) {
+    g_create_error = "null accumulator buffer";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (upkie_hip_device_count() <= 0) {
+    g_create_error = "no HIP device visible";
+    return UPKIE_ERR_NO_DEVICE;
+  }
+  const int grid = std::min((num_envs + upkie::EPISODES_THREADS - 1) / upkie::EPISODES_THREADS, 1024);
+  hipLaunchKernelGGL(upkie::episodes_reset_kernel, dim3((unsigned)grid), dim3(upkie::EPISODES_THREADS), 0, (hipStream_t)stream, num_envs, mask,
+                     ep_return, ep_length);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) {
     g_create_error = hipGetErrorString(err);

@@ -32,6 +32,8 @@ SOURCES = [
     os.path.join(_HERE, "csrc", "policy_mlp.hpp"),
     os.path.join(_HERE, "csrc", "vecnorm.hpp"),
     os.path.join(_HERE, "csrc", "ppo.hpp"),
+    os.path.join(_HERE, "csrc", "time_limits.hpp"),
+    os.path.join(_HERE, "csrc", "episodes.hpp"),
     os.path.join(_HERE, "csrc", "wave_io.hpp"),
     os.path.join(_HERE, "..", "include", "upkie_hip.h"),
 ]
@@ -109,6 +111,10 @@ EXPORTED_SYMBOLS = (
     "upkie_ppo_advantage_finish",
     "upkie_ppo_minibatch_gradient",
     "upkie_ppo_minibatch_apply",
+    "upkie_mlp_bootstrap_time_limits",
+    "upkie_episodes_workspace_bytes",
+    "upkie_episodes_step",
+    "upkie_episodes_reset",
 )
 
 
@@ -405,6 +411,16 @@ def load() -> C.CDLL:
         lib.upkie_ppo_minibatch_gradient.argtypes = [shape_p, cfg_p] + [C.c_int32] * 5 + [vp] * 12
         lib.upkie_ppo_minibatch_apply.restype = C.c_int
         lib.upkie_ppo_minibatch_apply.argtypes = [shape_p, cfg_p, C.c_int32, C.c_int32, vp, C.c_int32] + [vp] * 7
+    if hasattr(lib, "upkie_mlp_bootstrap_time_limits"):  # (the time-limit bootstrap: an older build lacks it, and still loads)
+        lib.upkie_mlp_bootstrap_time_limits.restype = C.c_int
+        lib.upkie_mlp_bootstrap_time_limits.argtypes = [C.c_int32, C.POINTER(abi.UpkieMlpShape), vp, vp, vp, vp, C.c_double, vp, vp]
+    if hasattr(lib, "upkie_episodes_step"):  # (the episode statistics: an older build lacks them, and still loads)
+        lib.upkie_episodes_workspace_bytes.restype = C.c_int64
+        lib.upkie_episodes_workspace_bytes.argtypes = [C.c_int32]
+        lib.upkie_episodes_step.restype = C.c_int
+        lib.upkie_episodes_step.argtypes = [C.c_int32, C.c_int32] + [vp] * 11
+        lib.upkie_episodes_reset.restype = C.c_int
+        lib.upkie_episodes_reset.argtypes = [C.c_int32, vp, vp, vp, vp]
     lib.upkie_rollout_gae.restype = C.c_int
     lib.upkie_rollout_gae.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
     _lib = lib

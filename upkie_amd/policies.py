@@ -454,6 +454,47 @@ class MlpActorCritic:
         self._launch(obs, True, {"value": v})
         return v
 
+    def bootstrap_time_limits(self, final_obs: torch.Tensor, terminated: torch.Tensor, truncated: torch.Tensor, reward: torch.Tensor,
+                              gamma: float) -> torch.Tensor:
+        """Stable-Baselines3's time-limit bootstrap (``collect_rollouts``), one launch: for every env with
+        ``truncated & ~terminated``, ``reward += gamma * value(final_obs)`` in float32 (two roundings, no fused
+        multiply-add), in place; returns ``reward``. The value is the critic's on ``final_obs`` normalised with the
+        policy's current statistics, bit for bit what `value` gives for the same rows. ``final_obs`` ``[N, ...]`` float32
+        (an env's ``info["final_obs"]``), ``terminated`` / ``truncated`` ``[N]`` bool or uint8, ``reward`` a contiguous
+        ``[N]`` float32 device tensor (e.g. ``buffer.rewards[t]``). No host synchronisation: it can be captured in a
+        graph.
+
+        Order inside a rollout step, as in SB3 (Monitor under VecNormalize):
+        1. ``policy.act``; 2. ``env.step``; 3. the user's reward; 4. `upkie_amd.episodes.EpisodeStatistics.step` on
+        the raw reward; 5. `RunningNormalizer.step` into ``buffer.rewards[t]``; 6. this, on the normalised slot
+        ``buffer.rewards[t]`` with ``buffer.gamma``. SB3's semantics assume same-step autoreset (``final_obs``: the
+        observation the ended episode stopped in)."""
+        if self.shape.critic_layers == 0:
+            raise UpkieRuntimeError("this policy has no critic: the time-limit bootstrap needs V(final_obs)")
+        final_obs = self._obs(final_obs)
+        n = final_obs.shape[0]
+        flags = []
+        for name, t in (("terminated", terminated), ("truncated", truncated)):
+            if (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype not in (torch.bool, torch.uint8) or not t.is_contiguous()
+                    or t.numel() != n):
+                raise ValueError(f"{name} must be a contiguous bool or uint8 tensor of {n} values on {self.device}")
+            flags.append(t)
+        if (not isinstance(reward, torch.Tensor) or reward.device != self.device or reward.dtype is not torch.float32 or not reward.is_contiguous()
+                or reward.numel() != n):
+            raise ValueError(f"reward must be a contiguous float32 tensor of {n} values on {self.device} (it is updated in place)")
+        gamma = float(gamma)
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError("gamma must be in [0, 1]")
+        if not hasattr(self._lib, "upkie_mlp_bootstrap_time_limits"):
+            raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_mlp_bootstrap_time_limits: rebuild it")
+        with torch.cuda.device(self.device):
+            status = self._lib.upkie_mlp_bootstrap_time_limits(n, C.byref(self.shape), self.packed.data_ptr(), final_obs.data_ptr(),
+                                                               flags[0].data_ptr(), flags[1].data_ptr(), gamma, reward.data_ptr(),
+                                                               torch.cuda.current_stream(self.device).cuda_stream)
+        if status < 0:
+            lib.check(status, None)
+        return reward
+
 
 class MlpPolicy(MlpActorCritic):
     """The actor of `MlpActorCritic` alone, deterministic (the Gaussian's mean, clamped to the action bounds):
