@@ -1101,6 +1101,92 @@ int upkie_ppo_minibatch_apply(const UpkieMlpShape* shape, const UpkiePpoConfig* 
                               int32_t max_minibatch, const void* slots, int32_t world, float* packed, float* adam_m,
                               float* adam_v, double* adam_scalars, void* workspace, float* stats, void* stream);
 
+/* ---- PPO update, controlled form: schedules and target_kl ---------------
+ * The hyper-parameters that change while training, and Stable-Baselines3's
+ * target_kl early stop, live in a control block in device memory instead of
+ * launch arguments, so that a captured update reads their current values and
+ * can end early without a host synchronisation. control: UPKIE_PPO_CTRL_WORDS
+ * doubles, 8-byte aligned, zeroed once by the caller; its first two words are
+ * adam_scalars' (lr, t), so one block serves both forms. */
+enum {
+  UPKIE_PPO_CTRL_LR = 0,               /* Adam's learning rate */
+  UPKIE_PPO_CTRL_T = 1,                /* Adam's step count: the minibatches applied */
+  UPKIE_PPO_CTRL_CLIP_RANGE = 2,       /* > 0; read as a float, replaces config->clip_range */
+  UPKIE_PPO_CTRL_CLIP_RANGE_VF = 3,    /* read as a float, replaces config->clip_range_vf; 0: none */
+  UPKIE_PPO_CTRL_TARGET_KL = 4,        /* 0: no early stop */
+  UPKIE_PPO_CTRL_STOPPED = 5,          /* 0 / 1: this update was stopped */
+  UPKIE_PPO_CTRL_N_UPDATES = 6,        /* SB3's _n_updates: the epochs entered since the block was zeroed */
+  UPKIE_PPO_CTRL_MINIBATCHES_RUN = 7,  /* statistics rows this update wrote, the stopping minibatch's included */
+  UPKIE_PPO_CTRL_WORDS = 8
+};
+
+/* Writes lr, clip_range, clip_range_vf and target_kl (one launch on `stream`;
+ * the other words are left alone). lr, clip_range_vf and target_kl finite and
+ * >= 0, clip_range finite and > 0, or UPKIE_ERR_INVALID_ARGUMENT. Call it
+ * between updates, not inside a captured sequence that should see new values:
+ * a captured call replays the values it was captured with. */
+int upkie_ppo_control_set(double* control, double lr, double clip_range, double clip_range_vf, double target_kl,
+                          void* stream);
+
+/* Starts an update: stopped = 0, minibatches_run = 0. One launch, capturable
+ * in front of the update's minibatches. */
+int upkie_ppo_update_begin(double* control, void* stream);
+
+/* upkie_ppo_minibatch_update with the control block in place of adam_scalars.
+ * Differences, in SB3's PPO.train order:
+ *   - clip_range and clip_range_vf are the block's (config's are checked, not
+ *     used);
+ *   - if stopped is set on entry: stats[0..6] = NaN, nothing else is written;
+ *   - otherwise n_updates += 1 when minibatch_start == 0 (an epoch is
+ *     entered), minibatches_run += 1, the stats row is written, and if
+ *     target_kl > 0 and approx_kl (the float32 of stats[4]) > 1.5 target_kl,
+ *     stopped = 1: t, the weights, m and v are NOT updated by this minibatch
+ *     nor by any later one until upkie_ppo_update_begin.
+ * With target_kl = 0 and the block's clip values equal to config's, every
+ * output is the same bits as upkie_ppo_minibatch_update's. Each of the three
+ * launches reads one word more; a stopped minibatch still costs its three
+ * launches, which return at once. */
+int upkie_ppo_minibatch_update_controlled(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total,
+                                          int32_t minibatch_start, int32_t minibatch_size, int32_t max_minibatch,
+                                          const int32_t* perm, const float* obs, const float* actions,
+                                          const float* old_values, const float* old_log_prob, const float* advantages,
+                                          const float* returns, const double* adv_stats, float* packed, float* adam_m,
+                                          float* adam_v, double* control, void* workspace, float* stats, void* stream);
+
+/* The data-parallel halves with a control block. The gradient half leaves the
+ * slot as it is once stopped is set. The apply half takes the decision from
+ * the exchanged slots' loss sums: every rank reads the same bits, so every
+ * rank stops at the same minibatch (each rank holds its own block; they stay
+ * equal). The caller cannot see the flag without a synchronisation, so it
+ * goes on exchanging slots after a stop; those exchanges change nothing.
+ * minibatch_start: this rank's, 0 for the first minibatch of an epoch. */
+int upkie_ppo_minibatch_gradient_controlled(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total,
+                                            int32_t minibatch_start, int32_t minibatch_size,
+                                            int32_t global_minibatch_size, int32_t max_minibatch, const int32_t* perm,
+                                            const float* obs, const float* actions, const float* old_values,
+                                            const float* old_log_prob, const float* advantages, const float* returns,
+                                            const double* adv_stats, float* packed, void* workspace, void* slot,
+                                            double* control, void* stream);
+
+int upkie_ppo_minibatch_apply_controlled(const UpkieMlpShape* shape, const UpkiePpoConfig* config,
+                                         int32_t minibatch_start, int32_t global_minibatch_size, int32_t max_minibatch,
+                                         const void* slots, int32_t world, float* packed, float* adam_m, float* adam_v,
+                                         double* control, void* workspace, float* stats, void* stream);
+
+/* SB3's train/explained_variance of the critic over the `total` samples of a
+ * rollout: out[0] = 1 - Var(returns - values) / Var(returns), population
+ * variances, NaN when Var(returns) == 0. fp64, two passes (means, then
+ * squared deviations) in a fixed order: the same bits every call. One launch
+ * of one block.
+ *   phase -1: one rank, everything in one launch (slots, slot unused).
+ * Data-parallel form (W ranks of `total` samples each, slot: 4 doubles,
+ * slots[r] = rank r's after an exchange; the sums in rank order):
+ *   phase 0: slot[0..1] = sum of returns, sum of (returns - values);
+ *   phase 1: slot[2..3] = the squared deviations about the global means;
+ *   phase 2: out[0] from the slots (returns, values unused). */
+int upkie_ppo_explained_variance(int32_t total, const float* returns, const float* values, int32_t phase,
+                                 const double* slots, int32_t world, double* slot, double* out, void* stream);
+
 /* ---- Time-limit bootstrap (SB3 collect_rollouts) ----------------------
  * For every env n < num_envs with truncated[n] && !terminated[n] (bytes;
  * terminated may be NULL: none terminated), in place:

@@ -333,6 +333,17 @@ STRUCT_IDS = {
 OPTIONAL_STRUCTS = {9: "upkie_mlp_actor_critic", 10: "upkie_ppo_minibatch_update"}
 MAX_GRAPH_CAPTURES = 8  # UPKIE_MAX_GRAPH_CAPTURES
 
+# the PPO control block's fp64 words (enum UPKIE_PPO_CTRL_*)
+PPO_CTRL_LR = 0
+PPO_CTRL_T = 1
+PPO_CTRL_CLIP_RANGE = 2
+PPO_CTRL_CLIP_RANGE_VF = 3
+PPO_CTRL_TARGET_KL = 4
+PPO_CTRL_STOPPED = 5
+PPO_CTRL_N_UPDATES = 6
+PPO_CTRL_MINIBATCHES_RUN = 7
+PPO_CTRL_WORDS = 8
+
 # observer memory words (enum UpkieObserverStateWord)
 O_WHEEL = 0
 O_UPPER_LEG_TORQUE = 10

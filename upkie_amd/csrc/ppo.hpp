@@ -41,6 +41,17 @@
 //
 // Every launch argument is constant for a given (epoch, minibatch) position: counters, t, lr and the permutation live
 // in device memory, so the whole sequence can be captured in a hipGraph and replayed.
+//
+// Controlled form (PpoDev::ctrl != nullptr; the *_controlled entry points): the hyper-parameters that change during
+// training and SB3's target_kl early stop live in a control block of PPO_CTRL_WORDS fp64 words (include/upkie_hip.h):
+// launch A reads clip_range / clip_range_vf from it instead of its arguments; launch B's last block, after it wrote the
+// statistics row, sets `stopped` when approx_kl > 1.5 target_kl and then neither advances t nor forms the step; once
+// `stopped` is set every launch of the remaining minibatches returns at once (launch B writes a NaN statistics row),
+// so the weights, m, v and t are those after the last minibatch that ran. The flag is written by one launch and read
+// by later ones: stream order makes it visible, no fence is added. ppo_begin_kernel re-arms the block per update.
+//
+// Explained variance (ppo_explained_variance_kernel): 1 - Var(returns - values) / Var(returns) over the T N samples,
+// one block, the same two fp64 passes and LDS tree as launch 0.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -62,6 +73,16 @@ enum {
   PPO_LDS_MAX = 4 * 16 * (256 + 4 * 256 + 64 + 64),
   PPO_MAX_GRID = 512,          // blocks of launch A
   PPO_STATS = 4,               // per-block loss sums: min(surrogates), (R - v_pred)^2, approx_kl terms, clipped count
+  // the control block's fp64 words (UPKIE_PPO_CTRL_* of include/upkie_hip.h); lr and t where adam_scalars has them
+  PPO_CTRL_LR = 0,
+  PPO_CTRL_T = 1,
+  PPO_CTRL_CLIP_RANGE = 2,
+  PPO_CTRL_CLIP_RANGE_VF = 3,  // 0: no value clipping
+  PPO_CTRL_TARGET_KL = 4,      // 0: no early stop
+  PPO_CTRL_STOPPED = 5,        // 0 / 1
+  PPO_CTRL_N_UPDATES = 6,      // epochs entered since the block was zeroed (SB3's _n_updates)
+  PPO_CTRL_MINIBATCHES_RUN = 7,  // statistics rows written by this update (the minibatch that stopped it included)
+  PPO_CTRL_WORDS = 8,
 };
 static const int64_t PPO_PARTIAL_CAP_BYTES = 48ll << 20;  // partial gradients (the grid shrinks for large networks)
 
@@ -94,6 +115,7 @@ struct PpoDev {
   float* m;
   float* v;
   double* scalars;  // lr, t
+  double* ctrl;     // the control block (scalars is its first two words), or nullptr: every value is a launch argument
   float* stats;     // [7]
   unsigned* ticket;
   float* header;
@@ -287,12 +309,22 @@ __device__ __forceinline__ void ppo_store(float* my, int off, int tiles, const f
       for (int i = 0; i < 4; ++i) my[off + (16 * t + 4 * q + i) * 16 + r] = h[t][i];
 }
 
+// The clipping constants of launch A: its arguments, or (controlled form) the control block's words.
+struct PpoClip {
+  float lo, hi, range, vf;
+  int vf_on;
+};
+
+__device__ __forceinline__ float ppo_uniform(float x) {  // (a value every lane holds: keep it in a scalar register)
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
+}
+
 // One tower of one chunk: forward, loss, backward, dW. ACTOR: the policy loss through the Gaussian head (and log_std);
 // otherwise the value loss through the critic's dot head. `st` collects the loss sums of the lane's sample (lanes of
 // group 0 only).
 template <int WT, int ACT, bool ACTOR>
-__device__ __forceinline__ void ppo_tower(const PpoDev& P, float* stage, int sample, bool valid, float* part, bool first, double (&st)[PPO_STATS],
-                                          int wave, int lane) {
+__device__ __forceinline__ void ppo_tower(const PpoDev& P, const PpoClip& K, float* stage, int sample, bool valid, float* part, bool first,
+                                          double (&st)[PPO_STATS], int wave, int lane) {
   const int q = lane >> 4, r = lane & 15, tid = wave * 64 + lane;
   const MlpTowerDev& T = ACTOR ? P.net.actor : P.net.critic;
   const PpoStage& S = P.stage[ACTOR ? 0 : 1];
@@ -352,14 +384,14 @@ __device__ __forceinline__ void ppo_tower(const PpoDev& P, float* stage, int sam
       const float adv = (float)(((double)P.advantages[sample] - as[0]) / as[1]);
       const float log_ratio = lp - P.old_log_prob[sample];
       const float ratio = expf(log_ratio);
-      const float a1 = adv * ratio, a2 = adv * fminf(fmaxf(ratio, P.clip_lo), P.clip_hi);
+      const float a1 = adv * ratio, a2 = adv * fminf(fmaxf(ratio, K.lo), K.hi);
       const float w1 = a1 < a2 ? 1.f : a1 == a2 ? 0.5f : 0.f, w2 = 1.f - w1;
-      const float pass = ratio >= P.clip_lo && ratio <= P.clip_hi ? 1.f : 0.f;
+      const float pass = ratio >= K.lo && ratio <= K.hi ? 1.f : 0.f;
       const float g_lp = valid ? -inv_b * (w1 * adv + w2 * adv * pass) * ratio : 0.f;
       if (valid && q == 0) {
         st[0] += (double)fminf(a1, a2);
         st[2] += (double)((ratio - 1.f) - log_ratio);
-        st[3] += fabsf(ratio - 1.f) > P.clip_range ? 1.0 : 0.0;
+        st[3] += fabsf(ratio - 1.f) > K.range ? 1.0 : 0.0;
       }
       // head dZ = d loss / d mean, and the per-sample log_std terms, into the stage
 #pragma unroll
@@ -384,10 +416,10 @@ __device__ __forceinline__ void ppo_tower(const PpoDev& P, float* stage, int sam
       const float v = mlp_dot<WT>(packed, T.head, h, lane);
       const float old_v = P.old_values[sample], ret = P.returns[sample];
       float vp = v, pass = 1.f;
-      if (P.vf_clip) {
+      if (K.vf_on) {
         const float dv = v - old_v;
-        vp = old_v + fminf(fmaxf(dv, -P.clip_vf), P.clip_vf);
-        pass = dv >= -P.clip_vf && dv <= P.clip_vf ? 1.f : 0.f;
+        vp = old_v + fminf(fmaxf(dv, -K.vf), K.vf);
+        pass = dv >= -K.vf && dv <= K.vf ? 1.f : 0.f;
       }
       const float e = ret - vp;
       dz_dot = valid ? P.vf_coef * 2.f * (vp - ret) * inv_b * pass : 0.f;
@@ -446,6 +478,13 @@ __global__ __launch_bounds__(256) void ppo_grad_kernel(const PpoDev P) {
   float* part = P.partials + (size_t)blockIdx.x * P.train_words;
   float* my = stage + wave * P.tile_floats;
   double st[PPO_STATS] = {0.0, 0.0, 0.0, 0.0};
+  PpoClip K = {P.clip_lo, P.clip_hi, P.clip_range, P.clip_vf, P.vf_clip};
+  if (P.ctrl) {  // (uniform over the grid: one scalar load; the clip constants as ppo_fill forms them from the config)
+    if (P.ctrl[PPO_CTRL_STOPPED] != 0.0) return;
+    const float cr = (float)P.ctrl[PPO_CTRL_CLIP_RANGE], cv = (float)P.ctrl[PPO_CTRL_CLIP_RANGE_VF];
+    K.range = ppo_uniform(cr), K.lo = ppo_uniform((float)(1.0 - (double)cr)), K.hi = ppo_uniform((float)(1.0 + (double)cr));
+    K.vf = ppo_uniform(cv), K.vf_on = K.vf > 0.f;
+  }
   const int chunks = (ppo_tiles(P.mb_size) + P.nw - 1) / P.nw;
   for (int c = blockIdx.x; c < chunks; c += gridDim.x) {
     const bool first = c == (int)blockIdx.x;
@@ -470,8 +509,8 @@ __global__ __launch_bounds__(256) void ppo_grad_kernel(const PpoDev P) {
         }
       }
     }
-    ppo_tower<WT, ACT, true>(P, stage, sample, valid, part, first, st, wave, lane);
-    ppo_tower<WT, ACT, false>(P, stage, sample, valid, part, first, st, wave, lane);
+    ppo_tower<WT, ACT, true>(P, K, stage, sample, valid, part, first, st, wave, lane);
+    ppo_tower<WT, ACT, false>(P, K, stage, sample, valid, part, first, st, wave, lane);
   }
   // loss sums: a fixed shuffle tree per wave, then the waves in order
 #pragma unroll
@@ -493,6 +532,10 @@ __global__ __launch_bounds__(256) void ppo_grad_kernel(const PpoDev P) {
 __global__ __launch_bounds__(PPO_THREADS) void ppo_fold_kernel(const PpoDev P) {
   __shared__ double lds[PPO_THREADS + 1];
   const int tid = threadIdx.x, i = blockIdx.x * PPO_THREADS + tid;
+  if (P.ctrl && P.ctrl[PPO_CTRL_STOPPED] != 0.0) {  // (read before any block's ticket, written after the last: no race)
+    if (blockIdx.x == 0 && tid < 7) P.stats[tid] = __builtin_nanf("");
+    return;
+  }
   double sq = 0.0;
   if (i < P.train_words) {
     float s = 0.f;
@@ -543,9 +586,21 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fold_kernel(const PpoDev P) {
   P.stats[1] = (float)vl;
   P.stats[2] = (float)ent_loss;
   P.stats[3] = (float)(pg + (double)P.ent_coef * ent_loss + (double)P.vf_coef * vl);
-  P.stats[4] = (float)(sums[2] / n);
+  const float approx_kl = (float)(sums[2] / n);
+  P.stats[4] = approx_kl;
   P.stats[5] = (float)(sums[3] / n);
   P.stats[6] = (float)norm;
+  if (P.ctrl) {
+    // SB3: n_updates counts the epochs entered; the losses are logged, then approx_kl (a float32) is held to 1.5 target_kl
+    // and the update ends BEFORE this minibatch's optimiser step
+    if (P.mb_start == 0) P.ctrl[PPO_CTRL_N_UPDATES] += 1.0;
+    P.ctrl[PPO_CTRL_MINIBATCHES_RUN] += 1.0;
+    const double target_kl = P.ctrl[PPO_CTRL_TARGET_KL];
+    if (target_kl > 0.0 && (double)approx_kl > 1.5 * target_kl) {
+      P.ctrl[PPO_CTRL_STOPPED] = 1.0;
+      return;
+    }
+  }
   const double t = P.scalars[1] + 1.0;
   P.scalars[1] = t;
   P.header[4] = (float)coef;
@@ -558,6 +613,7 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fold_kernel(const PpoDev P) {
 // padding word. No ticket: launch B runs on the exchanged slots.
 __global__ __launch_bounds__(PPO_THREADS) void ppo_local_fold_kernel(const PpoDev P) {
   const int tid = threadIdx.x, i = blockIdx.x * PPO_THREADS + tid;
+  if (P.ctrl && P.ctrl[PPO_CTRL_STOPPED] != 0.0) return;  // (the slot keeps its last contents: launch B ignores them)
   if (i < P.train_words) {
     float s = 0.f;
     const float* p = P.partials + i;
@@ -586,6 +642,7 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_local_fold_kernel(const PpoDe
 __global__ __launch_bounds__(PPO_THREADS) void ppo_adam_kernel(const PpoDev P) {
   const int i = blockIdx.x * PPO_THREADS + threadIdx.x;
   if (i >= P.train_words) return;
+  if (P.ctrl && P.ctrl[PPO_CTRL_STOPPED] != 0.0) return;  // (set by this minibatch's launch B, or an earlier one)
   const float coef = P.header[4], step = P.header[5], bc2 = P.header[6];
   const int w = P.train_off + i;
   const float g = P.grad[i] * coef;
@@ -676,6 +733,81 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_adv_finish_kernel(int total, 
   for (int r = 1; r < world; ++r) g += slots[(size_t)r * 2 * M + j], q += slots[(size_t)r * 2 * M + M + j];
   const double mean = g / cnt;
   out[2 * j] = mean, out[2 * j + 1] = sqrt(q / (cnt - 1.0)) + 1e-8;
+}
+
+// Re-arms a control block at the start of an update: the early stop of the previous update is over.
+__global__ void ppo_begin_kernel(double* ctrl) {
+  if (threadIdx.x == 0) ctrl[PPO_CTRL_STOPPED] = 0.0, ctrl[PPO_CTRL_MINIBATCHES_RUN] = 0.0;
+}
+
+// Writes the host-set words of a control block (upkie_ppo_control_set).
+__global__ void ppo_control_set_kernel(double* ctrl, double lr, double clip_range, double clip_range_vf, double target_kl) {
+  if (threadIdx.x != 0) return;
+  ctrl[PPO_CTRL_LR] = lr, ctrl[PPO_CTRL_CLIP_RANGE] = clip_range;
+  ctrl[PPO_CTRL_CLIP_RANGE_VF] = clip_range_vf, ctrl[PPO_CTRL_TARGET_KL] = target_kl;
+}
+
+// One pass of the explained variance over the n samples: (sum of y, sum of d) with y = returns, d = returns - values,
+// or of their squared deviations about (mean_y, mean_d) when `square`; ppo_adv_pass's order: 8 loads in flight per
+// thread, then a fixed LDS tree per sum. Every thread of the block calls it and gets both sums.
+__device__ __forceinline__ void ppo_ev_pass(double (*lds)[PPO_ADV_THREADS], int n, const float* __restrict__ ret, const float* __restrict__ val,
+                                            bool square, double mean_y, double mean_d, double* sum_y, double* sum_d) {
+  const int tid = threadIdx.x;
+  double sy = 0.0, sd = 0.0;
+  for (int64_t i0 = tid; i0 < n; i0 += 8 * PPO_ADV_THREADS) {
+    double y[8], d[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int64_t i = i0 + k * PPO_ADV_THREADS;
+      const bool in = i < n;
+      const double r = in ? (double)ret[i] : 0.0, v = in ? (double)val[i] : 0.0;
+      y[k] = in ? r - (square ? mean_y : 0.0) : 0.0;
+      d[k] = in ? (r - v) - (square ? mean_d : 0.0) : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) sy += square ? y[k] * y[k] : y[k], sd += square ? d[k] * d[k] : d[k];
+  }
+  lds[0][tid] = sy, lds[1][tid] = sd;
+  for (int h = PPO_ADV_THREADS / 2; h > 0; h >>= 1) {
+    __syncthreads();
+    if (tid < h) lds[0][tid] += lds[0][tid + h], lds[1][tid] += lds[1][tid + h];
+  }
+  __syncthreads();
+  *sum_y = lds[0][0], *sum_d = lds[1][0];
+  __syncthreads();
+}
+
+// Explained variance of the critic (SB3's explained_variance(values, returns): population variances, NaN when
+// Var(returns) == 0), one block. phase < 0: everything on this rank's n samples, out[0] = the result. Data-parallel form
+// (every rank n samples, slots[r] = rank r's 4 doubles): phase 0 writes the local sums to mine[0..1]; phase 1 forms the
+// global means from the slots in rank order and writes the local squared deviations to mine[2..3]; phase 2 (no pass
+// over the samples) sums those in rank order and writes out[0].
+__global__ __launch_bounds__(PPO_ADV_THREADS) void ppo_explained_variance_kernel(int n, const float* __restrict__ ret, const float* __restrict__ val,
+                                                                                int phase, const double* __restrict__ slots, int world,
+                                                                                double* __restrict__ mine, double* __restrict__ out) {
+  __shared__ double lds[2][PPO_ADV_THREADS];
+  const double cnt = (double)(phase < 0 ? 1 : world) * n;
+  double sy = 0.0, sd = 0.0, qy = 0.0, qd = 0.0;
+  if (phase <= 0) {
+    ppo_ev_pass(lds, n, ret, val, false, 0.0, 0.0, &sy, &sd);
+    if (phase == 0) {
+      if (threadIdx.x == 0) mine[0] = sy, mine[1] = sd;
+      return;
+    }
+  } else {
+    for (int r = 0; r < world; ++r) sy += slots[4 * r], sd += slots[4 * r + 1];
+  }
+  if (phase < 0 || phase == 1) {
+    ppo_ev_pass(lds, n, ret, val, true, sy / cnt, sd / cnt, &qy, &qd);
+    if (phase == 1) {
+      if (threadIdx.x == 0) mine[2] = qy, mine[3] = qd;
+      return;
+    }
+  } else {
+    for (int r = 0; r < world; ++r) qy += slots[4 * r + 2], qd += slots[4 * r + 3];
+  }
+  const double var_y = qy / cnt, var_d = qd / cnt;
+  if (threadIdx.x == 0) out[0] = var_y == 0.0 ? (double)__builtin_nanf("") : 1.0 - var_d / var_y;
 }
 
 #endif  // __HIPCC__

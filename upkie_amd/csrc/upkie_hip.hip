@@ -1744,11 +1744,25 @@ static int hip_status(hipError_t err) {
   return UPKIE_OK;
 }
 
-extern "C" int upkie_ppo_minibatch_update(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
-                                          int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm, const float* obs,
-                                          const float* actions, const float* old_values, const float* old_log_prob, const float* advantages,
-                                          const float* returns, const double* adv_stats, float* packed, float* adam_m, float* adam_v,
-                                          double* adam_scalars, void* workspace, float* stats, void* stream) {
+// A control block: PPO_CTRL_WORDS doubles in device memory.
+static bool ppo_control_ok(const double* control) {
+  if (!control) {
+    g_create_error = "null control block";
+    return false;
+  }
+  if ((uintptr_t)control % 8 != 0) {
+    g_create_error = "the control block must be 8-byte aligned";
+    return false;
+  }
+  return true;
+}
+
+// upkie_ppo_minibatch_update (control == nullptr) and upkie_ppo_minibatch_update_controlled.
+static int ppo_minibatch_update(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
+                                int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm, const float* obs, const float* actions,
+                                const float* old_values, const float* old_log_prob, const float* advantages, const float* returns,
+                                const double* adv_stats, float* packed, float* adam_m, float* adam_v, double* adam_scalars, double* control,
+                                void* workspace, float* stats, void* stream) {
   upkie::PpoPlan plan;
   upkie::PpoDev P;
   if (!adam_m || !adam_v || !adam_scalars || !stats) {
@@ -1758,7 +1772,7 @@ extern "C" int upkie_ppo_minibatch_update(const UpkieMlpShape* shape, const Upki
   const int status = ppo_gradient_setup(shape, config, total, minibatch_start, minibatch_size, minibatch_size, max_minibatch, perm, obs, actions,
                                         old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, &P, &plan);
   if (status != UPKIE_OK) return status;
-  P.m = adam_m, P.v = adam_v, P.scalars = adam_scalars, P.stats = stats;
+  P.m = adam_m, P.v = adam_v, P.scalars = adam_scalars, P.ctrl = control, P.stats = stats;
   const hipStream_t s = (hipStream_t)stream;
   hipError_t err = ppo_launch_gradient(*shape, P, plan, s);
   if (err == hipSuccess) {
@@ -1769,6 +1783,71 @@ extern "C" int upkie_ppo_minibatch_update(const UpkieMlpShape* shape, const Upki
   return hip_status(err);
 }
 
+extern "C" int upkie_ppo_minibatch_update(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
+                                          int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm, const float* obs,
+                                          const float* actions, const float* old_values, const float* old_log_prob, const float* advantages,
+                                          const float* returns, const double* adv_stats, float* packed, float* adam_m, float* adam_v,
+                                          double* adam_scalars, void* workspace, float* stats, void* stream) {
+  return ppo_minibatch_update(shape, config, total, minibatch_start, minibatch_size, max_minibatch, perm, obs, actions, old_values, old_log_prob,
+                              advantages, returns, adv_stats, packed, adam_m, adam_v, adam_scalars, nullptr, workspace, stats, stream);
+}
+
+// ---- controlled form (a control block instead of adam_scalars; include/upkie_hip.h)
+extern "C" int upkie_ppo_minibatch_update_controlled(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total,
+                                                     int32_t minibatch_start, int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm,
+                                                     const float* obs, const float* actions, const float* old_values, const float* old_log_prob,
+                                                     const float* advantages, const float* returns, const double* adv_stats, float* packed,
+                                                     float* adam_m, float* adam_v, double* control, void* workspace, float* stats, void* stream) {
+  if (!ppo_control_ok(control)) return UPKIE_ERR_INVALID_ARGUMENT;
+  return ppo_minibatch_update(shape, config, total, minibatch_start, minibatch_size, max_minibatch, perm, obs, actions, old_values, old_log_prob,
+                              advantages, returns, adv_stats, packed, adam_m, adam_v, control, control, workspace, stats, stream);
+}
+
+extern "C" int upkie_ppo_control_set(double* control, double lr, double clip_range, double clip_range_vf, double target_kl, void* stream) {
+  if (!ppo_control_ok(control)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!(lr >= 0.0) || !std::isfinite(lr) || !(clip_range > 0.0) || !std::isfinite(clip_range) || !(clip_range_vf >= 0.0) ||
+      !std::isfinite(clip_range_vf) || !(target_kl >= 0.0) || !std::isfinite(target_kl)) {
+    g_create_error = "control: lr, clip_range_vf (0: none) and target_kl (0: none) must be finite and not negative, clip_range positive";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (upkie_hip_device_count() <= 0) {
+    g_create_error = "no HIP device visible";
+    return UPKIE_ERR_NO_DEVICE;
+  }
+  hipLaunchKernelGGL(upkie::ppo_control_set_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, control, lr, clip_range, clip_range_vf, target_kl);
+  return hip_status(hipGetLastError());
+}
+
+extern "C" int upkie_ppo_update_begin(double* control, void* stream) {
+  if (!ppo_control_ok(control)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (upkie_hip_device_count() <= 0) {
+    g_create_error = "no HIP device visible";
+    return UPKIE_ERR_NO_DEVICE;
+  }
+  hipLaunchKernelGGL(upkie::ppo_begin_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, control);
+  return hip_status(hipGetLastError());
+}
+
+extern "C" int upkie_ppo_explained_variance(int32_t total, const float* returns, const float* values, int32_t phase, const double* slots,
+                                            int32_t world, double* slot, double* out, void* stream) {
+  if (total < 1 || phase < -1 || phase > 2 || (phase >= 0 && world < 1)) {
+    g_create_error = "total and world must be positive, phase -1 (one rank), 0, 1 or 2";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (((phase < 0 || phase == 0 || phase == 1) && (!returns || !values)) || ((phase == 0 || phase == 1) && !slot) || (phase >= 1 && !slots) ||
+      ((phase < 0 || phase == 2) && !out)) {
+    g_create_error = "null argument";
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  }
+  if (upkie_hip_device_count() <= 0) {
+    g_create_error = "no HIP device visible";
+    return UPKIE_ERR_NO_DEVICE;
+  }
+  hipLaunchKernelGGL(upkie::ppo_explained_variance_kernel, dim3(1), dim3(upkie::PPO_ADV_THREADS), 0, (hipStream_t)stream, (int)total, returns,
+                     values, (int)phase, slots, (int)world, slot, out);
+  return hip_status(hipGetLastError());
+}
+
 // ---- data-parallel form (several ranks; include/upkie_hip.h)
 extern "C" int64_t upkie_ppo_slot_bytes(const UpkieMlpShape* shape) {
   upkie::PpoPlan plan;
@@ -1776,11 +1855,11 @@ extern "C" int64_t upkie_ppo_slot_bytes(const UpkieMlpShape* shape) {
   return 4 * (int64_t)upkie::ppo_slot_words(plan);
 }
 
-extern "C" int upkie_ppo_minibatch_gradient(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
-                                            int32_t minibatch_size, int32_t global_minibatch_size, int32_t max_minibatch, const int32_t* perm,
-                                            const float* obs, const float* actions, const float* old_values, const float* old_log_prob,
-                                            const float* advantages, const float* returns, const double* adv_stats, float* packed, void* workspace,
-                                            void* slot, void* stream) {
+static int ppo_minibatch_gradient(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
+                                  int32_t minibatch_size, int32_t global_minibatch_size, int32_t max_minibatch, const int32_t* perm,
+                                  const float* obs, const float* actions, const float* old_values, const float* old_log_prob,
+                                  const float* advantages, const float* returns, const double* adv_stats, float* packed, void* workspace,
+                                  void* slot, double* control, void* stream) {
   upkie::PpoPlan plan;
   upkie::PpoDev P;
   if (!slot) {
@@ -1791,6 +1870,7 @@ extern "C" int upkie_ppo_minibatch_gradient(const UpkieMlpShape* shape, const Up
                                         actions, old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, &P, &plan);
   if (status != UPKIE_OK) return status;
   P.slot = (float*)slot;
+  P.ctrl = control;
   const hipStream_t s = (hipStream_t)stream;
   hipError_t err = ppo_launch_gradient(*shape, P, plan, s);
   if (err == hipSuccess) {
@@ -1800,14 +1880,34 @@ extern "C" int upkie_ppo_minibatch_gradient(const UpkieMlpShape* shape, const Up
   return hip_status(err);
 }
 
-extern "C" int upkie_ppo_minibatch_apply(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t global_minibatch_size,
-                                         int32_t max_minibatch, const void* slots, int32_t world, float* packed, float* adam_m, float* adam_v,
-                                         double* adam_scalars, void* workspace, float* stats, void* stream) {
+extern "C" int upkie_ppo_minibatch_gradient(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
+                                            int32_t minibatch_size, int32_t global_minibatch_size, int32_t max_minibatch, const int32_t* perm,
+                                            const float* obs, const float* actions, const float* old_values, const float* old_log_prob,
+                                            const float* advantages, const float* returns, const double* adv_stats, float* packed, void* workspace,
+                                            void* slot, void* stream) {
+  return ppo_minibatch_gradient(shape, config, total, minibatch_start, minibatch_size, global_minibatch_size, max_minibatch, perm, obs, actions,
+                                old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, slot, nullptr, stream);
+}
+
+extern "C" int upkie_ppo_minibatch_gradient_controlled(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total,
+                                                       int32_t minibatch_start, int32_t minibatch_size, int32_t global_minibatch_size,
+                                                       int32_t max_minibatch, const int32_t* perm, const float* obs, const float* actions,
+                                                       const float* old_values, const float* old_log_prob, const float* advantages,
+                                                       const float* returns, const double* adv_stats, float* packed, void* workspace, void* slot,
+                                                       double* control, void* stream) {
+  if (!ppo_control_ok(control)) return UPKIE_ERR_INVALID_ARGUMENT;
+  return ppo_minibatch_gradient(shape, config, total, minibatch_start, minibatch_size, global_minibatch_size, max_minibatch, perm, obs, actions,
+                                old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, slot, control, stream);
+}
+
+static int ppo_minibatch_apply(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t minibatch_start, int32_t global_minibatch_size,
+                               int32_t max_minibatch, const void* slots, int32_t world, float* packed, float* adam_m, float* adam_v,
+                               double* adam_scalars, double* control, void* workspace, float* stats, void* stream) {
   upkie::PpoPlan plan;
   if (!ppo_shape_ok(shape, &plan)) return UPKIE_ERR_INVALID_ARGUMENT;
   if (!ppo_config_ok(config)) return UPKIE_ERR_INVALID_ARGUMENT;
-  if (global_minibatch_size < 1 || max_minibatch < 1 || world < 1) {
-    g_create_error = "global_minibatch_size, max_minibatch and world must be positive";
+  if (global_minibatch_size < 1 || max_minibatch < 1 || world < 1 || minibatch_start < 0) {
+    g_create_error = "global_minibatch_size, max_minibatch and world must be positive, minibatch_start not negative";
     return UPKIE_ERR_INVALID_ARGUMENT;
   }
   if (!slots || !packed || !adam_m || !adam_v || !adam_scalars || !workspace || !stats) {
@@ -1821,6 +1921,7 @@ extern "C" int upkie_ppo_minibatch_apply(const UpkieMlpShape* shape, const Upkie
   upkie::PpoDev P{};
   ppo_fill(P, *shape, plan, *config, max_minibatch, workspace);
   P.count = global_minibatch_size;
+  P.mb_start = minibatch_start, P.ctrl = control;
   P.grid = world;  // (launch B's partials: the slots, in rank order)
   const int words = upkie::ppo_slot_words(plan);
   P.partials = (float*)slots;
@@ -1832,6 +1933,22 @@ extern "C" int upkie_ppo_minibatch_apply(const UpkieMlpShape* shape, const Upkie
   hipLaunchKernelGGL(upkie::ppo_fold_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
   hipLaunchKernelGGL(upkie::ppo_adam_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
   return hip_status(hipGetLastError());
+}
+
+extern "C" int upkie_ppo_minibatch_apply(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t global_minibatch_size,
+                                         int32_t max_minibatch, const void* slots, int32_t world, float* packed, float* adam_m, float* adam_v,
+                                         double* adam_scalars, void* workspace, float* stats, void* stream) {
+  return ppo_minibatch_apply(shape, config, 0, global_minibatch_size, max_minibatch, slots, world, packed, adam_m, adam_v, adam_scalars, nullptr,
+                             workspace, stats, stream);
+}
+
+extern "C" int upkie_ppo_minibatch_apply_controlled(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t minibatch_start,
+                                                    int32_t global_minibatch_size, int32_t max_minibatch, const void* slots, int32_t world,
+                                                    float* packed, float* adam_m, float* adam_v, double* control, void* workspace, float* stats,
+                                                    void* stream) {
+  if (!ppo_control_ok(control)) return UPKIE_ERR_INVALID_ARGUMENT;
+  return ppo_minibatch_apply(shape, config, minibatch_start, global_minibatch_size, max_minibatch, slots, world, packed, adam_m, adam_v, control,
+                             control, workspace, stats, stream);
 }
 
 extern "C" int64_t upkie_ppo_advantage_slot_bytes(int32_t total, int32_t batch_size) {

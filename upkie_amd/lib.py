@@ -111,6 +111,12 @@ EXPORTED_SYMBOLS = (
     "upkie_ppo_advantage_finish",
     "upkie_ppo_minibatch_gradient",
     "upkie_ppo_minibatch_apply",
+    "upkie_ppo_control_set",
+    "upkie_ppo_update_begin",
+    "upkie_ppo_minibatch_update_controlled",
+    "upkie_ppo_minibatch_gradient_controlled",
+    "upkie_ppo_minibatch_apply_controlled",
+    "upkie_ppo_explained_variance",
     "upkie_mlp_bootstrap_time_limits",
     "upkie_episodes_workspace_bytes",
     "upkie_episodes_step",
@@ -411,6 +417,20 @@ def load() -> C.CDLL:
         lib.upkie_ppo_minibatch_gradient.argtypes = [shape_p, cfg_p] + [C.c_int32] * 5 + [vp] * 12
         lib.upkie_ppo_minibatch_apply.restype = C.c_int
         lib.upkie_ppo_minibatch_apply.argtypes = [shape_p, cfg_p, C.c_int32, C.c_int32, vp, C.c_int32] + [vp] * 7
+    if hasattr(lib, "upkie_ppo_minibatch_update_controlled"):  # (the control block: an older build lacks it, and still loads)
+        shape_p, cfg_p = C.POINTER(abi.UpkieMlpShape), C.POINTER(abi.UpkiePpoConfig)
+        lib.upkie_ppo_control_set.restype = C.c_int
+        lib.upkie_ppo_control_set.argtypes = [vp] + [C.c_double] * 4 + [vp]
+        lib.upkie_ppo_update_begin.restype = C.c_int
+        lib.upkie_ppo_update_begin.argtypes = [vp, vp]
+        lib.upkie_ppo_minibatch_update_controlled.restype = C.c_int
+        lib.upkie_ppo_minibatch_update_controlled.argtypes = [shape_p, cfg_p] + [C.c_int32] * 4 + [vp] * 15
+        lib.upkie_ppo_minibatch_gradient_controlled.restype = C.c_int
+        lib.upkie_ppo_minibatch_gradient_controlled.argtypes = [shape_p, cfg_p] + [C.c_int32] * 5 + [vp] * 13
+        lib.upkie_ppo_minibatch_apply_controlled.restype = C.c_int
+        lib.upkie_ppo_minibatch_apply_controlled.argtypes = [shape_p, cfg_p, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32] + [vp] * 7
+        lib.upkie_ppo_explained_variance.restype = C.c_int
+        lib.upkie_ppo_explained_variance.argtypes = [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp]
     if hasattr(lib, "upkie_mlp_bootstrap_time_limits"):  # (the time-limit bootstrap: an older build lacks it, and still loads)
         lib.upkie_mlp_bootstrap_time_limits.restype = C.c_int
         lib.upkie_mlp_bootstrap_time_limits.argtypes = [C.c_int32, C.POINTER(abi.UpkieMlpShape), vp, vp, vp, vp, C.c_double, vp, vp]

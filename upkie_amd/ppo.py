@@ -4,7 +4,8 @@ rollout kernel reads, so captured rollout graphs pick up the new weights with no
 include/upkie_hip.h states the arithmetic (SB3's, restated there)."""
 
 import ctypes as C
-from typing import Optional
+import math
+from typing import Callable, Optional, Union
 
 import torch
 
@@ -12,6 +13,14 @@ from . import abi, lib
 from .exceptions import UpkieRuntimeError
 
 STAT_NAMES = ("policy_gradient_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction", "grad_norm")
+Schedule = Union[float, Callable[[float], float]]  # a constant, or SB3's schedule: a function of progress_remaining (1 -> 0)
+
+
+def _at(schedule, progress: float) -> Optional[float]:
+    """The value of a schedule (a callable of progress_remaining, a number, or None) at `progress`."""
+    if schedule is None:
+        return None
+    return float(schedule(progress)) if callable(schedule) else float(schedule)
 
 
 def trainable_offset(shape) -> int:
@@ -58,11 +67,24 @@ class PpoTrainer:
     and steps Adam (``upkie_ppo_minibatch_gradient`` / ``upkie_ppo_minibatch_apply``). `prepare` checks, collectively,
     that every rank has the same sample count; `broadcast_parameters` makes the replicas start identical. With a group
     of one rank the results are the same bits as without a group. An update with a group cannot be captured in a graph.
-    Give each rank's policy its own seed (e.g. ``seed + rank``): its noise is keyed by the local env index."""
+    Give each rank's policy its own seed (e.g. ``seed + rank``): its noise is keyed by the local env index.
 
-    def __init__(self, policy, lr: float = 3e-4, n_epochs: int = 10, batch_size: int = 64, clip_range: float = 0.2,
-                 clip_range_vf: Optional[float] = None, normalize_advantage: bool = True, ent_coef: float = 0.0, vf_coef: float = 0.5,
-                 max_grad_norm: float = 0.5, obs_normalized: bool = False, seed: int = 0, process_group=None):
+    Schedules and ``target_kl`` (the controlled form): ``lr``, ``clip_range`` and ``clip_range_vf`` may be callables of
+    SB3's ``progress_remaining`` (1 at the start of training, 0 at its end), evaluated on the host by
+    `set_progress`, and ``target_kl`` ends an update at the first minibatch whose ``approx_kl > 1.5 * target_kl``,
+    before that minibatch's optimiser step, as SB3 does. With any of these (or ``controlled=True``) the trainer takes
+    the ``*_controlled`` entry points: the values live in a control block in device memory (`control`, whose first two
+    words are `scalars`), the stop is decided on the device, and the launches of the minibatches after it return at
+    once and leave NaN statistics rows. A captured `update` therefore stays valid across `set_progress`,
+    `set_clip_range`, `set_target_kl` and across iterations that stop at different minibatches. Without them the
+    trainer issues exactly the launches it always did. With a process group every rank takes the same decision from
+    the same exchanged bits; the collectives of the minibatches after a stop still run (the host cannot see the flag
+    without a synchronisation) and change nothing. `log` returns SB3's ``train/*`` record with one device-to-host copy."""
+
+    def __init__(self, policy, lr: Schedule = 3e-4, n_epochs: int = 10, batch_size: int = 64, clip_range: Schedule = 0.2,
+                 clip_range_vf: Optional[Schedule] = None, normalize_advantage: bool = True, ent_coef: float = 0.0, vf_coef: float = 0.5,
+                 max_grad_norm: float = 0.5, obs_normalized: bool = False, seed: int = 0, process_group=None,
+                 target_kl: Optional[float] = None, controlled: Optional[bool] = None):
         from .policies import MlpActorCritic
 
         if not isinstance(policy, MlpActorCritic):
@@ -71,10 +93,21 @@ class PpoTrainer:
             raise ValueError("PPO needs a critic: the policy has none")
         if int(n_epochs) < 1 or int(batch_size) < 1:
             raise ValueError("n_epochs and batch_size must be positive")
+        self._schedules = {"lr": lr, "clip_range": clip_range, "clip_range_vf": clip_range_vf}
+        self.progress_remaining = 1.0
+        lr, clip_range, clip_range_vf = (_at(x, 1.0) for x in (lr, clip_range, clip_range_vf))
         if not clip_range > 0.0 or not max_grad_norm > 0.0:
             raise ValueError("clip_range and max_grad_norm must be positive")
         if clip_range_vf is not None and not clip_range_vf > 0.0:
             raise ValueError("clip_range_vf must be positive (or None)")
+        if target_kl is not None and not (float(target_kl) > 0.0 and math.isfinite(float(target_kl))):
+            raise ValueError("target_kl must be positive and finite (or None)")
+        uses = target_kl is not None or any(callable(x) for x in self._schedules.values())
+        if controlled is not None and not controlled and uses:
+            raise ValueError("target_kl and schedules need the controlled form (leave controlled unset)")
+        self.controlled = uses if controlled is None else bool(controlled)
+        self._clip_range, self._clip_range_vf = clip_range, clip_range_vf
+        self._target_kl = float(target_kl) if target_kl is not None else None
         self.policy = policy
         self.device = policy.device
         self.n_epochs, self.batch_size = int(n_epochs), int(batch_size)
@@ -93,7 +126,19 @@ class PpoTrainer:
         f32 = dict(dtype=torch.float32, device=self.device)
         self.m = torch.zeros(words, **f32)
         self.v = torch.zeros(words, **f32)
-        self.scalars = torch.tensor([float(lr), 0.0], dtype=torch.float64, device=self.device)  # lr, t
+        if self.controlled and not hasattr(self._lib, "upkie_ppo_minibatch_update_controlled"):
+            raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_ppo_minibatch_update_controlled: rebuild it for target_kl "
+                                    "and schedules")
+        # the control block (include/upkie_hip.h: UPKIE_PPO_CTRL_*); `scalars` (lr, t) is its first two words
+        self.control = torch.zeros(abi.PPO_CTRL_WORDS, dtype=torch.float64, device=self.device)
+        self.control[abi.PPO_CTRL_LR] = float(lr)
+        self.scalars = self.control[:2]
+        self._lr = float(lr)
+        if self.controlled:
+            self._write_control(float(lr))
+        self._values = None  # (the buffer's value tensor: explained_variance reads it)
+        self._log_words = torch.zeros(2, dtype=torch.float64, device=self.device)  # explained variance, std
+        self._ev_exchange = None
         self.generator = torch.Generator(device=self.device)
         self.generator.manual_seed(int(seed))
         self._total = None
@@ -109,6 +154,7 @@ class PpoTrainer:
             if not hasattr(self._lib, "upkie_ppo_minibatch_apply"):
                 raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_ppo_minibatch_apply: rebuild it for a process group")
             self._grad_exchange = SlotExchange(int(self._lib.upkie_ppo_slot_bytes(C.byref(policy.shape))) // 4, self.device, process_group)
+            self._ev_exchange = SlotExchange(8, self.device, process_group)  # (4 doubles per rank)
 
     # ---- buffers, allocated by the first train() (one rollout size per trainer)
     def _allocate(self, total: int) -> None:
@@ -169,6 +215,7 @@ class PpoTrainer:
             self._buffer = self._addresses(buffer)
         elif self._addresses(buffer) != self._buffer:
             raise ValueError("this trainer serves one rollout buffer (a captured update reads its tensors): build another trainer")
+        self._values = buffer.values
         self.advantages.copy_(buffer.advantages.reshape(total))
         self.returns.copy_(buffer.returns.reshape(total))
         self.shuffle()
@@ -195,6 +242,7 @@ class PpoTrainer:
         trainable = self.policy.packed[off:]
         for t in (trainable, self.m, self.v, self.scalars):
             broadcast_tensor_(t, src, self.process_group)
+        self._lr = None
         self.sync_modules()
 
     def shuffle(self) -> None:
@@ -224,8 +272,14 @@ class PpoTrainer:
             if sync:
                 self.sync_modules()
             return self.stats
+        # (the controlled entry point has upkie_ppo_minibatch_update's signature, the control block where adam_scalars is)
+        minibatch = lb.upkie_ppo_minibatch_update_controlled if self.controlled else lb.upkie_ppo_minibatch_update
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
+            if self.controlled:
+                status = lb.upkie_ppo_update_begin(p(self.control), stream)
+                if status < 0:
+                    lib.check(status, None)
             for e in range(self.n_epochs):
                 perm = self.perm[e]
                 status = lb.upkie_ppo_advantage_stats(total, self._mb, p(perm), adv, int(self.normalize_advantage), p(self.adv_stats[e]), stream)
@@ -233,9 +287,9 @@ class PpoTrainer:
                     lib.check(status, None)
                 for j in range(self.n_minibatches):
                     start = j * self._mb
-                    status = lb.upkie_ppo_minibatch_update(
+                    status = minibatch(
                         shape, cfg, total, start, min(self._mb, total - start), self._mb, p(perm), obs, act, vals, logp, adv, ret,
-                        p(self.adv_stats[e, j]), p(self.policy.packed), p(self.m), p(self.v), p(self.scalars), p(self.workspace),
+                        p(self.adv_stats[e, j]), p(self.policy.packed), p(self.m), p(self.v), p(self.control), p(self.workspace),
                         p(self.stats[e, j]), stream)
                     if status < 0:
                         lib.check(status, None)
@@ -255,6 +309,8 @@ class PpoTrainer:
 
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
+            if self.controlled:
+                ok(lb.upkie_ppo_update_begin(p(self.control), stream))
             for e in range(self.n_epochs):
                 perm = p(self.perm[e])
                 ok(lb.upkie_ppo_advantage_partials(total, mb, perm, adv, 0, None, W, p(ax.mine), stream))
@@ -265,6 +321,15 @@ class PpoTrainer:
                 for j in range(self.n_minibatches):
                     start = j * mb
                     size = min(mb, total - start)
+                    if self.controlled:
+                        ok(lb.upkie_ppo_minibatch_gradient_controlled(shape, cfg, total, start, size, W * size, mb, perm, obs, act, vals, logp, adv,
+                                                                      ret, p(self.adv_stats[e, j]), p(self.policy.packed), p(self.workspace),
+                                                                      p(gx.mine), p(self.control), stream))
+                        gx.exchange()  # (after a stop: still a collective every rank joins; the apply half ignores it)
+                        ok(lb.upkie_ppo_minibatch_apply_controlled(shape, cfg, start, W * size, mb, p(gx.slots), W, p(self.policy.packed),
+                                                                   p(self.m), p(self.v), p(self.control), p(self.workspace), p(self.stats[e, j]),
+                                                                   stream))
+                        continue
                     ok(lb.upkie_ppo_minibatch_gradient(shape, cfg, total, start, size, W * size, mb, perm, obs, act, vals, logp, adv, ret,
                                                        p(self.adv_stats[e, j]), p(self.policy.packed), p(self.workspace), p(gx.mine), stream))
                     gx.exchange()
@@ -280,6 +345,117 @@ class PpoTrainer:
     def set_lr(self, lr: float) -> None:
         """Write the learning rate (a device word: a captured update reads the new value)."""
         self.scalars[0].fill_(float(lr))
+        self._lr = float(lr)
+
+    # ---- the control block (schedules, target_kl)
+    def _need_control(self, what: str) -> None:
+        if not self.controlled:
+            raise UpkieRuntimeError(f"{what} needs the controlled form: build the trainer with target_kl, a schedule or controlled=True "
+                                    "(its update then reads the control block)")
+
+    def _write_control(self, lr: float) -> None:
+        """lr, clip_range, clip_range_vf and target_kl to the control block (one launch; outside any capture)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise UpkieRuntimeError("set the schedules' values outside a graph capture (a captured write would replay its old value)")
+        with torch.cuda.device(self.device):
+            status = self._lib.upkie_ppo_control_set(self.control.data_ptr(), float(lr), float(self._clip_range), float(self._clip_range_vf or 0.0),
+                                                     float(self._target_kl or 0.0), torch.cuda.current_stream(self.device).cuda_stream)
+        if status < 0:
+            lib.check(status, None)
+        self._lr = float(lr)
+
+    def set_progress(self, progress_remaining: float) -> None:
+        """SB3's ``_update_current_progress_remaining`` + ``_update_learning_rate``: evaluate the callables among ``lr``,
+        ``clip_range`` and ``clip_range_vf`` at ``progress_remaining`` on the host and write the words a captured update
+        reads. Constants stay as they are (a `set_lr` / `set_clip_range` value included)."""
+        progress = float(progress_remaining)
+        self.progress_remaining = progress
+        sch = self._schedules
+        if not any(callable(x) for x in sch.values()):
+            return
+        self._need_control("a schedule")
+        lr = _at(sch["lr"], progress) if callable(sch["lr"]) else None
+        if callable(sch["clip_range"]):
+            self._clip_range = _at(sch["clip_range"], progress)
+        if callable(sch["clip_range_vf"]):
+            self._clip_range_vf = _at(sch["clip_range_vf"], progress)
+        self._write_control(self._current_lr() if lr is None else lr)
+
+    def _current_lr(self) -> float:
+        if self._lr is None:  # (the word came from another rank: read it once)
+            self._lr = float(self.scalars[0].item())
+        return self._lr
+
+    def set_clip_range(self, clip_range: float, clip_range_vf: Optional[float] = None) -> None:
+        """Write ``clip_range`` (and ``clip_range_vf``; None: no value clipping) for the next update."""
+        self._need_control("set_clip_range")
+        if not float(clip_range) > 0.0 or (clip_range_vf is not None and not float(clip_range_vf) > 0.0):
+            raise ValueError("clip_range and clip_range_vf must be positive")
+        self._clip_range, self._clip_range_vf = float(clip_range), None if clip_range_vf is None else float(clip_range_vf)
+        self._write_control(self._current_lr())
+
+    def set_target_kl(self, target_kl: Optional[float]) -> None:
+        """Write ``target_kl`` for the next update; None switches the early stop off."""
+        self._need_control("set_target_kl")
+        if target_kl is not None and not (float(target_kl) > 0.0 and math.isfinite(float(target_kl))):
+            raise ValueError("target_kl must be positive and finite (or None)")
+        self._target_kl = None if target_kl is None else float(target_kl)
+        self._write_control(self._current_lr())
+
+    def explained_variance(self) -> torch.Tensor:
+        """SB3's ``explained_variance(values, returns)`` of the last `prepare`'s rollout (fp64, one launch, a device word;
+        with a process group over every rank's samples: two exchanges, so every rank calls it)."""
+        if self._values is None:
+            raise UpkieRuntimeError("call prepare(buffer) first")
+        if not hasattr(self._lib, "upkie_ppo_explained_variance"):
+            raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_ppo_explained_variance: rebuild it")
+        lb, ret, val, out, ex = self._lib, self.returns.data_ptr(), self._values.data_ptr(), self._log_words.data_ptr(), self._ev_exchange
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            if ex is None:
+                steps = [(-1, None, 1, None)]
+            else:
+                steps = [(0, None, ex.world, ex.mine.data_ptr()), (1, ex.slots.data_ptr(), ex.world, ex.mine.data_ptr()),
+                         (2, ex.slots.data_ptr(), ex.world, None)]
+            for phase, slots, world, mine in steps:
+                status = lb.upkie_ppo_explained_variance(self._total, ret, val, phase, slots, world, mine, out, stream)
+                if status < 0:
+                    lib.check(status, None)
+                if phase in (0, 1):
+                    ex.exchange()
+        return self._log_words[0]
+
+    def log(self) -> dict:
+        """SB3's ``train/*`` record of the last update, with ONE device-to-host copy: the seven `STAT_NAMES` averaged over
+        the minibatches that ran (NaN rows, those after an early stop, excluded; SB3 logs ``np.mean`` over every minibatch
+        of the update for each, ``approx_kl`` and ``clip_fraction`` included), ``explained_variance``, ``std``
+        (``exp(log_std).mean()``), ``n_updates``, ``clip_range``, ``clip_range_vf`` when set, ``learning_rate`` and
+        ``early_stopped_at``: the (epoch, minibatch) whose ``approx_kl`` ended the update, or None."""
+        if self._total is None:
+            raise UpkieRuntimeError("call train(buffer) first")
+        self.explained_variance()
+        off, A = trainable_offset(self.policy.shape), int(self.policy.shape.act_dim)
+        torch.mean(torch.exp(self.policy.packed[off:off + A]).double(), dim=0, out=self._log_words[1])
+        host = torch.cat([self.stats.reshape(-1).double(), self.control, self._log_words]).cpu().numpy()  # the one copy
+        n = self.stats.numel()
+        rows, ctrl, words = host[:n].reshape(-1, len(STAT_NAMES)), host[n:n + abi.PPO_CTRL_WORDS], host[n + abi.PPO_CTRL_WORDS:]
+        ran = rows[~(rows != rows).any(axis=1)]
+        record = {name: float(ran[:, k].mean()) if len(ran) else math.nan for k, name in enumerate(STAT_NAMES)}
+        stopped = self.controlled and ctrl[abi.PPO_CTRL_STOPPED] != 0.0
+        record.update(explained_variance=float(words[0]), std=float(words[1]), n_updates=self._n_updates(ctrl),
+                      clip_range=float(ctrl[abi.PPO_CTRL_CLIP_RANGE]) if self.controlled else float(self._clip_range),
+                      learning_rate=float(ctrl[abi.PPO_CTRL_LR]),
+                      early_stopped_at=divmod(int(ctrl[abi.PPO_CTRL_MINIBATCHES_RUN]) - 1, self.n_minibatches) if stopped else None)
+        if self._clip_range_vf is not None:
+            record["clip_range_vf"] = float(ctrl[abi.PPO_CTRL_CLIP_RANGE_VF]) if self.controlled else float(self._clip_range_vf)
+        return record
+
+    def _n_updates(self, ctrl) -> int:
+        """SB3's ``_n_updates``: the control block counts the epochs entered; without it every epoch of every update ran,
+        so it is the step count over the minibatches per epoch."""
+        if self.controlled:
+            return int(ctrl[abi.PPO_CTRL_N_UPDATES])
+        return int(ctrl[abi.PPO_CTRL_T]) // self.n_minibatches if self._total is not None else 0
 
     def sync_modules(self) -> None:
         """Write the packed weights back into the tensors the policy was built from (the modules' parameters, or the
@@ -314,10 +490,243 @@ class PpoTrainer:
 
     def state_dict(self) -> dict:
         """Adam's state: ``m`` and ``v`` as lists in ``policy.sources()`` order of the trainable tensors (log_std, then
-        weight and bias per layer of the actor and of the critic), the step count ``t`` and ``lr``."""
-        return {"m": self._unpack(self.m), "v": self._unpack(self.v), "t": int(self.scalars[1].item()), "lr": float(self.scalars[0].item())}
+        weight and bias per layer of the actor and of the critic), the step count ``t``, ``lr`` and ``n_updates`` (SB3's
+        ``_n_updates``: the epochs entered)."""
+        ctrl = self.control.cpu().numpy()
+        return {"m": self._unpack(self.m), "v": self._unpack(self.v), "t": int(ctrl[abi.PPO_CTRL_T]), "lr": float(ctrl[abi.PPO_CTRL_LR]),
+                "n_updates": self._n_updates(ctrl)}
 
     def load_state_dict(self, sd: dict) -> None:
         self._pack(sd["m"], self.m)
         self._pack(sd["v"], self.v)
         self.scalars.copy_(torch.tensor([float(sd["lr"]), float(sd["t"])], dtype=torch.float64))
+        self.control[abi.PPO_CTRL_N_UPDATES] = float(sd.get("n_updates", 0))
+        self._lr = float(sd["lr"])
+
+
+class Ppo:
+    """Stable-Baselines3's ``PPO(...).learn(...)`` on the device: the driver that owns the `RolloutBuffer`, the
+    `RunningNormalizer` (``normalize``), the `EpisodeStatistics`, the `PpoTrainer` and the rollout's `GraphedLoop`, and
+    runs them in the order examples/ppo_mlp_train_time_limits.py establishes. One rollout step is: store the episode
+    starts; ``policy.act`` (normalised observation, action, value and log-prob straight into the buffer); ``env.step``;
+    the reward (``reward_fn(next_obs, info)``, default the env's own); ``episodes.step`` on the raw reward;
+    ``normalizer.step`` (normalised reward and the next episode starts); the time-limit bootstrap
+    (``bootstrap_time_limits``). With ``graph=True`` an iteration is two graph replays (the ``n_steps`` rollout steps,
+    the update) around GAE and ``trainer.prepare``; capturing the rollout runs ONE real warm-up step first, as
+    `GraphedLoop` does, which is not counted in ``num_timesteps``. With a ``process_group`` (data-parallel: every rank
+    its own env, policy replica and `Ppo`) nothing is captured, because the normaliser and the update exchange slots
+    through collectives; ``num_timesteps`` then counts this rank's steps.
+
+    `learn` follows ``OnPolicyAlgorithm.learn``: ``num_timesteps += n_envs`` per step; after each rollout
+    ``progress_remaining = 1 - num_timesteps / total_timesteps`` goes to the trainer's schedules (`set_progress`) BEFORE
+    the update; every ``log_interval`` iterations one `PpoTrainer.log` (one device-to-host copy) plus
+    ``rollout/ep_rew_mean``, ``rollout/ep_len_mean``, ``time/total_timesteps`` and ``time/iterations`` make a record,
+    appended to ``records`` and given to ``callback(model, record)`` (called every iteration, ``record`` None off the
+    interval); a callback that returns False ends training, as SB3's does. ``learning_rate``, ``clip_range`` and
+    ``clip_range_vf`` take floats or callables of ``progress_remaining``; ``target_kl`` as SB3.
+
+    `save` / `load` carry everything the next iteration reads -- packed weights, Adam's moments and control block, the
+    trainer's generator, the policy's per-env noise counters, the normaliser, the episode statistics, the episode
+    starts, the counters and the env (the simulation's state block, its observation and step outputs) -- so a run
+    resumed in fresh objects continues bit for bit. Schedules and ``reward_fn`` are code: give them to `load` again."""
+
+    def __init__(self, env, policy, n_steps: int = 128, gamma: float = 0.99, gae_lambda: float = 0.95, n_epochs: int = 10, batch_size: int = 64,
+                 learning_rate: Schedule = 3e-4, clip_range: Schedule = 0.2, clip_range_vf: Optional[Schedule] = None,
+                 normalize_advantage: bool = True, ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5,
+                 target_kl: Optional[float] = None, normalize: bool = True, bootstrap_time_limits: bool = True, stats_window_size: int = 100,
+                 reward_fn: Optional[Callable] = None, graph: bool = True, seed: int = 0, process_group=None):
+        if int(n_steps) < 1:
+            raise ValueError("n_steps must be positive")
+        self.env, self.policy = env, policy
+        self.n_envs = int(env.num_envs)
+        self.n_steps, self.gamma, self.gae_lambda = int(n_steps), float(gamma), float(gae_lambda)
+        self.normalize, self.bootstrap, self.window = bool(normalize), bool(bootstrap_time_limits), int(stats_window_size)
+        self.reward_fn, self.seed, self.process_group = reward_fn, int(seed), process_group
+        self.graph = bool(graph) and process_group is None
+        self._trainer_args = dict(lr=learning_rate, n_epochs=n_epochs, batch_size=batch_size, clip_range=clip_range, clip_range_vf=clip_range_vf,
+                                  normalize_advantage=normalize_advantage, ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm,
+                                  target_kl=target_kl, obs_normalized=self.normalize, seed=seed, process_group=process_group)
+        self.num_timesteps, self.iterations, self.total_timesteps, self.progress_remaining = 0, 0, 0, 1.0
+        self.records = []
+        self.trainer = self.buffer = self.normalizer = self.episodes = None
+        self._loop = self._update_graph = None
+
+    # ---- the objects, built by the first learn() (or by load())
+    def _setup(self) -> None:
+        if self.buffer is not None:
+            return
+        from .episodes import EpisodeStatistics
+        from .normalize import RunningNormalizer
+        from .rollout import RolloutBuffer
+
+        env, pol, N, T = self.env, self.policy, self.n_envs, self.n_steps
+        dev = self.device = env.device
+        D, A = int(pol.shape.obs_dim), int(pol.shape.act_dim)
+        if self.normalize:
+            kw = {} if self.process_group is None else {"process_group": self.process_group}
+            self.normalizer = RunningNormalizer.for_env(env, gamma=self.gamma, **kw)
+            self.normalizer.attach(pol)
+        self.episodes = EpisodeStatistics(N, window=self.window, device=dev)
+        self.trainer = PpoTrainer(pol, **self._trainer_args)
+        if self.process_group is not None:
+            self.trainer.broadcast_parameters(0)
+            if self.normalizer is not None:
+                self.normalizer.broadcast_statistics(0)
+        self.buffer = RolloutBuffer(T, N, obs_shape=(D,), action_shape=(A,), device=dev, gamma=self.gamma, gae_lambda=self.gae_lambda)
+        reset = env.reset(seed=self.seed) if self.process_group is None else env.reset()
+        self._obs = getattr(env, "observation", None)
+        if self._obs is None:
+            self._obs = reset[0] if isinstance(reset, tuple) else reset
+        if self.normalizer is not None:
+            self.normalizer.reset(self._obs)
+        self._env_action = torch.empty(N, A, device=dev)
+        self._starts = torch.ones(N, dtype=torch.uint8, device=dev)
+        self._slot = self.n_steps - 1 if self.graph else 0  # (the capture's warm-up step takes the last slot)
+        if self.graph:
+            from .graphs import GraphedLoop
+
+            self._loop = GraphedLoop(self._rollout_step, unroll=T, warmup=1, device=dev)
+
+    def _rollout_step(self) -> None:
+        t, buf, pol, starts = self._slot, self.buffer, self.policy, self._starts
+        obs = self._obs
+        buf.episode_starts[t].copy_(starts)
+        out = {"action": buf.actions[t], "value": buf.values[t], "log_prob": buf.log_probs[t], "env_action": self._env_action}
+        if self.normalizer is not None:
+            out["norm_obs"] = buf.observations[t]
+        else:
+            buf.observations[t].copy_(obs)
+        action = pol.act(obs, out=out)[0]
+        stepped = self.env.step(action)
+        next_obs, reward, terminated, truncated = stepped[:4]
+        info = stepped[4] if len(stepped) > 4 else {}
+        if next_obs is not obs:  # (an env without a persistent observation buffer)
+            self._obs = next_obs
+        if self.reward_fn is not None:
+            reward = self.reward_fn(next_obs, info)
+        self.episodes.step(reward, terminated, truncated)  # Monitor: the raw reward
+        if self.normalizer is not None:
+            self.normalizer.step(next_obs, reward, terminated, truncated, out={"reward": buf.rewards[t], "episode_starts": starts})
+        else:
+            buf.rewards[t].copy_(reward)
+            torch.bitwise_or(terminated, truncated, out=starts)
+        if self.bootstrap:
+            final_obs = info.get("final_obs") if hasattr(info, "get") else None
+            if final_obs is None:
+                raise UpkieRuntimeError("bootstrap_time_limits needs info['final_obs'] (an env with autoreset_mode='same_step'); "
+                                        "or build Ppo with bootstrap_time_limits=False")
+            pol.bootstrap_time_limits(final_obs, terminated, truncated, buf.rewards[t], self.gamma)
+        self._slot = (t + 1) % self.n_steps
+
+    def collect_rollouts(self) -> None:
+        """``n_steps`` steps of every env into the buffer, then GAE (SB3's ``collect_rollouts``)."""
+        if self._loop is not None:
+            self._loop.replay()
+        else:
+            for _ in range(self.n_steps):
+                self._rollout_step()
+        self.num_timesteps += self.n_steps * self.n_envs
+        buf = self.buffer
+        buf.pos, buf.full = self.n_steps, True
+        buf.compute_returns_and_advantage(last_values=self.policy.value(self._obs), dones=self._starts)
+
+    def train(self) -> None:
+        """SB3's ``PPO.train`` on the collected rollout: `PpoTrainer.prepare`, then the update (a graph replay when
+        ``graph``)."""
+        tr = self.trainer
+        tr.prepare(self.buffer)
+        if not self.graph:
+            tr.update(self.buffer)
+            return
+        if self._update_graph is None:
+            state = [t.clone() for t in (self.policy.packed, tr.m, tr.v, tr.control, tr.stats)]
+            tr.update(self.buffer)  # (warm-up off the capture, undone below: the first replay is the first update)
+            torch.cuda.synchronize(self.device)
+            self._update_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._update_graph):
+                tr.update(self.buffer)
+            for dst, src in zip((self.policy.packed, tr.m, tr.v, tr.control, tr.stats), state):
+                dst.copy_(src)
+        self._update_graph.replay()
+
+    def learn(self, total_timesteps: int, callback: Optional[Callable] = None, log_interval: int = 1, reset_num_timesteps: bool = True):
+        """Train for ``total_timesteps`` env steps (whole iterations of ``n_steps * n_envs``, as SB3). With
+        ``reset_num_timesteps=False`` training continues: ``total_timesteps`` more steps, ``progress_remaining`` over
+        the sum, as SB3's ``_setup_learn``. Returns self."""
+        self._setup()
+        if reset_num_timesteps:
+            self.num_timesteps, self.iterations = 0, 0
+            self.total_timesteps = int(total_timesteps)
+        else:
+            self.total_timesteps = int(total_timesteps) + self.num_timesteps
+        while self.num_timesteps < self.total_timesteps:
+            self.collect_rollouts()
+            self.iterations += 1
+            self.progress_remaining = 1.0 - float(self.num_timesteps) / float(self.total_timesteps)
+            self.trainer.set_progress(self.progress_remaining)
+            self.train()
+            record = None
+            if log_interval and self.iterations % int(log_interval) == 0:
+                record = {f"train/{k}": v for k, v in self.trainer.log().items()}
+                record.update({"rollout/ep_rew_mean": self.episodes.ep_rew_mean(), "rollout/ep_len_mean": self.episodes.ep_len_mean(),
+                               "time/total_timesteps": self.num_timesteps, "time/iterations": self.iterations})
+                self.records.append(record)
+            if callback is not None and callback(self, record) is False:
+                break
+        return self
+
+    # ---- saving and loading
+    def _env_tensors(self):
+        sim = getattr(self.env, "sim", None)
+        named = {n: getattr(sim, n, None) for n in ("state", "reward", "terminated", "truncated", "contact_manifold", "observer_state")}
+        named["observation"] = self._obs
+        named["final_obs"] = getattr(self.env, "_final_obs", None)
+        return {k: v for k, v in named.items() if isinstance(v, torch.Tensor)}
+
+    def _state_tensors(self):
+        tr, ep = self.trainer, self.episodes
+        named = {"packed": self.policy.packed, "m": tr.m, "v": tr.v, "control": tr.control, "calls": self.policy.calls, "starts": self._starts,
+                 "ep_return": ep.ep_return, "ep_length": ep.ep_length, "ring_return": ep.ring_return, "ring_length": ep.ring_length,
+                 "ep_counters": ep.counters, "ep_means": ep.means}
+        named.update({f"env.{k}": v for k, v in self._env_tensors().items()})
+        return {k: v for k, v in named.items() if v is not None}
+
+    def save(self, path) -> None:
+        """``torch.save`` of the training state (tensors and numbers only)."""
+        self._setup()
+        torch.cuda.synchronize(self.device)
+        tr = self.trainer
+        sd = {"tensors": {k: v.cpu() for k, v in self._state_tensors().items()}, "generator": tr.generator.get_state().cpu(),
+              "normalizer": self.normalizer.state_dict() if self.normalizer is not None else None,
+              "counters": {"num_timesteps": self.num_timesteps, "iterations": self.iterations, "total_timesteps": self.total_timesteps,
+                           "progress_remaining": self.progress_remaining, "policy_seed": int(self.policy.seed)},
+              "trainer": {"clip_range": tr._clip_range, "clip_range_vf": tr._clip_range_vf, "target_kl": tr._target_kl, "lr": tr._current_lr()},
+              "sizes": {"n_envs": self.n_envs, "n_steps": self.n_steps}}
+        torch.save(sd, path)
+
+    @classmethod
+    def load(cls, path, env, policy, **kwargs):
+        """A `Ppo` on fresh ``env`` and ``policy`` objects (same sizes, same keyword arguments as the saved one) that
+        continues the saved run: ``learn(more, reset_num_timesteps=False)``."""
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        model = cls(env, policy, **kwargs)
+        if sd["sizes"] != {"n_envs": model.n_envs, "n_steps": model.n_steps}:
+            raise ValueError(f"the file holds a run of {sd['sizes']}, this one is {model.n_envs} envs x {model.n_steps} steps")
+        model._setup()
+        policy.reseed(sd["counters"]["policy_seed"])
+        tr = model.trainer
+        for name, dst in model._state_tensors().items():
+            if name not in sd["tensors"]:
+                raise ValueError(f"the file has no {name}: it was saved from another kind of env or policy")
+            dst.copy_(sd["tensors"][name])
+        tr.generator.set_state(sd["generator"])
+        if model.normalizer is not None:
+            model.normalizer.load_state_dict(sd["normalizer"])
+        c = sd["counters"]
+        model.num_timesteps, model.iterations, model.total_timesteps = c["num_timesteps"], c["iterations"], c["total_timesteps"]
+        model.progress_remaining = c["progress_remaining"]
+        t = sd["trainer"]
+        tr._clip_range, tr._clip_range_vf, tr._target_kl, tr._lr = t["clip_range"], t["clip_range_vf"], t["target_kl"], t["lr"]
+        tr.progress_remaining = model.progress_remaining
+        tr.sync_modules()
+        return model
