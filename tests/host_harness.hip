@@ -1,6 +1,6 @@
 // Test-only: runs the product's device functions on the HOST so that a single
 // physics substep can be compared with the oracle without a GPU.
-// (step_kernels.hpp + host_setup.hpp, not upkie_hip.hip: no launch, so no kernel is instantiated and this builds in seconds)
+// (step_kernels.hpp + host_setup.hpp, not the C-ABI's units: no launch, so no kernel is instantiated and this builds in seconds)
 #include <string>
 
 #include "../upkie_amd/csrc/host_setup.hpp"

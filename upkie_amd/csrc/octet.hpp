@@ -48,7 +48,7 @@
 // run as eight threads in lockstep and every exchange goes through a shared
 // slot array between two barriers.
 //
-// Included by upkie_hip.hip inside namespace upkie, after pair.hpp.
+// Included by step_kernels.hpp inside namespace upkie, after pair.hpp.
 #pragma once
 
 // ---------------------------------------------------------------- lane exchange

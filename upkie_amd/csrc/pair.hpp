@@ -13,7 +13,7 @@
 // (the left/right block of the contact matrix) is computed by the right lane
 // and copied, so both lanes hold bit-identical base quantities throughout.
 //
-// Included by upkie_hip.hip inside namespace upkie, after the one-lane kernel
+// Included by step_kernels.hpp inside namespace upkie, after the one-lane kernel
 // (it reuses DevConfig, Servo, joint_torque, sample_init_state, philox_*).
 #pragma once
 

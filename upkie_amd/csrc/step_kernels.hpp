@@ -1,7 +1,8 @@
 // step_kernels.hpp -- the fused env.step() kernels (one, two and eight lanes per env) and what they share: the
 // settings blocks, Philox streams, the servo torque law, the action and observation maps. Included by upkie_hip.hip (the
-// C-ABI, which only DECLARES the instantiations it launches: step_instances.hpp) and by step_instances.hip (which
-// defines them, one group per translation unit so that the library builds on all cores).
+// simulator's unit of the C-ABI, which only DECLARES the instantiations it launches: step_instances.hpp), by
+// step_instances.hip (which defines them, one group per translation unit so that the library builds on all cores) and,
+// for the Philox rounds alone, by policy_mlp.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 

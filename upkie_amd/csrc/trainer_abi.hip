@@ -1,0 +1,270 @@
+// trainer_abi.hip -- handle-free entry points of include/upkie_hip.h around a rollout: the MLP actor-critic policy, the
+// time-limit bootstrap, episode statistics, VecNormalize, the linear policy and GAE. Host code around the kernels of the
+// headers below; nothing here takes or touches a simulator, MPC or observer handle (upkie_hip.hip). The PPO update, the
+// other heavy set of kernel instantiations, is ppo_abi.hip's.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cstdint>
+
+#include "mlp_instances.hpp"
+#include "rollout.hpp"
+#include "vecnorm.hpp"
+#include "time_limits.hpp"
+#include "episodes.hpp"
+
+#include "abi_host.hpp"
+
+// ============================================================ MLP actor-critic policy
+extern "C" int64_t upkie_mlp_packed_words(const UpkieMlpShape* shape) {
+  if (!shape) return fail(UPKIE_ERR_INVALID_ARGUMENT, "null shape");
+  const int64_t words = upkie::mlp_layout(*shape, nullptr);
+  if (words >= 0) return words;
+  return fail(UPKIE_ERR_INVALID_ARGUMENT,
+              "MLP shape out of range (obs_dim 1-256, act_dim 1-64, 1-4 actor / 0-4 critic layers of 1-256 units, tanh or relu, clip_obs > 0)");
+}
+
+extern "C" int upkie_mlp_actor_critic(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* obs, uint32_t* calls,
+                                      uint64_t seed, int32_t deterministic, float* norm_obs, float* mean, float* action, float* env_action,
+                                      float* value, float* log_prob, void* stream) {
+  if (num_envs <= 0) return fail(UPKIE_ERR_INVALID_ARGUMENT, "num_envs must be positive");
+  if (!shape || !packed || !obs) return fail(UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  upkie::MlpDev P;
+  if (upkie::mlp_layout(*shape, &P) < 0)
+    return (int)upkie_mlp_packed_words(shape);  // (sets the message)
+  P.num_envs = num_envs;
+  P.run_actor = mean || action || env_action || log_prob;
+  P.run_critic = value != nullptr;
+  P.sample = P.run_actor && !deterministic;
+  if (P.run_critic && shape->critic_layers == 0) return fail(UPKIE_ERR_INVALID_ARGUMENT, "a value output needs a critic (critic_layers > 0)");
+  if (P.sample && !calls) return fail(UPKIE_ERR_INVALID_ARGUMENT, "sampling needs the per-env call counters");
+  P.seed_lo = (unsigned)(seed & 0xffffffffu);
+  P.seed_hi = (unsigned)(seed >> 32);
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  if (!P.run_actor && !P.run_critic && !norm_obs) return UPKIE_OK;
+  const upkie::MlpOutputs out{norm_obs, mean, action, env_action, value, log_prob};
+  const dim3 grid((unsigned)((num_envs + 15) / 16));
+  for_mlp_instance(*shape, [&](auto w, auto act) {
+    hipLaunchKernelGGL((upkie::mlp_actor_critic_kernel<w(), act()>), grid, dim3(128), 0, (hipStream_t)stream, P, packed, obs, calls, out);
+  });
+  return launch_status();
+}
+
+// ============================================================ time-limit bootstrap (SB3 collect_rollouts)
+extern "C" int upkie_mlp_bootstrap_time_limits(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* final_obs,
+                                               const uint8_t* terminated, const uint8_t* truncated, double gamma, float* reward, void* stream) {
+  if (num_envs <= 0) return fail(UPKIE_ERR_INVALID_ARGUMENT, "num_envs must be positive");
+  if (!shape || !packed || !final_obs || !truncated || !reward)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "null argument (shape, packed, final_obs, truncated and reward are required)");
+  upkie::MlpDev P;
+  if (upkie::mlp_layout(*shape, &P) < 0)
+    return (int)upkie_mlp_packed_words(shape);  // (sets the message)
+  if (shape->critic_layers == 0) return fail(UPKIE_ERR_INVALID_ARGUMENT, "the time-limit bootstrap needs a critic (critic_layers > 0)");
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(UPKIE_ERR_INVALID_ARGUMENT, "gamma must be in [0, 1]");
+  P.num_envs = num_envs;
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  const dim3 grid((unsigned)((num_envs + 15) / 16));
+  const float g32 = (float)gamma;
+  for_mlp_instance(*shape, [&](auto w, auto act) {
+    hipLaunchKernelGGL((upkie::mlp_bootstrap_time_limits_kernel<w(), act()>), grid, dim3(64), 0, (hipStream_t)stream, P, packed, final_obs,
+                       terminated, truncated, g32, reward);
+  });
+  return launch_status();
+}
+
+// ============================================================ episode statistics (SB3 Monitor + ep_info_buffer)
+static int check_episodes_shape(int32_t num_envs, int32_t window) {
+  if (num_envs <= 0 || window < 1 || window > upkie::EPISODES_MAX_WINDOW)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "num_envs must be positive and window in 1-65536");
+  return UPKIE_OK;
+}
+
+extern "C" int64_t upkie_episodes_workspace_bytes(int32_t num_envs) {
+  if (check_episodes_shape(num_envs, 1)) return UPKIE_ERR_INVALID_ARGUMENT;
+  return upkie::episodes_workspace_bytes(num_envs);
+}
+
+extern "C" int upkie_episodes_step(int32_t num_envs, int32_t window, const float* reward, const uint8_t* terminated, const uint8_t* truncated,
+                                   double* ep_return, int32_t* ep_length, double* ring_return, int32_t* ring_length, int64_t* counters,
+                                   double* means, void* workspace, void* stream) {
+  if (check_episodes_shape(num_envs, window)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!reward || !ep_return || !ep_length || !ring_return || !ring_length || !counters || !means || !workspace)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "null argument (only terminated and truncated may be NULL)");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  upkie::EpisodesDev P{};
+  P.num_envs = num_envs;
+  P.window = window;
+  P.blocks = upkie::episodes_blocks(num_envs, &P.rows);
+  P.reward = reward, P.terminated = terminated, P.truncated = truncated;
+  P.ep_return = ep_return, P.ep_length = ep_length, P.ring_return = ring_return, P.ring_length = ring_length;
+  P.counters = counters, P.means = means;
+  char* ws = (char*)workspace;
+  P.ticket = (unsigned*)ws;
+  P.counts = (int32_t*)(ws + upkie::EPISODES_COUNTS_OFFSET);
+  P.fin_return = (double*)(ws + upkie::EPISODES_COUNTS_OFFSET + upkie::EPISODES_MAX_BLOCKS * 4);
+  P.fin_length = (int32_t*)(ws + upkie::EPISODES_COUNTS_OFFSET + upkie::EPISODES_MAX_BLOCKS * 4 + (int64_t)num_envs * 8);
+  hipLaunchKernelGGL(upkie::episodes_step_kernel, dim3((unsigned)P.blocks), dim3(upkie::EPISODES_THREADS), 0, (hipStream_t)stream, P);
+  return launch_status();
+}
+
+extern "C" int upkie_episodes_reset(int32_t num_envs, const uint8_t* mask, double* ep_return, int32_t* ep_length, void* stream) {
+  if (check_episodes_shape(num_envs, 1)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!ep_return || !ep_length) return fail(UPKIE_ERR_INVALID_ARGUMENT, "null accumulator buffer");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  const int grid = std::min((num_envs + upkie::EPISODES_THREADS - 1) / upkie::EPISODES_THREADS, 1024);
+  hipLaunchKernelGGL(upkie::episodes_reset_kernel, dim3((unsigned)grid), dim3(upkie::EPISODES_THREADS), 0, (hipStream_t)stream, num_envs, mask,
+                     ep_return, ep_length);
+  return launch_status();
+}
+
+// ============================================================ running normalisation (VecNormalize)
+static int check_vecnorm_shape(int32_t num_envs, int32_t obs_dim) {
+  if (num_envs <= 0 || obs_dim < 1 || obs_dim > 256 || (int64_t)num_envs * obs_dim > INT_MAX)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "num_envs must be positive and obs_dim in 1-256 (num_envs * obs_dim below 2^31)");
+  return UPKIE_OK;
+}
+
+extern "C" int64_t upkie_vecnorm_workspace_bytes(int32_t num_envs, int32_t obs_dim) {
+  if (check_vecnorm_shape(num_envs, obs_dim)) return UPKIE_ERR_INVALID_ARGUMENT;
+  const int blocks = upkie::vecnorm_blocks(num_envs, obs_dim, nullptr);
+  return upkie::VECNORM_PARTIALS_OFFSET + (int64_t)blocks * 2 * (obs_dim + 1) * (int64_t)sizeof(double);
+}
+
+// The launch arguments of upkie_vecnorm_step (and of its data-parallel halves) after the argument checks; returns
+// UPKIE_OK or the error status. *moments / *apply: whether launch A / launch B runs.
+static int vecnorm_setup(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
+                         const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace, int32_t flags,
+                         double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32, float* std_f32, float* packed_stats,
+                         float* norm_obs, float* norm_reward, uint8_t* episode_starts, upkie::VecNormDev* out, bool* moments_out, bool* apply_out) {
+  if (check_vecnorm_shape(num_envs, obs_dim)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (flags & ~(UPKIE_VECNORM_TRAINING | UPKIE_VECNORM_NORM_OBS | UPKIE_VECNORM_NORM_REWARD | UPKIE_VECNORM_RESET))
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "unknown vecnorm flags");
+  if (!(gamma >= 0.0 && gamma <= 1.0) || !(epsilon > 0.0) || !(clip_obs > 0.0) || !(clip_reward > 0.0))
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "gamma must be in [0, 1], epsilon, clip_obs and clip_reward positive");
+  const bool training = flags & UPKIE_VECNORM_TRAINING, reset = flags & UPKIE_VECNORM_RESET;
+  upkie::VecNormDev P{};
+  P.num_envs = num_envs;
+  P.obs_dim = obs_dim;
+  P.packed_dp = (obs_dim + 3) / 4 * 4;
+  P.obs_cols = training && (flags & UPKIE_VECNORM_NORM_OBS) ? obs_dim : 0;
+  P.ret_col = training && !reset ? 1 : 0;
+  P.reset = reset;
+  P.norm_obs = (flags & UPKIE_VECNORM_NORM_OBS) != 0;
+  P.norm_reward = (flags & UPKIE_VECNORM_NORM_REWARD) != 0;
+  const bool moments = P.obs_cols + P.ret_col > 0;
+  const bool apply = !moments || norm_obs || (norm_reward && P.norm_reward);
+  P.outputs_in_moments = moments && !apply;
+  if (!obs_stats || !ret_stats || !returns || !mean_f32 || !std_f32)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "null statistics, returns or fp32 mirror buffer");
+  if ((P.obs_cols || norm_obs) && !obs) return fail(UPKIE_ERR_INVALID_ARGUMENT, "updating or normalising observations needs obs");
+  if ((P.ret_col || norm_reward) && !reward) return fail(UPKIE_ERR_INVALID_ARGUMENT, "updating the returns or writing norm_reward needs reward");
+  if (moments && !workspace) return fail(UPKIE_ERR_INVALID_ARGUMENT, "training needs the workspace");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  P.blocks = upkie::vecnorm_blocks(num_envs, obs_dim, &P.rows);
+  P.gamma = gamma, P.eps = epsilon, P.clip_obs = clip_obs, P.clip_reward = clip_reward;
+  P.obs = obs, P.reward = reward, P.terminated = terminated, P.truncated = truncated;
+  P.obs_stats = obs_stats, P.ret_stats = ret_stats, P.returns = returns;
+  P.ticket = (unsigned*)workspace;
+  P.partials = workspace ? (double*)((char*)workspace + upkie::VECNORM_PARTIALS_OFFSET) : nullptr;
+  P.mean_f32 = mean_f32, P.std_f32 = std_f32, P.packed = packed_stats;
+  P.norm_obs_out = norm_obs, P.reward_out = norm_reward, P.starts_out = episode_starts;
+  *out = P;
+  *moments_out = moments;
+  *apply_out = apply;
+  return UPKIE_OK;
+}
+
+static void vecnorm_launch_apply(const upkie::VecNormDev& P, hipStream_t s) {
+  const int64_t work = P.norm_obs_out ? (int64_t)P.num_envs * P.obs_dim : P.num_envs;
+  const int64_t grid = std::min<int64_t>((work + upkie::VECNORM_THREADS - 1) / upkie::VECNORM_THREADS, 1024);
+  hipLaunchKernelGGL(upkie::vecnorm_apply_kernel, dim3((unsigned)grid), dim3(upkie::VECNORM_THREADS), 0, s, P);
+}
+
+extern "C" int upkie_vecnorm_step(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
+                                  const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace, int32_t flags,
+                                  double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32, float* std_f32,
+                                  float* packed_stats, float* norm_obs, float* norm_reward, uint8_t* episode_starts, void* stream) {
+  upkie::VecNormDev P;
+  bool moments, apply;
+  const int status = vecnorm_setup(num_envs, obs_dim, obs, reward, terminated, truncated, obs_stats, ret_stats, returns, workspace, flags, gamma,
+                                   epsilon, clip_obs, clip_reward, mean_f32, std_f32, packed_stats, norm_obs, norm_reward, episode_starts, &P,
+                                   &moments, &apply);
+  if (status != UPKIE_OK) return status;
+  const hipStream_t s = (hipStream_t)stream;
+  if (moments) hipLaunchKernelGGL(upkie::vecnorm_moments_kernel, dim3((unsigned)P.blocks), dim3(upkie::VECNORM_THREADS), 0, s, P);
+  if (apply) vecnorm_launch_apply(P, s);
+  return launch_status();
+}
+
+// Whether a step with these flags moves a statistic (launch A runs): the steps of the data-parallel form.
+static bool vecnorm_moves(int32_t flags) {
+  return (flags & UPKIE_VECNORM_TRAINING) && ((flags & UPKIE_VECNORM_NORM_OBS) || !(flags & UPKIE_VECNORM_RESET));
+}
+
+extern "C" int64_t upkie_vecnorm_slot_bytes(int32_t obs_dim) {
+  if (obs_dim < 1 || obs_dim > 256) return fail(UPKIE_ERR_INVALID_ARGUMENT, "obs_dim must be in 1-256");
+  return 8 * (int64_t)upkie::vecnorm_slot_doubles(obs_dim);
+}
+
+extern "C" int upkie_vecnorm_moments_local(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
+                                           const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace,
+                                           int32_t flags, double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32,
+                                           float* std_f32, float* packed_stats, float* norm_obs, float* norm_reward, uint8_t* episode_starts,
+                                           double* slot, void* stream) {
+  if (!vecnorm_moves(flags) || !slot)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT,
+                "upkie_vecnorm_moments_local needs a step that moves a statistic (TRAINING, and NORM_OBS or not RESET) and a slot");
+  upkie::VecNormDev P;
+  bool moments, apply;
+  const int status = vecnorm_setup(num_envs, obs_dim, obs, reward, terminated, truncated, obs_stats, ret_stats, returns, workspace, flags, gamma,
+                                   epsilon, clip_obs, clip_reward, mean_f32, std_f32, packed_stats, norm_obs, norm_reward, episode_starts, &P,
+                                   &moments, &apply);
+  if (status != UPKIE_OK) return status;
+  P.slot = slot;
+  hipLaunchKernelGGL(upkie::vecnorm_moments_kernel, dim3((unsigned)P.blocks), dim3(upkie::VECNORM_THREADS), 0, (hipStream_t)stream, P);
+  return launch_status();
+}
+
+extern "C" int upkie_vecnorm_merge(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
+                                   const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace, int32_t flags,
+                                   double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32, float* std_f32,
+                                   float* packed_stats, float* norm_obs, float* norm_reward, uint8_t* episode_starts, const double* slots,
+                                   int32_t world, void* stream) {
+  if (!vecnorm_moves(flags) || !slots || world < 1)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "upkie_vecnorm_merge needs a step that moves a statistic, the exchanged slots and world >= 1");
+  upkie::VecNormDev P;
+  bool moments, apply;
+  const int status = vecnorm_setup(num_envs, obs_dim, obs, reward, terminated, truncated, obs_stats, ret_stats, returns, workspace, flags, gamma,
+                                   epsilon, clip_obs, clip_reward, mean_f32, std_f32, packed_stats, norm_obs, norm_reward, episode_starts, &P,
+                                   &moments, &apply);
+  if (status != UPKIE_OK) return status;
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(upkie::vecnorm_merge_kernel, dim3(1), dim3(upkie::VECNORM_THREADS), 0, s, P, slots, (int)world,
+                     upkie::vecnorm_slot_doubles(obs_dim));
+  if (apply) vecnorm_launch_apply(P, s);
+  return launch_status();
+}
+
+// ============================================================ rollout consumer
+extern "C" int upkie_linear_policy(int32_t num_envs, int32_t obs_dim, int32_t act_dim, const float* obs, const float* weights, const float* bias,
+                                  double clip, float* act, void* stream) {
+  if (num_envs <= 0 || obs_dim <= 0 || act_dim <= 0) return fail(UPKIE_ERR_INVALID_ARGUMENT, "num_envs, obs_dim and act_dim must be positive");
+  if (!obs || !weights || !act) return fail(UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  hipLaunchKernelGGL(upkie::linear_policy_kernel, dim3((unsigned)((num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, num_envs, obs_dim,
+                     act_dim, obs, weights, bias, (float)clip, act);
+  return launch_status();
+}
+
+extern "C" int upkie_rollout_gae(int32_t num_steps, int32_t num_envs, const float* rewards, const float* values,
+                                 const uint8_t* episode_starts, const float* last_values, const uint8_t* last_dones, double gamma,
+                                 double gae_lambda, float* advantages, float* returns, void* stream) {
+  if (num_steps <= 0 || num_envs <= 0) return fail(UPKIE_ERR_INVALID_ARGUMENT, "num_steps and num_envs must be positive");
+  if (!rewards || !values || !episode_starts || !last_values || !last_dones || !advantages || !returns)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  hipLaunchKernelGGL(upkie::gae_kernel, dim3((unsigned)((num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, num_steps, num_envs,
+                     rewards, values, episode_starts, last_values, last_dones, (float)gamma, (float)gae_lambda, advantages, returns);
+  return launch_status();
+}

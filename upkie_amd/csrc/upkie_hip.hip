@@ -1,11 +1,6 @@
-// upkie_hip.hip -- fused env.step() kernels for gfx950 and the C-ABI of
-// include/upkie_hip.h.
-//
-// One launch = one env.step() of B environments: each lane loads its env's
-// state words (struct-of-arrays, coalesced), runs the action map, the
-// nb_substeps x {6 servo torques -> physics substep} loop entirely in
-// registers, and writes state + observation + flags back. Model and config
-// constants are kernel arguments (scalar loads, SGPR-resident).
+// upkie_hip.hip -- the simulator half of the C-ABI of include/upkie_hip.h: the UpkieSim, UpkieMpc and UpkieObservers
+// handles, the choice and launch of the step kernels (compiled by groups from step_instances.hip) and the small kernels
+// around them (observe, contact queries, randomisation). The handle-free trainer entry points are trainer_abi.hip's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,16 +13,10 @@
 #include <string>
 #include <type_traits>
 
-#include "policy_mlp.hpp"
-#include "rollout.hpp"
-#include "vecnorm.hpp"
-#include "ppo.hpp"
-#include "time_limits.hpp"
-#include "episodes.hpp"
-
 #include "step_kernels.hpp"
 #include "step_instances.hpp"  // (the step kernels this unit launches are compiled elsewhere, by groups: declarations only)
 #include "host_setup.hpp"
+#include "abi_host.hpp"
 
 namespace upkie {
 
@@ -315,12 +304,11 @@ struct UpkieSim {
   std::string error;
 };
 
-static thread_local std::string g_create_error;
+thread_local std::string g_create_error;  // (abi_host.hpp)
 
 static int fail(UpkieSim* sim, int status, const std::string& msg) {
   if (sim) sim->error = msg;
-  g_create_error = msg;
-  return status;
+  return fail(status, msg);
 }
 
 static int check_hip(UpkieSim* sim, hipError_t err, const char* what) {
@@ -358,7 +346,7 @@ extern "C" int upkie_hip_device_count(void) {
 extern "C" int upkie_sim_create(const UpkieSimConfig* config, const UpkieModel* model, UpkieSim** out) {
   if (!config || !model || !out) return fail(nullptr, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
   *out = nullptr;
-  if (upkie_hip_device_count() <= 0) return fail(nullptr, UPKIE_ERR_NO_DEVICE, "no HIP device visible");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
   UpkieSim* sim = new (std::nothrow) UpkieSim();
   if (!sim) return fail(nullptr, UPKIE_ERR_INVALID_ARGUMENT, "out of host memory");
   std::string why;
@@ -943,8 +931,7 @@ struct UpkieMpc {
 
 static int mpc_fail(UpkieMpc* mpc, int status, const std::string& msg) {
   if (mpc) mpc->error = msg;
-  g_create_error = msg;
-  return status;
+  return fail(status, msg);
 }
 
 extern "C" int upkie_mpc_create(const UpkieMpcConfig* config, UpkieMpc** out) {
@@ -956,7 +943,7 @@ extern "C" int upkie_mpc_create(const UpkieMpcConfig* config, UpkieMpc** out) {
     return mpc_fail(nullptr, UPKIE_ERR_INVALID_ARGUMENT, "admm_relaxation must lie in (0, 2) (0: unset, the plain iteration)");
   if (config->nb_timesteps > 64)
     return mpc_fail(nullptr, UPKIE_ERR_INVALID_ARGUMENT, "nb_timesteps > 64 is not supported by the HIP path");
-  if (upkie_hip_device_count() <= 0) return mpc_fail(nullptr, UPKIE_ERR_NO_DEVICE, "no HIP device visible");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
   UpkieMpc* mpc = new (std::nothrow) UpkieMpc();
   if (!mpc) return mpc_fail(nullptr, UPKIE_ERR_INVALID_ARGUMENT, "out of host memory");
   mpc->tiles = (config->nb_timesteps + 15) / 16;
@@ -1114,8 +1101,7 @@ struct UpkieObservers {
 
 static int observers_fail(UpkieObservers* h, int status, const std::string& msg) {
   if (h) h->error = msg;
-  g_create_error = msg;
-  return status;
+  return fail(status, msg);
 }
 
 // UpkieObserverConfig -> device parameters for a spine period `dt`; false (with
@@ -1162,7 +1148,7 @@ extern "C" int upkie_observers_create(const UpkieObserverConfig* c, UpkieObserve
   upkie::ObserverDev dev;
   std::string why;
   if (!convert_observer_config(c, c->dt, &dev, &why)) return observers_fail(nullptr, UPKIE_ERR_INVALID_ARGUMENT, why);
-  if (upkie_hip_device_count() <= 0) return observers_fail(nullptr, UPKIE_ERR_NO_DEVICE, "no HIP device visible");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
   UpkieObservers* h = new (std::nothrow) UpkieObservers();
   if (!h) return observers_fail(nullptr, UPKIE_ERR_INVALID_ARGUMENT, "out of host memory");
   h->dev = dev;
@@ -1219,832 +1205,4 @@ extern "C" int upkie_observers_step(UpkieObservers* h, float* state, const Upkie
                      *in, *out);
   hipError_t err = hipGetLastError();
   return err == hipSuccess ? UPKIE_OK : observers_fail(h, UPKIE_ERR_HIP, hipGetErrorString(err));
-}
-
-// ============================================================ MLP actor-critic policy
-extern "C" int64_t upkie_mlp_packed_words(const UpkieMlpShape* shape) {
-  if (!shape) {
-    g_create_error = "null shape";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  const int64_t words = upkie::mlp_layout(*shape, nullptr);
-  if (words < 0) g_create_error = "MLP shape out of range (obs_dim 1-256, act_dim 1-64, 1-4 actor / 0-4 critic layers of 1-256 units, tanh or relu, clip_obs > 0)";
-  return words < 0 ? UPKIE_ERR_INVALID_ARGUMENT : words;
-}
-
-template <int W>
-static void launch_mlp(int activation, dim3 grid, hipStream_t stream, const upkie::MlpDev& P, const float* packed, const float* obs,
-                       uint32_t* calls, const upkie::MlpOutputs& out) {
-  if (activation == UPKIE_MLP_TANH)
-    hipLaunchKernelGGL((upkie::mlp_actor_critic_kernel<W, UPKIE_MLP_TANH>), grid, dim3(128), 0, stream, P, packed, obs, calls, out);
-  else
-    hipLaunchKernelGGL((upkie::mlp_actor_critic_kernel<W, UPKIE_MLP_RELU>), grid, dim3(128), 0, stream, P, packed, obs, calls, out);
-}
-
-extern "C" int upkie_mlp_actor_critic(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* obs, uint32_t* calls,
-                                      uint64_t seed, int32_t deterministic, float* norm_obs, float* mean, float* action, float* env_action,
-                                      float* value, float* log_prob, void* stream) {
-  if (num_envs <= 0) {
-    g_create_error = "num_envs must be positive";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (!shape || !packed || !obs) {
-    g_create_error = "null argument";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  upkie::MlpDev P;
-  if (upkie::mlp_layout(*shape, &P) < 0)
-    return (int)upkie_mlp_packed_words(shape);  // (sets the message)
-  P.num_envs = num_envs;
-  P.run_actor = mean || action || env_action || log_prob;
-  P.run_critic = value != nullptr;
-  P.sample = P.run_actor && !deterministic;
-  if (P.run_critic && shape->critic_layers == 0) {
-    g_create_error = "a value output needs a critic (critic_layers > 0)";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (P.sample && !calls) {
-    g_create_error = "sampling needs the per-env call counters";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  P.seed_lo = (unsigned)(seed & 0xffffffffu);
-  P.seed_hi = (unsigned)(seed >> 32);
-  if (upkie_hip_device_count() <= 0) {
-    g_create_error = "no HIP device visible";
-    return UPKIE_ERR_NO_DEVICE;
-  }
-  if (!P.run_actor && !P.run_critic && !norm_obs) return UPKIE_OK;
-  const upkie::MlpOutputs out{norm_obs, mean, action, env_action, value, log_prob};
-  const dim3 grid((unsigned)((num_envs + 15) / 16));
-  const hipStream_t s = (hipStream_t)stream;
-  switch (upkie::mlp_width_class(*shape)) {
-    case 16: launch_mlp<16>(shape->activation, grid, s, P, packed, obs, calls, out); break;
-    case 32: launch_mlp<32>(shape->activation, grid, s, P, packed, obs, calls, out); break;
-    case 64: launch_mlp<64>(shape->activation, grid, s, P, packed, obs, calls, out); break;
-    case 128: launch_mlp<128>(shape->activation, grid, s, P, packed, obs, calls, out); break;
-    default: launch_mlp<256>(shape->activation, grid, s, P, packed, obs, calls, out); break;
-  }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    g_create_error = hipGetErrorString(err);
-    return UPKIE_ERR_HIP;
-  }
-  return UPKIE_OK;
-}
-
-// ============================================================ time-limit bootstrap (SB3 collect_rollouts)
-template <int W>
-static void launch_bootstrap(int activation, dim3 grid, hipStream_t stream, const upkie::MlpDev& P, const float* packed, const float* final_obs,
-                             const uint8_t* terminated, const uint8_t* truncated, float gamma, float* reward) {
-  if (activation == UPKIE_MLP_TANH)
-    hipLaunchKernelGGL((upkie::mlp_bootstrap_time_limits_kernel<W, UPKIE_MLP_TANH>), grid, dim3(64), 0, stream, P, packed, final_obs, terminated,
-                       truncated, gamma, reward);
-  else
-    hipLaunchKernelGGL((upkie::mlp_bootstrap_time_limits_kernel<W, UPKIE_MLP_RELU>), grid, dim3(64), 0, stream, P, packed, final_obs, terminated,
-                       truncated, gamma, reward);
-}
-
-extern "C" int upkie_mlp_bootstrap_time_limits(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* final_obs,
-                                               const uint8_t* terminated, const uint8_t* truncated, double gamma, float* reward, void* stream) {
-  if (num_envs <= 0) {
-    g_create_error = "num_envs must be positive";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (!shape || !packed || !final_obs || !truncated || !reward) {
-    g_create_error = "null argument (shape, packed, final_obs, truncated and reward are required)";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  upkie::MlpDev P;
-  if (upkie::mlp_layout(*shape, &P) < 0)
-    return (int)upkie_mlp_packed_words(shape);  // (sets the message)
-  if (shape->critic_layers == 0) {
-    g_create_error = "the time-limit bootstrap needs a critic (critic_layers > 0)";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (!(gamma >= 0.0 && gamma <= 1.0)) {
-    g_create_error = "gamma must be in [0, 1]";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  P.num_envs = num_envs;
-  if (upkie_hip_device_count() <= 0) {
-    g_create_error = "no HIP device visible";
-    return UPKIE_ERR_NO_DEVICE;
-  }
-  const dim3 grid((unsigned)((num_envs + 15) / 16));
-  const hipStream_t s = (hipStream_t)stream;
-  const float g32 = (float)gamma;
-  switch (upkie::mlp_width_class(*shape)) {
-    case 16: launch_bootstrap<16>(shape->activation, grid, s, P, packed, final_obs, terminated, truncated, g32, reward); break;
-    case 32: launch_bootstrap<32>(shape->activation, grid, s, P, packed, final_obs, terminated, truncated, g32, reward); break;
-    case 64: launch_bootstrap<64>(shape->activation, grid, s, P, packed, final_obs, terminated, truncated, g32, reward); break;
-    case 128: launch_bootstrap<128>(shape->activation, grid, s, P, packed, final_obs, terminated, truncated, g32, reward); break;
-    default: launch_bootstrap<256>(shape->activation, grid, s, P, packed, final_obs, terminated, truncated, g32, reward); break;
-  }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    g_create_error = hipGetErrorString(err);
-    return UPKIE_ERR_HIP;
-  }
-  return UPKIE_OK;
-}
-
-// ============================================================ episode statistics (SB3 Monitor + ep_info_buffer)
-static bool episodes_shape_ok(int32_t num_envs, int32_t window) {
-  if (num_envs <= 0 || window < 1 || window > upkie::EPISODES_MAX_WINDOW) {
-    g_create_error = "num_envs must be positive and window in 1-65536";
-    return false;
-  }
-  return true;
-}
-
-extern "C" int64_t upkie_episodes_workspace_bytes(int32_t num_envs) {
-  if (!episodes_shape_ok(num_envs, 1)) return UPKIE_ERR_INVALID_ARGUMENT;
-  return upkie::episodes_workspace_bytes(num_envs);
-}
-
-extern "C" int upkie_episodes_step(int32_t num_envs, int32_t window, const float* reward, const uint8_t* terminated, const uint8_t* truncated,
-                                   double* ep_return, int32_t* ep_length, double* ring_return, int32_t* ring_length, int64_t* counters,
-                                   double* means, void* workspace, void* stream) {
-  if (!episodes_shape_ok(num_envs, window)) return UPKIE_ERR_INVALID_ARGUMENT;
-  if (!reward || !ep_return || !ep_length || !ring_return || !ring_length || !counters || !means || !workspace) {
-    g_create_error = "null argument (only terminated and truncated may be NULL)";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (upkie_hip_device_count() <= 0) {
-    g_create_error = "no HIP device visible";
-    return UPKIE_ERR_NO_DEVICE;
-  }
-  upkie::EpisodesDev P{};
-  P.num_envs = num_envs;
-  P.window = window;
-  P.blocks = upkie::episodes_blocks(num_envs, &P.rows);
-  P.reward = reward, P.terminated = terminated, P.truncated = truncated;
-  P.ep_return = ep_return, P.ep_length = ep_length, P.ring_return = ring_return, P.ring_length = ring_length;
-  P.counters = counters, P.means = means;
-  char* ws = (char*)workspace;
-  P.ticket = (unsigned*)ws;
-  P.counts = (int32_t*)(ws + upkie::EPISODES_COUNTS_OFFSET);
-  P.fin_return = (double*)(ws + upkie::EPISODES_COUNTS_OFFSET + upkie::EPISODES_MAX_BLOCKS * 4);
-  P.fin_length = (int32_t*)(ws + upkie::EPISODES_COUNTS_OFFSET + upkie::EPISODES_MAX_BLOCKS * 4 + (int64_t)num_envs * 8);
-  hipLaunchKernelGGL(upkie::episodes_step_kernel, dim3((unsigned)P.blocks), dim3(upkie::EPISODES_THREADS), 0, (hipStream_t)stream, P);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    g_create_error = hipGetErrorString(err);
-    return UPKIE_ERR_HIP;
-  }
-  return UPKIE_OK;
-}
-
-extern "C" int upkie_episodes_reset(int32_t num_envs, const uint8_t* mask, double* ep_return, int32_t* ep_length, void* stream) {
-  if (!episodes_shape_ok(num_envs, 1)) return UPKIE_ERR_INVALID_ARGUMENT;
-  if (!ep_return || !ep_length) {
-    g_create_error = "null accumulator buffer";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (upkie_hip_device_count() <= 0) {
-    g_create_error = "no HIP device visible";
-    return UPKIE_ERR_NO_DEVICE;
-  }
-  const int grid = std::min((num_envs + upkie::EPISODES_THREADS - 1) / upkie::EPISODES_THREADS, 1024);
-  hipLaunchKernelGGL(upkie::episodes_reset_kernel, dim3((unsigned)grid), dim3(upkie::EPISODES_THREADS), 0, (hipStream_t)stream, num_envs, mask,
-                     ep_return, ep_length);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    g_create_error = hipGetErrorString(err);
-    return UPKIE_ERR_HIP;
-  }
-  return UPKIE_OK;
-}
-
-// ============================================================ running normalisation (VecNormalize)
-static bool vecnorm_shape_ok(int32_t num_envs, int32_t obs_dim) {
-  if (num_envs <= 0 || obs_dim < 1 || obs_dim > 256 || (int64_t)num_envs * obs_dim > INT_MAX) {
-    g_create_error = "num_envs must be positive and obs_dim in 1-256 (num_envs * obs_dim below 2^31)";
-    return false;
-  }
-  return true;
-}
-
-extern "C" int64_t upkie_vecnorm_workspace_bytes(int32_t num_envs, int32_t obs_dim) {
-  if (!vecnorm_shape_ok(num_envs, obs_dim)) return UPKIE_ERR_INVALID_ARGUMENT;
-  const int blocks = upkie::vecnorm_blocks(num_envs, obs_dim, nullptr);
-  return upkie::VECNORM_PARTIALS_OFFSET + (int64_t)blocks * 2 * (obs_dim + 1) * (int64_t)sizeof(double);
-}
-
-// The launch arguments of upkie_vecnorm_step (and of its data-parallel halves) after the argument checks; returns
-// UPKIE_OK or the error status. *moments / *apply: whether launch A / launch B runs.
-static int vecnorm_setup(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
-                         const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace, int32_t flags,
-                         double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32, float* std_f32, float* packed_stats,
-                         float* norm_obs, float* norm_reward, uint8_t* episode_starts, upkie::VecNormDev* out, bool* moments_out, bool* apply_out) {
-  if (!vecnorm_shape_ok(num_envs, obs_dim)) return UPKIE_ERR_INVALID_ARGUMENT;
-  if (flags & ~(UPKIE_VECNORM_TRAINING | UPKIE_VECNORM_NORM_OBS | UPKIE_VECNORM_NORM_REWARD | UPKIE_VECNORM_RESET)) {
-    g_create_error = "unknown vecnorm flags";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (!(gamma >= 0.0 && gamma <= 1.0) || !(epsilon > 0.0) || !(clip_obs > 0.0) || !(clip_reward > 0.0)) {
-    g_create_error = "gamma must be in [0, 1], epsilon, clip_obs and clip_reward positive";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  const bool training = flags & UPKIE_VECNORM_TRAINING, reset = flags & UPKIE_VECNORM_RESET;
-  upkie::VecNormDev P{};
-  P.num_envs = num_envs;
-  P.obs_dim = obs_dim;
-  P.packed_dp = (obs_dim + 3) / 4 * 4;
-  P.obs_cols = training && (flags & UPKIE_VECNORM_NORM_OBS) ? obs_dim : 0;
-  P.ret_col = training && !reset ? 1 : 0;
-  P.reset = reset;
-  P.norm_obs = (flags & UPKIE_VECNORM_NORM_OBS) != 0;
-  P.norm_reward = (flags & UPKIE_VECNORM_NORM_REWARD) != 0;
-  const bool moments = P.obs_cols + P.ret_col > 0;
-  const bool apply = !moments || norm_obs || (norm_reward && P.norm_reward);
-  P.outputs_in_moments = moments && !apply;
-  if (!obs_stats || !ret_stats || !returns || !mean_f32 || !std_f32) {
-    g_create_error = "null statistics, returns or fp32 mirror buffer";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if ((P.obs_cols || norm_obs) && !obs) {
-    g_create_error = "updating or normalising observations needs obs";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if ((P.ret_col || norm_reward) && !reward) {
-    g_create_error = "updating the returns or writing norm_reward needs reward";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (moments && !workspace) {
-    g_create_error = "training needs the workspace";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (upkie_hip_device_count() <= 0) {
-    g_create_error = "no HIP device visible";
-    return UPKIE_ERR_NO_DEVICE;
-  }
-  P.blocks = upkie::vecnorm_blocks(num_envs, obs_dim, &P.rows);
-  P.gamma = gamma, P.eps = epsilon, P.clip_obs = clip_obs, P.clip_reward = clip_reward;
-  P.obs = obs, P.reward = reward, P.terminated = terminated, P.truncated = truncated;
-  P.obs_stats = obs_stats, P.ret_stats = ret_stats, P.returns = returns;
-  P.ticket = (unsigned*)workspace;
-  P.partials = workspace ? (double*)((char*)workspace + upkie::VECNORM_PARTIALS_OFFSET) : nullptr;
-  P.mean_f32 = mean_f32, P.std_f32 = std_f32, P.packed = packed_stats;
-  P.norm_obs_out = norm_obs, P.reward_out = norm_reward, P.starts_out = episode_starts;
-  *out = P;
-  *moments_out = moments;
-  *apply_out = apply;
-  return UPKIE_OK;
-}
-
-static void vecnorm_launch_apply(const upkie::VecNormDev& P, hipStream_t s) {
-  const int64_t work = P.norm_obs_out ? (int64_t)P.num_envs * P.obs_dim : P.num_envs;
-  const int64_t grid = std::min<int64_t>((work + upkie::VECNORM_THREADS - 1) / upkie::VECNORM_THREADS, 1024);
-  hipLaunchKernelGGL(upkie::vecnorm_apply_kernel, dim3((unsigned)grid), dim3(upkie::VECNORM_THREADS), 0, s, P);
-}
-
-static int launch_status() {
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    g_create_error = hipGetErrorString(err);
-    return UPKIE_ERR_HIP;
-  }
-  return UPKIE_OK;
-}
-
-extern "C" int upkie_vecnorm_step(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
-                                  const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace, int32_t flags,
-                                  double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32, float* std_f32,
-                                  float* packed_stats, float* norm_obs, float* norm_reward, uint8_t* episode_starts, void* stream) {
-  upkie::VecNormDev P;
-  bool moments, apply;
-  const int status = vecnorm_setup(num_envs, obs_dim, obs, reward, terminated, truncated, obs_stats, ret_stats, returns, workspace, flags, gamma,
-                                   epsilon, clip_obs, clip_reward, mean_f32, std_f32, packed_stats, norm_obs, norm_reward, episode_starts, &P,
-                                   &moments, &apply);
-  if (status != UPKIE_OK) return status;
-  const hipStream_t s = (hipStream_t)stream;
-  if (moments) hipLaunchKernelGGL(upkie::vecnorm_moments_kernel, dim3((unsigned)P.blocks), dim3(upkie::VECNORM_THREADS), 0, s, P);
-  if (apply) vecnorm_launch_apply(P, s);
-  return launch_status();
-}
-
-// Whether a step with these flags moves a statistic (launch A runs): the steps of the data-parallel form.
-static bool vecnorm_moves(int32_t flags) {
-  return (flags & UPKIE_VECNORM_TRAINING) && ((flags & UPKIE_VECNORM_NORM_OBS) || !(flags & UPKIE_VECNORM_RESET));
-}
-
-extern "C" int64_t upkie_vecnorm_slot_bytes(int32_t obs_dim) {
-  if (obs_dim < 1 || obs_dim > 256) {
-    g_create_error = "obs_dim must be in 1-256";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  return 8 * (int64_t)upkie::vecnorm_slot_doubles(obs_dim);
-}
-
-extern "C" int upkie_vecnorm_moments_local(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
-                                           const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace,
-                                           int32_t flags, double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32,
-                                           float* std_f32, float* packed_stats, float* norm_obs, float* norm_reward, uint8_t* episode_starts,
-                                           double* slot, void* stream) {
-  if (!vecnorm_moves(flags) || !slot) {
-    g_create_error = "upkie_vecnorm_moments_local needs a step that moves a statistic (TRAINING, and NORM_OBS or not RESET) and a slot";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  upkie::VecNormDev P;
-  bool moments, apply;
-  const int status = vecnorm_setup(num_envs, obs_dim, obs, reward, terminated, truncated, obs_stats, ret_stats, returns, workspace, flags, gamma,
-                                   epsilon, clip_obs, clip_reward, mean_f32, std_f32, packed_stats, norm_obs, norm_reward, episode_starts, &P,
-                                   &moments, &apply);
-  if (status != UPKIE_OK) return status;
-  P.slot = slot;
-  hipLaunchKernelGGL(upkie::vecnorm_moments_kernel, dim3((unsigned)P.blocks), dim3(upkie::VECNORM_THREADS), 0, (hipStream_t)stream, P);
-  return launch_status();
-}
-
-extern "C" int upkie_vecnorm_merge(int32_t num_envs, int32_t obs_dim, const float* obs, const float* reward, const uint8_t* terminated,
-                                   const uint8_t* truncated, double* obs_stats, double* ret_stats, double* returns, void* workspace, int32_t flags,
-                                   double gamma, double epsilon, double clip_obs, double clip_reward, float* mean_f32, float* std_f32,
-                                   float* packed_stats, float* norm_obs, float* norm_reward, uint8_t* episode_starts, const double* slots,
-                                   int32_t world, void* stream) {
-  if (!vecnorm_moves(flags) || !slots || world < 1) {
-    g_create_error = "upkie_vecnorm_merge needs a step that moves a statistic, the exchanged slots and world >= 1";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  upkie::VecNormDev P;
-  bool moments, apply;
-  const int status = vecnorm_setup(num_envs, obs_dim, obs, reward, terminated, truncated, obs_stats, ret_stats, returns, workspace, flags, gamma,
-                                   epsilon, clip_obs, clip_reward, mean_f32, std_f32, packed_stats, norm_obs, norm_reward, episode_starts, &P,
-                                   &moments, &apply);
-  if (status != UPKIE_OK) return status;
-  const hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(upkie::vecnorm_merge_kernel, dim3(1), dim3(upkie::VECNORM_THREADS), 0, s, P, slots, (int)world,
-                     upkie::vecnorm_slot_doubles(obs_dim));
-  if (apply) vecnorm_launch_apply(P, s);
-  return launch_status();
-}
-
-// ============================================================ PPO update (csrc/ppo.hpp)
-static bool ppo_shape_ok(const UpkieMlpShape* shape, upkie::PpoPlan* plan) {
-  if (!shape) {
-    g_create_error = "null shape";
-    return false;
-  }
-  if (upkie::mlp_layout(*shape, nullptr) < 0) {
-    upkie_mlp_packed_words(shape);  // (sets the message)
-    return false;
-  }
-  if (!upkie::ppo_plan(*shape, plan)) {
-    g_create_error = "PPO needs a critic (critic_layers > 0)";
-    return false;
-  }
-  return true;
-}
-
-extern "C" int64_t upkie_ppo_workspace_bytes(const UpkieMlpShape* shape, int32_t max_minibatch) {
-  upkie::PpoPlan plan;
-  if (!ppo_shape_ok(shape, &plan)) return UPKIE_ERR_INVALID_ARGUMENT;
-  if (max_minibatch < 1) {
-    g_create_error = "max_minibatch must be positive";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  return upkie::ppo_workspace_bytes(plan, upkie::ppo_grid(plan, max_minibatch));
-}
-
-extern "C" int upkie_ppo_advantage_stats(int32_t total, int32_t batch_size, const int32_t* perm, const float* advantages, int32_t normalize,
-                                         double* adv_stats, void* stream) {
-  if (total < 1 || batch_size < 1) {
-    g_create_error = "total and batch_size must be positive";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (!perm || !advantages || !adv_stats) {
-    g_create_error = "null argument";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (upkie_hip_device_count() <= 0) {
-    g_create_error = "no HIP device visible";
-    return UPKIE_ERR_NO_DEVICE;
-  }
-  const unsigned blocks = (unsigned)((total + (int64_t)batch_size - 1) / batch_size);
-  hipLaunchKernelGGL(upkie::ppo_adv_stats_kernel, dim3(blocks), dim3(upkie::PPO_ADV_THREADS), 0, (hipStream_t)stream, total, batch_size, perm,
-                     advantages, normalize ? 1 : 0, adv_stats);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    g_create_error = hipGetErrorString(err);
-    return UPKIE_ERR_HIP;
-  }
-  return UPKIE_OK;
-}
-
-template <int W, int ACT>
-static hipError_t launch_ppo_grad(const upkie::PpoDev& P, int lds_bytes, hipStream_t s) {
-  auto kernel = upkie::ppo_grad_kernel<W, ACT>;
-  if (lds_bytes > upkie::PPO_LDS_BUDGET) {
-    // (one tile of the widest shapes needs more than 64 KiB; MI355X has 160 KiB per CU). Raised once per instantiation, to
-    // what any valid shape of it can need, so that a later shape with a larger stage is covered too.
-    static const hipError_t raised = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, upkie::PPO_LDS_MAX);
-    if (raised != hipSuccess) return raised;
-  }
-  hipLaunchKernelGGL(kernel, dim3((unsigned)P.grid), dim3(64 * P.nw), (size_t)lds_bytes, s, P);
-  return hipGetLastError();
-}
-
-template <int W>
-static hipError_t launch_ppo_grad_w(int activation, const upkie::PpoDev& P, int lds_bytes, hipStream_t s) {
-  return activation == UPKIE_MLP_TANH ? launch_ppo_grad<W, UPKIE_MLP_TANH>(P, lds_bytes, s) : launch_ppo_grad<W, UPKIE_MLP_RELU>(P, lds_bytes, s);
-}
-
-static bool ppo_config_ok(const UpkiePpoConfig* config) {
-  if (!config) {
-    g_create_error = "null config";
-    return false;
-  }
-  const UpkiePpoConfig& c = *config;
-  if (!(c.clip_range > 0.f) || !(c.max_grad_norm > 0.f) || !(c.adam_eps > 0.f) || !(c.adam_beta1 >= 0.f && c.adam_beta1 < 1.f) ||
-      !(c.adam_beta2 >= 0.f && c.adam_beta2 < 1.f) || !std::isfinite(c.ent_coef) || !std::isfinite(c.vf_coef) || !(c.clip_range_vf == c.clip_range_vf)) {
-    g_create_error = "config: clip_range, max_grad_norm and adam_eps must be positive, adam betas in [0, 1), coefficients finite";
-    return false;
-  }
-  return true;
-}
-
-// The fields of every launch of a minibatch but the gradient launch's inputs, and the workspace layout for minibatches
-// of at most max_minibatch samples.
-static void ppo_fill(upkie::PpoDev& P, const UpkieMlpShape& shape, const upkie::PpoPlan& plan, const UpkiePpoConfig& c, int max_minibatch,
-                     void* workspace) {
-  upkie::mlp_layout(shape, &P.net);
-  P.stage[0] = plan.stage[0], P.stage[1] = plan.stage[1];
-  P.train_off = plan.train_off, P.train_words = plan.train_words;
-  P.nw = plan.nw, P.tile_floats = plan.tile_floats;
-  const int ws_grid = upkie::ppo_grid(plan, max_minibatch);  // (the workspace's layout)
-  P.fold_blocks = plan.fold_blocks;
-  P.part_stride = plan.train_words, P.stat_stride = upkie::PPO_STATS;
-  P.obs_normalized = c.obs_normalized ? 1 : 0;
-  P.vf_clip = c.clip_range_vf > 0.f;
-  P.clip_range = c.clip_range;
-  P.clip_lo = (float)(1.0 - (double)c.clip_range), P.clip_hi = (float)(1.0 + (double)c.clip_range);
-  P.clip_vf = c.clip_range_vf, P.ent_coef = c.ent_coef, P.vf_coef = c.vf_coef, P.max_grad_norm = c.max_grad_norm;
-  P.beta1 = c.adam_beta1, P.beta2 = c.adam_beta2, P.adam_eps = c.adam_eps;
-  char* ws = (char*)workspace;
-  P.ticket = (unsigned*)ws;
-  P.header = (float*)ws;
-  P.partials = (float*)(ws + upkie::PPO_HEADER_BYTES);
-  P.stat_partials = (double*)(ws + upkie::ppo_stat_partials_at(plan, ws_grid));
-  P.grad = (float*)(ws + upkie::ppo_grad_at(plan, ws_grid));
-  P.sq_partials = (double*)(ws + upkie::ppo_sq_at(plan, ws_grid));
-}
-
-// Checks and fields of the gradient launch (launch A) of minibatch [minibatch_start, + minibatch_size).
-static int ppo_gradient_setup(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
-                              int32_t minibatch_size, int32_t count, int32_t max_minibatch, const int32_t* perm, const float* obs,
-                              const float* actions, const float* old_values, const float* old_log_prob, const float* advantages,
-                              const float* returns, const double* adv_stats, float* packed, void* workspace, upkie::PpoDev* out,
-                              upkie::PpoPlan* plan) {
-  if (!ppo_shape_ok(shape, plan)) return UPKIE_ERR_INVALID_ARGUMENT;
-  if (!ppo_config_ok(config)) return UPKIE_ERR_INVALID_ARGUMENT;
-  if (total < 1 || minibatch_size < 1 || max_minibatch < 1 || minibatch_start < 0 || minibatch_size > max_minibatch ||
-      (int64_t)minibatch_start + minibatch_size > total || count < minibatch_size) {
-    g_create_error =
-        "minibatch out of range: 0 <= minibatch_start, 1 <= minibatch_size <= max_minibatch, start + size <= total, global size >= size";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if ((int64_t)total * (shape->obs_dim > shape->act_dim ? shape->obs_dim : shape->act_dim) > INT_MAX) {
-    g_create_error = "total * obs_dim (or act_dim) must stay below 2^31";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (!perm || !obs || !actions || !old_values || !old_log_prob || !advantages || !returns || !adv_stats || !packed || !workspace) {
-    g_create_error = "null argument";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (upkie_hip_device_count() <= 0) {
-    g_create_error = "no HIP device visible";
-    return UPKIE_ERR_NO_DEVICE;
-  }
-  upkie::PpoDev P{};
-  ppo_fill(P, *shape, *plan, *config, max_minibatch, workspace);
-  P.mb_start = minibatch_start, P.mb_size = minibatch_size, P.count = count;
-  P.grid = upkie::ppo_grid(*plan, minibatch_size);
-  P.perm = perm, P.obs = obs, P.actions = actions, P.old_values = old_values, P.old_log_prob = old_log_prob;
-  P.advantages = advantages, P.returns = returns, P.adv_stats = adv_stats;
-  P.packed = packed;
-  *out = P;
-  return UPKIE_OK;
-}
-
-static hipError_t ppo_launch_gradient(const UpkieMlpShape& shape, const upkie::PpoDev& P, const upkie::PpoPlan& plan, hipStream_t s) {
-  switch (upkie::mlp_width_class(shape)) {
-    case 16: return launch_ppo_grad_w<16>(shape.activation, P, plan.lds_bytes, s);
-    case 32: return launch_ppo_grad_w<32>(shape.activation, P, plan.lds_bytes, s);
-    case 64: return launch_ppo_grad_w<64>(shape.activation, P, plan.lds_bytes, s);
-    case 128: return launch_ppo_grad_w<128>(shape.activation, P, plan.lds_bytes, s);
-    default: return launch_ppo_grad_w<256>(shape.activation, P, plan.lds_bytes, s);
-  }
-}
-
-static int hip_status(hipError_t err) {
-  if (err != hipSuccess) {
-    g_create_error = hipGetErrorString(err);
-    return UPKIE_ERR_HIP;
-  }
-  return UPKIE_OK;
-}
-
-// A control block: PPO_CTRL_WORDS doubles in device memory.
-static bool ppo_control_ok(const double* control) {
-  if (!control) {
-    g_create_error = "null control block";
-    return false;
-  }
-  if ((uintptr_t)control % 8 != 0) {
-    g_create_error = "the control block must be 8-byte aligned";
-    return false;
-  }
-  return true;
-}
-
-// upkie_ppo_minibatch_update (control == nullptr) and upkie_ppo_minibatch_update_controlled.
-static int ppo_minibatch_update(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
-                                int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm, const float* obs, const float* actions,
-                                const float* old_values, const float* old_log_prob, const float* advantages, const float* returns,
-                                const double* adv_stats, float* packed, float* adam_m, float* adam_v, double* adam_scalars, double* control,
-                                void* workspace, float* stats, void* stream) {
-  upkie::PpoPlan plan;
-  upkie::PpoDev P;
-  if (!adam_m || !adam_v || !adam_scalars || !stats) {
-    g_create_error = "null argument";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  const int status = ppo_gradient_setup(shape, config, total, minibatch_start, minibatch_size, minibatch_size, max_minibatch, perm, obs, actions,
-                                        old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, &P, &plan);
-  if (status != UPKIE_OK) return status;
-  P.m = adam_m, P.v = adam_v, P.scalars = adam_scalars, P.ctrl = control, P.stats = stats;
-  const hipStream_t s = (hipStream_t)stream;
-  hipError_t err = ppo_launch_gradient(*shape, P, plan, s);
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(upkie::ppo_fold_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
-    hipLaunchKernelGGL(upkie::ppo_adam_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
-    err = hipGetLastError();
-  }
-  return hip_status(err);
-}
-
-extern "C" int upkie_ppo_minibatch_update(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
-                                          int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm, const float* obs,
-                                          const float* actions, const float* old_values, const float* old_log_prob, const float* advantages,
-                                          const float* returns, const double* adv_stats, float* packed, float* adam_m, float* adam_v,
-                                          double* adam_scalars, void* workspace, float* stats, void* stream) {
-  return ppo_minibatch_update(shape, config, total, minibatch_start, minibatch_size, max_minibatch, perm, obs, actions, old_values, old_log_prob,
-                              advantages, returns, adv_stats, packed, adam_m, adam_v, adam_scalars, nullptr, workspace, stats, stream);
-}
-
-// ---- controlled form (a control block instead of adam_scalars; include/upkie_hip.h)
-extern "C" int upkie_ppo_minibatch_update_controlled(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total,
-                                                     int32_t minibatch_start, int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm,
-                                                     const float* obs, const float* actions, const float* old_values, const float* old_log_prob,
-                                                     const float* advantages, const float* returns, const double* adv_stats, float* packed,
-                                                     float* adam_m, float* adam_v, double* control, void* workspace, float* stats, void* stream) {
-  if (!ppo_control_ok(control)) return UPKIE_ERR_INVALID_ARGUMENT;
-  return ppo_minibatch_update(shape, config, total, minibatch_start, minibatch_size, max_minibatch, perm, obs, actions, old_values, old_log_prob,
-                              advantages, returns, adv_stats, packed, adam_m, adam_v, control, control, workspace, stats, stream);
-}
-
-extern "C" int upkie_ppo_control_set(double* control, double lr, double clip_range, double clip_range_vf, double target_kl, void* stream) {
-  if (!ppo_control_ok(control)) return UPKIE_ERR_INVALID_ARGUMENT;
-  if (!(lr >= 0.0) || !std::isfinite(lr) || !(clip_range > 0.0) || !std::isfinite(clip_range) || !(clip_range_vf >= 0.0) ||
-      !std::isfinite(clip_range_vf) || !(target_kl >= 0.0) || !std::isfinite(target_kl)) {
-    g_create_error = "control: lr, clip_range_vf (0: none) and target_kl (0: none) must be finite and not negative, clip_range positive";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (upkie_hip_device_count() <= 0) {
-    g_create_error = "no HIP device visible";
-    return UPKIE_ERR_NO_DEVICE;
-  }
-  hipLaunchKernelGGL(upkie::ppo_control_set_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, control, lr, clip_range, clip_range_vf, target_kl);
-  return hip_status(hipGetLastError());
-}
-
-extern "C" int upkie_ppo_update_begin(double* control, void* stream) {
-  if (!ppo_control_ok(control)) return UPKIE_ERR_INVALID_ARGUMENT;
-  if (upkie_hip_device_count() <= 0) {
-    g_create_error = "no HIP device visible";
-    return UPKIE_ERR_NO_DEVICE;
-  }
-  hipLaunchKernelGGL(upkie::ppo_begin_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, control);
-  return hip_status(hipGetLastError());
-}
-
-extern "C" int upkie_ppo_explained_variance(int32_t total, const float* returns, const float* values, int32_t phase, const double* slots,
-                                            int32_t world, double* slot, double* out, void* stream) {
-  if (total < 1 || phase < -1 || phase > 2 || (phase >= 0 && world < 1)) {
-    g_create_error = "total and world must be positive, phase -1 (one rank), 0, 1 or 2";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (((phase < 0 || phase == 0 || phase == 1) && (!returns || !values)) || ((phase == 0 || phase == 1) && !slot) || (phase >= 1 && !slots) ||
-      ((phase < 0 || phase == 2) && !out)) {
-    g_create_error = "null argument";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (upkie_hip_device_count() <= 0) {
-    g_create_error = "no HIP device visible";
-    return UPKIE_ERR_NO_DEVICE;
-  }
-  hipLaunchKernelGGL(upkie::ppo_explained_variance_kernel, dim3(1), dim3(upkie::PPO_ADV_THREADS), 0, (hipStream_t)stream, (int)total, returns,
-                     values, (int)phase, slots, (int)world, slot, out);
-  return hip_status(hipGetLastError());
-}
-
-// ---- data-parallel form (several ranks; include/upkie_hip.h)
-extern "C" int64_t upkie_ppo_slot_bytes(const UpkieMlpShape* shape) {
-  upkie::PpoPlan plan;
-  if (!ppo_shape_ok(shape, &plan)) return UPKIE_ERR_INVALID_ARGUMENT;
-  return 4 * (int64_t)upkie::ppo_slot_words(plan);
-}
-
-static int ppo_minibatch_gradient(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
-                                  int32_t minibatch_size, int32_t global_minibatch_size, int32_t max_minibatch, const int32_t* perm,
-                                  const float* obs, const float* actions, const float* old_values, const float* old_log_prob,
-                                  const float* advantages, const float* returns, const double* adv_stats, float* packed, void* workspace,
-                                  void* slot, double* control, void* stream) {
-  upkie::PpoPlan plan;
-  upkie::PpoDev P;
-  if (!slot) {
-    g_create_error = "null slot";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  const int status = ppo_gradient_setup(shape, config, total, minibatch_start, minibatch_size, global_minibatch_size, max_minibatch, perm, obs,
-                                        actions, old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, &P, &plan);
-  if (status != UPKIE_OK) return status;
-  P.slot = (float*)slot;
-  P.ctrl = control;
-  const hipStream_t s = (hipStream_t)stream;
-  hipError_t err = ppo_launch_gradient(*shape, P, plan, s);
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(upkie::ppo_local_fold_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
-    err = hipGetLastError();
-  }
-  return hip_status(err);
-}
-
-extern "C" int upkie_ppo_minibatch_gradient(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
-                                            int32_t minibatch_size, int32_t global_minibatch_size, int32_t max_minibatch, const int32_t* perm,
-                                            const float* obs, const float* actions, const float* old_values, const float* old_log_prob,
-                                            const float* advantages, const float* returns, const double* adv_stats, float* packed, void* workspace,
-                                            void* slot, void* stream) {
-  return ppo_minibatch_gradient(shape, config, total, minibatch_start, minibatch_size, global_minibatch_size, max_minibatch, perm, obs, actions,
-                                old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, slot, nullptr, stream);
-}
-
-extern "C" int upkie_ppo_minibatch_gradient_controlled(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total,
-                                                       int32_t minibatch_start, int32_t minibatch_size, int32_t global_minibatch_size,
-                                                       int32_t max_minibatch, const int32_t* perm, const float* obs, const float* actions,
-                                                       const float* old_values, const float* old_log_prob, const float* advantages,
-                                                       const float* returns, const double* adv_stats, float* packed, void* workspace, void* slot,
-                                                       double* control, void* stream) {
-  if (!ppo_control_ok(control)) return UPKIE_ERR_INVALID_ARGUMENT;
-  return ppo_minibatch_gradient(shape, config, total, minibatch_start, minibatch_size, global_minibatch_size, max_minibatch, perm, obs, actions,
-                                old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, slot, control, stream);
-}
-
-static int ppo_minibatch_apply(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t minibatch_start, int32_t global_minibatch_size,
-                               int32_t max_minibatch, const void* slots, int32_t world, float* packed, float* adam_m, float* adam_v,
-                               double* adam_scalars, double* control, void* workspace, float* stats, void* stream) {
-  upkie::PpoPlan plan;
-  if (!ppo_shape_ok(shape, &plan)) return UPKIE_ERR_INVALID_ARGUMENT;
-  if (!ppo_config_ok(config)) return UPKIE_ERR_INVALID_ARGUMENT;
-  if (global_minibatch_size < 1 || max_minibatch < 1 || world < 1 || minibatch_start < 0) {
-    g_create_error = "global_minibatch_size, max_minibatch and world must be positive, minibatch_start not negative";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (!slots || !packed || !adam_m || !adam_v || !adam_scalars || !workspace || !stats) {
-    g_create_error = "null argument";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (upkie_hip_device_count() <= 0) {
-    g_create_error = "no HIP device visible";
-    return UPKIE_ERR_NO_DEVICE;
-  }
-  upkie::PpoDev P{};
-  ppo_fill(P, *shape, plan, *config, max_minibatch, workspace);
-  P.count = global_minibatch_size;
-  P.mb_start = minibatch_start, P.ctrl = control;
-  P.grid = world;  // (launch B's partials: the slots, in rank order)
-  const int words = upkie::ppo_slot_words(plan);
-  P.partials = (float*)slots;
-  P.part_stride = words;
-  P.stat_partials = (double*)((float*)slots + upkie::ppo_slot_stats_at(plan));
-  P.stat_stride = words / 2;
-  P.packed = packed, P.m = adam_m, P.v = adam_v, P.scalars = adam_scalars, P.stats = stats;
-  const hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(upkie::ppo_fold_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
-  hipLaunchKernelGGL(upkie::ppo_adam_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
-  return hip_status(hipGetLastError());
-}
-
-extern "C" int upkie_ppo_minibatch_apply(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t global_minibatch_size,
-                                         int32_t max_minibatch, const void* slots, int32_t world, float* packed, float* adam_m, float* adam_v,
-                                         double* adam_scalars, void* workspace, float* stats, void* stream) {
-  return ppo_minibatch_apply(shape, config, 0, global_minibatch_size, max_minibatch, slots, world, packed, adam_m, adam_v, adam_scalars, nullptr,
-                             workspace, stats, stream);
-}
-
-extern "C" int upkie_ppo_minibatch_apply_controlled(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t minibatch_start,
-                                                    int32_t global_minibatch_size, int32_t max_minibatch, const void* slots, int32_t world,
-                                                    float* packed, float* adam_m, float* adam_v, double* control, void* workspace, float* stats,
-                                                    void* stream) {
-  if (!ppo_control_ok(control)) return UPKIE_ERR_INVALID_ARGUMENT;
-  return ppo_minibatch_apply(shape, config, minibatch_start, global_minibatch_size, max_minibatch, slots, world, packed, adam_m, adam_v, control,
-                             control, workspace, stats, stream);
-}
-
-extern "C" int64_t upkie_ppo_advantage_slot_bytes(int32_t total, int32_t batch_size) {
-  if (total < 1 || batch_size < 1) {
-    g_create_error = "total and batch_size must be positive";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  return 16 * ((total + (int64_t)batch_size - 1) / batch_size);
-}
-
-extern "C" int upkie_ppo_advantage_partials(int32_t total, int32_t batch_size, const int32_t* perm, const float* advantages, int32_t phase,
-                                            const double* slots, int32_t world, double* slot, void* stream) {
-  if (total < 1 || batch_size < 1 || (phase != 0 && phase != 1) || world < 1) {
-    g_create_error = "total, batch_size and world must be positive, phase 0 or 1";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (!perm || !advantages || !slot || (phase == 1 && !slots)) {
-    g_create_error = "null argument";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (upkie_hip_device_count() <= 0) {
-    g_create_error = "no HIP device visible";
-    return UPKIE_ERR_NO_DEVICE;
-  }
-  const unsigned blocks = (unsigned)((total + (int64_t)batch_size - 1) / batch_size);
-  hipLaunchKernelGGL(upkie::ppo_adv_partials_kernel, dim3(blocks), dim3(upkie::PPO_ADV_THREADS), 0, (hipStream_t)stream, total, batch_size, perm,
-                     advantages, phase, slots, world, slot);
-  return hip_status(hipGetLastError());
-}
-
-extern "C" int upkie_ppo_advantage_finish(int32_t total, int32_t batch_size, int32_t normalize, const double* slots, int32_t world,
-                                          double* adv_stats, void* stream) {
-  if (total < 1 || batch_size < 1 || world < 1) {
-    g_create_error = "total, batch_size and world must be positive";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (!slots || !adv_stats) {
-    g_create_error = "null argument";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (upkie_hip_device_count() <= 0) {
-    g_create_error = "no HIP device visible";
-    return UPKIE_ERR_NO_DEVICE;
-  }
-  const int M = (int)((total + (int64_t)batch_size - 1) / batch_size);
-  hipLaunchKernelGGL(upkie::ppo_adv_finish_kernel, dim3((unsigned)((M + upkie::PPO_THREADS - 1) / upkie::PPO_THREADS)), dim3(upkie::PPO_THREADS), 0,
-                     (hipStream_t)stream, total, batch_size, M, normalize ? 1 : 0, slots, world, adv_stats);
-  return hip_status(hipGetLastError());
-}
-
-// ============================================================ rollout consumer
-extern "C" int upkie_linear_policy(int32_t num_envs, int32_t obs_dim, int32_t act_dim, const float* obs, const float* weights, const float* bias,
-                                  double clip, float* act, void* stream) {
-  if (num_envs <= 0 || obs_dim <= 0 || act_dim <= 0) {
-    g_create_error = "num_envs, obs_dim and act_dim must be positive";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (!obs || !weights || !act) {
-    g_create_error = "null argument";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (upkie_hip_device_count() <= 0) {
-    g_create_error = "no HIP device visible";
-    return UPKIE_ERR_NO_DEVICE;
-  }
-  hipLaunchKernelGGL(upkie::linear_policy_kernel, dim3((unsigned)((num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, num_envs, obs_dim,
-                     act_dim, obs, weights, bias, (float)clip, act);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    g_create_error = hipGetErrorString(err);
-    return UPKIE_ERR_HIP;
-  }
-  return UPKIE_OK;
-}
-
-extern "C" int upkie_rollout_gae(int32_t num_steps, int32_t num_envs, const float* rewards, const float* values,
-                                 const uint8_t* episode_starts, const float* last_values, const uint8_t* last_dones, double gamma,
-                                 double gae_lambda, float* advantages, float* returns, void* stream) {
-  if (num_steps <= 0 || num_envs <= 0) {
-    g_create_error = "num_steps and num_envs must be positive";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (!rewards || !values || !episode_starts || !last_values || !last_dones || !advantages || !returns) {
-    g_create_error = "null argument";
-    return UPKIE_ERR_INVALID_ARGUMENT;
-  }
-  if (upkie_hip_device_count() <= 0) {
-    g_create_error = "no HIP device visible";
-    return UPKIE_ERR_NO_DEVICE;
-  }
-  hipLaunchKernelGGL(upkie::gae_kernel, dim3((unsigned)((num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, num_steps, num_envs,
-                     rewards, values, episode_starts, last_values, last_dones, (float)gamma, (float)gae_lambda, advantages, returns);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    g_create_error = hipGetErrorString(err);
-    return UPKIE_ERR_HIP;
-  }
-  return UPKIE_OK;
 }

@@ -83,8 +83,7 @@ class EpisodeStatistics:
                                                    self.ep_return.data_ptr(), self.ep_length.data_ptr(), self.ring_return.data_ptr(),
                                                    self.ring_length.data_ptr(), self.counters.data_ptr(), self.means.data_ptr(),
                                                    self.workspace.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-        if status < 0:
-            lib.check(status, None)
+        lib.check(status, None)
         return self.means
 
     def reset(self, mask: Optional[torch.Tensor] = None) -> None:
@@ -94,8 +93,7 @@ class EpisodeStatistics:
         with torch.cuda.device(self.device):
             status = self._lib.upkie_episodes_reset(self.num_envs, None if mask is None else mask.data_ptr(), self.ep_return.data_ptr(),
                                                     self.ep_length.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-        if status < 0:
-            lib.check(status, None)
+        lib.check(status, None)
 
     # ---- host reads (each synchronises with the device)
     @property

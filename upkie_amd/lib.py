@@ -15,113 +15,144 @@ from .exceptions import UpkieRuntimeError
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UPKIE_HIP_LIBRARY: another build of the same sources (A/B measurements of a kernel change on one GPU box)
 LIB_PATH = os.environ.get("UPKIE_HIP_LIBRARY") or os.path.join(_HERE, "_lib", "libupkie_hip.so")
+_CSRC = os.path.join(_HERE, "csrc")
+# the files hipcc is handed (`build()`); everything else below is a header of theirs
+SIM_ABI_SOURCE = os.path.join(_CSRC, "upkie_hip.hip")  # the simulator, MPC and observer handles
+TRAINER_ABI_SOURCE = os.path.join(_CSRC, "trainer_abi.hip")  # the handle-free entry points around a rollout
+PPO_ABI_SOURCE = os.path.join(_CSRC, "ppo_abi.hip")  # the PPO update
+INSTANCES_SOURCE = os.path.join(_CSRC, "step_instances.hip")  # the step kernels, by groups
 SOURCES = [
-    os.path.join(_HERE, "csrc", "upkie_hip.hip"),
-    os.path.join(_HERE, "csrc", "step_instances.hip"),
-    os.path.join(_HERE, "csrc", "step_instances.hpp"),
-    os.path.join(_HERE, "csrc", "step_kernels.hpp"),
-    os.path.join(_HERE, "csrc", "host_setup.hpp"),
-    os.path.join(_HERE, "csrc", "dynamics.hpp"),
-    os.path.join(_HERE, "csrc", "bullet_like.hpp"),
-    os.path.join(_HERE, "csrc", "state_words.hpp"),
-    os.path.join(_HERE, "csrc", "mpc.hpp"),
-    os.path.join(_HERE, "csrc", "pair.hpp"),
-    os.path.join(_HERE, "csrc", "octet.hpp"),
-    os.path.join(_HERE, "csrc", "observers.hpp"),
-    os.path.join(_HERE, "csrc", "rollout.hpp"),
-    os.path.join(_HERE, "csrc", "policy_mlp.hpp"),
-    os.path.join(_HERE, "csrc", "vecnorm.hpp"),
-    os.path.join(_HERE, "csrc", "ppo.hpp"),
-    os.path.join(_HERE, "csrc", "time_limits.hpp"),
-    os.path.join(_HERE, "csrc", "episodes.hpp"),
-    os.path.join(_HERE, "csrc", "wave_io.hpp"),
+    SIM_ABI_SOURCE,
+    TRAINER_ABI_SOURCE,
+    PPO_ABI_SOURCE,
+    INSTANCES_SOURCE,
+    os.path.join(_CSRC, "abi_host.hpp"),
+    os.path.join(_CSRC, "mlp_instances.hpp"),
+    os.path.join(_CSRC, "step_instances.hpp"),
+    os.path.join(_CSRC, "step_kernels.hpp"),
+    os.path.join(_CSRC, "host_setup.hpp"),
+    os.path.join(_CSRC, "dynamics.hpp"),
+    os.path.join(_CSRC, "bullet_like.hpp"),
+    os.path.join(_CSRC, "state_words.hpp"),
+    os.path.join(_CSRC, "mpc.hpp"),
+    os.path.join(_CSRC, "pair.hpp"),
+    os.path.join(_CSRC, "octet.hpp"),
+    os.path.join(_CSRC, "observers.hpp"),
+    os.path.join(_CSRC, "rollout.hpp"),
+    os.path.join(_CSRC, "policy_mlp.hpp"),
+    os.path.join(_CSRC, "vecnorm.hpp"),
+    os.path.join(_CSRC, "ppo.hpp"),
+    os.path.join(_CSRC, "time_limits.hpp"),
+    os.path.join(_CSRC, "episodes.hpp"),
+    os.path.join(_CSRC, "wave_io.hpp"),
     os.path.join(_HERE, "..", "include", "upkie_hip.h"),
 ]
 
-INSTANCES_SOURCE = SOURCES[1]
 
+def _abi_table():
+    """The ABI, one row per function `include/upkie_hip.h` declares: (name, result type, argument types, group).
+    `argtypes` None: left unset. `group` None: every library has the function, and `load()` fails without it. Otherwise
+    the group is named by its probe symbol: an OLDER build of the library, loaded through UPKIE_HIP_LIBRARY for an A/B
+    run on one GPU box (tools/ab_step.py), lacks the probe and with it the whole group; those rows are skipped and the
+    library still loads. The shipped library exports them all (tests/test_abi.py)."""
+    vp, i32, f64, status = C.c_void_p, C.c_int32, C.c_double, C.c_int
+    P = C.POINTER
+    shape_p, cfg_p = P(abi.UpkieMlpShape), P(abi.UpkiePpoConfig)
+    step = [vp] * 8
+    vecnorm = [i32, i32] + [vp] * 8 + [i32] + [f64] * 4  # (the arguments every vecnorm launch begins with)
+    controlled = "upkie_ppo_minibatch_update_controlled"
+    return (
+        ("upkie_hip_device_count", status, None, None),
+        ("upkie_hip_struct_bytes", C.c_int64, [C.c_int], "upkie_hip_struct_bytes"),  # (see _check_struct_sizes)
+        ("upkie_sim_create", status, [P(abi.UpkieSimConfig), P(abi.UpkieModel), P(vp)], None),
+        ("upkie_sim_set_config", status, [vp, P(abi.UpkieSimConfig)], None),
+        ("upkie_sim_destroy", status, [vp], None),
+        ("upkie_sim_last_error", C.c_char_p, [vp], None),
+        ("upkie_sim_pgs_tolerance", f64, [vp], None),
+        ("upkie_sim_state_bytes", C.c_int64, [vp], None),
+        ("upkie_sim_lanes_per_env", status, [vp], None),
+        ("upkie_sim_set_census", status, [vp, vp], None),
+        ("upkie_sim_set_lanes_per_env", status, [vp, C.c_int], None),
+        ("upkie_sim_release_graph_captures", status, [vp], None),
+        ("upkie_sim_guard_counts", status, [vp, P(C.c_uint32), C.c_int, vp], None),
+        ("upkie_sim_set_final_observation", status, [vp, vp], None),
+        ("upkie_sim_lanes_per_env_of", status, [vp, C.c_int], "upkie_sim_lanes_per_env_of"),
+        ("upkie_sim_set_contact_manifold", status, [vp, vp], "upkie_sim_set_contact_manifold"),
+        ("upkie_sim_servo_policy", status, [vp, vp, P(abi.UpkieServoPolicy), vp, vp], None),
+        ("upkie_sim_step_servos_policy", status, [vp, vp, P(abi.UpkieServoPolicy), vp, vp, vp, vp, vp, vp], None),
+        ("upkie_sim_set_randomization", status, [vp, vp, vp, P(f64)], None),
+        ("upkie_sim_set_external_forces", status, [vp, vp, P(abi.UpkieExternalForces)], None),
+        ("upkie_sim_sample_body_inertials", status, [vp, vp, vp, f64, vp], None),
+        ("upkie_sim_contact_sweeps", status, [vp, i32, vp, vp, vp, vp, vp, vp], None),
+        ("upkie_sim_sample_pushes", status, [vp, vp, C.c_uint32, f64, vp], None),
+        ("upkie_sim_reset", status, [vp, vp, vp, vp, vp], None),
+        ("upkie_sim_step_pendulum", status, step, None),
+        ("upkie_sim_step_gyropod", status, step, None),
+        ("upkie_sim_step_servos", status, step, None),
+        ("upkie_sim_step_pendulum_agent", status, [vp] * 7, None),
+        ("upkie_sim_step_pendulum_packed", status, [vp] * 5, None),
+        ("upkie_sim_step_pendulum_agent_packed", status, [vp] * 4, None),
+        ("upkie_sim_step_pendulum_agent_records", status, [vp] * 5, None),
+        ("upkie_sim_step_pendulum_agent_rollout", status, [vp, vp, vp, vp, i32, vp], None),
+        ("upkie_sim_step_base_velocity", status, [vp] * 11, None),
+        ("upkie_sim_step_base_velocity_mpc", status, [vp] * 13, None),
+        ("upkie_sim_observe", status, [vp, vp, P(abi.UpkieSpineObservation), C.c_int, vp], None),
+        ("upkie_sim_autoreset_done", status, [vp, C.c_int, vp, vp, vp, vp], None),
+        ("upkie_sim_contact_points", status, [vp, vp, vp, vp], None),
+        ("upkie_mpc_create", status, [P(abi.UpkieMpcConfig), P(vp)], None),
+        ("upkie_mpc_destroy", status, [vp], None),
+        ("upkie_mpc_last_error", C.c_char_p, [vp], None),
+        ("upkie_mpc_workspace_bytes", C.c_int64, [vp], None),
+        ("upkie_mpc_reset", status, [vp, vp, vp, vp, vp], None),
+        ("upkie_mpc_step", status, [vp, vp, vp, vp, vp, f64, vp, vp, vp], None),
+        ("upkie_mpc_step_env", status, [vp, vp, vp, vp, vp, vp, f64, vp, vp], None),
+        ("upkie_sim_attach_observers", status, [vp, P(abi.UpkieObserverConfig), vp], None),
+        ("upkie_observers_create", status, [P(abi.UpkieObserverConfig), P(vp)], None),
+        ("upkie_observers_destroy", status, [vp], None),
+        ("upkie_observers_last_error", C.c_char_p, [vp], None),
+        ("upkie_observers_state_bytes", C.c_int64, [vp], None),
+        ("upkie_observers_reset", status, [vp, vp, vp, vp], None),
+        ("upkie_observers_step", status, [vp, vp, P(abi.UpkieObserverInput), P(abi.UpkieObserverOutput), vp], None),
+        ("upkie_rollout_gae", status, [i32, i32, vp, vp, vp, vp, vp, f64, f64, vp, vp, vp], None),
+        ("upkie_linear_policy", status, [i32, i32, i32, vp, vp, vp, f64, vp, vp], "upkie_linear_policy"),
+        # the MLP actor-critic policy
+        ("upkie_mlp_packed_words", C.c_int64, [shape_p], "upkie_mlp_actor_critic"),
+        ("upkie_mlp_actor_critic", status, [i32, shape_p, vp, vp, vp, C.c_uint64, i32] + [vp] * 7, "upkie_mlp_actor_critic"),
+        # VecNormalize
+        ("upkie_vecnorm_workspace_bytes", C.c_int64, [i32, i32], "upkie_vecnorm_step"),
+        ("upkie_vecnorm_step", status, vecnorm + [vp] * 7, "upkie_vecnorm_step"),
+        # the PPO update
+        ("upkie_ppo_workspace_bytes", C.c_int64, [shape_p, i32], "upkie_ppo_minibatch_update"),
+        ("upkie_ppo_advantage_stats", status, [i32, i32, vp, vp, i32, vp, vp], "upkie_ppo_minibatch_update"),
+        ("upkie_ppo_minibatch_update", status, [shape_p, cfg_p] + [i32] * 4 + [vp] * 15, "upkie_ppo_minibatch_update"),
+        # the data-parallel halves of VecNormalize and of the PPO update
+        ("upkie_vecnorm_slot_bytes", C.c_int64, [i32], "upkie_vecnorm_merge"),
+        ("upkie_vecnorm_moments_local", status, vecnorm + [vp] * 8, "upkie_vecnorm_merge"),
+        ("upkie_vecnorm_merge", status, vecnorm + [vp] * 6 + [vp, i32, vp], "upkie_vecnorm_merge"),
+        ("upkie_ppo_slot_bytes", C.c_int64, [shape_p], "upkie_ppo_minibatch_apply"),
+        ("upkie_ppo_advantage_slot_bytes", C.c_int64, [i32, i32], "upkie_ppo_minibatch_apply"),
+        ("upkie_ppo_advantage_partials", status, [i32, i32, vp, vp, i32, vp, i32, vp, vp], "upkie_ppo_minibatch_apply"),
+        ("upkie_ppo_advantage_finish", status, [i32, i32, i32, vp, i32, vp, vp], "upkie_ppo_minibatch_apply"),
+        ("upkie_ppo_minibatch_gradient", status, [shape_p, cfg_p] + [i32] * 5 + [vp] * 12, "upkie_ppo_minibatch_apply"),
+        ("upkie_ppo_minibatch_apply", status, [shape_p, cfg_p, i32, i32, vp, i32] + [vp] * 7, "upkie_ppo_minibatch_apply"),
+        # the control block of PPO.learn
+        ("upkie_ppo_control_set", status, [vp] + [f64] * 4 + [vp], controlled),
+        ("upkie_ppo_update_begin", status, [vp, vp], controlled),
+        ("upkie_ppo_minibatch_update_controlled", status, [shape_p, cfg_p] + [i32] * 4 + [vp] * 15, controlled),
+        ("upkie_ppo_minibatch_gradient_controlled", status, [shape_p, cfg_p] + [i32] * 5 + [vp] * 13, controlled),
+        ("upkie_ppo_minibatch_apply_controlled", status, [shape_p, cfg_p, i32, i32, i32, vp, i32] + [vp] * 7, controlled),
+        ("upkie_ppo_explained_variance", status, [i32, vp, vp, i32, vp, i32, vp, vp, vp], controlled),
+        # the time-limit bootstrap and the episode statistics
+        ("upkie_mlp_bootstrap_time_limits", status, [i32, shape_p, vp, vp, vp, vp, f64, vp, vp], "upkie_mlp_bootstrap_time_limits"),
+        ("upkie_episodes_workspace_bytes", C.c_int64, [i32], "upkie_episodes_step"),
+        ("upkie_episodes_step", status, [i32, i32] + [vp] * 11, "upkie_episodes_step"),
+        ("upkie_episodes_reset", status, [i32, vp, vp, vp, vp], "upkie_episodes_step"),
+    )
+
+
+_ABI = _abi_table()
 ## Every symbol `include/upkie_hip.h` declares.
-EXPORTED_SYMBOLS = (
-    "upkie_hip_device_count",
-    "upkie_hip_struct_bytes",
-    "upkie_sim_create",
-    "upkie_sim_destroy",
-    "upkie_sim_set_config",
-    "upkie_sim_last_error",
-    "upkie_sim_state_bytes",
-    "upkie_sim_pgs_tolerance",
-    "upkie_sim_lanes_per_env",
-    "upkie_sim_lanes_per_env_of",
-    "upkie_sim_set_census",
-    "upkie_sim_set_lanes_per_env",
-    "upkie_sim_guard_counts",
-    "upkie_sim_release_graph_captures",
-    "upkie_sim_set_final_observation",
-    "upkie_sim_set_contact_manifold",
-    "upkie_sim_set_randomization",
-    "upkie_sim_set_external_forces",
-    "upkie_sim_sample_body_inertials",
-    "upkie_sim_sample_pushes",
-    "upkie_sim_contact_sweeps",
-    "upkie_sim_reset",
-    "upkie_sim_step_pendulum",
-    "upkie_sim_step_pendulum_agent",
-    "upkie_sim_step_pendulum_packed",
-    "upkie_sim_step_pendulum_agent_packed",
-    "upkie_sim_step_pendulum_agent_records",
-    "upkie_sim_step_pendulum_agent_rollout",
-    "upkie_sim_step_gyropod",
-    "upkie_sim_step_servos",
-    "upkie_sim_servo_policy",
-    "upkie_sim_step_servos_policy",
-    "upkie_sim_step_base_velocity",
-    "upkie_sim_step_base_velocity_mpc",
-    "upkie_sim_observe",
-    "upkie_sim_contact_points",
-    "upkie_sim_autoreset_done",
-    "upkie_mpc_create",
-    "upkie_mpc_destroy",
-    "upkie_mpc_last_error",
-    "upkie_mpc_workspace_bytes",
-    "upkie_mpc_reset",
-    "upkie_mpc_step",
-    "upkie_mpc_step_env",
-    "upkie_sim_attach_observers",
-    "upkie_observers_create",
-    "upkie_observers_destroy",
-    "upkie_observers_last_error",
-    "upkie_observers_state_bytes",
-    "upkie_observers_reset",
-    "upkie_observers_step",
-    "upkie_rollout_gae",
-    "upkie_linear_policy",
-    "upkie_mlp_packed_words",
-    "upkie_mlp_actor_critic",
-    "upkie_vecnorm_workspace_bytes",
-    "upkie_vecnorm_step",
-    "upkie_ppo_workspace_bytes",
-    "upkie_ppo_advantage_stats",
-    "upkie_ppo_minibatch_update",
-    "upkie_vecnorm_slot_bytes",
-    "upkie_vecnorm_moments_local",
-    "upkie_vecnorm_merge",
-    "upkie_ppo_slot_bytes",
-    "upkie_ppo_advantage_slot_bytes",
-    "upkie_ppo_advantage_partials",
-    "upkie_ppo_advantage_finish",
-    "upkie_ppo_minibatch_gradient",
-    "upkie_ppo_minibatch_apply",
-    "upkie_ppo_control_set",
-    "upkie_ppo_update_begin",
-    "upkie_ppo_minibatch_update_controlled",
-    "upkie_ppo_minibatch_gradient_controlled",
-    "upkie_ppo_minibatch_apply_controlled",
-    "upkie_ppo_explained_variance",
-    "upkie_mlp_bootstrap_time_limits",
-    "upkie_episodes_workspace_bytes",
-    "upkie_episodes_step",
-    "upkie_episodes_reset",
-)
+EXPORTED_SYMBOLS = tuple(name for name, _, _, _ in _ABI)
 
 
 class UpkieHipError(UpkieRuntimeError):
@@ -154,8 +185,10 @@ HIPCC_FLAGS = [
 
 def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
     """Compile the HIP library for gfx950 with hipcc (in-tree): the C-ABI's
-    translation unit (`upkie_hip.hip`: host code and the small kernels) and the
-    ~100 step-kernel instantiations in `INSTANCE_GROUPS` groups
+    three translation units (`upkie_hip.hip`: the simulator, MPC and observer
+    handles and the small kernels around the step; `trainer_abi.hip` and
+    `ppo_abi.hip`: the handle-free trainer entry points and their kernels) and
+    the ~100 step-kernel instantiations in `INSTANCE_GROUPS` groups
     (`step_instances.hip -DUPKIE_INSTANCE_GROUP=g`), compiled side by side on
     `jobs` cores (default: all this process may use), then linked."""
     stale = force or not os.path.exists(LIB_PATH)
@@ -167,10 +200,12 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
     if stale:
         os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
         tag = f"{LIB_PATH}.{os.getpid()}"
-        # (the heaviest units first -- the one-lane kernels, groups 0-7, then the C-ABI's own unit --: the build ends when the
-        # total work does, not when a late-started heavy group does)
-        units = [(INSTANCES_SOURCE, [f"-DUPKIE_INSTANCE_GROUP={g}"], f"{tag}.g{g}.o") for g in range(8)]
-        units += [(SOURCES[0], [], f"{tag}.abi.o")]
+        # (the heaviest units first, so that the build ends when the total work does, not when a late-started heavy unit
+        # does. Alone on one core: the PPO unit 112 s and the trainer unit 58 s -- thirty MFMA template kernels between them,
+        # the build is as long as the first of the two --, a one-lane group, 0-7, 19 s, the simulator's unit 11 s)
+        units = [(PPO_ABI_SOURCE, [], f"{tag}.ppo.o"), (TRAINER_ABI_SOURCE, [], f"{tag}.trainer.o")]
+        units += [(INSTANCES_SOURCE, [f"-DUPKIE_INSTANCE_GROUP={g}"], f"{tag}.g{g}.o") for g in range(8)]
+        units += [(SIM_ABI_SOURCE, [], f"{tag}.sim.o")]
         units += [(INSTANCES_SOURCE, [f"-DUPKIE_INSTANCE_GROUP={g}"], f"{tag}.g{g}.o") for g in range(8, INSTANCE_GROUPS)]
         jobs = jobs or (len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
         partial = f"{tag}.partial"  # (a library is never loadable half-written: built beside it, renamed into place)
@@ -253,196 +288,14 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
 
     lib = C.CDLL(LIB_PATH)
-    vp = C.c_void_p
     _check_struct_sizes(lib)
-    lib.upkie_hip_device_count.restype = C.c_int
-    lib.upkie_sim_create.restype = C.c_int
-    lib.upkie_sim_create.argtypes = [
-        C.POINTER(abi.UpkieSimConfig),
-        C.POINTER(abi.UpkieModel),
-        C.POINTER(vp),
-    ]
-    lib.upkie_sim_set_config.restype = C.c_int
-    lib.upkie_sim_set_config.argtypes = [vp, C.POINTER(abi.UpkieSimConfig)]
-    lib.upkie_sim_destroy.restype = C.c_int
-    lib.upkie_sim_destroy.argtypes = [vp]
-    lib.upkie_sim_last_error.restype = C.c_char_p
-    lib.upkie_sim_last_error.argtypes = [vp]
-    lib.upkie_sim_pgs_tolerance.restype = C.c_double
-    lib.upkie_sim_pgs_tolerance.argtypes = [vp]
-    lib.upkie_sim_state_bytes.restype = C.c_int64
-    lib.upkie_sim_state_bytes.argtypes = [vp]
-    lib.upkie_sim_lanes_per_env.restype = C.c_int
-    lib.upkie_sim_lanes_per_env.argtypes = [vp]
-    lib.upkie_sim_set_census.restype = C.c_int
-    lib.upkie_sim_set_census.argtypes = [vp, vp]
-    lib.upkie_sim_set_lanes_per_env.restype = C.c_int
-    lib.upkie_sim_set_lanes_per_env.argtypes = [vp, C.c_int]
-    lib.upkie_sim_release_graph_captures.restype = C.c_int
-    lib.upkie_sim_release_graph_captures.argtypes = [vp]
-    lib.upkie_sim_guard_counts.restype = C.c_int
-    lib.upkie_sim_guard_counts.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int, vp]
-    lib.upkie_sim_set_final_observation.restype = C.c_int
-    lib.upkie_sim_set_final_observation.argtypes = [vp, vp]
-    # (round-4 entry points: bound when present, so that tools/ab_step.py can still load an OLDER build of the library
-    # through UPKIE_HIP_LIBRARY for an A/B on one box; the shipped library exports them all: tests/test_abi.py)
-    if hasattr(lib, "upkie_sim_lanes_per_env_of"):
-        lib.upkie_sim_lanes_per_env_of.restype = C.c_int
-        lib.upkie_sim_lanes_per_env_of.argtypes = [vp, C.c_int]
-    if hasattr(lib, "upkie_sim_set_contact_manifold"):
-        lib.upkie_sim_set_contact_manifold.restype = C.c_int
-        lib.upkie_sim_set_contact_manifold.argtypes = [vp, vp]
-    lib.upkie_sim_servo_policy.restype = C.c_int
-    lib.upkie_sim_servo_policy.argtypes = [vp, vp, C.POINTER(abi.UpkieServoPolicy), vp, vp]
-    lib.upkie_sim_step_servos_policy.restype = C.c_int
-    lib.upkie_sim_step_servos_policy.argtypes = [vp, vp, C.POINTER(abi.UpkieServoPolicy), vp, vp, vp, vp, vp, vp]
-    lib.upkie_sim_set_randomization.restype = C.c_int
-    lib.upkie_sim_set_randomization.argtypes = [vp, vp, vp, C.POINTER(C.c_double)]
-    lib.upkie_sim_set_external_forces.restype = C.c_int
-    lib.upkie_sim_set_external_forces.argtypes = [vp, vp, C.POINTER(abi.UpkieExternalForces)]
-    lib.upkie_sim_sample_body_inertials.restype = C.c_int
-    lib.upkie_sim_sample_body_inertials.argtypes = [vp, vp, vp, C.c_double, vp]
-    lib.upkie_sim_contact_sweeps.restype = C.c_int
-    lib.upkie_sim_contact_sweeps.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp]
-    lib.upkie_sim_sample_pushes.restype = C.c_int
-    lib.upkie_sim_sample_pushes.argtypes = [vp, vp, C.c_uint32, C.c_double, vp]
-    lib.upkie_sim_reset.restype = C.c_int
-    lib.upkie_sim_reset.argtypes = [vp, vp, vp, vp, vp]
-    for name in (
-        "upkie_sim_step_pendulum",
-        "upkie_sim_step_gyropod",
-        "upkie_sim_step_servos",
-    ):
+    for name, restype, argtypes, group in _ABI:
+        if group is not None and not hasattr(lib, group):
+            continue
         fn = getattr(lib, name)
-        fn.restype = C.c_int
-        fn.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.upkie_sim_step_pendulum_agent.restype = C.c_int
-    lib.upkie_sim_step_pendulum_agent.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    lib.upkie_sim_step_pendulum_packed.restype = C.c_int
-    lib.upkie_sim_step_pendulum_packed.argtypes = [vp, vp, vp, vp, vp]
-    lib.upkie_sim_step_pendulum_agent_packed.restype = C.c_int
-    lib.upkie_sim_step_pendulum_agent_packed.argtypes = [vp, vp, vp, vp]
-    lib.upkie_sim_step_pendulum_agent_records.restype = C.c_int
-    lib.upkie_sim_step_pendulum_agent_records.argtypes = [vp, vp, vp, vp, vp]
-    lib.upkie_sim_step_pendulum_agent_rollout.restype = C.c_int
-    lib.upkie_sim_step_pendulum_agent_rollout.argtypes = [vp, vp, vp, vp, C.c_int32, vp]
-    lib.upkie_sim_step_base_velocity.restype = C.c_int
-    lib.upkie_sim_step_base_velocity.argtypes = [vp] * 11
-    lib.upkie_sim_step_base_velocity_mpc.restype = C.c_int
-    lib.upkie_sim_step_base_velocity_mpc.argtypes = [vp] * 13
-    lib.upkie_sim_observe.restype = C.c_int
-    lib.upkie_sim_observe.argtypes = [
-        vp,
-        vp,
-        C.POINTER(abi.UpkieSpineObservation),
-        C.c_int,
-        vp,
-    ]
-    lib.upkie_sim_autoreset_done.restype = C.c_int
-    lib.upkie_sim_autoreset_done.argtypes = [vp, C.c_int, vp, vp, vp, vp]
-    lib.upkie_sim_contact_points.restype = C.c_int
-    lib.upkie_sim_contact_points.argtypes = [vp, vp, vp, vp]
-    lib.upkie_mpc_create.restype = C.c_int
-    lib.upkie_mpc_create.argtypes = [C.POINTER(abi.UpkieMpcConfig), C.POINTER(vp)]
-    lib.upkie_mpc_destroy.restype = C.c_int
-    lib.upkie_mpc_destroy.argtypes = [vp]
-    lib.upkie_mpc_last_error.restype = C.c_char_p
-    lib.upkie_mpc_last_error.argtypes = [vp]
-    lib.upkie_mpc_workspace_bytes.restype = C.c_int64
-    lib.upkie_mpc_workspace_bytes.argtypes = [vp]
-    lib.upkie_mpc_reset.restype = C.c_int
-    lib.upkie_mpc_reset.argtypes = [vp, vp, vp, vp, vp]
-    lib.upkie_mpc_step.restype = C.c_int
-    lib.upkie_mpc_step.argtypes = [vp, vp, vp, vp, vp, C.c_double, vp, vp, vp]
-    lib.upkie_mpc_step_env.restype = C.c_int
-    lib.upkie_mpc_step_env.argtypes = [vp, vp, vp, vp, vp, vp, C.c_double, vp, vp]
-    lib.upkie_sim_attach_observers.restype = C.c_int
-    lib.upkie_sim_attach_observers.argtypes = [vp, C.POINTER(abi.UpkieObserverConfig), vp]
-    lib.upkie_observers_create.restype = C.c_int
-    lib.upkie_observers_create.argtypes = [C.POINTER(abi.UpkieObserverConfig), C.POINTER(vp)]
-    lib.upkie_observers_destroy.restype = C.c_int
-    lib.upkie_observers_destroy.argtypes = [vp]
-    lib.upkie_observers_last_error.restype = C.c_char_p
-    lib.upkie_observers_last_error.argtypes = [vp]
-    lib.upkie_observers_state_bytes.restype = C.c_int64
-    lib.upkie_observers_state_bytes.argtypes = [vp]
-    lib.upkie_observers_reset.restype = C.c_int
-    lib.upkie_observers_reset.argtypes = [vp, vp, vp, vp]
-    lib.upkie_observers_step.restype = C.c_int
-    lib.upkie_observers_step.argtypes = [
-        vp,
-        vp,
-        C.POINTER(abi.UpkieObserverInput),
-        C.POINTER(abi.UpkieObserverOutput),
-        vp,
-    ]
-    if hasattr(lib, "upkie_linear_policy"):  # (round 4; older builds loaded for A/B runs lack it)
-        lib.upkie_linear_policy.restype = C.c_int
-        lib.upkie_linear_policy.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_double, vp, vp]
-    if hasattr(lib, "upkie_mlp_actor_critic"):  # (newer entry points: an older build loaded for an A/B run lacks them)
-        lib.upkie_mlp_packed_words.restype = C.c_int64
-        lib.upkie_mlp_packed_words.argtypes = [C.POINTER(abi.UpkieMlpShape)]
-        lib.upkie_mlp_actor_critic.restype = C.c_int
-        lib.upkie_mlp_actor_critic.argtypes = [C.c_int32, C.POINTER(abi.UpkieMlpShape), vp, vp, vp, C.c_uint64, C.c_int32] + [vp] * 7
-    if hasattr(lib, "upkie_vecnorm_step"):  # (newer entry points: an older build loaded for an A/B run lacks them)
-        lib.upkie_vecnorm_workspace_bytes.restype = C.c_int64
-        lib.upkie_vecnorm_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
-        lib.upkie_vecnorm_step.restype = C.c_int
-        lib.upkie_vecnorm_step.argtypes = ([C.c_int32, C.c_int32] + [vp] * 8 + [C.c_int32] + [C.c_double] * 4 + [vp] * 7)
-    if hasattr(lib, "upkie_ppo_minibatch_update"):  # (newer entry points: an older build loaded for an A/B run lacks them)
-        lib.upkie_ppo_workspace_bytes.restype = C.c_int64
-        lib.upkie_ppo_workspace_bytes.argtypes = [C.POINTER(abi.UpkieMlpShape), C.c_int32]
-        lib.upkie_ppo_advantage_stats.restype = C.c_int
-        lib.upkie_ppo_advantage_stats.argtypes = [C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp]
-        lib.upkie_ppo_minibatch_update.restype = C.c_int
-        lib.upkie_ppo_minibatch_update.argtypes = ([C.POINTER(abi.UpkieMlpShape), C.POINTER(abi.UpkiePpoConfig)] + [C.c_int32] * 4 + [vp] * 15)
-    if hasattr(lib, "upkie_vecnorm_merge"):  # (the data-parallel halves: an older build lacks them, and still loads)
-        lib.upkie_vecnorm_slot_bytes.restype = C.c_int64
-        lib.upkie_vecnorm_slot_bytes.argtypes = [C.c_int32]
-        lib.upkie_vecnorm_moments_local.restype = C.c_int
-        lib.upkie_vecnorm_moments_local.argtypes = ([C.c_int32, C.c_int32] + [vp] * 8 + [C.c_int32] + [C.c_double] * 4 + [vp] * 8)
-        lib.upkie_vecnorm_merge.restype = C.c_int
-        lib.upkie_vecnorm_merge.argtypes = ([C.c_int32, C.c_int32] + [vp] * 8 + [C.c_int32] + [C.c_double] * 4 + [vp] * 6 + [vp, C.c_int32, vp])
-    if hasattr(lib, "upkie_ppo_minibatch_apply"):
-        shape_p, cfg_p = C.POINTER(abi.UpkieMlpShape), C.POINTER(abi.UpkiePpoConfig)
-        lib.upkie_ppo_slot_bytes.restype = C.c_int64
-        lib.upkie_ppo_slot_bytes.argtypes = [shape_p]
-        lib.upkie_ppo_advantage_slot_bytes.restype = C.c_int64
-        lib.upkie_ppo_advantage_slot_bytes.argtypes = [C.c_int32, C.c_int32]
-        lib.upkie_ppo_advantage_partials.restype = C.c_int
-        lib.upkie_ppo_advantage_partials.argtypes = [C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp]
-        lib.upkie_ppo_advantage_finish.restype = C.c_int
-        lib.upkie_ppo_advantage_finish.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp]
-        lib.upkie_ppo_minibatch_gradient.restype = C.c_int
-        lib.upkie_ppo_minibatch_gradient.argtypes = [shape_p, cfg_p] + [C.c_int32] * 5 + [vp] * 12
-        lib.upkie_ppo_minibatch_apply.restype = C.c_int
-        lib.upkie_ppo_minibatch_apply.argtypes = [shape_p, cfg_p, C.c_int32, C.c_int32, vp, C.c_int32] + [vp] * 7
-    if hasattr(lib, "upkie_ppo_minibatch_update_controlled"):  # (the control block: an older build lacks it, and still loads)
-        shape_p, cfg_p = C.POINTER(abi.UpkieMlpShape), C.POINTER(abi.UpkiePpoConfig)
-        lib.upkie_ppo_control_set.restype = C.c_int
-        lib.upkie_ppo_control_set.argtypes = [vp] + [C.c_double] * 4 + [vp]
-        lib.upkie_ppo_update_begin.restype = C.c_int
-        lib.upkie_ppo_update_begin.argtypes = [vp, vp]
-        lib.upkie_ppo_minibatch_update_controlled.restype = C.c_int
-        lib.upkie_ppo_minibatch_update_controlled.argtypes = [shape_p, cfg_p] + [C.c_int32] * 4 + [vp] * 15
-        lib.upkie_ppo_minibatch_gradient_controlled.restype = C.c_int
-        lib.upkie_ppo_minibatch_gradient_controlled.argtypes = [shape_p, cfg_p] + [C.c_int32] * 5 + [vp] * 13
-        lib.upkie_ppo_minibatch_apply_controlled.restype = C.c_int
-        lib.upkie_ppo_minibatch_apply_controlled.argtypes = [shape_p, cfg_p, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32] + [vp] * 7
-        lib.upkie_ppo_explained_variance.restype = C.c_int
-        lib.upkie_ppo_explained_variance.argtypes = [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp]
-    if hasattr(lib, "upkie_mlp_bootstrap_time_limits"):  # (the time-limit bootstrap: an older build lacks it, and still loads)
-        lib.upkie_mlp_bootstrap_time_limits.restype = C.c_int
-        lib.upkie_mlp_bootstrap_time_limits.argtypes = [C.c_int32, C.POINTER(abi.UpkieMlpShape), vp, vp, vp, vp, C.c_double, vp, vp]
-    if hasattr(lib, "upkie_episodes_step"):  # (the episode statistics: an older build lacks them, and still loads)
-        lib.upkie_episodes_workspace_bytes.restype = C.c_int64
-        lib.upkie_episodes_workspace_bytes.argtypes = [C.c_int32]
-        lib.upkie_episodes_step.restype = C.c_int
-        lib.upkie_episodes_step.argtypes = [C.c_int32, C.c_int32] + [vp] * 11
-        lib.upkie_episodes_reset.restype = C.c_int
-        lib.upkie_episodes_reset.argtypes = [C.c_int32, vp, vp, vp, vp]
-    lib.upkie_rollout_gae.restype = C.c_int
-    lib.upkie_rollout_gae.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
+        fn.restype = restype
+        if argtypes is not None:
+            fn.argtypes = argtypes
     _lib = lib
     return lib
 

@@ -197,8 +197,7 @@ class RunningNormalizer:
                 if status >= 0:
                     ex.exchange()
                     status = self._lib.upkie_vecnorm_merge(*args, ex.slots.data_ptr(), ex.world, stream)
-        if status < 0:
-            lib.check(status, None)
+        lib.check(status, None)
 
     def broadcast_statistics(self, src: int = 0) -> None:
         """Copy the statistics of group rank `src` to every rank (with their fp32 mirrors and an attached policy's packed

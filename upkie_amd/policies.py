@@ -58,8 +58,7 @@ class LinearPolicy:
             status = self._lib.upkie_linear_policy(n, self.obs_dim, self.act_dim, obs.data_ptr(), self.weights.data_ptr(),
                                                    None if self.bias is None else self.bias.data_ptr(), self.clip, self._act.data_ptr(),
                                                    torch.cuda.current_stream(obs.device).cuda_stream)
-        if status < 0:
-            lib.check(status, None)
+        lib.check(status, None)
         return self._act
 
 
@@ -426,8 +425,7 @@ class MlpActorCritic:
             status = self._lib.upkie_mlp_actor_critic(
                 n, C.byref(self.shape), self.packed.data_ptr(), obs.data_ptr(), self.calls.data_ptr(), self.seed, int(bool(deterministic)),
                 *[ptr(name) for name in OUTPUT_NAMES], torch.cuda.current_stream(self.device).cuda_stream)
-        if status < 0:
-            lib.check(status, None)
+        lib.check(status, None)
 
     def act(self, obs: torch.Tensor, deterministic: bool = False, out: Optional[dict] = None):
         """(env_action, action, value, log_prob) of a batch of observations ``[N, ...]``; value is None without a
@@ -491,8 +489,7 @@ class MlpActorCritic:
             status = self._lib.upkie_mlp_bootstrap_time_limits(n, C.byref(self.shape), self.packed.data_ptr(), final_obs.data_ptr(),
                                                                flags[0].data_ptr(), flags[1].data_ptr(), gamma, reward.data_ptr(),
                                                                torch.cuda.current_stream(self.device).cuda_stream)
-        if status < 0:
-            lib.check(status, None)
+        lib.check(status, None)
         return reward
 
 

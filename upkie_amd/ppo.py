@@ -278,21 +278,18 @@ class PpoTrainer:
             stream = torch.cuda.current_stream(self.device).cuda_stream
             if self.controlled:
                 status = lb.upkie_ppo_update_begin(p(self.control), stream)
-                if status < 0:
-                    lib.check(status, None)
+                lib.check(status, None)
             for e in range(self.n_epochs):
                 perm = self.perm[e]
                 status = lb.upkie_ppo_advantage_stats(total, self._mb, p(perm), adv, int(self.normalize_advantage), p(self.adv_stats[e]), stream)
-                if status < 0:
-                    lib.check(status, None)
+                lib.check(status, None)
                 for j in range(self.n_minibatches):
                     start = j * self._mb
                     status = minibatch(
                         shape, cfg, total, start, min(self._mb, total - start), self._mb, p(perm), obs, act, vals, logp, adv, ret,
                         p(self.adv_stats[e, j]), p(self.policy.packed), p(self.m), p(self.v), p(self.control), p(self.workspace),
                         p(self.stats[e, j]), stream)
-                    if status < 0:
-                        lib.check(status, None)
+                    lib.check(status, None)
         if sync:
             self.sync_modules()
         return self.stats
@@ -303,38 +300,34 @@ class PpoTrainer:
         p = lambda t: t.data_ptr()  # noqa: E731
         W, mb = gx.world, self._mb
 
-        def ok(status):
-            if status < 0:
-                lib.check(status, None)
-
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             if self.controlled:
-                ok(lb.upkie_ppo_update_begin(p(self.control), stream))
+                lib.check(lb.upkie_ppo_update_begin(p(self.control), stream))
             for e in range(self.n_epochs):
                 perm = p(self.perm[e])
-                ok(lb.upkie_ppo_advantage_partials(total, mb, perm, adv, 0, None, W, p(ax.mine), stream))
+                lib.check(lb.upkie_ppo_advantage_partials(total, mb, perm, adv, 0, None, W, p(ax.mine), stream))
                 ax.exchange()
-                ok(lb.upkie_ppo_advantage_partials(total, mb, perm, adv, 1, p(ax.slots), W, p(ax.mine), stream))
+                lib.check(lb.upkie_ppo_advantage_partials(total, mb, perm, adv, 1, p(ax.slots), W, p(ax.mine), stream))
                 ax.exchange()
-                ok(lb.upkie_ppo_advantage_finish(total, mb, int(self.normalize_advantage), p(ax.slots), W, p(self.adv_stats[e]), stream))
+                lib.check(lb.upkie_ppo_advantage_finish(total, mb, int(self.normalize_advantage), p(ax.slots), W, p(self.adv_stats[e]), stream))
                 for j in range(self.n_minibatches):
                     start = j * mb
                     size = min(mb, total - start)
                     if self.controlled:
-                        ok(lb.upkie_ppo_minibatch_gradient_controlled(shape, cfg, total, start, size, W * size, mb, perm, obs, act, vals, logp, adv,
-                                                                      ret, p(self.adv_stats[e, j]), p(self.policy.packed), p(self.workspace),
-                                                                      p(gx.mine), p(self.control), stream))
+                        lib.check(lb.upkie_ppo_minibatch_gradient_controlled(shape, cfg, total, start, size, W * size, mb, perm, obs, act, vals, logp,
+                                                                             adv, ret, p(self.adv_stats[e, j]), p(self.policy.packed),
+                                                                             p(self.workspace), p(gx.mine), p(self.control), stream))
                         gx.exchange()  # (after a stop: still a collective every rank joins; the apply half ignores it)
-                        ok(lb.upkie_ppo_minibatch_apply_controlled(shape, cfg, start, W * size, mb, p(gx.slots), W, p(self.policy.packed),
-                                                                   p(self.m), p(self.v), p(self.control), p(self.workspace), p(self.stats[e, j]),
-                                                                   stream))
+                        lib.check(lb.upkie_ppo_minibatch_apply_controlled(shape, cfg, start, W * size, mb, p(gx.slots), W, p(self.policy.packed),
+                                                                          p(self.m), p(self.v), p(self.control), p(self.workspace),
+                                                                          p(self.stats[e, j]), stream))
                         continue
-                    ok(lb.upkie_ppo_minibatch_gradient(shape, cfg, total, start, size, W * size, mb, perm, obs, act, vals, logp, adv, ret,
-                                                       p(self.adv_stats[e, j]), p(self.policy.packed), p(self.workspace), p(gx.mine), stream))
+                    lib.check(lb.upkie_ppo_minibatch_gradient(shape, cfg, total, start, size, W * size, mb, perm, obs, act, vals, logp, adv, ret,
+                                                              p(self.adv_stats[e, j]), p(self.policy.packed), p(self.workspace), p(gx.mine), stream))
                     gx.exchange()
-                    ok(lb.upkie_ppo_minibatch_apply(shape, cfg, W * size, mb, p(gx.slots), W, p(self.policy.packed), p(self.m), p(self.v),
-                                                    p(self.scalars), p(self.workspace), p(self.stats[e, j]), stream))
+                    lib.check(lb.upkie_ppo_minibatch_apply(shape, cfg, W * size, mb, p(gx.slots), W, p(self.policy.packed), p(self.m), p(self.v),
+                                                           p(self.scalars), p(self.workspace), p(self.stats[e, j]), stream))
 
     def train(self, buffer, sync: bool = True) -> torch.Tensor:
         """`prepare` then `update`: SB3's ``PPO.train`` on one full rollout buffer. Returns ``[n_epochs, n_minibatches, 7]``
@@ -360,8 +353,7 @@ class PpoTrainer:
         with torch.cuda.device(self.device):
             status = self._lib.upkie_ppo_control_set(self.control.data_ptr(), float(lr), float(self._clip_range), float(self._clip_range_vf or 0.0),
                                                      float(self._target_kl or 0.0), torch.cuda.current_stream(self.device).cuda_stream)
-        if status < 0:
-            lib.check(status, None)
+        lib.check(status, None)
         self._lr = float(lr)
 
     def set_progress(self, progress_remaining: float) -> None:
@@ -419,8 +411,7 @@ class PpoTrainer:
                          (2, ex.slots.data_ptr(), ex.world, None)]
             for phase, slots, world, mine in steps:
                 status = lb.upkie_ppo_explained_variance(self._total, ret, val, phase, slots, world, mine, out, stream)
-                if status < 0:
-                    lib.check(status, None)
+                lib.check(status, None)
                 if phase in (0, 1):
                     ex.exchange()
         return self._log_words[0]

@@ -88,8 +88,7 @@ class BatchedSim:
         return torch.cuda.current_stream(self.device).cuda_stream
 
     def _check(self, status: int) -> None:
-        if status < 0:
-            lib.check(status, self._handle)
+        lib.check(status, self._handle)
 
     def _launch(self, fn, *args) -> None:
         """One call into the library on torch's current stream of this handle's device. A Python-level RL loop pays
@@ -99,8 +98,7 @@ class BatchedSim:
         else:
             with torch.cuda.device(self.device):
                 status = fn(self._handle, *args, self._stream())
-        if status < 0:
-            lib.check(status, self._handle)
+        lib.check(status, self._handle)
 
     def push_config(self) -> None:
         """Hand the (mutated) ``self.config`` to the library."""
@@ -261,8 +259,7 @@ class BatchedSim:
             def step_agent() -> None:
                 if raw_stream is not None and current_device() == index:
                     status = fn(handle, state, obs_p, rew, term, trunc, raw_stream(index))
-                    if status < 0:
-                        lib.check(status, handle)
+                    lib.check(status, handle)
                 else:
                     slow(fn, state, obs_p, rew, term, trunc)
 
@@ -271,8 +268,7 @@ class BatchedSim:
         def step(action_address: int) -> None:
             if raw_stream is not None and current_device() == index:
                 status = fn(handle, state, action_address, obs_p, rew, term, trunc, raw_stream(index))
-                if status < 0:
-                    lib.check(status, handle)
+                lib.check(status, handle)
             else:
                 slow(fn, state, action_address, obs_p, rew, term, trunc)
 
@@ -301,8 +297,7 @@ class BatchedSim:
             else:
                 with torch.cuda.device(device):
                     status = call(self._stream())
-            if status < 0:
-                lib.check(status, handle)
+            lib.check(status, handle)
 
         if kind in ("pendulum", "gyropod", "servos"):
             fn = {"pendulum": lib_.upkie_sim_step_pendulum, "gyropod": lib_.upkie_sim_step_gyropod, "servos": lib_.upkie_sim_step_servos}[kind]
