@@ -1250,6 +1250,96 @@ int upkie_episodes_step(int32_t num_envs, int32_t window, const float* reward, c
 
 int upkie_episodes_reset(int32_t num_envs, const uint8_t* mask, double* ep_return, int32_t* ep_length, void* stream);
 
+/* ---- Agent pipeline (action shaping, noise, VecFrameStack) --------------
+ * What an agent wraps around the env before PPO sees it, csrc/
+ * agent_pipeline.hpp: N = num_envs envs, D = obs_dim words per env
+ * observation, A = act_dim (1-64), K = stack frames (>= 1) of
+ * F = D + (A with ACTION_IN_OBSERVATION) words, K F <= 256 (the obs_dim cap of
+ * upkie_mlp_actor_critic, which reads the stack). State, device buffers, zero
+ * before the first reset:
+ *   prev_command [N][A] float32: the command last sent to the env
+ *   observation [N][K][F] float32: the stack, oldest frame first
+ *     (Stable-Baselines3's VecFrameStack on a flat observation)
+ *   calls [N] uint32: the call counter of the env's noise
+ * Settings, the arguments every launch begins with: flags, a set of
+ * UpkiePipelineFlag; dt > 0; action_lag (s; read with ACTION_LAG only);
+ * params, a DEVICE buffer of 3 A + D float32 words low[A], high[A], action
+ * sigma[A], observation sigma[D]; seed. upkie_pipeline_params checks HOST
+ * arrays (low <= high, sigmas non-negative and finite; a NULL sigma array: all
+ * zero) and packs them into `params` (host, may be NULL: check only); it
+ * returns the word count 3 A + D or a negative status. dt and alpha =
+ * dt / action_lag are rounded to float32 once; the arithmetic below is
+ * float32, fl() one rounding, fma() a fused multiply-add, clip(v) =
+ * min(max(v, low[a]), high[a]).
+ *
+ * upkie_pipeline_shape_action (one launch, between the policy and the env):
+ * action [N][A] is the policy's env_action. Per word, p = prev_command, each
+ * stage only with its flag:
+ *   INTEGRATE_ACTION: u = clip(fma(action, dt, p)), otherwise u = action
+ *   ACTION_NOISE:     u = clip(fma(sigma_a[a], z, u))
+ *   ACTION_LAG:       c = fma(alpha, fl(u - p), p), otherwise c = u
+ *     (utils/filters.py's low_pass_filter; alpha >= 0.5 is refused)
+ *   command = c; prev_command = c.
+ * A word whose action or result is not finite: command = 0 (the neutral
+ * command) and prev_command keeps its value (the step kernels' rule).
+ *
+ * upkie_pipeline_observe (one launch, behind the env step): the new frame of
+ * env n is fma(sigma_o[d], z, next_obs[n][d]) for d < D (next_obs[n][d] as it
+ * is without OBSERVATION_NOISE), then command[n][0..A) with
+ * ACTION_IN_OBSERVATION. done = terminated | truncated (bytes, NULL: none).
+ *   not done: the stack moves one frame towards its old end, in place, and
+ *     the new frame takes the last slot.
+ *   done (same-step autoreset: next_obs is the reset observation):
+ *     final_observation[n] = the OLD stack moved one frame with, in the last
+ *     slot, the frame of final_obs[n] (noised with draws of its own, followed
+ *     by the command that was just applied); then the stack is zero but for
+ *     its last slot, which takes the frame of next_obs with a zero command,
+ *     and prev_command[n] = 0. final_obs NULL (no same-step autoreset): the
+ *     restart alone. The final_observation rows of envs that did not end keep
+ *     what they held (the time-limit bootstrap reads truncated rows only).
+ * upkie_pipeline_reset: that restart from obs for the envs with mask[n] != 0
+ * (bytes, NULL: every env); the others keep their state.
+ *
+ * Noise: z is a standard normal from Philox4x32-10 with counter (n, calls[n],
+ * 0, 5 << 24 | block) and key (seed lo, seed hi), Box-Muller on the block's
+ * four words as upkie_mlp_actor_critic (whose tag is 4; the step kernels use
+ * 0-3): element i & 3 of block i >> 2 for action word / observation column i,
+ * block 64 + (i >> 2) for column i of the terminal frame. A launch that
+ * draws (shape_action with ACTION_NOISE; observe with OBSERVATION_NOISE, every
+ * env; reset with OBSERVATION_NOISE, the masked envs) reads calls[n] and
+ * leaves calls[n] + 1: the draws of an env do not depend on the batch and a
+ * saved counter resumes them. Without a noise flag no Philox round runs and
+ * calls is not touched (it may be NULL).
+ *
+ * One wavefront serves whole envs; no allocation, no host synchronisation, no
+ * host argument that changes between steps: every call can be captured in a
+ * hipGraph. No CPU fallback: UPKIE_ERR_NO_DEVICE without a HIP device. Errors
+ * are reported through upkie_sim_last_error(NULL). */
+enum UpkiePipelineFlag {
+  UPKIE_PIPELINE_ACTION_IN_OBSERVATION = 1,
+  UPKIE_PIPELINE_INTEGRATE_ACTION = 2,
+  UPKIE_PIPELINE_ACTION_NOISE = 4,
+  UPKIE_PIPELINE_ACTION_LAG = 8,
+  UPKIE_PIPELINE_OBSERVATION_NOISE = 16
+};
+
+int64_t upkie_pipeline_params(int32_t obs_dim, int32_t act_dim, const float* action_low, const float* action_high,
+                              const float* action_noise, const float* observation_noise, float* params);
+
+int upkie_pipeline_shape_action(int32_t num_envs, int32_t obs_dim, int32_t act_dim, int32_t stack, int32_t flags,
+                                double dt, double action_lag, const float* params, uint64_t seed, const float* action,
+                                float* prev_command, uint32_t* calls, float* command, void* stream);
+
+int upkie_pipeline_observe(int32_t num_envs, int32_t obs_dim, int32_t act_dim, int32_t stack, int32_t flags, double dt,
+                           double action_lag, const float* params, uint64_t seed, const float* next_obs,
+                           const uint8_t* terminated, const uint8_t* truncated, const float* final_obs,
+                           const float* command, float* prev_command, uint32_t* calls, float* observation,
+                           float* final_observation, void* stream);
+
+int upkie_pipeline_reset(int32_t num_envs, int32_t obs_dim, int32_t act_dim, int32_t stack, int32_t flags, double dt,
+                         double action_lag, const float* params, uint64_t seed, const float* obs, const uint8_t* mask,
+                         float* prev_command, uint32_t* calls, float* observation, void* stream);
+
 /* ---- Rollout consumer (BASELINE.json configs[3]) ---
  * Generalized advantage estimation over a rollout resident in HBM: rewards,
  * values, episode_starts, advantages, returns are [num_steps][num_envs]

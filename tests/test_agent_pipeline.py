@@ -1,0 +1,346 @@
+"""The agent pipeline without a GPU: the numpy twin (tests/agent_pipeline_reference.py) against an actual deque per env,
+its lag stage against `upkie_amd.utils.filters.low_pass_filter`, the keying of its noise, every refusal (Python's and,
+through the built library, the C-ABI's), and the order of `Ppo`'s rollout step with a pipeline on the CPU oracle env."""
+
+import ctypes as C
+import math
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle as O
+from tests import agent_pipeline_reference as P
+from tests import mlp_reference as MR
+from upkie_amd import abi, lib
+from upkie_amd import pipeline as pipeline_module
+from upkie_amd.pipeline import AgentPipeline
+from upkie_amd.ppo import Ppo
+from upkie_amd.utils.filters import low_pass_filter
+
+F32 = np.float32
+
+
+@pytest.fixture(scope="module")
+def library():
+    lib.build()
+    return lib.load()
+
+
+# ---------------------------------------------------------------- the twin's index arithmetic against a deque
+@pytest.mark.parametrize("K, D, A, in_obs", [(4, 3, 2, True), (1, 4, 1, True), (8, 4, 1, True), (3, 5, 2, False)])
+def test_twin_is_a_deque_of_frames_per_env(K, D, A, in_obs):
+    rng = np.random.default_rng(K * 100 + D)
+    T = 3 * K + 2
+    ends = [set(), {0}, {1}, {K - 1}, {K}, {2, 3}, {0, 1, 2}, {K, K + 1, 2 * K}]  # ending at steps 0, 1, K - 1, K, twice in a row
+    F = D + (A if in_obs else 0)
+    for with_final in (True, False):
+        for e, when in enumerate(ends):
+            tw = P.Twin(e, D, [-1.0] * A, [1.0] * A, 0.005, stack=K, action_in_observation=in_obs)
+            dq = P.DequeStack(K, F)
+            first = rng.normal(size=D).astype(F32)
+            flat = tw.reset(first)
+            dq.restart(np.concatenate([first, np.zeros(A, dtype=F32)])[:F])
+            assert np.array_equal(flat, dq.flat())
+            for t in range(T):
+                action = rng.uniform(-1, 1, size=A).astype(F32)
+                nxt, fin = rng.normal(size=D).astype(F32), rng.normal(size=D).astype(F32)
+                done = t in when
+                cmd = tw.shape_action(action)
+                assert np.array_equal(cmd, action), "no stage switched on: the command is the action"
+                flat = tw.observe(nxt, done, fin if with_final else None)
+                tail = cmd if in_obs else np.zeros(0, dtype=F32)
+                dq.step(np.concatenate([nxt, tail]), done, np.concatenate([fin, tail]) if with_final else None,
+                        np.concatenate([nxt, np.zeros_like(tail)]))
+                assert np.array_equal(flat, dq.flat()), (e, t)
+                if done:
+                    assert not tw.prev_command.any()
+                    if with_final:
+                        assert np.array_equal(tw.final.reshape(-1), dq.final), (e, t)
+            assert tw.calls == 0, "no noise: the counter does not move"
+            assert (tw.final is None) == (not when or not with_final)
+
+
+def test_lag_stage_is_the_projects_low_pass_filter():
+    dt, lag = 0.005, 0.04
+    tw = P.Twin(0, 4, [-2.0], [2.0], dt, stack=1, action_lag=lag)
+    rng = np.random.default_rng(3)
+    prev = 0.0
+    for _ in range(50):
+        a = F32(rng.uniform(-2, 2))
+        got = float(tw.shape_action([a])[0])
+        want = low_pass_filter(prev, lag, float(a), dt)
+        assert got == pytest.approx(want, rel=2e-7, abs=1e-7)  # (alpha and the result rounded to float32)
+        prev = got
+    with pytest.raises(AssertionError):
+        low_pass_filter(0.0, 0.01, 1.0, dt)  # alpha = 0.5
+    with pytest.raises(ValueError, match="low_pass_filter"):
+        AgentPipeline(4, 4, [-1.0], [1.0], dt, action_lag=0.01)
+
+
+def test_integration_and_noise_stay_inside_the_bounds():
+    tw = P.Twin(7, 4, [-0.5], [0.25], 0.1, stack=2, integrate_action=True, action_noise=[0.3], action_lag=0.5, seed=11)
+    prev = 0.0
+    for t in range(40):
+        c = float(tw.shape_action([1.0 if t < 25 else -1.0])[0])
+        u = np.clip(prev + (1.0 if t < 25 else -1.0) * float(F32(0.1)), -0.5, 0.25)
+        u = np.clip(u + float(F32(0.3)) * tw.last_z[0], -0.5, 0.25)
+        assert c == F32(prev + float(F32(0.1 / 0.5)) * (u - prev))
+        assert -0.5 <= c <= 0.25
+        prev = c
+    assert tw.calls == 40
+    poisoned = tw.shape_action([math.nan])
+    assert poisoned[0] == 0.0 and float(tw.prev_command[0]) == prev, "the neutral command, prev_command kept"
+
+
+# ---------------------------------------------------------------- noise
+def test_draws_depend_on_env_call_and_seed_only_and_never_meet_the_policys():
+    kw = dict(stack=2, action_noise=[0.1, 0.2], observation_noise=[0.01] * 3, seed=5)
+    rng = np.random.default_rng(0)
+    acts, obs = rng.uniform(-1, 1, size=(6, 7, 2)).astype(F32), rng.normal(size=(6, 7, 3)).astype(F32)
+    done = rng.uniform(size=(6, 7)) < 0.3
+    runs = {}
+    for n in (3, 7):  # the same envs in a batch of 3 and in a batch of 7
+        twins = [P.Twin(e, 3, [-1, -1], [1, 1], 0.01, **kw) for e in range(n)]
+        for e, tw in enumerate(twins):
+            tw.reset(obs[0, e])
+        out = []
+        for t in range(6):
+            out.append(P.run_batch(twins, acts[t, :n], obs[t, :n], done[t, :n], obs[(t + 1) % 6, :n]))
+        runs[n] = out
+    for (c3, o3), (c7, o7) in zip(runs[3], runs[7]):
+        assert np.array_equal(c3, c7[:3]) and np.array_equal(o3, o7[:3])
+    # shape_action and observe of one step use different counters; the terminal frame has blocks of its own
+    tw = P.Twin(2, 3, [-1, -1], [1, 1], 0.01, **kw)
+    tw.reset(obs[0, 2])
+    assert tw.calls == 1
+    tw.shape_action(acts[0, 2])
+    assert tw.calls == 2
+    tw.observe(obs[1, 2], True, obs[2, 2])
+    assert tw.calls == 3
+    # the raw Philox words under the pipeline's tag and the policy's, same seed, env, call and block: nothing shared
+    assert P.STREAM_PIPELINE not in (0, 1, 2, 3, MR.STREAM_POLICY)
+    for env, call, block in ((0, 0, 0), (5, 17, 1), (4095, 123456, 3)):
+        key = [5, 0]
+        mine = O.philox([env, call, 0, (P.STREAM_PIPELINE << 24) | block], key)
+        theirs = O.philox([env, call, 0, (MR.STREAM_POLICY << 24) | block], key)
+        assert not set(int(x) for x in mine) & set(int(x) for x in theirs)
+        for a in range(4):
+            assert P.philox_normal(env, call, block, a, 5) != MR.philox_normal(env, call, 4 * block + a, 5)
+            assert P.philox_normal(env, call, block, a, 5, tag=MR.STREAM_POLICY) == MR.philox_normal(env, call, 4 * block + a, 5)
+    z = np.array([P.philox_normal(e, c, 0, k, 9) for e in range(40) for c in range(25) for k in range(4)])
+    assert abs(z.mean()) < 0.08 and abs(z.std() - 1.0) < 0.06
+
+
+# ---------------------------------------------------------------- refusals
+def test_python_refuses_every_listed_limit_before_any_device_use():
+    ok = dict(num_envs=4, obs_dim=4, action_low=[-1.0], action_high=[1.0], dt=0.005)
+    bad = [
+        (dict(stack=52), "256"),  # 52 * 5 = 260 words
+        (dict(stack=0), "stack"),
+        (dict(dt=0.0), "dt"),
+        (dict(dt=math.inf), "dt"),
+        (dict(action_low=[1.0], action_high=[-1.0]), "low <= high"),
+        (dict(action_low=[-1.0] * 65, action_high=[1.0] * 65, stack=1), "act_dim"),
+        (dict(action_low=[], action_high=[]), "act_dim"),
+        (dict(action_noise=[-0.1]), "action_noise"),
+        (dict(action_noise=[math.inf]), "action_noise"),
+        (dict(observation_noise=[0.1, 0.1, math.nan, 0.1]), "observation_noise"),
+        (dict(observation_noise=[-1e-3] * 4), "observation_noise"),
+        (dict(action_lag=0.01), "low_pass_filter"),
+        (dict(action_lag=0.0), "low_pass_filter"),
+        (dict(num_envs=0), "num_envs"),
+    ]
+    for change, match in bad:
+        with pytest.raises(ValueError, match=match):
+            AgentPipeline(**dict(ok, **change))
+    from upkie_amd.exceptions import UpkieRuntimeError
+
+    with pytest.raises(UpkieRuntimeError, match="no CPU fallback"):
+        AgentPipeline(**ok, device="cpu")
+    pipe = AgentPipeline.__new__(AgentPipeline)  # the packing, which needs no device
+    pipe.obs_dim, pipe.act_dim = 2, 1
+    pipe.action_low, pipe.action_high, pipe.action_noise, pipe.observation_noise = [-1.0], [2.0], None, [0.5, 0.25]
+    assert pipe.packed_params().tolist() == [-1.0, 2.0, 0.0, 0.5, 0.25]
+
+
+def test_library_refuses_every_listed_limit_without_a_gpu(library):
+    for name in ("upkie_pipeline_params", "upkie_pipeline_shape_action", "upkie_pipeline_observe", "upkie_pipeline_reset"):
+        assert name in lib.EXPORTED_SYMBOLS and getattr(library, name) is not None
+    err = lambda: library.upkie_sim_last_error(None)  # noqa: E731
+    buf = (C.c_float * 1024)()
+    flags_all = 31
+    ok = dict(num_envs=4, obs_dim=4, act_dim=1, stack=8, flags=flags_all, dt=0.005, lag=0.04, params=buf)
+
+    def shape(**change):
+        a = dict(ok, **change)
+        return library.upkie_pipeline_shape_action(a["num_envs"], a["obs_dim"], a["act_dim"], a["stack"], a["flags"], a["dt"], a["lag"], a["params"], 0,
+                                                   buf, buf, buf, buf, None)
+
+    def observe(**change):
+        a = dict(ok, **change)
+        return library.upkie_pipeline_observe(a["num_envs"], a["obs_dim"], a["act_dim"], a["stack"], a["flags"], a["dt"], a["lag"], a["params"], 0,
+                                              buf, None, None, a.get("final_obs"), buf, buf, buf, buf, a.get("final_observation", buf), None)
+
+    def reset(**change):
+        a = dict(ok, **change)
+        return library.upkie_pipeline_reset(a["num_envs"], a["obs_dim"], a["act_dim"], a["stack"], a["flags"], a["dt"], a["lag"], a["params"], 0, buf,
+                                            None, buf, buf, buf, None)
+
+    cases = [(dict(stack=52), b"256"), (dict(stack=0), b"stack"), (dict(act_dim=0), b"act_dim"), (dict(act_dim=65, stack=1), b"act_dim"),
+             (dict(obs_dim=0), b"obs_dim"), (dict(dt=0.0), b"dt"), (dict(dt=-1.0), b"dt"), (dict(dt=math.nan), b"dt"), (dict(dt=math.inf), b"dt"),
+             (dict(lag=0.01), b"low_pass_filter"), (dict(lag=0.0), b"low_pass_filter"), (dict(num_envs=0), b"num_envs"),
+             (dict(flags=32), b"flags"), (dict(params=None), b"params")]
+    for call in (shape, observe, reset):
+        for change, word in cases:
+            assert call(**change) == abi.ERR_INVALID_ARGUMENT, (call.__name__, change)
+            assert word in err(), (call.__name__, change, err())
+    assert shape(stack=51) != abi.ERR_INVALID_ARGUMENT, "51 * 5 = 255 words fit"
+    assert shape(stack=64, flags=flags_all & ~1) != abi.ERR_INVALID_ARGUMENT, "without the command a frame is 4 words: 256 fit"
+    assert shape(lag=0.01, flags=flags_all & ~8) != abi.ERR_INVALID_ARGUMENT, "the lag is read with its flag only"
+    assert observe(final_obs=buf, final_observation=None) == abi.ERR_INVALID_ARGUMENT and b"final_observation" in err()
+    # the host arrays behind params
+    f = lambda *v: (C.c_float * len(v))(*v)  # noqa: E731
+    out = (C.c_float * 16)()
+    params = library.upkie_pipeline_params
+    assert params(4, 2, f(-1, -2), f(1, 2), f(0.1, 0.0), None, out) == 10
+    assert list(out[:10]) == [-1.0, -2.0, 1.0, 2.0, F32(0.1), 0.0, 0.0, 0.0, 0.0, 0.0]
+    assert params(4, 2, f(-1, -2), f(1, 2), None, f(1, 2, 3, 4), None) == 10, "a NULL output: the check alone"
+    for args, word in (((4, 2, f(-1, 3), f(1, 2), None, None, out), b"low <= high"), ((4, 2, f(-1, math.nan), f(1, 2), None, None, out), b"low <= high"),
+                       ((4, 2, f(-1, -2), f(1, 2), f(0.1, -0.1), None, out), b"action_noise"),
+                       ((4, 2, f(-1, -2), f(1, 2), f(math.inf, 0.1), None, out), b"action_noise"),
+                       ((4, 2, f(-1, -2), f(1, 2), None, f(0, 0, math.nan, 0), out), b"observation_noise"),
+                       ((4, 2, f(-1, -2), f(1, 2), None, f(0, 0, -1, 0), out), b"observation_noise"),
+                       ((4, 2, None, f(1, 2), None, None, out), b"bounds"), ((4, 0, f(), f(), None, None, out), b"act_dim"),
+                       ((4, 65, f(), f(), None, None, out), b"act_dim"), ((0, 1, f(0), f(0), None, None, out), b"obs_dim")):
+        assert params(*args) == abi.ERR_INVALID_ARGUMENT, args[:2]
+        assert word in err(), (word, err())
+    if library.upkie_hip_device_count() == 0:
+        assert shape() == abi.ERR_NO_DEVICE and observe() == abi.ERR_NO_DEVICE and reset() == abi.ERR_NO_DEVICE
+        assert b"no HIP device" in err()
+
+
+# ---------------------------------------------------------------- Ppo wiring
+class _TwinPipeline:
+    """`AgentPipeline`'s interface on the numpy twins and CPU tensors; records the order of its calls."""
+
+    def __init__(self, N, D, A, K, log):
+        self.num_envs, self.obs_dim, self.act_dim, self.stack = N, D, A, K
+        self.frame_dim, self.stacked_dim = D + A, K * (D + A)
+        self.twins = [P.Twin(e, D, [-1.0] * A, [1.0] * A, 0.005, stack=K, integrate_action=True) for e in range(N)]
+        self.observation, self.final_observation = torch.zeros(N, self.stacked_dim), torch.zeros(N, self.stacked_dim)
+        self.command = torch.zeros(N, A)
+        self.log = log
+
+    def reset(self, obs):
+        self.log.append("reset")
+        for e, tw in enumerate(self.twins):
+            self.observation[e] = torch.from_numpy(tw.reset(obs[e].numpy()).copy())
+        return self.observation
+
+    def shape_action(self, a):
+        self.log.append("shape_action")
+        for e, tw in enumerate(self.twins):
+            self.command[e] = torch.from_numpy(tw.shape_action(a[e].numpy()))
+        return self.command
+
+    def observe(self, next_obs, terminated, truncated, final_obs=None):
+        self.log.append("observe")
+        assert final_obs is not None
+        for e, tw in enumerate(self.twins):
+            done = bool(terminated[e]) or bool(truncated[e])
+            self.observation[e] = torch.from_numpy(tw.observe(next_obs[e].numpy(), done, final_obs[e].numpy()).copy())
+            if done:
+                self.final_observation[e] = torch.from_numpy(tw.final.reshape(-1).copy())
+        return self.observation
+
+
+def test_ppo_checks_the_pipeline_against_the_policy_and_the_env():
+    env = types.SimpleNamespace(num_envs=4)
+    policy = lambda d, a: types.SimpleNamespace(shape=types.SimpleNamespace(obs_dim=d, act_dim=a))  # noqa: E731
+    pipe = _TwinPipeline(4, 4, 1, 8, [])
+    assert Ppo(env, policy(40, 1), pipeline=pipe).pipeline is pipe
+    with pytest.raises(ValueError, match="stacks 8 frames of 5 = 40"):
+        Ppo(env, policy(4, 1), pipeline=pipe)
+    with pytest.raises(ValueError, match="actions"):
+        Ppo(env, policy(40, 2), pipeline=pipe)
+    with pytest.raises(ValueError, match="envs"):
+        Ppo(types.SimpleNamespace(num_envs=8), policy(40, 1), pipeline=pipe)
+    assert Ppo(env, object()).pipeline is None
+
+
+def test_ppo_rollout_step_with_a_pipeline_on_the_cpu_env():
+    """`Ppo._rollout_step_pipeline` on the CPU oracle env (tests/fake_sim.py), a recording policy and the twins: the
+    order of the calls, what each one is given, and the buffer's rows."""
+    import upkie_amd.envs as envs
+    from tests.fake_sim import oracle_sim_factory
+    from upkie_amd.utils.robot_state import RobotState
+    from upkie_amd.utils.robot_state_randomization import RobotStateRandomization
+
+    N, K, T = 3, 4, 9
+    log = []
+    init = RobotState(randomization=RobotStateRandomization(pitch=0.1))
+    env = envs.make("Upkie-HIP-Pendulum-Vec", num_envs=N, frequency=200.0, init_state=init, autoreset_mode="same_step", max_episode_steps=4,
+                    sim_factory=oracle_sim_factory)
+    pipe = _TwinPipeline(N, 4, 1, K, log)
+    seen = {"act": [], "bootstrap": [], "reward": []}
+
+    class Policy:
+        shape = types.SimpleNamespace(obs_dim=K * 5, act_dim=1)
+
+        def act(self, obs, out):
+            log.append("act")
+            assert obs is pipe.observation
+            seen["act"].append(obs.clone())
+            out["env_action"].fill_(0.5)
+            out["action"].fill_(0.5)
+            return (out["env_action"],)
+
+        def bootstrap_time_limits(self, final_obs, terminated, truncated, reward, gamma):
+            log.append("bootstrap")
+            assert final_obs is pipe.final_observation
+            seen["bootstrap"].append((final_obs.clone(), truncated.clone()))
+
+    def reward_fn(next_obs, info):
+        log.append("reward")
+        assert next_obs.shape == (N, 4), "the reward sees the RAW observation"
+        seen["reward"].append(next_obs.clone())
+        return 1.0 - next_obs[:, 0].abs()
+
+    with env:
+        model = Ppo(env, Policy(), n_steps=T, pipeline=pipe, normalize=False, graph=False, reward_fn=reward_fn)
+        model.device = torch.device("cpu")
+        model.episodes = types.SimpleNamespace(step=lambda r, te, tr: log.append("episodes"))
+        model.buffer = types.SimpleNamespace(
+            observations=torch.zeros(T, N, K * 5), actions=torch.zeros(T, N, 1), values=torch.zeros(T, N), log_probs=torch.zeros(T, N),
+            rewards=torch.zeros(T, N), episode_starts=torch.zeros(T, N, dtype=torch.uint8))
+        reset = env.reset(seed=0)
+        model._obs = reset[0] if isinstance(reset, tuple) else reset
+        raw0 = model._obs.clone()
+        model._policy_obs = pipe.reset(model._obs)
+        model._env_action = torch.empty(N, 1)
+        model._starts = torch.ones(N, dtype=torch.uint8)
+        model._slot = 0
+        ended = 0
+        for t in range(T):
+            del log[:]
+            model._rollout_step_pipeline()
+            assert log == ["act", "shape_action", "reward", "episodes", "observe", "bootstrap"], log
+            ended += int(model._starts.sum())
+        assert ended >= N, "every env hit its time limit at least once"
+        assert model._slot == 0
+    buf = model.buffer
+    assert torch.equal(buf.observations[0, :, -5:-1], raw0) and not buf.observations[0, :, :-5].any()
+    for t in range(T):
+        assert torch.equal(buf.observations[t], seen["act"][t])
+    # the stack of the recorded raw observations: rows of step t + 1 hold the raw observation of step t last, and the
+    # integrated command 0.5 * dt * (steps since the restart) beside it
+    for t in range(T - 1):
+        assert torch.equal(buf.observations[t + 1, :, -5:-1], seen["reward"][t])
+        started = buf.episode_starts[t + 1].bool()
+        assert not buf.observations[t + 1][started][:, :-5].any() and not buf.observations[t + 1][started][:, -1].any()
+        assert (buf.observations[t + 1][~started][:, -1] > 0).all()
+    final, truncated = seen["bootstrap"][3]
+    assert truncated.all(), "max_episode_steps = 4: the fourth step truncates every env"
+    assert (final[:, -1] > 0).all() and final[:, :5].any(), "the terminal stack keeps the ended episode's frames and command"

@@ -1,0 +1,195 @@
+// agent_pipeline.hpp -- what an agent wraps around the env before PPO sees it, on the device: the policy's output shaped
+// into the command the env receives (integration, actuator noise, a first-order lag), and the observation the policy
+// reads built from the env's (sensor noise, the command appended, the last K frames stacked as Stable-Baselines3's
+// VecFrameStack does, with its per-env restart and its stacked terminal observation). include/upkie_hip.h states the
+// arithmetic; Python: upkie_amd/pipeline.py.
+//
+// Two launches per rollout step (shape_action between the policy and the env, observe behind the env) and a masked
+// reset. State per env: prev_command[A], the stack [K][F] (oldest frame first), one uint32 call counter of the noise.
+//
+// Mapping: one wavefront serves whole envs, its lanes run over words. An env of the stack is K F <= 256 contiguous
+// words (160 bytes at K = 8, F = 5), so a wavefront takes max(1, floor(256 / (K F))) consecutive envs, at most 256
+// contiguous words, four per lane at a stride of 64: every load and store of the stack is one contiguous run of the
+// wavefront's lanes. The shift is in place: a lane's new word w of a live env is the old word w + F of the same env,
+// loaded by the lane itself; every lane loads all it needs, the wavefront waits for its loads, then stores (the
+// envs of a wavefront are touched by no other, so there is no ping-pong buffer whose address would alternate under a
+// captured graph). shape_action gives a wavefront floor(64 / A) envs, one lane per command word, for the same reason:
+// the lane that advances an env's counter shares a wavefront with every lane that reads it.
+//
+// Noise: Philox4x32-10 with counter (env, call, 0, STREAM_PIPELINE << 24 | block) under the pipeline's seed, Box-Muller
+// as policy_mlp.hpp's mlp_normal4 (four normals per block). shape_action draws action a from element a & 3 of block
+// a >> 2; observe draws column d of the new frame from element d & 3 of block d >> 2 and column d of the terminal
+// frame from block 64 + (d >> 2). Every noisy call of an env uses the env's counter once and advances it, so no two
+// calls share a block; without noise no Philox round is executed and the counters stay.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "step_kernels.hpp"  // philox4x32_10
+
+namespace upkie {
+
+// Tag of the pipeline's Philox draws (the step kernels use tags 0-3, the MLP policy 4).
+enum { STREAM_PIPELINE = 5 };
+
+enum { PIPELINE_THREADS = 256, PIPELINE_WAVE_WORDS = 256, PIPELINE_FINAL_BLOCK = 64 };
+
+struct PipelineDev {
+  int num_envs, obs_dim, act_dim, stack;
+  int frame, words;      // F = obs_dim (+ act_dim), K F
+  int group, group_act;  // envs per wavefront: observe / reset, shape_action
+  int action_in_obs, integrate, action_noise, lag, obs_noise;
+  float dt, alpha;
+  unsigned seed_lo, seed_hi;
+  const float* params;  // low[A], high[A], action sigma[A], observation sigma[D]
+};
+
+// Fills the sizes derived from (obs_dim, act_dim, stack, action_in_obs); false when a size is out of range.
+inline bool pipeline_sizes(PipelineDev& P) {
+  if (P.obs_dim < 1 || P.act_dim < 1 || P.act_dim > 64 || P.stack < 1) return false;
+  const int64_t frame = (int64_t)P.obs_dim + (P.action_in_obs ? P.act_dim : 0);
+  if (frame * P.stack > PIPELINE_WAVE_WORDS) return false;
+  P.frame = (int)frame;
+  P.words = (int)frame * P.stack;
+  P.group = PIPELINE_WAVE_WORDS / P.words;
+  P.group_act = 64 / P.act_dim;
+  return true;
+}
+
+inline int pipeline_blocks(int num_envs, int group) {
+  const int waves = (num_envs + group - 1) / group;
+  return (waves + PIPELINE_THREADS / 64 - 1) / (PIPELINE_THREADS / 64);
+}
+
+#if defined(__HIPCC__)
+
+// Element `elem` of the four standard normals of one Philox block (the arithmetic of mlp_normal4).
+__device__ __forceinline__ float pipeline_normal(unsigned env, unsigned call, unsigned block, unsigned elem, unsigned k0, unsigned k1) {
+  unsigned r[4];
+  philox4x32_10(env, call, 0u, ((unsigned)STREAM_PIPELINE << 24) | block, k0, k1, r);
+  const unsigned p = elem >> 1;
+  const unsigned ra = p ? r[2] : r[0], rb = p ? r[3] : r[1];
+  const float u1 = ((float)(ra >> 8) + 1.0f) * (1.0f / 16777216.0f);
+  const float u2 = (float)(rb >> 8) * (1.0f / 16777216.0f);
+  const float radius = sqrtf(-2.0f * logf(u1));
+  float sn, cs;
+  sincosf(6.283185307179586f * u2, &sn, &cs);
+  return radius * ((elem & 1u) ? sn : cs);
+}
+
+__device__ __forceinline__ float pipeline_clip(float v, float low, float high) { return fminf(fmaxf(v, low), high); }
+
+__global__ __launch_bounds__(PIPELINE_THREADS) void pipeline_shape_action_kernel(const PipelineDev P, const float* __restrict__ action,
+                                                                                 float* prev_command, uint32_t* calls, float* command) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)((blockIdx.x * PIPELINE_THREADS + threadIdx.x) >> 6);
+  const int A = P.act_dim;
+  const int local = lane / A, a = lane - local * A;
+  const int64_t e = (int64_t)wave * P.group_act + local;
+  if (local >= P.group_act || e >= P.num_envs) return;
+  const int64_t i = e * A + a;
+  const float x = action[i], prev = prev_command[i];
+  const float low = P.params[a], high = P.params[A + a];
+  float u = x;
+  if (P.integrate) u = pipeline_clip(fmaf(x, P.dt, prev), low, high);
+  unsigned call = 0u;
+  if (P.action_noise) {
+    call = calls[e];
+    const float z = pipeline_normal((unsigned)e, call, (unsigned)a >> 2, (unsigned)a & 3u, P.seed_lo, P.seed_hi);
+    u = pipeline_clip(fmaf(P.params[2 * A + a], z, u), low, high);
+  }
+  float c = u;
+  if (P.lag) c = fmaf(P.alpha, u - prev, prev);
+  // a poisoned word: the neutral command, and prev_command keeps its value (the step kernels' rule for commands)
+  const bool poisoned = !(fabsf(x) < 3.0e38f) || !(fabsf(c) < 3.0e38f);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every lane of the env has read its counter
+  command[i] = poisoned ? 0.f : c;
+  if (!poisoned) prev_command[i] = c;
+  if (P.action_noise && a == 0) calls[e] = call + 1u;
+}
+
+// RESET = false: one env step (observe). RESET = true: the restart of the envs with ended[e] != 0 (all when NULL);
+// the others are not touched, next_obs is the observation to restart from.
+template <bool RESET>
+__global__ __launch_bounds__(PIPELINE_THREADS) void pipeline_observe_kernel(const PipelineDev P, const float* __restrict__ next_obs,
+                                                                            const uint8_t* __restrict__ terminated,
+                                                                            const uint8_t* __restrict__ truncated,
+                                                                            const float* __restrict__ final_obs, const float* __restrict__ command,
+                                                                            float* prev_command, uint32_t* calls, float* observation,
+                                                                            float* final_observation) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)((blockIdx.x * PIPELINE_THREADS + threadIdx.x) >> 6);
+  const int S = P.words, F = P.frame, D = P.obs_dim, A = P.act_dim;
+  const int64_t e0 = (int64_t)wave * P.group;
+  if (e0 >= P.num_envs) return;
+  const int64_t left = P.num_envs - e0;
+  const int total = (int)(left < P.group ? left : P.group) * S;  // <= PIPELINE_WAVE_WORDS
+  constexpr int R = PIPELINE_WAVE_WORDS / 64;
+  float now[R], fin[R];
+  int word[R];
+  int64_t env[R];
+  unsigned call[R];
+  bool ended[R], write[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int idx = lane + 64 * r;
+    write[r] = idx < total;
+    ended[r] = false;
+    now[r] = fin[r] = 0.f;
+    word[r] = 0, env[r] = 0, call[r] = 0u;
+    if (!write[r]) continue;
+    const int le = (int)((unsigned)idx / (unsigned)S), w = idx - le * S;
+    const int64_t e = e0 + le;
+    word[r] = w, env[r] = e;
+    const bool done = (terminated && terminated[e] != 0) || (truncated && truncated[e] != 0);
+    ended[r] = RESET ? (!terminated || terminated[e] != 0) : done;
+    if (RESET && !ended[r]) {
+      write[r] = false;
+      continue;
+    }
+    if (P.obs_noise) call[r] = calls[e];
+    if (w < S - F) {  // an older slot: the frame one slot newer, or zero after a restart
+      const float old = RESET ? 0.f : observation[e * S + w + F];
+      now[r] = ended[r] ? 0.f : old;
+      fin[r] = old;
+      continue;
+    }
+    const int f = w - (S - F);
+    if (f < D) {
+      float v = next_obs[e * D + f];
+      if (P.obs_noise) {
+        const float sigma = P.params[3 * A + f];
+        v = fmaf(sigma, pipeline_normal((unsigned)e, call[r], (unsigned)f >> 2, (unsigned)f & 3u, P.seed_lo, P.seed_hi), v);
+        if (!RESET && ended[r] && final_obs)
+          fin[r] = fmaf(sigma, pipeline_normal((unsigned)e, call[r], PIPELINE_FINAL_BLOCK + ((unsigned)f >> 2), (unsigned)f & 3u, P.seed_lo, P.seed_hi),
+                        final_obs[e * D + f]);
+      } else if (!RESET && ended[r] && final_obs) {
+        fin[r] = final_obs[e * D + f];
+      }
+      now[r] = v;
+    } else {  // the command that was just applied; zero in the first frame of an episode
+      const float c = RESET ? 0.f : command[e * A + (f - D)];
+      now[r] = ended[r] ? 0.f : c;
+      fin[r] = c;
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the shift is in place: every load of the wavefront before its first store
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (!write[r]) continue;
+    const int64_t e = env[r];
+    const int w = word[r];
+    observation[e * S + w] = now[r];
+    if (ended[r]) {
+      if (!RESET && final_obs && final_observation) final_observation[e * S + w] = fin[r];
+      for (int k = w; k < A; k += S) prev_command[e * A + k] = 0.f;
+    }
+    if (P.obs_noise && w == 0) calls[e] = call[r] + 1u;
+  }
+}
+
+#endif  // __HIPCC__
+
+}  // namespace upkie

@@ -1,11 +1,12 @@
 // trainer_abi.hip -- handle-free entry points of include/upkie_hip.h around a rollout: the MLP actor-critic policy, the
-// time-limit bootstrap, episode statistics, VecNormalize, the linear policy and GAE. Host code around the kernels of the
+// time-limit bootstrap, episode statistics, the agent pipeline, VecNormalize, the linear policy and GAE. Host code around the kernels of the
 // headers below; nothing here takes or touches a simulator, MPC or observer handle (upkie_hip.hip). The PPO update, the
 // other heavy set of kernel instantiations, is ppo_abi.hip's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstdint>
 
 #include "mlp_instances.hpp"
@@ -13,6 +14,7 @@
 #include "vecnorm.hpp"
 #include "time_limits.hpp"
 #include "episodes.hpp"
+#include "agent_pipeline.hpp"
 
 #include "abi_host.hpp"
 
@@ -115,6 +117,108 @@ extern "C" int upkie_episodes_reset(int32_t num_envs, const uint8_t* mask, doubl
   const int grid = std::min((num_envs + upkie::EPISODES_THREADS - 1) / upkie::EPISODES_THREADS, 1024);
   hipLaunchKernelGGL(upkie::episodes_reset_kernel, dim3((unsigned)grid), dim3(upkie::EPISODES_THREADS), 0, (hipStream_t)stream, num_envs, mask,
                      ep_return, ep_length);
+  return launch_status();
+}
+
+// ============================================================ agent pipeline (action shaping, noise, VecFrameStack)
+extern "C" int64_t upkie_pipeline_params(int32_t obs_dim, int32_t act_dim, const float* action_low, const float* action_high,
+                                         const float* action_noise, const float* observation_noise, float* params) {
+  if (obs_dim < 1 || obs_dim > 256 || act_dim < 1 || act_dim > 64)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "pipeline: obs_dim must be in 1-256 and act_dim in 1-64");
+  if (!action_low || !action_high) return fail(UPKIE_ERR_INVALID_ARGUMENT, "pipeline: null action bounds");
+  for (int a = 0; a < act_dim; ++a)
+    if (!(action_low[a] <= action_high[a])) return fail(UPKIE_ERR_INVALID_ARGUMENT, "pipeline: action bounds need low <= high (and no NaN)");
+  for (int a = 0; action_noise && a < act_dim; ++a)
+    if (!(action_noise[a] >= 0.f) || !std::isfinite(action_noise[a]))
+      return fail(UPKIE_ERR_INVALID_ARGUMENT, "pipeline: action_noise sigmas must be non-negative and finite");
+  for (int d = 0; observation_noise && d < obs_dim; ++d)
+    if (!(observation_noise[d] >= 0.f) || !std::isfinite(observation_noise[d]))
+      return fail(UPKIE_ERR_INVALID_ARGUMENT, "pipeline: observation_noise sigmas must be non-negative and finite");
+  if (params) {
+    for (int a = 0; a < act_dim; ++a) {
+      params[a] = action_low[a];
+      params[act_dim + a] = action_high[a];
+      params[2 * act_dim + a] = action_noise ? action_noise[a] : 0.f;
+    }
+    for (int d = 0; d < obs_dim; ++d) params[3 * act_dim + d] = observation_noise ? observation_noise[d] : 0.f;
+  }
+  return 3 * (int64_t)act_dim + obs_dim;
+}
+
+// The settings every pipeline launch begins with, checked; UPKIE_OK or the error status (message set).
+static int pipeline_setup(int32_t num_envs, int32_t obs_dim, int32_t act_dim, int32_t stack, int32_t flags, double dt, double action_lag,
+                          const float* params, uint64_t seed, upkie::PipelineDev* out) {
+  const int32_t known = UPKIE_PIPELINE_ACTION_IN_OBSERVATION | UPKIE_PIPELINE_INTEGRATE_ACTION | UPKIE_PIPELINE_ACTION_NOISE |
+                        UPKIE_PIPELINE_ACTION_LAG | UPKIE_PIPELINE_OBSERVATION_NOISE;
+  if (num_envs <= 0 || num_envs > INT_MAX / upkie::PIPELINE_WAVE_WORDS)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "pipeline: num_envs must be positive (and num_envs * 256 below 2^31)");
+  if (flags & ~known) return fail(UPKIE_ERR_INVALID_ARGUMENT, "pipeline: unknown flags");
+  upkie::PipelineDev P{};
+  P.num_envs = num_envs, P.obs_dim = obs_dim, P.act_dim = act_dim, P.stack = stack;
+  P.action_in_obs = (flags & UPKIE_PIPELINE_ACTION_IN_OBSERVATION) != 0;
+  P.integrate = (flags & UPKIE_PIPELINE_INTEGRATE_ACTION) != 0;
+  P.action_noise = (flags & UPKIE_PIPELINE_ACTION_NOISE) != 0;
+  P.lag = (flags & UPKIE_PIPELINE_ACTION_LAG) != 0;
+  P.obs_noise = (flags & UPKIE_PIPELINE_OBSERVATION_NOISE) != 0;
+  if (stack < 1) return fail(UPKIE_ERR_INVALID_ARGUMENT, "pipeline: stack must be at least 1");
+  if (act_dim < 1 || act_dim > 64) return fail(UPKIE_ERR_INVALID_ARGUMENT, "pipeline: act_dim must be in 1-64");
+  if (obs_dim < 1 || !upkie::pipeline_sizes(P))
+    return fail(UPKIE_ERR_INVALID_ARGUMENT,
+                "pipeline: obs_dim must be positive and stack * (obs_dim + act_dim in the observation) at most 256 words (the policy's obs_dim)");
+  if (!(dt > 0.0) || !std::isfinite(dt)) return fail(UPKIE_ERR_INVALID_ARGUMENT, "pipeline: dt must be positive and finite");
+  if (P.lag && (!(action_lag > 0.0) || !(dt / action_lag < 0.5)))
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "pipeline: low_pass_filter needs dt / action_lag < 0.5 (Nyquist-Shannon) and action_lag > 0");
+  if (!params) return fail(UPKIE_ERR_INVALID_ARGUMENT, "pipeline: null params (upkie_pipeline_params packs them)");
+  P.dt = (float)dt;
+  P.alpha = P.lag ? (float)(dt / action_lag) : 0.f;
+  P.seed_lo = (unsigned)(seed & 0xffffffffu);
+  P.seed_hi = (unsigned)(seed >> 32);
+  P.params = params;
+  *out = P;
+  return UPKIE_OK;
+}
+
+extern "C" int upkie_pipeline_shape_action(int32_t num_envs, int32_t obs_dim, int32_t act_dim, int32_t stack, int32_t flags, double dt,
+                                           double action_lag, const float* params, uint64_t seed, const float* action, float* prev_command,
+                                           uint32_t* calls, float* command, void* stream) {
+  upkie::PipelineDev P;
+  if (pipeline_setup(num_envs, obs_dim, act_dim, stack, flags, dt, action_lag, params, seed, &P)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!action || !prev_command || !command || (P.action_noise && !calls))
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "pipeline: null argument (action, prev_command, command; calls with action noise)");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  hipLaunchKernelGGL(upkie::pipeline_shape_action_kernel, dim3((unsigned)upkie::pipeline_blocks(num_envs, P.group_act)),
+                     dim3(upkie::PIPELINE_THREADS), 0, (hipStream_t)stream, P, action, prev_command, calls, command);
+  return launch_status();
+}
+
+extern "C" int upkie_pipeline_observe(int32_t num_envs, int32_t obs_dim, int32_t act_dim, int32_t stack, int32_t flags, double dt,
+                                      double action_lag, const float* params, uint64_t seed, const float* next_obs, const uint8_t* terminated,
+                                      const uint8_t* truncated, const float* final_obs, const float* command, float* prev_command,
+                                      uint32_t* calls, float* observation, float* final_observation, void* stream) {
+  upkie::PipelineDev P;
+  if (pipeline_setup(num_envs, obs_dim, act_dim, stack, flags, dt, action_lag, params, seed, &P)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!next_obs || !prev_command || !observation || (P.obs_noise && !calls) || (P.action_in_obs && !command))
+    return fail(UPKIE_ERR_INVALID_ARGUMENT,
+                "pipeline: null argument (next_obs, prev_command, observation; calls with observation noise; command when it is in the observation)");
+  if (final_obs && !final_observation) return fail(UPKIE_ERR_INVALID_ARGUMENT, "pipeline: final_obs needs final_observation");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  hipLaunchKernelGGL(upkie::pipeline_observe_kernel<false>, dim3((unsigned)upkie::pipeline_blocks(num_envs, P.group)),
+                     dim3(upkie::PIPELINE_THREADS), 0, (hipStream_t)stream, P, next_obs, terminated, truncated, final_obs, command, prev_command,
+                     calls, observation, final_observation);
+  return launch_status();
+}
+
+extern "C" int upkie_pipeline_reset(int32_t num_envs, int32_t obs_dim, int32_t act_dim, int32_t stack, int32_t flags, double dt,
+                                    double action_lag, const float* params, uint64_t seed, const float* obs, const uint8_t* mask,
+                                    float* prev_command, uint32_t* calls, float* observation, void* stream) {
+  upkie::PipelineDev P;
+  if (pipeline_setup(num_envs, obs_dim, act_dim, stack, flags, dt, action_lag, params, seed, &P)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!obs || !prev_command || !observation || (P.obs_noise && !calls))
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "pipeline: null argument (obs, prev_command, observation; calls with observation noise)");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  hipLaunchKernelGGL(upkie::pipeline_observe_kernel<true>, dim3((unsigned)upkie::pipeline_blocks(num_envs, P.group)),
+                     dim3(upkie::PIPELINE_THREADS), 0, (hipStream_t)stream, P, obs, mask, (const uint8_t*)nullptr, (const float*)nullptr,
+                     (const float*)nullptr, prev_command, calls, observation, (float*)nullptr);
   return launch_status();
 }
 

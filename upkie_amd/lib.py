@@ -44,6 +44,7 @@ SOURCES = [
     os.path.join(_CSRC, "ppo.hpp"),
     os.path.join(_CSRC, "time_limits.hpp"),
     os.path.join(_CSRC, "episodes.hpp"),
+    os.path.join(_CSRC, "agent_pipeline.hpp"),
     os.path.join(_CSRC, "wave_io.hpp"),
     os.path.join(_HERE, "..", "include", "upkie_hip.h"),
 ]
@@ -60,6 +61,7 @@ def _abi_table():
     shape_p, cfg_p = P(abi.UpkieMlpShape), P(abi.UpkiePpoConfig)
     step = [vp] * 8
     vecnorm = [i32, i32] + [vp] * 8 + [i32] + [f64] * 4  # (the arguments every vecnorm launch begins with)
+    pipeline = [i32] * 5 + [f64, f64, vp, C.c_uint64]  # (the settings every pipeline launch begins with)
     controlled = "upkie_ppo_minibatch_update_controlled"
     return (
         ("upkie_hip_device_count", status, None, None),
@@ -147,6 +149,11 @@ def _abi_table():
         ("upkie_episodes_workspace_bytes", C.c_int64, [i32], "upkie_episodes_step"),
         ("upkie_episodes_step", status, [i32, i32] + [vp] * 11, "upkie_episodes_step"),
         ("upkie_episodes_reset", status, [i32, vp, vp, vp, vp], "upkie_episodes_step"),
+        # the agent pipeline
+        ("upkie_pipeline_params", C.c_int64, [i32, i32, vp, vp, vp, vp, vp], "upkie_pipeline_observe"),
+        ("upkie_pipeline_shape_action", status, pipeline + [vp] * 5, "upkie_pipeline_observe"),
+        ("upkie_pipeline_observe", status, pipeline + [vp] * 10, "upkie_pipeline_observe"),
+        ("upkie_pipeline_reset", status, pipeline + [vp] * 6, "upkie_pipeline_observe"),
     )
 
 

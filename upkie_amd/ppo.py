@@ -525,9 +525,18 @@ class Ppo:
                  learning_rate: Schedule = 3e-4, clip_range: Schedule = 0.2, clip_range_vf: Optional[Schedule] = None,
                  normalize_advantage: bool = True, ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5,
                  target_kl: Optional[float] = None, normalize: bool = True, bootstrap_time_limits: bool = True, stats_window_size: int = 100,
-                 reward_fn: Optional[Callable] = None, graph: bool = True, seed: int = 0, process_group=None):
+                 reward_fn: Optional[Callable] = None, graph: bool = True, seed: int = 0, process_group=None, pipeline=None):
         if int(n_steps) < 1:
             raise ValueError("n_steps must be positive")
+        if pipeline is not None:
+            words = int(policy.shape.obs_dim)
+            if words != pipeline.stacked_dim:
+                raise ValueError(f"the policy reads {words} observation words, the pipeline stacks {pipeline.stack} frames of "
+                                 f"{pipeline.frame_dim} = {pipeline.stacked_dim}")
+            if int(policy.shape.act_dim) != pipeline.act_dim or int(env.num_envs) != pipeline.num_envs:
+                raise ValueError(f"the pipeline serves {pipeline.num_envs} envs and {pipeline.act_dim} actions, the env has {int(env.num_envs)} "
+                                 f"and the policy {int(policy.shape.act_dim)}")
+        self.pipeline = pipeline
         self.env, self.policy = env, policy
         self.n_envs = int(env.num_envs)
         self.n_steps, self.gamma, self.gae_lambda = int(n_steps), float(gamma), float(gae_lambda)
@@ -555,7 +564,10 @@ class Ppo:
         D, A = int(pol.shape.obs_dim), int(pol.shape.act_dim)
         if self.normalize:
             kw = {} if self.process_group is None else {"process_group": self.process_group}
-            self.normalizer = RunningNormalizer.for_env(env, gamma=self.gamma, **kw)
+            if self.pipeline is None:
+                self.normalizer = RunningNormalizer.for_env(env, gamma=self.gamma, **kw)
+            else:  # (SB3: VecNormalize over VecFrameStack, so its columns are the stack's, not the env's)
+                self.normalizer = RunningNormalizer(N, D, gamma=self.gamma, device=dev, **kw)
             self.normalizer.attach(pol)
         self.episodes = EpisodeStatistics(N, window=self.window, device=dev)
         self.trainer = PpoTrainer(pol, **self._trainer_args)
@@ -568,15 +580,17 @@ class Ppo:
         self._obs = getattr(env, "observation", None)
         if self._obs is None:
             self._obs = reset[0] if isinstance(reset, tuple) else reset
+        self._policy_obs = self._obs if self.pipeline is None else self.pipeline.reset(self._obs)
         if self.normalizer is not None:
-            self.normalizer.reset(self._obs)
+            self.normalizer.reset(self._policy_obs)
         self._env_action = torch.empty(N, A, device=dev)
         self._starts = torch.ones(N, dtype=torch.uint8, device=dev)
         self._slot = self.n_steps - 1 if self.graph else 0  # (the capture's warm-up step takes the last slot)
         if self.graph:
             from .graphs import GraphedLoop
 
-            self._loop = GraphedLoop(self._rollout_step, unroll=T, warmup=1, device=dev)
+            step = self._rollout_step if self.pipeline is None else self._rollout_step_pipeline
+            self._loop = GraphedLoop(step, unroll=T, warmup=1, device=dev)
 
     def _rollout_step(self) -> None:
         t, buf, pol, starts = self._slot, self.buffer, self.policy, self._starts
@@ -609,17 +623,52 @@ class Ppo:
             pol.bootstrap_time_limits(final_obs, terminated, truncated, buf.rewards[t], self.gamma)
         self._slot = (t + 1) % self.n_steps
 
+    def _rollout_step_pipeline(self) -> None:
+        """`_rollout_step` with an `AgentPipeline` between the policy and the env: the policy reads the stacked
+        observation, the env receives the shaped command, the reward is the user's function of the RAW observation,
+        and the normaliser and the bootstrap see the stack and its terminal form."""
+        t, buf, pol, starts, pipe = self._slot, self.buffer, self.policy, self._starts, self.pipeline
+        buf.episode_starts[t].copy_(starts)
+        out = {"action": buf.actions[t], "value": buf.values[t], "log_prob": buf.log_probs[t], "env_action": self._env_action}
+        if self.normalizer is not None:
+            out["norm_obs"] = buf.observations[t]
+        else:
+            buf.observations[t].copy_(pipe.observation)
+        pol.act(pipe.observation, out=out)
+        stepped = self.env.step(pipe.shape_action(self._env_action))
+        next_obs, reward, terminated, truncated = stepped[:4]
+        info = stepped[4] if len(stepped) > 4 else {}
+        self._obs = next_obs
+        if self.reward_fn is not None:
+            reward = self.reward_fn(next_obs, info)
+        self.episodes.step(reward, terminated, truncated)  # Monitor: the raw reward
+        final_obs = info.get("final_obs") if hasattr(info, "get") else None
+        if self.bootstrap and final_obs is None:
+            raise UpkieRuntimeError("bootstrap_time_limits needs info['final_obs'] (an env with autoreset_mode='same_step'); "
+                                    "or build Ppo with bootstrap_time_limits=False")
+        pipe.observe(next_obs, terminated, truncated, final_obs=final_obs)
+        if self.normalizer is not None:
+            self.normalizer.step(pipe.observation, reward, terminated, truncated, out={"reward": buf.rewards[t], "episode_starts": starts})
+        else:
+            buf.rewards[t].copy_(reward)
+            torch.bitwise_or(terminated, truncated, out=starts)
+        if self.bootstrap:
+            pol.bootstrap_time_limits(pipe.final_observation, terminated, truncated, buf.rewards[t], self.gamma)
+        self._slot = (t + 1) % self.n_steps
+
     def collect_rollouts(self) -> None:
         """``n_steps`` steps of every env into the buffer, then GAE (SB3's ``collect_rollouts``)."""
         if self._loop is not None:
             self._loop.replay()
         else:
+            step = self._rollout_step if self.pipeline is None else self._rollout_step_pipeline
             for _ in range(self.n_steps):
-                self._rollout_step()
+                step()
         self.num_timesteps += self.n_steps * self.n_envs
         buf = self.buffer
         buf.pos, buf.full = self.n_steps, True
-        buf.compute_returns_and_advantage(last_values=self.policy.value(self._obs), dones=self._starts)
+        last_obs = self._obs if self.pipeline is None else self.pipeline.observation
+        buf.compute_returns_and_advantage(last_values=self.policy.value(last_obs), dones=self._starts)
 
     def train(self) -> None:
         """SB3's ``PPO.train`` on the collected rollout: `PpoTrainer.prepare`, then the update (a graph replay when
@@ -680,6 +729,8 @@ class Ppo:
                  "ep_return": ep.ep_return, "ep_length": ep.ep_length, "ring_return": ep.ring_return, "ring_length": ep.ring_length,
                  "ep_counters": ep.counters, "ep_means": ep.means}
         named.update({f"env.{k}": v for k, v in self._env_tensors().items()})
+        if self.pipeline is not None:
+            named.update({f"pipeline.{k}": v for k, v in self.pipeline.state_tensors().items()})
         return {k: v for k, v in named.items() if v is not None}
 
     def save(self, path) -> None:
