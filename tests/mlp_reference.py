@@ -101,8 +101,8 @@ def _layout(shape):
     W = next(c for c in (16, 32, 64, 128, 256) if max(widths) <= c)
     pair = 2 if W >= 32 else 1
     off = 0
-    lay = {}
-    dp = (shape.obs_dim + 3) // 4 * 4
+    lay = {"W": W, "pair": pair}
+    dp =(shape.obs_dim + 3) // 4 * 4
     for name, n in (("mean", dp), ("std", dp), ("low", 16 * tiles(shape.act_dim)), ("high", 16 * tiles(shape.act_dim)), ("log_std", 16 * tiles(shape.act_dim))):
         lay[name] = off
         off += n

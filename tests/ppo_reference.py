@@ -102,6 +102,52 @@ def minibatch(shape, sources, obs, actions, old_values, old_log_prob, advantages
     return stats, grads, ratio
 
 
+# ---------------------------------------------------------------- the launch geometry (ppo_plan, csrc/ppo.hpp)
+LDS_BUDGET = 65280  # dynamic LDS of the gradient launch while one tile's stage fits
+MAX_GRID = 512
+PARTIAL_CAP_BYTES = 48 << 20
+HEADER_BYTES, STATS, FOLD_THREADS = 256, 4, 256
+
+
+def plan(shape):
+    """The gradient launch's geometry for a shape: the LDS stage of one 16-sample tile per tower in floats (the input,
+    every hidden layer's padded output tiles, the head's dZ -- one row of 16 for a dot head -- and the actor's log_std
+    terms), the waves per block `nw`, the grid cap and the trainable words."""
+    lay = R._layout(shape)
+    in_tiles = (int(shape.obs_dim) + 15) // 16
+    act_tiles = (int(shape.act_dim) + 15) // 16
+
+    def stage(layers, actor):
+        floats = 256 * in_tiles
+        for kind, _, _, _, out_t in layers:
+            floats += 16 if kind == "dot" else 256 * out_t
+        return floats + (256 * act_tiles if actor else 0)
+
+    stages = (stage(lay["actor"], True), stage(lay["critic"], False))
+    tile_floats = max(stages)
+    nw = min(4, max(1, LDS_BUDGET // (4 * tile_floats)))
+    train_words = lay["words"] - lay["log_std"]
+    return {"stage_floats": stages, "tile_floats": tile_floats, "nw": nw, "lds_bytes": 4 * nw * tile_floats, "train_off": lay["log_std"],
+            "train_words": train_words, "grid_cap": min(MAX_GRID, max(1, PARTIAL_CAP_BYTES // (4 * train_words))),
+            "fold_blocks": (train_words + FOLD_THREADS - 1) // FOLD_THREADS}
+
+
+def chunks(p, n):
+    """Chunks of `nw` tiles a minibatch of n samples has; a block takes chunks b, b + grid, ..."""
+    return ((n + 15) // 16 + p["nw"] - 1) // p["nw"]
+
+
+def grid(p, n):
+    return min(chunks(p, n), p["grid_cap"])
+
+
+def workspace_bytes(p, n):
+    """upkie_ppo_workspace_bytes: the header, one partial gradient and STATS fp64 loss sums per block, the folded gradient
+    and the fold's fp64 partial squares."""
+    g = grid(p, n)
+    return HEADER_BYTES + 4 * g * p["train_words"] + 8 * g * STATS + 4 * p["train_words"] + 8 * p["fold_blocks"]
+
+
 def trainable(shape, sources):
     """The trainable sources (log_std, then weight and bias per layer, actor then critic), fp64, shaped."""
     _, _, _, _, log_std, actor, critic = R.split_sources(shape, sources)

@@ -15,6 +15,8 @@ import torch
 import torch.nn as nn
 
 from tests import mlp_reference as R
+from tests.mlp_shapes import MATRIX
+from tests.mlp_shapes import tower as _tower
 from upkie_amd import abi, lib
 from upkie_amd.exceptions import UpkieRuntimeError
 from upkie_amd.policies import MlpActorCritic, MlpPolicy, mlp_shape, pack_index, sb3_parameters
@@ -30,20 +32,17 @@ SHAPES = [
     (5, [7, 33, 20, 1], 17, [], "tanh"),
     (17, [48], 64, [3, 256, 5, 9], "relu"),
 ]
+# and every row of the GPU shape matrix (tests/mlp_shapes.py) that is not above already
+for _row in MATRIX:
+    if (_row.obs_dim, _row.actor, _row.act_dim, _row.critic, _row.activation) not in SHAPES:
+        SHAPES.append((_row.obs_dim, _row.actor, _row.act_dim, _row.critic, _row.activation))
+SHAPE_IDS = [f"{s[0]}-{s[1]}-{s[2]}-{s[4]}" if s in SHAPES[:6] else f"{s[0]}-{s[1]}-{s[2]}-{s[3]}-{s[4]}".replace(" ", "") for s in SHAPES]
 
 
 @pytest.fixture(scope="module")
 def library():
     lib.build()
     return lib.load()
-
-
-def _tower(d_in, widths, d_out, act):
-    mods, n = [], d_in
-    for w in widths:
-        mods += [nn.Linear(n, w), nn.Tanh() if act == "tanh" else nn.ReLU()]
-        n = w
-    return nn.Sequential(*mods, nn.Linear(n, d_out))
 
 
 def _sources(shape, seed=0, normalize=False):
@@ -138,7 +137,7 @@ def test_sb3_state_dict_loads_the_same_network():
         sb3_parameters({k: v for k, v in sd.items() if k != "log_std"})
 
 
-@pytest.mark.parametrize("spec", SHAPES, ids=[f"{s[0]}-{s[1]}-{s[2]}-{s[4]}" for s in SHAPES])
+@pytest.mark.parametrize("spec", SHAPES, ids=SHAPE_IDS)
 def test_pack_unpack_round_trip_and_layout_size(spec, library):
     shape = _shape(*spec)
     sources = _sources(shape)
@@ -154,7 +153,7 @@ def test_pack_unpack_round_trip_and_layout_size(spec, library):
     assert back[:-1].tobytes() == flat[:-1].tobytes()  # bit for bit
 
 
-@pytest.mark.parametrize("spec", SHAPES, ids=[f"{s[0]}-{s[1]}-{s[2]}-{s[4]}" for s in SHAPES])
+@pytest.mark.parametrize("spec", SHAPES, ids=SHAPE_IDS)
 @pytest.mark.parametrize("normalize", [False, True])
 def test_kernel_lane_arithmetic_on_the_packed_buffer_is_the_network(spec, normalize):
     """The packing read through the kernel's MFMA fragment maps (emulated in fp64) computes the network."""

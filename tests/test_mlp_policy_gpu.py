@@ -12,47 +12,16 @@ import torch
 import torch.nn as nn
 
 from tests import mlp_reference as R
+from tests.mlp_shapes import CASES, DEV
+from tests.mlp_shapes import policy as _policy
+from tests.mlp_shapes import sources_of as _src
+from tests.mlp_shapes import tower as _tower
 from upkie_amd.graphs import GraphedLoop
 from upkie_amd.policies import MlpActorCritic, MlpPolicy
 from upkie_amd.rollout import RolloutBuffer
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-
-# (N, obs_dim, hidden widths (both towers), act_dim, activation)
-CASES = [
-    (4096, 4, [64, 64], 1, "tanh"),
-    (333, 6, [64, 64], 2, "relu"),
-    (1000, 30, [256, 256, 128], 36, "tanh"),
-    (1, 3, [16], 2, "relu"),
-    (1001, 5, [40, 24], 3, "tanh"),  # N not a multiple of 16 or 32, widths not of 16
-]
-
-
-def _tower(d_in, widths, d_out, act):
-    mods, n = [], d_in
-    for w in widths:
-        mods += [nn.Linear(n, w), nn.Tanh() if act == "tanh" else nn.ReLU()]
-        n = w
-    return nn.Sequential(*mods, nn.Linear(n, d_out))
-
-
-def _policy(D, widths, A, act, seed=0, normalize=False, log_std=None, low=-1.0, high=1.0):
-    torch.manual_seed(seed)
-    actor, critic = _tower(D, widths, A, act).to(DEV), _tower(D, widths, 1, act).to(DEV)
-    log_std = torch.full((A,), -0.5, device=DEV) if log_std is None else log_std
-    kw = {}
-    if normalize:
-        g = torch.Generator().manual_seed(seed + 1)
-        kw = dict(obs_mean=0.3 * torch.randn(D, generator=g), obs_var=torch.rand(D, generator=g) * 3 + 0.2, clip_obs=3.0)
-    pol = MlpActorCritic.from_modules(actor, critic, log_std, torch.full((A,), low), torch.full((A,), high), seed=seed, **kw)
-    return pol, actor, critic, log_std
-
-
-def _src(pol):
-    return [t.detach().double().cpu().numpy() for t in pol.sources()]
-
 
 @pytest.mark.parametrize("case", CASES, ids=[f"{c[0]}-{c[1]}-{c[2]}-{c[3]}-{c[4]}" for c in CASES])
 def test_deterministic_outputs_against_fp64_and_torch(case):

@@ -12,6 +12,8 @@ import torch
 import torch.nn as nn
 
 from tests import ppo_reference as R
+from tests.mlp_shapes import CASES, IDS, WIDEST, T
+from tests.mlp_shapes import tower as _tower
 from upkie_amd.exceptions import UpkieRuntimeError
 from upkie_amd.normalize import RunningNormalizer
 from upkie_amd.policies import MlpActorCritic
@@ -21,29 +23,7 @@ from upkie_amd.rollout import RolloutBuffer
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
-T = 2  # rollout steps: the buffers are [T, N, ...]
-
-# tests/test_mlp_policy_gpu.py's CASES: (N, obs_dim, hidden widths (both towers), act_dim, activation)
-CASES = [
-    (4096, 4, [64, 64], 1, "tanh"),
-    (333, 6, [64, 64], 2, "relu"),
-    (1000, 30, [256, 256, 128], 36, "tanh"),
-    (1, 3, [16], 2, "relu"),
-    (1001, 5, [40, 24], 3, "tanh"),  # N not a multiple of 16 or 32, widths not of 16
-]
-IDS = [f"{c[0]}-{c[1]}-{c[2]}-{c[3]}-{c[4]}" for c in CASES]
-# the widest shape upkie_mlp_packed_words accepts: one tile's LDS stage (88 KiB) is above the 64 KiB default, so the
-# gradient launch runs one-wave blocks with the raised dynamic-LDS limit
-WIDEST = (100, 256, [256, 256, 256, 256], 64, "relu")
 BETA1_F32 = np.float32(1.0) - np.float32(0.9)
-
-
-def _tower(d_in, widths, d_out, act):
-    mods, n = [], d_in
-    for w in widths:
-        mods += [nn.Linear(n, w), nn.Tanh() if act == "tanh" else nn.ReLU()]
-        n = w
-    return nn.Sequential(*mods, nn.Linear(n, d_out))
 
 
 def _setup(case, seed=0, first=False, normalize=False):

@@ -14,7 +14,9 @@ import torch
 
 from tests import episodes_reference as R
 from tests import mlp_reference as M
-from tests.test_mlp_policy_gpu import CASES, _policy, _src
+from tests.mlp_shapes import CASES
+from tests.mlp_shapes import policy as _policy
+from tests.mlp_shapes import sources_of as _src
 from upkie_amd.episodes import EpisodeStatistics
 from upkie_amd.graphs import GraphedLoop
 from upkie_amd.normalize import RunningNormalizer
