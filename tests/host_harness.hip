@@ -1,8 +1,10 @@
 // Test-only: runs the product's device functions on the HOST so that a single
 // physics substep can be compared with the oracle without a GPU.
-// (step_kernels.hpp + host_setup.hpp, not the C-ABI's units: no launch, so no kernel is instantiated and this builds in seconds)
+// (step_kernels.hpp + host_setup.hpp, not the C-ABI's units: no launch and none of their template kernels is instantiated, so this
+// builds in seconds; agent_pipeline.hpp, read for its two host inline functions, brings its one non-template kernel into the device pass)
 #include <string>
 
+#include "../upkie_amd/csrc/agent_pipeline.hpp"
 #include "../upkie_amd/csrc/host_setup.hpp"
 
 extern "C" int harness_substep(const UpkieModel* model, float* st, const float* tau, float h, const float* records,
@@ -257,3 +259,14 @@ extern "C" int harness_mpc_host_setup(const UpkieMpcConfig* config, int np, floa
   std::copy(g1.begin(), g1.end(), gv);
   return (int)h.size();
 }
+
+// The agent pipeline's plan (csrc/agent_pipeline.hpp: host inline functions), for tests/test_agent_pipeline_matrix.py.
+// out [4] = frame, words, group, group_act; returns 0 when pipeline_sizes refuses the sizes.
+extern "C" int harness_pipeline_sizes(int obs_dim, int act_dim, int stack, int action_in_obs, int* out) {
+  upkie::PipelineDev P{};
+  P.obs_dim = obs_dim, P.act_dim = act_dim, P.stack = stack, P.action_in_obs = action_in_obs;
+  if (!upkie::pipeline_sizes(P)) return 0;
+  out[0] = P.frame, out[1] = P.words, out[2] = P.group, out[3] = P.group_act;
+  return 1;
+}
+extern "C" int harness_pipeline_blocks(int num_envs, int group) { return upkie::pipeline_blocks(num_envs, group); }

@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from tests import agent_pipeline_reference as P
+from tests.agent_pipeline_shapes import _dev, _np
 from upkie_amd.pipeline import AgentPipeline
 from upkie_amd.ppo import Ppo
 
@@ -20,14 +21,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 F32 = np.float32
 EPS = 2.0 ** -24
-
-
-def _dev(a, dtype=None):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(DEV)
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
 
 
 # ---------------------------------------------------------------- data movement
