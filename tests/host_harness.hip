@@ -6,6 +6,7 @@
 
 #include "../upkie_amd/csrc/agent_pipeline.hpp"
 #include "../upkie_amd/csrc/host_setup.hpp"
+#include "../upkie_amd/csrc/step_dispatch.hpp"
 
 extern "C" int harness_substep(const UpkieModel* model, float* st, const float* tau, float h, const float* records,
                                const float* ext_forces, const UpkieExternalForces* ext_slots) {
@@ -270,3 +271,17 @@ extern "C" int harness_pipeline_sizes(int obs_dim, int act_dim, int stack, int a
   return 1;
 }
 extern "C" int harness_pipeline_blocks(int num_envs, int group) { return upkie::pipeline_blocks(num_envs, group); }
+
+// The choice of the step kernel (csrc/step_dispatch.hpp), for tests/test_step_dispatch.py: `count` rows, facts [count][13] =
+// the fields of StepFacts in their order, out [count][9] = the fields of StepInstance in theirs.
+extern "C" void harness_select_step_instances(int count, const int* facts, int* out) {
+  for (int i = 0; i < count; ++i, facts += 13, out += 9) {
+    upkie::StepFacts f;
+    f.mode = facts[0], f.num_envs = facts[1], f.lanes_per_env = facts[2], f.spine = facts[3], f.manifold = facts[4];
+    f.ext_on_leg_links = facts[5], f.randomized = facts[6], f.always_rand = facts[7], f.default_scalars = facts[8];
+    f.final_obs_set = facts[9], f.autoreset_mode = facts[10], f.done_pass = facts[11], f.packed = facts[12];
+    const upkie::StepInstance k = upkie::select_step_instance(f);
+    out[0] = k.family, out[1] = k.rand, out[2] = k.waves, out[3] = k.spine, out[4] = k.bullet, out[5] = k.default_scalars;
+    out[6] = k.in_place, out[7] = k.done_pass_follows, out[8] = k.refused;
+  }
+}

@@ -15,6 +15,7 @@
 
 #include "step_kernels.hpp"
 #include "step_instances.hpp"  // (the step kernels this unit launches are compiled elsewhere, by groups: declarations only)
+#include "step_dispatch.hpp"
 #include "host_setup.hpp"
 #include "abi_host.hpp"
 
@@ -484,59 +485,32 @@ extern "C" int upkie_sim_sample_pushes(UpkieSim* sim, float* force, uint32_t pus
   return check_hip(sim, hipGetLastError(), "push_kernel");
 }
 
-// 256 CUs x 4 SIMDs x 64 lanes x 2 waves
-static const int kDenseBatch = 131072;
-// up to this many envs two lanes per env still fit one wave per SIMD (1024 SIMDs x 64 lanes / 2)
-static const int kPairBatch = 32768;
-
-// up to this many envs the eight-lane kernel (step_kernel_octet) is at least as fast as the two-lane one: one wave per
-// SIMD up to 8192 envs (16.5 us), two from there to 16384, where both mappings take 25.3 us -- the two co-resident
-// waves do overlap, but the SIMD's issue port is then busy for the whole launch (profiles/r03_two_waves_per_simd_pmc.json)
-// -- and the eight-lane kernel is the one that can carry the MPC balancer (upkie_sim_step_base_velocity_mpc) and the
-// SAME_STEP autoreset inside its launch
-static const int kOctetBatch = 16384;
-// ... except the Servos kernels, which take the whole 512-entry register file (joint stops solved in registers): one
-// wave per SIMD, 8192 envs
-static const int kOctetBatchServos = 8192;
-
-// Lanes per env of a step launch: eight (one quad per leg, one lane per body:
-// octet.hpp) while that leaves the chip under-subscribed, two (one lane per
-// leg: pair.hpp) up to one wave per SIMD, one beyond. The in-step spine
-// observers exist in the one- and two-lane kernels only.
-static int mapped_lanes(const UpkieSim* sim) {
-  // the eight-lane kernel restates neither the in-step spine observers nor forces on leg links, and addresses the state
-  // with 32-bit byte offsets (state_words.hpp): a forced eight-lane mapping yields to the others beyond 2^32 bytes
-  bool eight = !sim->spine_state && (unsigned long long)sim->config.num_envs * UPKIE_STATE_WORDS * sizeof(float) < (1ull << 32);
+// What the choice of a step kernel (step_dispatch.hpp) reads from the handle, for an entry point that launches `mode`.
+static StepFacts step_facts(const UpkieSim* sim, int mode) {
+  StepFacts f;
+  f.mode = mode;
+  f.num_envs = sim->config.num_envs;
+  f.lanes_per_env = sim->lanes_per_env;
+  f.spine = sim->spine_state != nullptr;
+  f.manifold = sim->manifold != nullptr;
   if (sim->ext_force)
-    for (int i = 0; i < sim->config.ext.count; ++i) eight = eight && sim->config.ext.body[i] == 0;
-  if (sim->lanes_per_env == 8 || sim->lanes_per_env == 2 || sim->lanes_per_env == 1) {
-    if (sim->lanes_per_env == 8 && !eight) return sim->manifold ? 1 : 2;
-    if (sim->manifold && sim->lanes_per_env == 2) return 1;
-    return sim->lanes_per_env;
-  }
-  if (sim->config.num_envs <= kOctetBatch && eight) return 8;
-  if (sim->manifold) return 1;  // the Bullet-like contact model exists in the one- and eight-lane kernels (bullet_like.hpp, octet.hpp)
-  return sim->config.num_envs <= kPairBatch ? 2 : 1;
+    for (int i = 0; i < sim->config.ext.count; ++i) f.ext_on_leg_links = f.ext_on_leg_links || sim->config.ext.body[i] != 0;
+  f.randomized = sim->body_inertials || sim->ext_force;
+  f.default_scalars = sim->default_scalars;
+  f.final_obs_set = sim->final_obs != nullptr;
+  f.autoreset_mode = sim->config.autoreset_mode;
+  return f;
 }
+// Lanes per env of the step kernel an entry point launches
+static int lanes_of(const UpkieSim* sim, int mode) { return select_step_instance(step_facts(sim, mode)).family; }
 // fewer lanes than envs x 2: several env.step() of the fused agent can share a launch (state in registers)
-static bool uses_lane_pairs(const UpkieSim* sim) { return mapped_lanes(sim) >= 2; }
+static bool uses_lane_pairs(const UpkieSim* sim) { return lanes_of(sim, MODE_PENDULUM_ROLLOUT) >= 2; }
 
-extern "C" int upkie_sim_lanes_per_env(const UpkieSim* sim) { return !sim ? 0 : mapped_lanes(sim); }
+extern "C" int upkie_sim_lanes_per_env(const UpkieSim* sim) { return !sim ? 0 : lanes_of(sim, MODE_PENDULUM); }
 
-// ... of the step kernel a given entry point launches: the Servos kernels leave the eight-lane mapping earlier
-static int mapped_lanes_of_mode(const UpkieSim* sim, int mode) {
-  int lanes = mapped_lanes(sim);
-  // (round 5: the Bullet-like contact model's eight-lane variant serves UpkieServos steps too)
-  if (mode == MODE_SERVOS && lanes == 8 && sim->lanes_per_env != 8 && sim->config.num_envs > kOctetBatchServos) lanes = sim->manifold ? 1 : 2;
-  // (round 6, ADVICE r5: on the eight-lane Bullet-like kernel a joint within reach of its stop is now a row of the specification's
-  // own 50 sweeps -- octet_limit_path_scratch<BULLET_LIKE>, general_constraint_solve_bullet_like -- as on the one-lane kernels, so
-  // Servos steps stay on eight lanes up to kOctetBatchServos envs; what the mapping still does not restate is SEVERAL cached
-  // points on one tire, a robot lying flat on its side: upkie_sim_set_lanes_per_env(sim, 1) selects the one-lane kernels)
-  return lanes;
-}
 extern "C" int upkie_sim_lanes_per_env_of(const UpkieSim* sim, int observation_layout) {
   if (!sim) return 0;
-  return mapped_lanes_of_mode(sim, observation_layout == UPKIE_OBSERVATION_SERVOS ? MODE_SERVOS : MODE_PENDULUM);
+  return lanes_of(sim, observation_layout == UPKIE_OBSERVATION_SERVOS ? MODE_SERVOS : MODE_PENDULUM);
 }
 
 extern "C" int upkie_sim_set_lanes_per_env(UpkieSim* sim, int lanes) {
@@ -636,170 +610,144 @@ static const DevParams* current_params(UpkieSim* sim, void* stream) {
   return sim->d_params[sim->params_slot];
 }
 
+// The buffers and settings of one step call; an entry point fills what it uses.
+struct StepArgs {
+  float* state = nullptr;
+  const float* act = nullptr;
+  float* obs = nullptr;
+  float* reward = nullptr;
+  uint8_t* terminated = nullptr;
+  uint8_t* truncated = nullptr;
+  const uint8_t* mask = nullptr;
+  void* stream = nullptr;
+  int packed = 0;
+  BaseVelocityPtrs bv = BaseVelocityPtrs{};
+  bool done_pass = false;
+  float* final_obs = nullptr;
+  int n_steps = 1;
+  const UpkieServoPolicy* policy = nullptr;
+};
+
+// (the arguments of an unpacked step)
+static StepArgs step_args(float* state, const float* act, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated, void* stream) {
+  StepArgs a;
+  a.state = state, a.act = act, a.obs = obs, a.reward = reward, a.terminated = terminated, a.truncated = truncated, a.stream = stream;
+  return a;
+}
+// (... of a step that writes packed records)
+static StepArgs packed_step_args(float* state, const float* act, float* records, void* stream) {
+  StepArgs a;
+  a.state = state, a.act = act, a.obs = records, a.stream = stream, a.packed = 1;
+  return a;
+}
+
 template <int MODE>
-static int launch_step(UpkieSim* sim, float* state, const float* act, float* obs, float* reward, uint8_t* terminated,
-                       uint8_t* truncated, const uint8_t* mask, void* stream, int packed = 0,
-                       BaseVelocityPtrs bv = BaseVelocityPtrs{}, bool done_pass = false,
-                       float* final_obs = nullptr, int n_steps = 1, const UpkieServoPolicy* policy = nullptr) {
-  if (!sim || !state) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
-  if (MODE != MODE_RESET && (!obs || (!packed && !done_pass && (!reward || !terminated || !truncated))))
+static int launch_done_pass(UpkieSim* sim, float* state, float* obs, float* final_obs, int packed, void* stream);
+
+template <int MODE>
+static int launch_step(UpkieSim* sim, const StepArgs& a) {
+  if (!sim || !a.state) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  if (MODE != MODE_RESET && (!a.obs || (!a.packed && !a.done_pass && (!a.reward || !a.terminated || !a.truncated))))
     return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null output buffer");
-  if ((MODE == MODE_PENDULUM || MODE == MODE_GYROPOD || MODE == MODE_SERVOS || MODE == MODE_BASE_VELOCITY) && !act && !done_pass)
+  if ((MODE == MODE_PENDULUM || MODE == MODE_GYROPOD || MODE == MODE_SERVOS || MODE == MODE_BASE_VELOCITY) && !a.act && !a.done_pass)
     return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null action buffer");
   DevConfig config = sim->config;
-  if (done_pass) config.autoreset_mode = AUTORESET_DONE_PASS;
-  // SAME_STEP autoreset completed by the step call itself (upkie_sim_set_final_observation): inside the launch on the
-  // eight-lane mapping, by a second launch (the DONE pass) behind this one on the others
-  constexpr bool RESETS_IN_PLACE = MODE == MODE_PENDULUM || MODE == MODE_GYROPOD || MODE == MODE_SERVOS;
-  const bool same_step = RESETS_IN_PLACE && !done_pass && packed != 1 && sim->final_obs != nullptr && config.autoreset_mode == UPKIE_AUTORESET_DISABLED;
-  const bool same_step_in_kernel = same_step && mapped_lanes_of_mode(sim, MODE) == 8;  // (round 5: the Bullet-like eight-lane kernels have their IN_PLACE instantiations too)
-  if (same_step_in_kernel) final_obs = sim->final_obs;
+  if (a.done_pass) config.autoreset_mode = AUTORESET_DONE_PASS;
   // (UPKIE_ALWAYS_RAND_KERNELS=1: launch the randomisation-capable instantiation even without inertial records or forces
   // -- null pointers, tested at run time --: the A/B that decides whether the RAND = false instantiations of the one- and
   // two-lane kernels earn their place in the library, profiles/r05_ab_rand_instantiations.txt)
   static const bool always_rand = [] { const char* v = std::getenv("UPKIE_ALWAYS_RAND_KERNELS"); return v && v[0] == '1'; }();
-  const bool rnd = sim->body_inertials || sim->ext_force || (always_rand && mapped_lanes_of_mode(sim, MODE) != 8);
-  dim3 grid = grid_for(sim->config.num_envs), block(block_lanes());
-  const float* scale = rnd ? sim->body_inertials : nullptr;
-  const float* force = rnd ? sim->ext_force : nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  // more than two waves per SIMD in flight: favour occupancy over registers;
-  // fewer lanes than SIMD slots: split every env over two lanes (pair.hpp)
-  const bool dense = sim->config.num_envs >= kDenseBatch;
-  // SPINE: the spine observers run inside the step (a separate instantiation:
-  // compiled in but switched off they would still cost the common path 2 %)
-#define UPKIE_LAUNCH_S(R, W, S)                                                                                                   \
-  hipLaunchKernelGGL((step_kernel<MODE, R, W, S, false>), grid, block, 0, st, sim->d_model, sim->limits, config, state, act, obs, \
-                     reward, terminated, truncated, mask, scale, force, packed, bv, sim->spine_state, final_obs, (float*)nullptr)
-#define UPKIE_LAUNCH_BULLET(R)                                                                                                          \
-  hipLaunchKernelGGL((step_kernel<MODE, R, 1, false, true>), grid, block, 0, st, sim->d_model, sim->limits, config, state, act, obs, \
-                     reward, terminated, truncated, mask, scale, force, packed, bv, (float*)nullptr, final_obs, sim->manifold)
-#define UPKIE_LAUNCH(R, W) \
-  do { if (spine) UPKIE_LAUNCH_S(R, W, true); else UPKIE_LAUNCH_S(R, W, false); } while (0)
-#define UPKIE_LAUNCH_PAIR_S(R, S)                                                                                                 \
-  hipLaunchKernelGGL((step_kernel_pair<MODE, R, S>), grid_for(2 * sim->config.num_envs), block, 0, st, sim->d_model, sim->limits, \
-                     config, state, act, obs, reward, terminated, truncated, mask, scale, force, packed, bv, sim->spine_state, final_obs, \
-                     n_steps)
-#define UPKIE_LAUNCH_PAIR(R) \
-  do { if (spine) UPKIE_LAUNCH_PAIR_S(R, true); else UPKIE_LAUNCH_PAIR_S(R, false); } while (0)
-#define UPKIE_LAUNCH_OCTET_D(R, D, IP)                                                                                          \
-  hipLaunchKernelGGL((step_kernel_octet<MODE, R, D, IP, false>), octet_grid_for(sim->config.num_envs), dim3(UPKIE_OCTET_BLOCK), 0, st, \
-                     sim->d_model, params, done_pass ? 1 : 0, sim->config.num_envs, state, act, obs, reward, terminated, truncated, mask, scale, \
-                     force, packed, bv, final_obs, n_steps, sim->census, policy_arg, (float*)nullptr)
-#define UPKIE_LAUNCH_OCTET_BULLET_IP(R, IP)                                                                                     \
-  hipLaunchKernelGGL((step_kernel_octet<MODE, R, false, IP, true>), octet_grid_for(sim->config.num_envs), dim3(UPKIE_OCTET_BLOCK), 0, st, \
-                     sim->d_model, params, done_pass ? 1 : 0, sim->config.num_envs, state, act, obs, reward, terminated, truncated, mask, scale, \
-                     force, packed, bv, final_obs, n_steps, sim->census, policy_arg, sim->manifold)
-#define UPKIE_LAUNCH_OCTET_BULLET(R)                                                             \
-  do {                                                                                           \
-    bool launched = false;                                                                       \
-    if constexpr (octet_resets_in_place(MODE)) {                                                 \
-      if (same_step_in_kernel) { UPKIE_LAUNCH_OCTET_BULLET_IP(R, true); launched = true; }       \
-    }                                                                                            \
-    if (!launched) UPKIE_LAUNCH_OCTET_BULLET_IP(R, false);                                       \
-  } while (0)
-  // which instantiation (step_instances.hpp lists them): the SAME_STEP autoreset inside the launch has its own (the second
-  // pass makes the whole step a loop body: spills); the Pendulum / Gyropod steps also exist with the default model's
-  // scalars as constants
-#define UPKIE_LAUNCH_OCTET(R)                                                                    \
-  do {                                                                                           \
-    bool launched = false;                                                                       \
-    if constexpr (octet_resets_in_place(MODE) && octet_has_default_scalars(MODE)) {              \
-      if (same_step_in_kernel && sim->default_scalars) { UPKIE_LAUNCH_OCTET_D(R, true, true); launched = true; } \
-    }                                                                                            \
-    if constexpr (octet_resets_in_place(MODE)) {                                                 \
-      if (!launched && same_step_in_kernel) { UPKIE_LAUNCH_OCTET_D(R, false, true); launched = true; } \
-    }                                                                                            \
-    if constexpr (octet_has_default_scalars(MODE)) {                                             \
-      if (!launched && sim->default_scalars) { UPKIE_LAUNCH_OCTET_D(R, true, false); launched = true; } \
-    }                                                                                            \
-    if (!launched) UPKIE_LAUNCH_OCTET_D(R, false, false);                                        \
-  } while (0)
-  const bool spine = sim->spine_state != nullptr;
-  const int lanes = mapped_lanes_of_mode(sim, MODE);
+  StepFacts facts = step_facts(sim, MODE);
+  facts.always_rand = always_rand;
+  facts.done_pass = a.done_pass;
+  facts.packed = a.packed;
+  const StepInstance k = select_step_instance(facts);  // which instantiation (step_instances.hpp lists them)
+  if (k.refused) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "several steps per launch need the two-lane mapping");
+  const int B = sim->config.num_envs;
+  const float* scale = k.rand ? sim->body_inertials : nullptr;
+  const float* force = k.rand ? sim->ext_force : nullptr;
+  float* final_obs = k.in_place ? sim->final_obs : a.final_obs;
+  hipStream_t st = (hipStream_t)a.stream;
   ServoPolicyArg<MODE> policy_arg{};
   if constexpr (MODE == MODE_SERVOS) {
-    if (policy) policy_arg = *policy;
+    if (a.policy) policy_arg = *a.policy;
   }
   // the eight-lane kernels read limits and config from this handle's device block
-  const DevParams* params = lanes == 8 ? current_params(sim, stream) : nullptr;
-  if (lanes == 8 && !params)
+  const DevParams* params = k.family == STEP_OCTET ? current_params(sim, a.stream) : nullptr;
+  if (k.family == STEP_OCTET && !params)
     return fail(sim, UPKIE_ERR_HIP, sim->params_refused  // (the branch that actually failed: ADVICE r5)
                                         ? "this handle's steps have been recorded into UPKIE_MAX_GRAPH_CAPTURES hipGraph captures already: destroy graphs that are no longer "
                                           "replayed and call upkie_sim_release_graph_captures (include/upkie_hip.h, Streams and hipGraphs)"
                                         : "could not refresh the device block of the handle's settings (the store kernel's launch failed)");
-  if (lanes == 8 && sim->manifold) {
-    if (rnd) UPKIE_LAUNCH_OCTET_BULLET(true); else UPKIE_LAUNCH_OCTET_BULLET(false);
-  } else if (lanes == 8) {
-    if (rnd) UPKIE_LAUNCH_OCTET(true); else UPKIE_LAUNCH_OCTET(false);
-  } else if (lanes == 2) {
-    if (rnd) UPKIE_LAUNCH_PAIR(true); else UPKIE_LAUNCH_PAIR(false);
-  } else if constexpr (MODE == MODE_PENDULUM_ROLLOUT) {
-    return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "several steps per launch need the two-lane mapping");
-  } else if (sim->manifold) {  // the Bullet-like contact model (upkie_sim_set_contact_manifold)
-    if (rnd) UPKIE_LAUNCH_BULLET(true); else UPKIE_LAUNCH_BULLET(false);
-  } else if (rnd) {
-    if (dense) UPKIE_LAUNCH(true, 2); else UPKIE_LAUNCH(true, 1);
-  } else {
-    if (dense) UPKIE_LAUNCH(false, 2); else UPKIE_LAUNCH(false, 1);
-  }
-#undef UPKIE_LAUNCH_OCTET
-#undef UPKIE_LAUNCH_OCTET_BULLET
-#undef UPKIE_LAUNCH_OCTET_BULLET_IP
-#undef UPKIE_LAUNCH_BULLET
-#undef UPKIE_LAUNCH_OCTET_D
-#undef UPKIE_LAUNCH_PAIR_S
-#undef UPKIE_LAUNCH_S
-#undef UPKIE_LAUNCH_PAIR
-#undef UPKIE_LAUNCH
+  with_step_instance<MODE>(k, [&](auto family, auto rand, auto waves, auto spine, auto bullet, auto default_scalars, auto in_place) {
+    if constexpr (family() == STEP_OCTET)
+      hipLaunchKernelGGL((step_kernel_octet<MODE, rand(), default_scalars(), in_place(), bullet()>), octet_grid_for(B), dim3(UPKIE_OCTET_BLOCK), 0, st,
+                         sim->d_model, params, a.done_pass ? 1 : 0, B, a.state, a.act, a.obs, a.reward, a.terminated, a.truncated, a.mask, scale,
+                         force, a.packed, a.bv, final_obs, a.n_steps, sim->census, policy_arg, sim->manifold);
+    else if constexpr (family() == STEP_PAIR)
+      hipLaunchKernelGGL((step_kernel_pair<MODE, rand(), spine()>), grid_for(2 * B), dim3(block_lanes()), 0, st, sim->d_model, sim->limits, config,
+                         a.state, a.act, a.obs, a.reward, a.terminated, a.truncated, a.mask, scale, force, a.packed, a.bv, sim->spine_state,
+                         final_obs, a.n_steps);
+    else
+      hipLaunchKernelGGL((step_kernel<MODE, rand(), waves(), spine(), bullet()>), grid_for(B), dim3(block_lanes()), 0, st, sim->d_model, sim->limits,
+                         config, a.state, a.act, a.obs, a.reward, a.terminated, a.truncated, a.mask, scale, force, a.packed, a.bv,
+                         bullet() ? nullptr : sim->spine_state, final_obs, sim->manifold);
+  });
   const int status = check_hip(sim, hipGetLastError(), "step_kernel");
-  if constexpr (RESETS_IN_PLACE) {
-    if (status == UPKIE_OK && same_step && !same_step_in_kernel)
-      return launch_step<MODE>(sim, state, nullptr, obs, nullptr, nullptr, nullptr, nullptr, stream, 0, BaseVelocityPtrs{}, true, sim->final_obs);
-  }
+  if (status == UPKIE_OK && k.done_pass_follows) return launch_done_pass<MODE>(sim, a.state, a.obs, sim->final_obs, 0, a.stream);
   return status;
 }
 
+// The DONE pass of a SAME_STEP autoreset: envs whose DONE word is set leave their observation in `final_obs` and are reset.
+template <int MODE>
+static int launch_done_pass(UpkieSim* sim, float* state, float* obs, float* final_obs, int packed, void* stream) {
+  StepArgs a;
+  a.state = state, a.obs = obs, a.final_obs = final_obs, a.packed = packed, a.stream = stream, a.done_pass = true;
+  return launch_step<MODE>(sim, a);
+}
+
 extern "C" int upkie_sim_reset(UpkieSim* sim, float* state, const uint8_t* mask, float* obs6, void* stream) {
-  return launch_step<MODE_RESET>(sim, state, nullptr, obs6, nullptr, nullptr, nullptr, mask, stream);
+  StepArgs a;
+  a.state = state, a.mask = mask, a.obs = obs6, a.stream = stream;
+  return launch_step<MODE_RESET>(sim, a);
 }
 
 extern "C" int upkie_sim_step_pendulum(UpkieSim* sim, float* state, const float* act, float* obs, float* reward,
                                        uint8_t* terminated, uint8_t* truncated, void* stream) {
-  return launch_step<MODE_PENDULUM>(sim, state, act, obs, reward, terminated, truncated, nullptr, stream);
+  return launch_step<MODE_PENDULUM>(sim, step_args(state, act, obs, reward, terminated, truncated, stream));
 }
 
 extern "C" int upkie_sim_step_pendulum_agent(UpkieSim* sim, float* state, float* obs, float* reward, uint8_t* terminated,
                                              uint8_t* truncated, void* stream) {
-  return launch_step<MODE_PENDULUM_AGENT>(sim, state, nullptr, obs, reward, terminated, truncated, nullptr, stream);
+  return launch_step<MODE_PENDULUM_AGENT>(sim, step_args(state, nullptr, obs, reward, terminated, truncated, stream));
 }
 
 extern "C" int upkie_sim_step_pendulum_packed(UpkieSim* sim, float* state, const float* act, float* records, void* stream) {
-  return launch_step<MODE_PENDULUM>(sim, state, act, records, nullptr, nullptr, nullptr, nullptr, stream, 1);
+  return launch_step<MODE_PENDULUM>(sim, packed_step_args(state, act, records, stream));
 }
 
 extern "C" int upkie_sim_step_pendulum_agent_packed(UpkieSim* sim, float* state, float* records, void* stream) {
-  return launch_step<MODE_PENDULUM_AGENT>(sim, state, nullptr, records, nullptr, nullptr, nullptr, nullptr, stream, 1);
+  return launch_step<MODE_PENDULUM_AGENT>(sim, packed_step_args(state, nullptr, records, stream));
 }
 
 extern "C" int upkie_sim_step_pendulum_agent_records(UpkieSim* sim, float* state, const float* prev_records, float* records,
                                                     void* stream) {
   if (!prev_records) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
-  return launch_step<MODE_PENDULUM_AGENT>(sim, state, prev_records, records, nullptr, nullptr, nullptr, nullptr, stream, 1);
+  return launch_step<MODE_PENDULUM_AGENT>(sim, packed_step_args(state, prev_records, records, stream));
 }
 
 extern "C" int upkie_sim_step_pendulum_agent_rollout(UpkieSim* sim, float* state, const float* prev_records, float* records,
                                                     int32_t num_steps, void* stream) {
   if (!prev_records || !records || num_steps < 1) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument or num_steps < 1");
   if (!sim) return UPKIE_ERR_INVALID_ARGUMENT;
-  const BaseVelocityPtrs none{};
-  if (uses_lane_pairs(sim))  // one launch: the state stays in registers from step to step
-    return launch_step<MODE_PENDULUM_ROLLOUT>(sim, state, prev_records, records, nullptr, nullptr, nullptr, nullptr, stream, 1, none, false,
-                                              nullptr, num_steps);
+  if (uses_lane_pairs(sim)) {  // one launch: the state stays in registers from step to step
+    StepArgs a = packed_step_args(state, prev_records, records, stream);
+    a.n_steps = num_steps;
+    return launch_step<MODE_PENDULUM_ROLLOUT>(sim, a);
+  }
   const size_t stride = (size_t)8 * sim->config.num_envs;  // large batches: launch overhead is already amortised
   for (int32_t k = 0; k < num_steps; ++k) {
-    const int status = launch_step<MODE_PENDULUM_AGENT>(sim, state, k ? records + (k - 1) * stride : prev_records, records + k * stride,
-                                                        nullptr, nullptr, nullptr, nullptr, stream, 1);
+    const int status = launch_step<MODE_PENDULUM_AGENT>(sim, packed_step_args(state, k ? records + (k - 1) * stride : prev_records, records + k * stride, stream));
     if (status != UPKIE_OK) return status;
   }
   return UPKIE_OK;
@@ -807,20 +755,21 @@ extern "C" int upkie_sim_step_pendulum_agent_rollout(UpkieSim* sim, float* state
 
 extern "C" int upkie_sim_step_gyropod(UpkieSim* sim, float* state, const float* act, float* obs, float* reward,
                                       uint8_t* terminated, uint8_t* truncated, void* stream) {
-  return launch_step<MODE_GYROPOD>(sim, state, act, obs, reward, terminated, truncated, nullptr, stream);
+  return launch_step<MODE_GYROPOD>(sim, step_args(state, act, obs, reward, terminated, truncated, stream));
 }
 
 extern "C" int upkie_sim_step_base_velocity(UpkieSim* sim, float* state, const float* act, const float* commanded_velocity,
                                             float* obs, float* mpc_x0, uint8_t* mpc_contact, float* reward,
                                             uint8_t* terminated, uint8_t* truncated, void* stream) {
   if (!commanded_velocity || !mpc_x0 || !mpc_contact) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null MPC buffer");
-  return launch_step<MODE_BASE_VELOCITY>(sim, state, act, obs, reward, terminated, truncated, nullptr, stream, 0,
-                                         BaseVelocityPtrs{commanded_velocity, mpc_x0, mpc_contact});
+  StepArgs a = step_args(state, act, obs, reward, terminated, truncated, stream);
+  a.bv = BaseVelocityPtrs{commanded_velocity, mpc_x0, mpc_contact};
+  return launch_step<MODE_BASE_VELOCITY>(sim, a);
 }
 
 extern "C" int upkie_sim_step_servos(UpkieSim* sim, float* state, const float* act, float* obs, float* reward,
                                      uint8_t* terminated, uint8_t* truncated, void* stream) {
-  return launch_step<MODE_SERVOS>(sim, state, act, obs, reward, terminated, truncated, nullptr, stream);
+  return launch_step<MODE_SERVOS>(sim, step_args(state, act, obs, reward, terminated, truncated, stream));
 }
 
 // Servo-level policy on the device (include/upkie_hip.h, upkie_sim_servo_policy): HBM bound, 12 state words in,
@@ -861,28 +810,24 @@ extern "C" int upkie_sim_servo_policy(UpkieSim* sim, float* state, const UpkieSe
 extern "C" int upkie_sim_step_servos_policy(UpkieSim* sim, float* state, const UpkieServoPolicy* policy, float* act, float* obs, float* reward,
                                             uint8_t* terminated, uint8_t* truncated, void* stream) {
   if (!sim || !state || !policy || !act) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
-  if (mapped_lanes_of_mode(sim, MODE_SERVOS) != 8) {  // the other mappings: the policy's own launch into `act`, then the step
+  StepArgs a = step_args(state, act, obs, reward, terminated, truncated, stream);
+  if (lanes_of(sim, MODE_SERVOS) != 8) {  // the other mappings: the policy's own launch into `act`, then the step
     const int status = upkie_sim_servo_policy(sim, state, policy, act, stream);
     if (status != UPKIE_OK) return status;
-    return launch_step<MODE_SERVOS>(sim, state, act, obs, reward, terminated, truncated, nullptr, stream);
+    return launch_step<MODE_SERVOS>(sim, a);
   }
-  // (`packed` == 2 tells the eight-lane Servos kernel to take its actions from the policy argument; `act` is not read)
-  return launch_step<MODE_SERVOS>(sim, state, act, obs, reward, terminated, truncated, nullptr, stream, 2, BaseVelocityPtrs{}, false, nullptr, 1, policy);
+  a.packed = 2;  // (tells the eight-lane Servos kernel to take its actions from the policy argument; `act` is not read)
+  a.policy = policy;
+  return launch_step<MODE_SERVOS>(sim, a);
 }
 
 extern "C" int upkie_sim_autoreset_done(UpkieSim* sim, int observation, float* state, float* obs, float* final_obs, void* stream) {
-  const BaseVelocityPtrs none{};
   switch (observation) {
-    case UPKIE_OBSERVATION_PENDULUM:
-      return launch_step<MODE_PENDULUM>(sim, state, nullptr, obs, nullptr, nullptr, nullptr, nullptr, stream, 0, none, true, final_obs);
-    case UPKIE_OBSERVATION_PENDULUM_RECORDS:
-      return launch_step<MODE_PENDULUM>(sim, state, nullptr, obs, nullptr, nullptr, nullptr, nullptr, stream, 1, none, true, final_obs);
-    case UPKIE_OBSERVATION_GYROPOD:
-      return launch_step<MODE_GYROPOD>(sim, state, nullptr, obs, nullptr, nullptr, nullptr, nullptr, stream, 0, none, true, final_obs);
-    case UPKIE_OBSERVATION_SERVOS:
-      return launch_step<MODE_SERVOS>(sim, state, nullptr, obs, nullptr, nullptr, nullptr, nullptr, stream, 0, none, true, final_obs);
-    default:
-      return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "unknown observation layout");
+    case UPKIE_OBSERVATION_PENDULUM: return launch_done_pass<MODE_PENDULUM>(sim, state, obs, final_obs, 0, stream);
+    case UPKIE_OBSERVATION_PENDULUM_RECORDS: return launch_done_pass<MODE_PENDULUM>(sim, state, obs, final_obs, 1, stream);
+    case UPKIE_OBSERVATION_GYROPOD: return launch_done_pass<MODE_GYROPOD>(sim, state, obs, final_obs, 0, stream);
+    case UPKIE_OBSERVATION_SERVOS: return launch_done_pass<MODE_SERVOS>(sim, state, obs, final_obs, 0, stream);
+    default: return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "unknown observation layout");
   }
 }
 
@@ -1078,19 +1023,19 @@ extern "C" int upkie_sim_step_base_velocity_mpc(UpkieSim* sim, UpkieMpc* mpc, fl
     return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
   if (mpc->dev.num_envs != sim->config.num_envs) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "balancer and simulation differ in num_envs");
   if (!(sim->config.dt / 0.1 < 0.5)) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "dt too large for the 0.1 s low-pass (filters.py:78-79)");
-  if ((mapped_lanes(sim) == 2 || mapped_lanes(sim) == 8) && mpc->tiles == 1) {
-    BaseVelocityPtrs bv{commanded_velocity, mpc_x0, mpc_contact};
-    bv.mpc_fused = 1;
-    bv.mpc = mpc->dev;
-    bv.mpc_ws = workspace;
-    bv.mpc_commanded = commanded_velocity;
-    return launch_step<MODE_BASE_VELOCITY>(sim, state, act, obs, reward, terminated, truncated, nullptr, stream, 0, bv);
+  StepArgs a = step_args(state, act, obs, reward, terminated, truncated, stream);
+  a.bv = BaseVelocityPtrs{commanded_velocity, mpc_x0, mpc_contact};
+  if (lanes_of(sim, MODE_BASE_VELOCITY) >= 2 && mpc->tiles == 1) {
+    a.bv.mpc_fused = 1;
+    a.bv.mpc = mpc->dev;
+    a.bv.mpc_ws = workspace;
+    a.bv.mpc_commanded = commanded_velocity;
+    return launch_step<MODE_BASE_VELOCITY>(sim, a);
   }
   const float* done = sim->config.autoreset_mode != 0 ? state + (size_t)UPKIE_S_DONE * sim->config.num_envs : nullptr;
   const int status = mpc_launch(mpc, workspace, mpc_x0, act, 2, mpc_contact, done, sim->config.dt, commanded_velocity, nullptr, stream);
   if (status != UPKIE_OK) return fail(sim, status, mpc->error);
-  return launch_step<MODE_BASE_VELOCITY>(sim, state, act, obs, reward, terminated, truncated, nullptr, stream, 0,
-                                         BaseVelocityPtrs{commanded_velocity, mpc_x0, mpc_contact});
+  return launch_step<MODE_BASE_VELOCITY>(sim, a);
 }
 
 // =========================================================== observer pipeline

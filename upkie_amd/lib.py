@@ -29,6 +29,7 @@ SOURCES = [
     os.path.join(_CSRC, "abi_host.hpp"),
     os.path.join(_CSRC, "mlp_instances.hpp"),
     os.path.join(_CSRC, "step_instances.hpp"),
+    os.path.join(_CSRC, "step_dispatch.hpp"),
     os.path.join(_CSRC, "step_kernels.hpp"),
     os.path.join(_CSRC, "host_setup.hpp"),
     os.path.join(_CSRC, "dynamics.hpp"),
