@@ -61,7 +61,7 @@ for mode in modes:
 
         timed(eager, 200)
         us = timed(eager, steps)
-        print(f"B={B} autoreset={mode} max_episode_steps={limit} policy={policy_kind}: {us:.1f} us per env.step() from Python, {B / us * 1e6:.3e} env-steps/s")
+        print(f"B={B} autoreset={mode} max_episode_steps={limit} policy={policy_kind}: {us:.2f} us per env.step() from Python, {B / us * 1e6:.3e} env-steps/s")
         # where the loop's time goes: the policy's kernels alone (same ops, result dropped), and the host side alone
         us_policy = timed(lambda: policy(state["obs"]), steps)
         t0 = time.perf_counter()
@@ -69,7 +69,7 @@ for mode in modes:
             eager()
         host = (time.perf_counter() - t0) / steps * 1e6  # (no synchronisation: what the interpreter needs to ISSUE a step)
         torch.cuda.synchronize()
-        print(f"    policy ops alone {us_policy:.1f} us per call; host time to issue one loop iteration {host:.1f} us")
+        print(f"    policy ops alone {us_policy:.1f} us per call; host time to issue one loop iteration {host:.2f} us")
         if "--no-graph" not in sys.argv and policy_kind != "in_launch":
             for unroll in (1, 4, 16):
                 graphed = GraphedEnvStep(env, policy, unroll=unroll)

@@ -12,6 +12,7 @@ import torch
 
 from . import lib
 from .exceptions import UpkieRuntimeError
+from .launch import check, launcher, ptr
 
 
 class EpisodeStatistics:
@@ -49,8 +50,8 @@ class EpisodeStatistics:
         if not hasattr(self._lib, "upkie_episodes_step"):
             raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_episodes_step: rebuild it")
         nbytes = int(self._lib.upkie_episodes_workspace_bytes(self.num_envs))
-        if nbytes < 0:
-            lib.check(nbytes, None)
+        check(nbytes)
+        self._launcher = launcher(self.device)
         N, W = self.num_envs, self.window
         self.ep_return = torch.zeros(N, dtype=torch.float64, device=self.device)
         self.ep_length = torch.zeros(N, dtype=torch.int32, device=self.device)
@@ -77,23 +78,16 @@ class EpisodeStatistics:
         reward = self._vector(reward, "reward", (torch.float32,), required=True)
         terminated = self._vector(terminated, "terminated", (torch.bool, torch.uint8))
         truncated = self._vector(truncated, "truncated", (torch.bool, torch.uint8))
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        with torch.cuda.device(self.device):
-            status = self._lib.upkie_episodes_step(self.num_envs, self.window, reward.data_ptr(), ptr(terminated), ptr(truncated),
-                                                   self.ep_return.data_ptr(), self.ep_length.data_ptr(), self.ring_return.data_ptr(),
-                                                   self.ring_length.data_ptr(), self.counters.data_ptr(), self.means.data_ptr(),
-                                                   self.workspace.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-        lib.check(status, None)
+        self._launcher(self._lib.upkie_episodes_step, self.num_envs, self.window, reward.data_ptr(), ptr(terminated), ptr(truncated),
+                       self.ep_return.data_ptr(), self.ep_length.data_ptr(), self.ring_return.data_ptr(), self.ring_length.data_ptr(),
+                       self.counters.data_ptr(), self.means.data_ptr(), self.workspace.data_ptr())
         return self.means
 
     def reset(self, mask: Optional[torch.Tensor] = None) -> None:
         """Discard the running episodes of the envs with ``mask`` set ([N] bool or uint8; None: every env) without
         recording them (``Monitor.reset``). The ring and the means are kept."""
         mask = self._vector(mask, "mask", (torch.bool, torch.uint8))
-        with torch.cuda.device(self.device):
-            status = self._lib.upkie_episodes_reset(self.num_envs, None if mask is None else mask.data_ptr(), self.ep_return.data_ptr(),
-                                                    self.ep_length.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-        lib.check(status, None)
+        self._launcher(self._lib.upkie_episodes_reset, self.num_envs, ptr(mask), self.ep_return.data_ptr(), self.ep_length.data_ptr())
 
     # ---- host reads (each synchronises with the device)
     @property

@@ -307,16 +307,3 @@ def load() -> C.CDLL:
     _lib = lib
     return lib
 
-
-def check(status: int, handle=None, what: str = "sim") -> None:
-    """Raise `UpkieHipError` on a negative status."""
-    if status >= 0:
-        return
-    lib = load()
-    if what == "mpc":
-        msg = lib.upkie_mpc_last_error(handle)
-    elif what == "observers":
-        msg = lib.upkie_observers_last_error(handle)
-    else:
-        msg = lib.upkie_sim_last_error(handle)
-    raise UpkieHipError(status, msg.decode() if msg else "")

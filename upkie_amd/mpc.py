@@ -8,10 +8,7 @@ import torch
 
 from . import abi, lib
 from .exceptions import UpkieRuntimeError
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+from .launch import launcher, ptr
 
 
 class BatchedMpc:
@@ -27,9 +24,10 @@ class BatchedMpc:
         self.config = config
         self.num_envs = int(config.num_envs)
         self._handle = C.c_void_p()
+        self._launch = launcher(self.device, self._handle, self._lib.upkie_mpc_last_error)
         with torch.cuda.device(self.device):
             status = self._lib.upkie_mpc_create(C.byref(config), C.byref(self._handle))
-        lib.check(status, None, what="mpc")
+        self._launch.check(status)
         N, B = int(config.nb_timesteps), self.num_envs
         assert self._lib.upkie_mpc_workspace_bytes(self._handle) == 2 * N * B * 4
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -41,6 +39,7 @@ class BatchedMpc:
         if getattr(self, "_handle", None):
             self._lib.upkie_mpc_destroy(self._handle)
             self._handle = None
+            self._launch.release()
 
     def __del__(self):
         try:
@@ -48,36 +47,18 @@ class BatchedMpc:
         except Exception:
             pass
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def reset(self, mask: Optional[torch.Tensor] = None) -> None:
         """MPCBalancer.reset (mpc_balancer.py:228-235) for masked envs."""
         if mask is not None:
             mask = mask.to(self.device, torch.uint8).contiguous()
-        with torch.cuda.device(self.device):
-            status = self._lib.upkie_mpc_reset(
-                self._handle, _ptr(self.workspace), _ptr(self.commanded_velocity), _ptr(mask), self._stream()
-            )
-        lib.check(status, self._handle, what="mpc")
+        self._launch(self._lib.upkie_mpc_reset, ptr(self.workspace), ptr(self.commanded_velocity), ptr(mask))
 
     def step_env(self, x0: torch.Tensor, act: torch.Tensor, contact: torch.Tensor, done: Optional[torch.Tensor], dt: float):
         """First half of the fused UpkieBaseVelocity step: target velocity of
         env e is ``act[e, 0]``; envs flagged in ``done`` (a float row of the
         simulation state) are reset instead of solved."""
-        with torch.cuda.device(self.device):
-            status = self._lib.upkie_mpc_step_env(
-                self._handle,
-                _ptr(self.workspace),
-                _ptr(x0),
-                _ptr(act),
-                _ptr(contact),
-                _ptr(done),
-                float(dt),
-                _ptr(self.commanded_velocity),
-                self._stream(),
-            )
-        lib.check(status, self._handle, what="mpc")
+        self._launch(self._lib.upkie_mpc_step_env, ptr(self.workspace), ptr(x0), ptr(act), ptr(contact), ptr(done), float(dt),
+                     ptr(self.commanded_velocity))
         return self.commanded_velocity
 
     def step(self, x0: torch.Tensor, target_velocity: torch.Tensor, contact: torch.Tensor, dt: float):
@@ -87,17 +68,6 @@ class BatchedMpc:
         x0 = x0.to(self.device, torch.float32).contiguous()
         target_velocity = target_velocity.to(self.device, torch.float32).contiguous()
         contact = contact.to(self.device, torch.uint8).contiguous()
-        with torch.cuda.device(self.device):
-            status = self._lib.upkie_mpc_step(
-                self._handle,
-                _ptr(self.workspace),
-                _ptr(x0),
-                _ptr(target_velocity),
-                _ptr(contact),
-                float(dt),
-                _ptr(self.commanded_velocity),
-                _ptr(self.first_input),
-                self._stream(),
-            )
-        lib.check(status, self._handle, what="mpc")
+        self._launch(self._lib.upkie_mpc_step, ptr(self.workspace), ptr(x0), ptr(target_velocity), ptr(contact), float(dt),
+                     ptr(self.commanded_velocity), ptr(self.first_input))
         return self.commanded_velocity, self.first_input

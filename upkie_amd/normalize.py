@@ -14,6 +14,7 @@ import torch
 
 from . import lib
 from .exceptions import UpkieRuntimeError
+from .launch import check, launcher, ptr
 
 # enum UpkieVecNormFlag
 TRAINING, NORM_OBS, NORM_REWARD, RESET = 1, 2, 4, 8
@@ -65,8 +66,8 @@ class RunningNormalizer:
         if not hasattr(self._lib, "upkie_vecnorm_step"):
             raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_vecnorm_step")
         nbytes = int(self._lib.upkie_vecnorm_workspace_bytes(self.num_envs, self.obs_dim))
-        if nbytes < 0:
-            lib.check(nbytes, None)
+        check(nbytes)
+        self._launcher = launcher(self.device)
         N, D = self.num_envs, self.obs_dim
         f64 = dict(dtype=torch.float64, device=self.device)
         self.obs_stats = torch.zeros(2 * D + 1, **f64)  # mean[D], var[D], count
@@ -176,28 +177,25 @@ class RunningNormalizer:
     def _launch(self, flags, obs=None, reward=None, terminated=None, truncated=None, norm_obs=None, norm_reward=None, starts=None) -> None:
         if self.device.type != "cuda":
             raise UpkieRuntimeError("RunningNormalizer runs on the HIP device only (there is no CPU fallback): build it with device='cuda:0'")
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         packed = None if self._policy is None else self._policy.packed
         training, reset = bool(flags & TRAINING), bool(flags & RESET)
         shared = self._exchange is not None and training and (bool(flags & NORM_OBS) or not reset)  # (a statistic moves)
         if shared and torch.cuda.is_current_stream_capturing():
             raise UpkieRuntimeError("a RunningNormalizer with a process group cannot be captured in a graph (its step exchanges the "
                                     "moments through a collective)")
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            args = (self.num_envs, self.obs_dim, ptr(obs), ptr(reward), ptr(terminated), ptr(truncated), self.obs_stats.data_ptr(),
-                    self.ret_stats.data_ptr(), self.returns.data_ptr(), self.workspace.data_ptr(), flags, self.gamma, self.epsilon, self.clip_obs,
-                    self.clip_reward, self.obs_mean_f32.data_ptr(), self.obs_std_f32.data_ptr(), ptr(packed), ptr(norm_obs), ptr(norm_reward),
-                    ptr(starts))
-            if not shared:
-                status = self._lib.upkie_vecnorm_step(*args, stream)
-            else:
-                ex = self._exchange
-                status = self._lib.upkie_vecnorm_moments_local(*args, ex.mine.data_ptr(), stream)
-                if status >= 0:
-                    ex.exchange()
-                    status = self._lib.upkie_vecnorm_merge(*args, ex.slots.data_ptr(), ex.world, stream)
-        lib.check(status, None)
+        launch = self._launcher
+        args = (self.num_envs, self.obs_dim, ptr(obs), ptr(reward), ptr(terminated), ptr(truncated), self.obs_stats.data_ptr(),
+                self.ret_stats.data_ptr(), self.returns.data_ptr(), self.workspace.data_ptr(), flags, self.gamma, self.epsilon, self.clip_obs,
+                self.clip_reward, self.obs_mean_f32.data_ptr(), self.obs_std_f32.data_ptr(), ptr(packed), ptr(norm_obs), ptr(norm_reward),
+                ptr(starts))
+        if not shared:
+            launch(self._lib.upkie_vecnorm_step, *args)
+            return
+        ex = self._exchange
+        with torch.cuda.device(self.device):  # (around the whole block: the collective between the two launches relies on it)
+            launch(self._lib.upkie_vecnorm_moments_local, *args, ex.mine.data_ptr())
+            ex.exchange()
+            launch(self._lib.upkie_vecnorm_merge, *args, ex.slots.data_ptr(), ex.world)
 
     def broadcast_statistics(self, src: int = 0) -> None:
         """Copy the statistics of group rank `src` to every rank (with their fp32 mirrors and an attached policy's packed

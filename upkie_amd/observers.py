@@ -18,10 +18,7 @@ import torch
 
 from . import abi, lib
 from .exceptions import UpkieRuntimeError
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None
+from .launch import launcher, ptr
 
 
 def observer_config_from_spine_config(num_envs: int, dt: float, spine_config: Optional[dict] = None) -> abi.UpkieObserverConfig:
@@ -113,9 +110,10 @@ class BatchedObservers:
         self.config = config
         self.num_envs = int(config.num_envs)
         self._handle = C.c_void_p()
+        self._launch = launcher(self.device, self._handle, self._lib.upkie_observers_last_error)
         with torch.cuda.device(self.device):
             status = self._lib.upkie_observers_create(C.byref(config), C.byref(self._handle))
-        lib.check(status, None, what="observers")
+        self._launch.check(status)
         B = self.num_envs
         assert self._lib.upkie_observers_state_bytes(self._handle) == abi.OBSERVER_STATE_WORDS * B * 4
         self.state = torch.zeros((abi.OBSERVER_STATE_WORDS, B), dtype=torch.float32, device=self.device)
@@ -124,6 +122,7 @@ class BatchedObservers:
         if getattr(self, "_handle", None):
             self._lib.upkie_observers_destroy(self._handle)
             self._handle = None
+            self._launch.release()
 
     def __del__(self):
         try:
@@ -131,16 +130,11 @@ class BatchedObservers:
         except Exception:
             pass
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def reset(self, mask: Optional[torch.Tensor] = None) -> None:
         """Observer::reset of the three observers for masked envs."""
         if mask is not None:
             mask = mask.to(self.device, torch.uint8).contiguous()
-        with torch.cuda.device(self.device):
-            status = self._lib.upkie_observers_reset(self._handle, C.c_void_p(self.state.data_ptr()), _ptr(mask), self._stream())
-        lib.check(status, self._handle, what="observers")
+        self._launch(self._lib.upkie_observers_reset, ptr(self.state), ptr(mask))
 
     def step(
         self,
@@ -171,7 +165,7 @@ class BatchedObservers:
         if cross_button is not None:
             cross_button = cross_button.to(dev, torch.uint8).contiguous()
         inp = abi.UpkieObserverInput(
-            _ptr(servo), _ptr(imu_orientation), _ptr(imu_angular_velocity), _ptr(cross_button)
+            ptr(servo), ptr(imu_orientation), ptr(imu_angular_velocity), ptr(cross_button)
         )
         have_imu = imu_orientation is not None
         tensors = {
@@ -183,12 +177,8 @@ class BatchedObservers:
             "wheel_contact": torch.empty((B, 2, 4), **f32),
             "wheel_odometry": torch.empty((B, 2), **f32),
         }
-        out = abi.UpkieObserverOutput(*[_ptr(tensors[name]) for name, _ in abi.UpkieObserverOutput._fields_])
-        with torch.cuda.device(dev):
-            status = self._lib.upkie_observers_step(
-                self._handle, C.c_void_p(self.state.data_ptr()), C.byref(inp), C.byref(out), self._stream()
-            )
-        lib.check(status, self._handle, what="observers")
+        out = abi.UpkieObserverOutput(*[ptr(tensors[name]) for name, _ in abi.UpkieObserverOutput._fields_])
+        self._launch(self._lib.upkie_observers_step, ptr(self.state), C.byref(inp), C.byref(out))
         if servo is None:
             return {k: v for k, v in observer_blocks(tensors).items() if k == "base_orientation"}
         return observer_blocks(tensors)

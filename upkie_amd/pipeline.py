@@ -16,6 +16,7 @@ import torch
 
 from . import lib
 from .exceptions import UpkieRuntimeError
+from .launch import check, launcher, ptr
 
 # enum UpkiePipelineFlag
 ACTION_IN_OBSERVATION, INTEGRATE_ACTION, ACTION_NOISE, ACTION_LAG, OBSERVATION_NOISE = 1, 2, 4, 8, 16
@@ -110,6 +111,7 @@ class AgentPipeline:
         self._lib = lib.load()
         if not hasattr(self._lib, "upkie_pipeline_observe"):
             raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_pipeline_observe: rebuild it")
+        self._launcher = launcher(self.device)
         self.params = torch.from_numpy(self.packed_params()).to(self.device)
         N, A, S = self.num_envs, self.act_dim, self.stacked_dim
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -129,8 +131,7 @@ class AgentPipeline:
         out = np.zeros(3 * self.act_dim + self.obs_dim, dtype=np.float32)
         words = int(library.upkie_pipeline_params(self.obs_dim, self.act_dim, arr(self.action_low), arr(self.action_high), arr(self.action_noise),
                                                   arr(self.observation_noise), out.ctypes.data))
-        if words < 0:
-            lib.check(words, None)
+        check(words)
         return out
 
     # ---- arguments
@@ -154,10 +155,8 @@ class AgentPipeline:
     def shape_action(self, env_action: torch.Tensor) -> torch.Tensor:
         """``env_action`` [N, A] float32 (the policy's clamped output) into `command`, which is returned."""
         a = self._tensor(env_action, "env_action", (self.num_envs, self.act_dim))
-        with torch.cuda.device(self.device):
-            status = self._lib.upkie_pipeline_shape_action(*self._settings(), a.data_ptr(), self.prev_command.data_ptr(), self.calls.data_ptr(),
-                                                           self.command.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-        lib.check(status, None)
+        self._launcher(self._lib.upkie_pipeline_shape_action, *self._settings(), a.data_ptr(), self.prev_command.data_ptr(), self.calls.data_ptr(),
+                       self.command.data_ptr())
         return self.command
 
     def observe(self, next_obs: torch.Tensor, terminated: Optional[torch.Tensor] = None, truncated: Optional[torch.Tensor] = None,
@@ -169,12 +168,9 @@ class AgentPipeline:
         term = self._tensor(terminated, "terminated", (N,), (torch.bool, torch.uint8), required=False)
         trunc = self._tensor(truncated, "truncated", (N,), (torch.bool, torch.uint8), required=False)
         final = self._tensor(final_obs, "final_obs", (N, D), required=False)
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        with torch.cuda.device(self.device):
-            status = self._lib.upkie_pipeline_observe(*self._settings(), obs.data_ptr(), ptr(term), ptr(trunc), ptr(final), self.command.data_ptr(),
-                                                      self.prev_command.data_ptr(), self.calls.data_ptr(), self.observation.data_ptr(),
-                                                      self.final_observation.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-        lib.check(status, None)
+        self._launcher(self._lib.upkie_pipeline_observe, *self._settings(), obs.data_ptr(), ptr(term), ptr(trunc), ptr(final),
+                       self.command.data_ptr(), self.prev_command.data_ptr(), self.calls.data_ptr(), self.observation.data_ptr(),
+                       self.final_observation.data_ptr())
         return self.observation
 
     def reset(self, obs: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -182,11 +178,8 @@ class AgentPipeline:
         with the frame of ``obs`` (noised, zero command) last, ``prev_command`` zero. Returns `observation`."""
         obs = self._tensor(obs, "obs", (self.num_envs, self.obs_dim))
         mask = self._tensor(mask, "mask", (self.num_envs,), (torch.bool, torch.uint8), required=False)
-        with torch.cuda.device(self.device):
-            status = self._lib.upkie_pipeline_reset(*self._settings(), obs.data_ptr(), None if mask is None else mask.data_ptr(),
-                                                    self.prev_command.data_ptr(), self.calls.data_ptr(), self.observation.data_ptr(),
-                                                    torch.cuda.current_stream(self.device).cuda_stream)
-        lib.check(status, None)
+        self._launcher(self._lib.upkie_pipeline_reset, *self._settings(), obs.data_ptr(), ptr(mask), self.prev_command.data_ptr(),
+                       self.calls.data_ptr(), self.observation.data_ptr())
         return self.observation
 
     def state_tensors(self) -> dict:

@@ -15,6 +15,7 @@ import torch
 
 from . import abi, lib
 from .exceptions import UpkieRuntimeError
+from .launch import check, launcher, ptr
 
 
 class LinearPolicy:
@@ -39,7 +40,7 @@ class LinearPolicy:
         if clip is not None and not self.clip > 0.0:
             raise ValueError("clip must be positive (None: no clamp)")
         self._act = None
-        self._lib = None
+        self._lib = self._launcher = None
 
     def __call__(self, obs: torch.Tensor) -> torch.Tensor:
         if not obs.is_cuda:
@@ -54,11 +55,9 @@ class LinearPolicy:
             self._lib = lib.load()
             if not hasattr(self._lib, "upkie_linear_policy"):
                 raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_linear_policy")
-        with torch.cuda.device(obs.device):
-            status = self._lib.upkie_linear_policy(n, self.obs_dim, self.act_dim, obs.data_ptr(), self.weights.data_ptr(),
-                                                   None if self.bias is None else self.bias.data_ptr(), self.clip, self._act.data_ptr(),
-                                                   torch.cuda.current_stream(obs.device).cuda_stream)
-        lib.check(status, None)
+            self._launcher = launcher(obs.device)  # (the observations' device, as the action buffer)
+        self._launcher(self._lib.upkie_linear_policy, n, self.obs_dim, self.act_dim, obs.data_ptr(), self.weights.data_ptr(), ptr(self.bias),
+                       self.clip, self._act.data_ptr())
         return self._act
 
 
@@ -269,8 +268,8 @@ class MlpActorCritic:
         if not hasattr(self._lib, "upkie_mlp_actor_critic"):
             raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_mlp_actor_critic")
         words = int(self._lib.upkie_mlp_packed_words(C.byref(shape)))
-        if words < 0:
-            lib.check(words, None)
+        check(words)
+        self._launcher = launcher(self.device)
 
         def vec(v, n, fill, name):
             t = torch.full((n,), fill, dtype=torch.float64) if v is None else torch.as_tensor(v, dtype=torch.float64).detach().cpu().reshape(-1)
@@ -419,13 +418,8 @@ class MlpActorCritic:
         return t
 
     def _launch(self, obs, deterministic: bool, outs: dict) -> None:
-        n = obs.shape[0]
-        ptr = lambda name: outs[name].data_ptr() if outs.get(name) is not None else None  # noqa: E731
-        with torch.cuda.device(self.device):
-            status = self._lib.upkie_mlp_actor_critic(
-                n, C.byref(self.shape), self.packed.data_ptr(), obs.data_ptr(), self.calls.data_ptr(), self.seed, int(bool(deterministic)),
-                *[ptr(name) for name in OUTPUT_NAMES], torch.cuda.current_stream(self.device).cuda_stream)
-        lib.check(status, None)
+        self._launcher(self._lib.upkie_mlp_actor_critic, obs.shape[0], C.byref(self.shape), self.packed.data_ptr(), obs.data_ptr(),
+                       self.calls.data_ptr(), self.seed, int(bool(deterministic)), *[ptr(outs.get(name)) for name in OUTPUT_NAMES])
 
     def act(self, obs: torch.Tensor, deterministic: bool = False, out: Optional[dict] = None):
         """(env_action, action, value, log_prob) of a batch of observations ``[N, ...]``; value is None without a
@@ -485,11 +479,8 @@ class MlpActorCritic:
             raise ValueError("gamma must be in [0, 1]")
         if not hasattr(self._lib, "upkie_mlp_bootstrap_time_limits"):
             raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_mlp_bootstrap_time_limits: rebuild it")
-        with torch.cuda.device(self.device):
-            status = self._lib.upkie_mlp_bootstrap_time_limits(n, C.byref(self.shape), self.packed.data_ptr(), final_obs.data_ptr(),
-                                                               flags[0].data_ptr(), flags[1].data_ptr(), gamma, reward.data_ptr(),
-                                                               torch.cuda.current_stream(self.device).cuda_stream)
-        lib.check(status, None)
+        self._launcher(self._lib.upkie_mlp_bootstrap_time_limits, n, C.byref(self.shape), self.packed.data_ptr(), final_obs.data_ptr(),
+                       flags[0].data_ptr(), flags[1].data_ptr(), gamma, reward.data_ptr())
         return reward
 
 

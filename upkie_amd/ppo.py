@@ -11,6 +11,7 @@ import torch
 
 from . import abi, lib
 from .exceptions import UpkieRuntimeError
+from .launch import check, launcher, ptr
 
 STAT_NAMES = ("policy_gradient_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction", "grad_norm")
 Schedule = Union[float, Callable[[float], float]]  # a constant, or SB3's schedule: a function of progress_remaining (1 -> 0)
@@ -122,6 +123,7 @@ class PpoTrainer:
         self._lib = lib.load()
         if not hasattr(self._lib, "upkie_ppo_minibatch_update"):
             raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_ppo_minibatch_update")
+        self._launcher = launcher(self.device)
         words = policy.packed.numel()
         f32 = dict(dtype=torch.float32, device=self.device)
         self.m = torch.zeros(words, **f32)
@@ -166,8 +168,7 @@ class PpoTrainer:
         mb = min(self.batch_size, total)
         self.n_minibatches = (total + mb - 1) // mb
         nbytes = int(self._lib.upkie_ppo_workspace_bytes(C.byref(self.policy.shape), mb))
-        if nbytes < 0:
-            lib.check(nbytes, None)
+        check(nbytes)
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self.perm = torch.empty((self.n_epochs, total), dtype=torch.int32, device=self.device)
         self.adv_stats = torch.zeros((self.n_epochs, self.n_minibatches, 2), dtype=torch.float64, device=self.device)
@@ -260,10 +261,9 @@ class PpoTrainer:
             raise UpkieRuntimeError("call prepare(buffer) first: it copies the advantages and returns update() reads")
         if self._addresses(buffer) != self._buffer:
             raise ValueError("this trainer serves one rollout buffer (a captured update reads its tensors): build another trainer")
-        lb, shape, cfg = self._lib, C.byref(self.policy.shape), C.byref(self.config)
-        p = lambda t: t.data_ptr()  # noqa: E731
-        obs, act = p(buffer.observations), p(buffer.actions)
-        vals, logp, adv, ret = p(buffer.values), p(buffer.log_probs), p(self.advantages), p(self.returns)
+        lb, launch, shape, cfg = self._lib, self._launcher, C.byref(self.policy.shape), C.byref(self.config)
+        obs, act = ptr(buffer.observations), ptr(buffer.actions)
+        vals, logp, adv, ret = ptr(buffer.values), ptr(buffer.log_probs), ptr(self.advantages), ptr(self.returns)
         if self.process_group is not None:
             if torch.cuda.is_current_stream_capturing():
                 raise UpkieRuntimeError("a PpoTrainer with a process group cannot be captured in a graph (every minibatch exchanges the "
@@ -274,60 +274,51 @@ class PpoTrainer:
             return self.stats
         # (the controlled entry point has upkie_ppo_minibatch_update's signature, the control block where adam_scalars is)
         minibatch = lb.upkie_ppo_minibatch_update_controlled if self.controlled else lb.upkie_ppo_minibatch_update
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):  # (around the whole block: every launch then takes the launcher's fast path)
             if self.controlled:
-                status = lb.upkie_ppo_update_begin(p(self.control), stream)
-                lib.check(status, None)
+                launch(lb.upkie_ppo_update_begin, ptr(self.control))
             for e in range(self.n_epochs):
                 perm = self.perm[e]
-                status = lb.upkie_ppo_advantage_stats(total, self._mb, p(perm), adv, int(self.normalize_advantage), p(self.adv_stats[e]), stream)
-                lib.check(status, None)
+                launch(lb.upkie_ppo_advantage_stats, total, self._mb, ptr(perm), adv, int(self.normalize_advantage), ptr(self.adv_stats[e]))
                 for j in range(self.n_minibatches):
                     start = j * self._mb
-                    status = minibatch(
-                        shape, cfg, total, start, min(self._mb, total - start), self._mb, p(perm), obs, act, vals, logp, adv, ret,
-                        p(self.adv_stats[e, j]), p(self.policy.packed), p(self.m), p(self.v), p(self.control), p(self.workspace),
-                        p(self.stats[e, j]), stream)
-                    lib.check(status, None)
+                    launch(minibatch, shape, cfg, total, start, min(self._mb, total - start), self._mb, ptr(perm), obs, act, vals, logp, adv, ret,
+                           ptr(self.adv_stats[e, j]), ptr(self.policy.packed), ptr(self.m), ptr(self.v), ptr(self.control), ptr(self.workspace),
+                           ptr(self.stats[e, j]))
         if sync:
             self.sync_modules()
         return self.stats
 
     def _update_shared(self, total, shape, cfg, obs, act, vals, logp, adv, ret) -> None:
         """`update`'s epochs and minibatches in the data-parallel form: the same launches split around the exchanges."""
-        lb, gx, ax = self._lib, self._grad_exchange, self._adv_exchange
-        p = lambda t: t.data_ptr()  # noqa: E731
+        lb, launch, gx, ax = self._lib, self._launcher, self._grad_exchange, self._adv_exchange
         W, mb = gx.world, self._mb
 
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):  # (around the whole block: the collectives between the launches rely on it)
             if self.controlled:
-                lib.check(lb.upkie_ppo_update_begin(p(self.control), stream))
+                launch(lb.upkie_ppo_update_begin, ptr(self.control))
             for e in range(self.n_epochs):
-                perm = p(self.perm[e])
-                lib.check(lb.upkie_ppo_advantage_partials(total, mb, perm, adv, 0, None, W, p(ax.mine), stream))
+                perm = ptr(self.perm[e])
+                launch(lb.upkie_ppo_advantage_partials, total, mb, perm, adv, 0, None, W, ptr(ax.mine))
                 ax.exchange()
-                lib.check(lb.upkie_ppo_advantage_partials(total, mb, perm, adv, 1, p(ax.slots), W, p(ax.mine), stream))
+                launch(lb.upkie_ppo_advantage_partials, total, mb, perm, adv, 1, ptr(ax.slots), W, ptr(ax.mine))
                 ax.exchange()
-                lib.check(lb.upkie_ppo_advantage_finish(total, mb, int(self.normalize_advantage), p(ax.slots), W, p(self.adv_stats[e]), stream))
+                launch(lb.upkie_ppo_advantage_finish, total, mb, int(self.normalize_advantage), ptr(ax.slots), W, ptr(self.adv_stats[e]))
                 for j in range(self.n_minibatches):
                     start = j * mb
                     size = min(mb, total - start)
                     if self.controlled:
-                        lib.check(lb.upkie_ppo_minibatch_gradient_controlled(shape, cfg, total, start, size, W * size, mb, perm, obs, act, vals, logp,
-                                                                             adv, ret, p(self.adv_stats[e, j]), p(self.policy.packed),
-                                                                             p(self.workspace), p(gx.mine), p(self.control), stream))
+                        launch(lb.upkie_ppo_minibatch_gradient_controlled, shape, cfg, total, start, size, W * size, mb, perm, obs, act, vals, logp,
+                               adv, ret, ptr(self.adv_stats[e, j]), ptr(self.policy.packed), ptr(self.workspace), ptr(gx.mine), ptr(self.control))
                         gx.exchange()  # (after a stop: still a collective every rank joins; the apply half ignores it)
-                        lib.check(lb.upkie_ppo_minibatch_apply_controlled(shape, cfg, start, W * size, mb, p(gx.slots), W, p(self.policy.packed),
-                                                                          p(self.m), p(self.v), p(self.control), p(self.workspace),
-                                                                          p(self.stats[e, j]), stream))
+                        launch(lb.upkie_ppo_minibatch_apply_controlled, shape, cfg, start, W * size, mb, ptr(gx.slots), W, ptr(self.policy.packed),
+                               ptr(self.m), ptr(self.v), ptr(self.control), ptr(self.workspace), ptr(self.stats[e, j]))
                         continue
-                    lib.check(lb.upkie_ppo_minibatch_gradient(shape, cfg, total, start, size, W * size, mb, perm, obs, act, vals, logp, adv, ret,
-                                                              p(self.adv_stats[e, j]), p(self.policy.packed), p(self.workspace), p(gx.mine), stream))
+                    launch(lb.upkie_ppo_minibatch_gradient, shape, cfg, total, start, size, W * size, mb, perm, obs, act, vals, logp, adv, ret,
+                           ptr(self.adv_stats[e, j]), ptr(self.policy.packed), ptr(self.workspace), ptr(gx.mine))
                     gx.exchange()
-                    lib.check(lb.upkie_ppo_minibatch_apply(shape, cfg, W * size, mb, p(gx.slots), W, p(self.policy.packed), p(self.m), p(self.v),
-                                                           p(self.scalars), p(self.workspace), p(self.stats[e, j]), stream))
+                    launch(lb.upkie_ppo_minibatch_apply, shape, cfg, W * size, mb, ptr(gx.slots), W, ptr(self.policy.packed), ptr(self.m),
+                           ptr(self.v), ptr(self.scalars), ptr(self.workspace), ptr(self.stats[e, j]))
 
     def train(self, buffer, sync: bool = True) -> torch.Tensor:
         """`prepare` then `update`: SB3's ``PPO.train`` on one full rollout buffer. Returns ``[n_epochs, n_minibatches, 7]``
@@ -350,10 +341,8 @@ class PpoTrainer:
         """lr, clip_range, clip_range_vf and target_kl to the control block (one launch; outside any capture)."""
         if torch.cuda.is_current_stream_capturing():
             raise UpkieRuntimeError("set the schedules' values outside a graph capture (a captured write would replay its old value)")
-        with torch.cuda.device(self.device):
-            status = self._lib.upkie_ppo_control_set(self.control.data_ptr(), float(lr), float(self._clip_range), float(self._clip_range_vf or 0.0),
-                                                     float(self._target_kl or 0.0), torch.cuda.current_stream(self.device).cuda_stream)
-        lib.check(status, None)
+        self._launcher(self._lib.upkie_ppo_control_set, self.control.data_ptr(), float(lr), float(self._clip_range),
+                       float(self._clip_range_vf or 0.0), float(self._target_kl or 0.0))
         self._lr = float(lr)
 
     def set_progress(self, progress_remaining: float) -> None:
@@ -402,16 +391,14 @@ class PpoTrainer:
         if not hasattr(self._lib, "upkie_ppo_explained_variance"):
             raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_ppo_explained_variance: rebuild it")
         lb, ret, val, out, ex = self._lib, self.returns.data_ptr(), self._values.data_ptr(), self._log_words.data_ptr(), self._ev_exchange
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):  # (around the whole block: the collectives between the launches rely on it)
             if ex is None:
                 steps = [(-1, None, 1, None)]
             else:
                 steps = [(0, None, ex.world, ex.mine.data_ptr()), (1, ex.slots.data_ptr(), ex.world, ex.mine.data_ptr()),
                          (2, ex.slots.data_ptr(), ex.world, None)]
             for phase, slots, world, mine in steps:
-                status = lb.upkie_ppo_explained_variance(self._total, ret, val, phase, slots, world, mine, out, stream)
-                lib.check(status, None)
+                self._launcher(lb.upkie_ppo_explained_variance, self._total, ret, val, phase, slots, world, mine, out)
                 if phase in (0, 1):
                     ex.exchange()
         return self._log_words[0]

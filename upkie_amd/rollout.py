@@ -5,17 +5,13 @@ tensors; advantages are computed by one HIP kernel (`gae_kernel`,
 csrc/rollout.hpp). Method names follow the rollout buffer of stable-baselines3,
 the learner the reference's RL playgrounds use (README.md:107-109)."""
 
-import ctypes as C
 from typing import Dict, Iterator, Optional, Tuple
 
 import torch
 
 from . import lib
 from .exceptions import UpkieRuntimeError
-
-
-def _ptr(t: torch.Tensor):
-    return C.c_void_p(t.data_ptr())
+from .launch import launcher, ptr
 
 
 def compute_gae(
@@ -39,14 +35,8 @@ def compute_gae(
     last_values, last_dones = f(last_values, (N,)), u(last_dones, (N,))
     advantages = torch.empty((T, N), dtype=torch.float32, device=dev)
     returns = torch.empty((T, N), dtype=torch.float32, device=dev)
-    library = lib.load()
-    with torch.cuda.device(dev):
-        status = library.upkie_rollout_gae(
-            T, N, _ptr(rewards), _ptr(values), _ptr(episode_starts), _ptr(last_values), _ptr(last_dones),
-            float(gamma), float(gae_lambda), _ptr(advantages), _ptr(returns),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
-        )
-    lib.check(status, None)
+    launcher(dev)(lib.load().upkie_rollout_gae, T, N, ptr(rewards), ptr(values), ptr(episode_starts), ptr(last_values), ptr(last_dones),
+                  float(gamma), float(gae_lambda), ptr(advantages), ptr(returns))
     return advantages, returns
 
 

@@ -7,6 +7,7 @@ independent robots living in one ``[STATE_WORDS, B]`` fp32 tensor.
 """
 
 import ctypes as C
+from functools import partial
 from typing import Optional
 
 import numpy as np
@@ -14,16 +15,16 @@ import torch
 
 from . import abi, lib
 from .exceptions import UpkieRuntimeError
+from .launch import launcher, ptr
 from .model.default_model import default_model
 
-
-def _ptr(t: Optional[torch.Tensor]):
-    # (a plain integer: ctypes turns it into the c_void_p the argtypes ask for, without an object per argument)
-    return t.data_ptr() if t is not None else None
-
-
-# the raw handle of torch's current stream on a device without building a torch.cuda.Stream object per call
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+# env kind: (step entry point, the observation buffer it writes by default, that buffer's shape per env)
+_STEPS = {
+    "pendulum": ("upkie_sim_step_pendulum", "obs4", (4,)),
+    "gyropod": ("upkie_sim_step_gyropod", "obs6", (6,)),
+    "servos": ("upkie_sim_step_servos", "obs_servos", (6, 5)),
+    "pendulum_agent": ("upkie_sim_step_pendulum_agent", "obs4", (4,)),
+}
 
 
 class BatchedSim:
@@ -42,16 +43,17 @@ class BatchedSim:
             )
         self._lib = lib.load()
         self.device = torch.device(device)
-        self._device_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self.config = config
         self.model = model if model is not None else default_model()
         self.num_envs = int(config.num_envs)
         self._handle = C.c_void_p()
+        # every call into the library on torch's current stream of this handle's device: `self._launch(fn, *args)`
+        self._launch = launcher(self.device, self._handle, self._lib.upkie_sim_last_error)
         with torch.cuda.device(self.device):
             status = self._lib.upkie_sim_create(
                 C.byref(self.config), C.byref(self.model), C.byref(self._handle)
             )
-        lib.check(status, None)
+        self._check(status)
         B = self.num_envs
         nbytes = self._lib.upkie_sim_state_bytes(self._handle)
         assert nbytes == abi.STATE_WORDS * B * 4
@@ -75,6 +77,7 @@ class BatchedSim:
         if getattr(self, "_handle", None) is not None and self._handle:
             self._lib.upkie_sim_destroy(self._handle)
             self._handle = None
+            self._launch.release()
 
     def __del__(self):
         try:
@@ -82,23 +85,16 @@ class BatchedSim:
         except Exception:
             pass
 
-    def _stream(self):
-        if _raw_stream is not None:
-            return _raw_stream(self._device_index)
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def _check(self, status: int) -> None:
-        lib.check(status, self._handle)
+        self._launch.check(status)
 
-    def _launch(self, fn, *args) -> None:
-        """One call into the library on torch's current stream of this handle's device. A Python-level RL loop pays
-        this once per `env.step()`: no device context manager when the device is already current, no stream object."""
-        if torch.cuda.current_device() == self._device_index:
-            status = fn(self._handle, *args, self._stream())
-        else:
-            with torch.cuda.device(self.device):
-                status = fn(self._handle, *args, self._stream())
-        lib.check(status, self._handle)
+    def _scratch(self, name: str, shape) -> torch.Tensor:
+        """The buffer ``self.<name>`` of ``[B, *shape]`` fp32, allocated by the first method that needs it."""
+        buf = getattr(self, name, None)
+        if buf is None:
+            buf = torch.zeros((self.num_envs,) + tuple(shape), dtype=torch.float32, device=self.device)
+            setattr(self, name, buf)
+        return buf
 
     def push_config(self) -> None:
         """Hand the (mutated) ``self.config`` to the library."""
@@ -115,16 +111,7 @@ class BatchedSim:
         if self.body_inertials is None:
             self.body_inertials = torch.zeros((abi.NB * abi.INERTIAL_WORDS, self.num_envs), dtype=torch.float32, device=self.device)
             self.link_scale = torch.ones((abi.MAX_LINKS, self.num_envs), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            self._check(
-                self._lib.upkie_sim_sample_body_inertials(
-                    self._handle,
-                    _ptr(self.body_inertials),
-                    _ptr(self.link_scale),
-                    float(inertia_variation),
-                    self._stream(),
-                )
-            )
+        self._launch(self._lib.upkie_sim_sample_body_inertials, ptr(self.body_inertials), ptr(self.link_scale), float(inertia_variation))
         self._push_randomization()
         return self.body_inertials
 
@@ -202,26 +189,17 @@ class BatchedSim:
         return out
 
     def _push_randomization(self):
-        self._check(self._lib.upkie_sim_set_randomization(self._handle, _ptr(self.body_inertials), None, None))
+        self._check(self._lib.upkie_sim_set_randomization(self._handle, ptr(self.body_inertials), None, None))
         slots = getattr(self, "_ext_slots", None)
         if self.ext_force is not None and slots is not None:
-            self._check(self._lib.upkie_sim_set_external_forces(self._handle, _ptr(self.ext_force), C.byref(slots)))
+            self._check(self._lib.upkie_sim_set_external_forces(self._handle, ptr(self.ext_force), C.byref(slots)))
 
     # ---------------------------------------------------------------- API
     def reset(self, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Reset masked envs (all if None); returns the Gyropod obs [B, 6]."""
         if mask is not None:
             mask = mask.to(self.device, torch.uint8).contiguous()
-        with torch.cuda.device(self.device):
-            self._check(
-                self._lib.upkie_sim_reset(
-                    self._handle,
-                    _ptr(self.state),
-                    _ptr(mask),
-                    _ptr(self.obs6),
-                    self._stream(),
-                )
-            )
+        self._launch(self._lib.upkie_sim_reset, ptr(self.state), ptr(mask), ptr(self.obs6))
         return self.obs6
 
     def _step(self, fn, act, obs):
@@ -245,32 +223,23 @@ class BatchedSim:
         output buffers (``obs4`` / ``obs6`` / ``obs_servos``, ``reward``,
         ``terminated``, ``truncated``). What `UpkieVecEnv.step` runs (a Python RL
         loop pays this per step: 2-3 us instead of 8)."""
-        if kind == "servos" and self.obs_servos is None:
-            self.obs_servos = torch.zeros((self.num_envs, 6, 5), dtype=torch.float32, device=self.device)
-        fn, obs = {"pendulum": (self._lib.upkie_sim_step_pendulum, self.obs4), "gyropod": (self._lib.upkie_sim_step_gyropod, self.obs6),
-                   "servos": (self._lib.upkie_sim_step_servos, self.obs_servos),
-                   "pendulum_agent": (self._lib.upkie_sim_step_pendulum_agent, self.obs4)}[kind]
-        handle, index, raw_stream = self._handle, self._device_index, _raw_stream
-        state, obs_p, rew, term, trunc = self.state.data_ptr(), obs.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(), self.truncated.data_ptr()
-        current_device = torch.cuda.current_device
-        slow = self._launch
+        name, obs_name, obs_shape = _STEPS[kind]
+        fn, launch = getattr(self._lib, name), self._launch
+        state, obs = self.state.data_ptr(), self._scratch(obs_name, obs_shape).data_ptr()
+        rew, term, trunc = self.reward.data_ptr(), self.terminated.data_ptr(), self.truncated.data_ptr()
         if kind == "pendulum_agent":  # (no action buffer: the linear agent acts on the observation held in `obs4`)
-
-            def step_agent() -> None:
-                if raw_stream is not None and current_device() == index:
-                    status = fn(handle, state, obs_p, rew, term, trunc, raw_stream(index))
-                    lib.check(status, handle)
-                else:
-                    slow(fn, state, obs_p, rew, term, trunc)
-
-            return step_agent
+            return partial(launch, fn, state, obs, rew, term, trunc)
+        # The one closure that does not go through `launch`: `UpkieVecEnv.step` pays it per step, and the action address
+        # sits between constant arguments, so binding it would cost a second Python frame per step.
+        handle, index, raw_stream, current_device = self._handle, launch.index, launch.raw_stream, torch.cuda.current_device
 
         def step(action_address: int) -> None:
             if raw_stream is not None and current_device() == index:
-                status = fn(handle, state, action_address, obs_p, rew, term, trunc, raw_stream(index))
-                lib.check(status, handle)
+                status = fn(handle, state, action_address, obs, rew, term, trunc, raw_stream(index))
+                if status < 0:
+                    launch.check(status)
             else:
-                slow(fn, state, action_address, obs_p, rew, term, trunc)
+                launch(fn, state, action_address, obs, rew, term, trunc)
 
         return step
 
@@ -286,34 +255,19 @@ class BatchedSim:
         step to step). The step writes straight into the addresses it is given
         -- e.g. a slot of the staging buffer a collective ships
         (`upkie_amd.distributed.ShardedVecEnv`) -- no copy, no packing launch."""
-        lib_, handle, index, raw_stream = self._lib, self._handle, self._device_index, _raw_stream
-        state = self.state.data_ptr()
-        current_device = torch.cuda.current_device
-        device = self.device
-
-        def launch(call):
-            if raw_stream is not None and current_device() == index:
-                status = call(raw_stream(index))
-            else:
-                with torch.cuda.device(device):
-                    status = call(self._stream())
-            lib.check(status, handle)
-
+        lib_, launch, state = self._lib, self._launch, self.state.data_ptr()
         if kind in ("pendulum", "gyropod", "servos"):
-            fn = {"pendulum": lib_.upkie_sim_step_pendulum, "gyropod": lib_.upkie_sim_step_gyropod, "servos": lib_.upkie_sim_step_servos}[kind]
-            return lambda act, obs, rew, term, trunc: launch(lambda st: fn(handle, state, act, obs, rew, term, trunc, st))
+            return partial(launch, getattr(lib_, _STEPS[kind][0]), state)
         if kind == "servos_policy":
             assert policy is not None
-            if getattr(self, "_policy_act", None) is None:
-                self._policy_act = torch.zeros((self.num_envs, 6, 6), dtype=torch.float32, device=self.device)
-            policy_act, policy_ref = self._policy_act.data_ptr(), C.byref(policy)
+            policy_act, policy_ref = self._scratch("_policy_act", (6, 6)).data_ptr(), C.byref(policy)
             fn = lib_.upkie_sim_step_servos_policy
-            return lambda act, obs, rew, term, trunc: launch(lambda st: fn(handle, state, policy_ref, policy_act, obs, rew, term, trunc, st))
+            return lambda act, obs, rew, term, trunc: launch(fn, state, policy_ref, policy_act, obs, rew, term, trunc)
         if kind == "base_velocity":
             assert mpc is not None and mpc_x0 is not None and mpc_contact is not None
             ws, commanded, x0, contact = mpc.workspace.data_ptr(), mpc.commanded_velocity.data_ptr(), mpc_x0.data_ptr(), mpc_contact.data_ptr()
             fn, mpc_handle = lib_.upkie_sim_step_base_velocity_mpc, mpc._handle
-            return lambda act, obs, rew, term, trunc: launch(lambda st: fn(handle, mpc_handle, state, ws, act, commanded, obs, x0, contact, rew, term, trunc, st))
+            return lambda act, obs, rew, term, trunc: launch(fn, mpc_handle, state, ws, act, commanded, obs, x0, contact, rew, term, trunc)
         raise ValueError(f"unknown env kind '{kind}'")
 
     def step_pendulum(self, act):
@@ -326,28 +280,18 @@ class BatchedSim:
 
     def step_servos(self, act):
         act = self._as_action(act, (self.num_envs, 6, 6))
-        if self.obs_servos is None:
-            self.obs_servos = torch.zeros(
-                (self.num_envs, 6, 5), dtype=torch.float32, device=self.device
-            )
-        return self._step(self._lib.upkie_sim_step_servos, act, self.obs_servos)
+        return self._step(self._lib.upkie_sim_step_servos, act, self._scratch("obs_servos", (6, 5)))
 
     def step_base_velocity_mpc(self, mpc, act, mpc_x0, mpc_contact):
         """UpkieBaseVelocity's whole step in one call (`upkie_sim_step_base_velocity_mpc`):
         the MPC balancer `mpc` (a `BatchedMpc`) on the previous observation, then
         the step; one launch where the lane mapping and the horizon allow it."""
         act = self._as_action(act, (self.num_envs, 2))
-        if getattr(self, "obs3", None) is None:
-            self.obs3 = torch.zeros((self.num_envs, 3), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            self._check(
-                self._lib.upkie_sim_step_base_velocity_mpc(
-                    self._handle, mpc._handle, _ptr(self.state), _ptr(mpc.workspace), _ptr(act), _ptr(mpc.commanded_velocity),
-                    _ptr(self.obs3), _ptr(mpc_x0), _ptr(mpc_contact), _ptr(self.reward), _ptr(self.terminated), _ptr(self.truncated),
-                    self._stream(),
-                )
-            )
-        return self.obs3, self.reward, self.terminated, self.truncated
+        obs3 = self._scratch("obs3", (3,))
+        self._launch(self._lib.upkie_sim_step_base_velocity_mpc, mpc._handle, ptr(self.state), ptr(mpc.workspace), ptr(act),
+                     ptr(mpc.commanded_velocity), ptr(obs3), ptr(mpc_x0), ptr(mpc_contact), ptr(self.reward), ptr(self.terminated),
+                     ptr(self.truncated))
+        return obs3, self.reward, self.terminated, self.truncated
 
     def servo_policy(self, policy: "abi.UpkieServoPolicy", act: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Write the next `step_servos` action ``[B, 6, 6]`` from the state with
@@ -355,9 +299,7 @@ class BatchedSim:
         launch, no host round trip); fallen envs are flagged for the NEXT_STEP
         autoreset."""
         if act is None:
-            if getattr(self, "_policy_act", None) is None:
-                self._policy_act = torch.zeros((self.num_envs, 6, 6), dtype=torch.float32, device=self.device)
-            act = self._policy_act
+            act = self._scratch("_policy_act", (6, 6))
         self._launch(self._lib.upkie_sim_servo_policy, self.state.data_ptr(), C.byref(policy), act.data_ptr())
         return act
 
@@ -365,13 +307,10 @@ class BatchedSim:
         """`servo_policy` + `step_servos` as one call (`upkie_sim_step_servos_policy`):
         one launch up to 8192 envs (the policy evaluated by the step's own lanes),
         two otherwise."""
-        if getattr(self, "_policy_act", None) is None:
-            self._policy_act = torch.zeros((self.num_envs, 6, 6), dtype=torch.float32, device=self.device)
-        if self.obs_servos is None:
-            self.obs_servos = torch.zeros((self.num_envs, 6, 5), dtype=torch.float32, device=self.device)
-        self._launch(self._lib.upkie_sim_step_servos_policy, self.state.data_ptr(), C.byref(policy), self._policy_act.data_ptr(),
-                     self.obs_servos.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(), self.truncated.data_ptr())
-        return self.obs_servos, self.reward, self.terminated, self.truncated
+        policy_act, obs = self._scratch("_policy_act", (6, 6)), self._scratch("obs_servos", (6, 5))
+        self._launch(self._lib.upkie_sim_step_servos_policy, self.state.data_ptr(), C.byref(policy), policy_act.data_ptr(), obs.data_ptr(),
+                     self.reward.data_ptr(), self.terminated.data_ptr(), self.truncated.data_ptr())
+        return obs, self.reward, self.terminated, self.truncated
 
     def step_base_velocity(self, act, commanded_velocity, mpc_x0, mpc_contact):
         """Second half of the fused UpkieBaseVelocity step: ``act[B, 2]`` =
@@ -379,25 +318,10 @@ class BatchedSim:
         balancer; returns the SE(2) observation ``[B, 3]`` and refreshes the
         balancer's next inputs in place."""
         act = self._as_action(act, (self.num_envs, 2))
-        if getattr(self, "obs3", None) is None:
-            self.obs3 = torch.zeros((self.num_envs, 3), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            self._check(
-                self._lib.upkie_sim_step_base_velocity(
-                    self._handle,
-                    _ptr(self.state),
-                    _ptr(act),
-                    _ptr(commanded_velocity),
-                    _ptr(self.obs3),
-                    _ptr(mpc_x0),
-                    _ptr(mpc_contact),
-                    _ptr(self.reward),
-                    _ptr(self.terminated),
-                    _ptr(self.truncated),
-                    self._stream(),
-                )
-            )
-        return self.obs3, self.reward, self.terminated, self.truncated
+        obs3 = self._scratch("obs3", (3,))
+        self._launch(self._lib.upkie_sim_step_base_velocity, ptr(self.state), ptr(act), ptr(commanded_velocity), ptr(obs3), ptr(mpc_x0),
+                     ptr(mpc_contact), ptr(self.reward), ptr(self.terminated), ptr(self.truncated))
+        return obs3, self.reward, self.terminated, self.truncated
 
     def step_pendulum_agent(self):
         """Pendulum step with the README's linear agent evaluated on-device
@@ -411,12 +335,7 @@ class BatchedSim:
         ``prev_records`` and writing this step's records to ``records``."""
         assert records.shape == (self.num_envs, 8) and prev_records.shape == (self.num_envs, 8)
         assert records.is_contiguous() and prev_records.is_contiguous()
-        with torch.cuda.device(self.device):
-            self._check(
-                self._lib.upkie_sim_step_pendulum_agent_records(
-                    self._handle, _ptr(self.state), _ptr(prev_records), _ptr(records), self._stream()
-                )
-            )
+        self._launch(self._lib.upkie_sim_step_pendulum_agent_records, ptr(self.state), ptr(prev_records), ptr(records))
         return records
 
     def step_pendulum_records_raw(self, prev_records_ptr: int, records_ptr: int) -> None:
@@ -432,12 +351,7 @@ class BatchedSim:
         state stays in registers between the steps)."""
         assert records.dim() == 3 and records.shape[1:] == (self.num_envs, 8) and prev_records.shape == (self.num_envs, 8)
         assert records.is_contiguous() and prev_records.is_contiguous()
-        with torch.cuda.device(self.device):
-            self._check(
-                self._lib.upkie_sim_step_pendulum_agent_rollout(
-                    self._handle, _ptr(self.state), _ptr(prev_records), _ptr(records), int(records.shape[0]), self._stream()
-                )
-            )
+        self._launch(self._lib.upkie_sim_step_pendulum_agent_rollout, ptr(self.state), ptr(prev_records), ptr(records), int(records.shape[0]))
         return records
 
     def step_pendulum_packed(self, records: torch.Tensor, act=None) -> torch.Tensor:
@@ -445,17 +359,11 @@ class BatchedSim:
         truncated, 0]`` record per env into ``records[B, 8]``; with
         ``act=None`` the on-device linear agent acts on the previous record."""
         assert records.shape == (self.num_envs, 8) and records.is_contiguous()
-        with torch.cuda.device(self.device):
-            if act is None:
-                status = self._lib.upkie_sim_step_pendulum_agent_packed(
-                    self._handle, _ptr(self.state), _ptr(records), self._stream()
-                )
-            else:
-                act = self._as_action(act, (self.num_envs,))
-                status = self._lib.upkie_sim_step_pendulum_packed(
-                    self._handle, _ptr(self.state), _ptr(act), _ptr(records), self._stream()
-                )
-        self._check(status)
+        if act is None:
+            self._launch(self._lib.upkie_sim_step_pendulum_agent_packed, ptr(self.state), ptr(records))
+        else:
+            act = self._as_action(act, (self.num_envs,))
+            self._launch(self._lib.upkie_sim_step_pendulum_packed, ptr(self.state), ptr(act), ptr(records))
         return records
 
     def observe(self, update_imu: bool = True) -> dict:
@@ -479,16 +387,7 @@ class BatchedSim:
         so = abi.UpkieSpineObservation()
         for name, t in out.items():
             setattr(so, name, t.data_ptr())
-        with torch.cuda.device(dev):
-            self._check(
-                self._lib.upkie_sim_observe(
-                    self._handle,
-                    _ptr(self.state),
-                    C.byref(so),
-                    1 if update_imu else 0,
-                    self._stream(),
-                )
-            )
+        self._launch(self._lib.upkie_sim_observe, ptr(self.state), C.byref(so), 1 if update_imu else 0)
         return out
 
     def use_bullet_like_contacts(self, on: bool = True) -> Optional[torch.Tensor]:
@@ -505,7 +404,7 @@ class BatchedSim:
         `set_lanes_per_env(1)`); about 2 x the default model's step: a fidelity
         option, not the fast path."""
         self.contact_manifold = torch.zeros((abi.CONTACT_MANIFOLD_WORDS, self.num_envs), dtype=torch.float32, device=self.device) if on else None
-        self._check(self._lib.upkie_sim_set_contact_manifold(self._handle, _ptr(self.contact_manifold)))
+        self._check(self._lib.upkie_sim_set_contact_manifold(self._handle, ptr(self.contact_manifold)))
         return self.contact_manifold
 
     def set_final_observation(self, final_obs: Optional[torch.Tensor]) -> None:
@@ -516,14 +415,14 @@ class BatchedSim:
         if final_obs is not None:
             assert final_obs.is_contiguous() and final_obs.dtype == torch.float32 and final_obs.device == self.device
         self.final_obs = final_obs  # (kept alive here: the library holds the raw pointer)
-        self._check(self._lib.upkie_sim_set_final_observation(self._handle, _ptr(final_obs)))
+        self._check(self._lib.upkie_sim_set_final_observation(self._handle, ptr(final_obs)))
 
     def autoreset_done(self, layout: int, obs: torch.Tensor, final_obs: Optional[torch.Tensor]) -> torch.Tensor:
         """gymnasium SAME_STEP autoreset in one launch: envs whose DONE word is
         set are re-initialised; their rows of ``obs`` (what the step of layout
         `abi.OBSERVATION_*` just wrote) go to ``final_obs`` and are replaced
         by the reset observation. Returns ``obs``."""
-        self._launch(self._lib.upkie_sim_autoreset_done, int(layout), self.state.data_ptr(), obs.data_ptr(), _ptr(final_obs))
+        self._launch(self._lib.upkie_sim_autoreset_done, int(layout), self.state.data_ptr(), obs.data_ptr(), ptr(final_obs))
         return obs
 
     def contact_points(self) -> torch.Tensor:
@@ -532,8 +431,7 @@ class BatchedSim:
         (PyBulletBackend.get_contact_points, pybullet_backend.py:660-716). A
         query, not part of the step: one extra small launch."""
         out = torch.empty((self.num_envs, 2, abi.CONTACT_POINT_WORDS), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            self._check(self._lib.upkie_sim_contact_points(self._handle, _ptr(self.state), _ptr(out), self._stream()))
+        self._launch(self._lib.upkie_sim_contact_points, ptr(self.state), ptr(out))
         return out
 
     def get_contact_points(self, link_name: Optional[str] = None, env: int = 0) -> list:
@@ -555,7 +453,7 @@ class BatchedSim:
             return None
         self.observer_state = torch.zeros((abi.OBSERVER_STATE_WORDS, self.num_envs), dtype=torch.float32, device=self.device)
         self._observer_config = config
-        self._check(self._lib.upkie_sim_attach_observers(self._handle, C.byref(config), _ptr(self.observer_state)))
+        self._check(self._lib.upkie_sim_attach_observers(self._handle, C.byref(config), ptr(self.observer_state)))
         return self.observer_state
 
     def flag_done(self, done: torch.Tensor) -> None:
@@ -599,8 +497,7 @@ class BatchedSim:
         replaced by the initial state (those envs reported `terminated`), since
         creation or the last ``reset=True``. Waits for the current stream."""
         counts = (C.c_uint32 * 2)()
-        with torch.cuda.device(self.device):
-            self._check(self._lib.upkie_sim_guard_counts(self._handle, counts, 1 if reset else 0, self._stream()))
+        self._launch(self._lib.upkie_sim_guard_counts, counts, 1 if reset else 0)
         return {"commands_replaced": int(counts[0]), "states_replaced": int(counts[1])}
 
     CENSUS_FIELDS = ("joint_limit", "sweep_cap_hits", "friction_cone", "active_set_solves", "wavefront_substeps_limit", "wavefront_substeps_sweeps", "sweeps_total", "sweeps_max")
@@ -609,7 +506,7 @@ class BatchedSim:
         """Rare-path census of the eight-lane step kernel (`upkie_sim_set_census`):
         a zeroed device buffer the kernels count into, or None when switched off."""
         self.census = torch.zeros(abi.CENSUS_WORDS, dtype=torch.int32, device=self.device) if on else None
-        self._check(self._lib.upkie_sim_set_census(self._handle, _ptr(self.census)))
+        self._check(self._lib.upkie_sim_set_census(self._handle, ptr(self.census)))
         return self.census
 
     def census_counts(self) -> dict:
