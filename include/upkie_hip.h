@@ -1340,6 +1340,101 @@ int upkie_pipeline_reset(int32_t num_envs, int32_t obs_dim, int32_t act_dim, int
                          double action_lag, const float* params, uint64_t seed, const float* obs, const uint8_t* mask,
                          float* prev_command, uint32_t* calls, float* observation, void* stream);
 
+/* ---- Reward terms (a declarative reward, per-term episode sums) ----------
+ * The reference leaves the reward to the agent (upkie_env.py:230); this is
+ * a reward of K weighted terms (1-16) over N = num_envs envs with raw
+ * observations of D = obs_dim words (1-256) and actions of A = act_dim words
+ * (1-64), evaluated in ONE launch per env step, csrc/reward_terms.hpp. State,
+ * device buffers, zero before the first step, struct-of-arrays so that every
+ * access of a wavefront is contiguous:
+ *   prev_action [A][N] float32: the action of the env's previous step
+ *   term_sum [K][N] fp64: per term the sum over the running episode
+ *   term_last [K][N] fp64: the same of the env's last finished episode
+ *   finished [N] int32: episodes the env has finished
+ * Term k has n_k taps (1-8), a shape, a weight w_k and a scale s_k. A tap is
+ * (source, index, fn, c): source one of UpkieRewardSource, index the word of
+ * the source (below D for OBS, below A for ACTION and ACTION_RATE, ignored
+ * otherwise), fn one of UpkieRewardFn, c its coefficient.
+ * upkie_reward_terms_params checks HOST arrays (the per-term arrays hold K
+ * entries, the tap arrays the taps of all terms one after another in term
+ * order; sizes and indices in range, weights, coefficients and scales finite,
+ * s_k > 0 for the shapes that read it, dt > 0 finite, clip_low <= clip_high
+ * and neither NaN; infinite: no clamp) and packs the term table into `params`
+ * (host, UPKIE_REWARD_PARAMS_BYTES bytes, may be NULL: check only), which the
+ * caller copies to the device once; it returns that byte count or a negative
+ * status. The table holds inv_dt = the float32 nearest 1 / dt (fp64 division):
+ * the rate MULTIPLIES by it.
+ *
+ * upkie_reward_terms_step, per env e, float32 with one rounding fl() per
+ * operation and no contraction unless fma() says so:
+ *   ended = terminated[e] | truncated[e] (bytes; either may be NULL: 0)
+ *   o = final_obs[e] if ended and final_obs is given, else next_obs[e]
+ *     (same-step autoreset: next_obs of an ended env is the reset observation,
+ *     final_obs the one its episode stopped in)
+ *   a = action[e] ([N][A]: what the caller applied this step)
+ *   source value: OBS o[index]; ACTION a[index]; ACTION_RATE
+ *     fl(fl(a[index] - prev_action[index][e]) * inv_dt); ONE 1; TERMINATED
+ *     1 if terminated[e] else 0 (a time limit does not set it)
+ *   x_k = 0; over the taps in order: x_k = fma(c_j, g_j(source value), x_k),
+ *     g the identity, sinf or cosf
+ *   y_k by shape: IDENTITY x; ABS |x|; SQUARE fl(x x); EXP_ABS
+ *     expf(-fl(|x| / s)); EXP_SQUARE q = fl(x / s), expf(-fl(q q)); DEADBAND
+ *     t = fl(|x| - s), 0 if t < 0 else t
+ *   v_k = fl(w_k y_k);  r = 0; over the terms in order: r = fl(r + v_k)
+ *   reward[e] = clip_low if r < clip_low, clip_high if r > clip_high, else r
+ *   term_sum[k][e] += (double)v_k   (fp64, in step order, unclamped)
+ *   ended: term_last[k][e] = term_sum[k][e]; term_sum[k][e] = 0;
+ *     finished[e] += 1; prev_action[.][e] = 0
+ *   otherwise prev_action[.][e] = a.
+ * Non-finite inputs pass through (comparisons with a NaN are false: it is
+ * neither clamped nor dead-banded away): a poisoned term_sum lasts until the
+ * env's episode ends.
+ * upkie_reward_terms_reset: term_sum and prev_action of the envs with
+ * mask[n] != 0 (all when mask is NULL) back to 0; term_last and finished are
+ * kept, as upkie_episodes_reset keeps its ring.
+ * obs_dim, act_dim and num_terms of a step must be the ones `params` was
+ * packed for: a launch on another table writes nothing. No LDS, no atomics, no
+ * block that reads what another writes, no allocation, no host
+ * synchronisation, no host argument that changes between steps: the same bits
+ * every call, and the step can be captured in a hipGraph. No CPU fallback:
+ * UPKIE_ERR_NO_DEVICE without a HIP device. Errors are reported through
+ * upkie_sim_last_error(NULL). */
+#define UPKIE_REWARD_MAX_TERMS 16
+#define UPKIE_REWARD_MAX_TAPS 8
+#define UPKIE_REWARD_PARAMS_BYTES 2336
+
+enum UpkieRewardSource {
+  UPKIE_REWARD_OBS = 0,
+  UPKIE_REWARD_ACTION = 1,
+  UPKIE_REWARD_ACTION_RATE = 2,
+  UPKIE_REWARD_ONE = 3,
+  UPKIE_REWARD_TERMINATED = 4
+};
+
+enum UpkieRewardFn { UPKIE_REWARD_FN_ID = 0, UPKIE_REWARD_FN_SIN = 1, UPKIE_REWARD_FN_COS = 2 };
+
+enum UpkieRewardShape {
+  UPKIE_REWARD_IDENTITY = 0,
+  UPKIE_REWARD_ABS = 1,
+  UPKIE_REWARD_SQUARE = 2,
+  UPKIE_REWARD_EXP_ABS = 3,
+  UPKIE_REWARD_EXP_SQUARE = 4,
+  UPKIE_REWARD_DEADBAND = 5
+};
+
+int64_t upkie_reward_terms_params(int32_t obs_dim, int32_t act_dim, int32_t num_terms, double dt, const int32_t* shapes,
+                                  const float* weights, const float* scales, const int32_t* tap_counts,
+                                  const int32_t* tap_sources, const int32_t* tap_indices, const int32_t* tap_fns,
+                                  const float* tap_coefs, double clip_low, double clip_high, void* params);
+
+int upkie_reward_terms_step(int32_t num_envs, int32_t obs_dim, int32_t act_dim, int32_t num_terms, const void* params,
+                            const float* next_obs, const float* action, const uint8_t* terminated,
+                            const uint8_t* truncated, const float* final_obs, float* prev_action, double* term_sum,
+                            double* term_last, int32_t* finished, float* reward, void* stream);
+
+int upkie_reward_terms_reset(int32_t num_envs, int32_t act_dim, int32_t num_terms, const uint8_t* mask,
+                             float* prev_action, double* term_sum, void* stream);
+
 /* ---- Rollout consumer (BASELINE.json configs[3]) ---
  * Generalized advantage estimation over a rollout resident in HBM: rewards,
  * values, episode_starts, advantages, returns are [num_steps][num_envs]

@@ -355,6 +355,17 @@ CONTACT_POINT_WORDS = 8  # UPKIE_CONTACT_POINT_WORDS
 # enum UpkieObservationLayout
 OBSERVATION_PENDULUM, OBSERVATION_PENDULUM_RECORDS, OBSERVATION_GYROPOD, OBSERVATION_SERVOS = 1, 2, 3, 4
 
+# the reward terms (upkie_reward_terms_*)
+REWARD_MAX_TERMS = 16  # UPKIE_REWARD_MAX_TERMS
+REWARD_MAX_TAPS = 8  # UPKIE_REWARD_MAX_TAPS
+REWARD_PARAMS_BYTES = 2336  # UPKIE_REWARD_PARAMS_BYTES
+# enum UpkieRewardSource
+REWARD_OBS, REWARD_ACTION, REWARD_ACTION_RATE, REWARD_ONE, REWARD_TERMINATED = 0, 1, 2, 3, 4
+# enum UpkieRewardFn
+REWARD_FN_ID, REWARD_FN_SIN, REWARD_FN_COS = 0, 1, 2
+# enum UpkieRewardShape
+REWARD_IDENTITY, REWARD_ABS, REWARD_SQUARE, REWARD_EXP_ABS, REWARD_EXP_SQUARE, REWARD_DEADBAND = 0, 1, 2, 3, 4, 5
+
 
 def default_sim_config(
     num_envs: int = 1,

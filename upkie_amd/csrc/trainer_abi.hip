@@ -1,5 +1,5 @@
 // trainer_abi.hip -- handle-free entry points of include/upkie_hip.h around a rollout: the MLP actor-critic policy, the
-// time-limit bootstrap, episode statistics, the agent pipeline, VecNormalize, the linear policy and GAE. Host code around the kernels of the
+// time-limit bootstrap, episode statistics, the agent pipeline, the reward terms, VecNormalize, the linear policy and GAE. Host code around the kernels of the
 // headers below; nothing here takes or touches a simulator, MPC or observer handle (upkie_hip.hip). The PPO update, the
 // other heavy set of kernel instantiations, is ppo_abi.hip's.
 #include <hip/hip_runtime.h>
@@ -8,6 +8,8 @@
 #include <climits>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <string>
 
 #include "mlp_instances.hpp"
 #include "rollout.hpp"
@@ -15,6 +17,7 @@
 #include "time_limits.hpp"
 #include "episodes.hpp"
 #include "agent_pipeline.hpp"
+#include "reward_terms.hpp"
 
 #include "abi_host.hpp"
 
@@ -219,6 +222,89 @@ extern "C" int upkie_pipeline_reset(int32_t num_envs, int32_t obs_dim, int32_t a
   hipLaunchKernelGGL(upkie::pipeline_observe_kernel<true>, dim3((unsigned)upkie::pipeline_blocks(num_envs, P.group)),
                      dim3(upkie::PIPELINE_THREADS), 0, (hipStream_t)stream, P, obs, mask, (const uint8_t*)nullptr, (const float*)nullptr,
                      (const float*)nullptr, prev_command, calls, observation, (float*)nullptr);
+  return launch_status();
+}
+
+// ============================================================ reward terms (a declarative reward, per-term episode sums)
+static int check_reward_sizes(int32_t obs_dim, int32_t act_dim, int32_t num_terms) {
+  if (obs_dim < 1 || obs_dim > 256 || act_dim < 1 || act_dim > 64 || num_terms < 1 || num_terms > UPKIE_REWARD_MAX_TERMS)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: obs_dim must be in 1-256, act_dim in 1-64 and num_terms in 1-16");
+  return UPKIE_OK;
+}
+
+extern "C" int64_t upkie_reward_terms_params(int32_t obs_dim, int32_t act_dim, int32_t num_terms, double dt, const int32_t* shapes,
+                                             const float* weights, const float* scales, const int32_t* tap_counts,
+                                             const int32_t* tap_sources, const int32_t* tap_indices, const int32_t* tap_fns,
+                                             const float* tap_coefs, double clip_low, double clip_high, void* params) {
+  if (check_reward_sizes(obs_dim, act_dim, num_terms)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!(dt > 0.0) || !std::isfinite(dt)) return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: dt must be positive and finite");
+  if (!shapes || !weights || !scales || !tap_counts || !tap_sources || !tap_indices || !tap_fns || !tap_coefs)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: null term or tap array");
+  if (!(clip_low <= clip_high)) return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: the clamp needs clip_low <= clip_high (and no NaN)");
+  upkie::RewardTable T{};
+  T.magic = upkie::REWARD_MAGIC, T.num_terms = num_terms, T.obs_dim = obs_dim, T.act_dim = act_dim;
+  T.inv_dt = (float)(1.0 / dt);
+  T.clip_low = (float)clip_low, T.clip_high = (float)clip_high;
+  if (!std::isfinite(T.inv_dt)) return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: 1 / dt must be a finite float32");
+  int at = 0;
+  for (int k = 0; k < num_terms; ++k) {
+    upkie::RewardTerm& term = T.terms[k];
+    term.shape = shapes[k], term.num_taps = tap_counts[k], term.weight = weights[k], term.scale = scales[k];
+    if (term.shape < UPKIE_REWARD_IDENTITY || term.shape > UPKIE_REWARD_DEADBAND)
+      return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: term " + std::to_string(k) + ": unknown shape");
+    if (term.num_taps < 1 || term.num_taps > UPKIE_REWARD_MAX_TAPS)
+      return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: term " + std::to_string(k) + ": a term has 1-8 taps");
+    if (!std::isfinite(term.weight)) return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: term " + std::to_string(k) + ": the weight must be finite");
+    const bool reads_scale = term.shape == UPKIE_REWARD_EXP_ABS || term.shape == UPKIE_REWARD_EXP_SQUARE || term.shape == UPKIE_REWARD_DEADBAND;
+    if (reads_scale && (!(term.scale > 0.f) || !std::isfinite(term.scale)))
+      return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: term " + std::to_string(k) + ": this shape needs a positive, finite scale");
+    if (!reads_scale) term.scale = 1.f;
+    for (int j = 0; j < term.num_taps; ++j, ++at) {
+      upkie::RewardTap& tap = term.taps[j];
+      tap.source = tap_sources[at], tap.index = tap_indices[at], tap.fn = tap_fns[at], tap.coef = tap_coefs[at];
+      if (tap.source < UPKIE_REWARD_OBS || tap.source > UPKIE_REWARD_TERMINATED)
+        return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: term " + std::to_string(k) + ": unknown tap source");
+      if (tap.fn < UPKIE_REWARD_FN_ID || tap.fn > UPKIE_REWARD_FN_COS)
+        return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: term " + std::to_string(k) + ": unknown tap function");
+      if (!std::isfinite(tap.coef)) return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: term " + std::to_string(k) + ": tap coefficients must be finite");
+      const int limit = tap.source == UPKIE_REWARD_OBS ? obs_dim : (tap.source == UPKIE_REWARD_ACTION || tap.source == UPKIE_REWARD_ACTION_RATE) ? act_dim : 0;
+      if (limit == 0) tap.index = 0;
+      else if (tap.index < 0 || tap.index >= limit)
+        return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: term " + std::to_string(k) + ": tap index " + std::to_string(tap.index) + " is beyond the " +
+                                                     (tap.source == UPKIE_REWARD_OBS ? "observation's " : "action's ") + std::to_string(limit) + " words");
+    }
+  }
+  if (params) std::memcpy(params, &T, sizeof(T));
+  return (int64_t)sizeof(T);
+}
+
+extern "C" int upkie_reward_terms_step(int32_t num_envs, int32_t obs_dim, int32_t act_dim, int32_t num_terms, const void* params,
+                                       const float* next_obs, const float* action, const uint8_t* terminated, const uint8_t* truncated,
+                                       const float* final_obs, float* prev_action, double* term_sum, double* term_last, int32_t* finished,
+                                       float* reward, void* stream) {
+  if (num_envs <= 0) return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: num_envs must be positive");
+  if (check_reward_sizes(obs_dim, act_dim, num_terms)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!params || !next_obs || !action || !prev_action || !term_sum || !term_last || !finished || !reward)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: null argument (only terminated, truncated and final_obs may be NULL)");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  upkie::RewardDev P{};
+  P.num_envs = num_envs, P.obs_dim = obs_dim, P.act_dim = act_dim, P.num_terms = num_terms;
+  P.row16 = obs_dim == 4 && (((uintptr_t)next_obs | (uintptr_t)final_obs) & 15u) == 0;
+  P.table = params, P.next_obs = next_obs, P.action = action, P.terminated = terminated, P.truncated = truncated, P.final_obs = final_obs;
+  P.prev_action = prev_action, P.term_sum = term_sum, P.term_last = term_last, P.finished = finished, P.reward = reward;
+  hipLaunchKernelGGL(upkie::reward_terms_step_kernel, dim3((unsigned)((num_envs + upkie::REWARD_THREADS - 1) / upkie::REWARD_THREADS)),
+                     dim3(upkie::REWARD_THREADS), 0, (hipStream_t)stream, P);
+  return launch_status();
+}
+
+extern "C" int upkie_reward_terms_reset(int32_t num_envs, int32_t act_dim, int32_t num_terms, const uint8_t* mask, float* prev_action,
+                                        double* term_sum, void* stream) {
+  if (num_envs <= 0) return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: num_envs must be positive");
+  if (check_reward_sizes(1, act_dim, num_terms)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!prev_action || !term_sum) return fail(UPKIE_ERR_INVALID_ARGUMENT, "reward: null state buffer");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  hipLaunchKernelGGL(upkie::reward_terms_reset_kernel, dim3((unsigned)((num_envs + upkie::REWARD_THREADS - 1) / upkie::REWARD_THREADS)),
+                     dim3(upkie::REWARD_THREADS), 0, (hipStream_t)stream, num_envs, act_dim, num_terms, mask, prev_action, term_sum);
   return launch_status();
 }
 

@@ -46,6 +46,7 @@ SOURCES = [
     os.path.join(_CSRC, "time_limits.hpp"),
     os.path.join(_CSRC, "episodes.hpp"),
     os.path.join(_CSRC, "agent_pipeline.hpp"),
+    os.path.join(_CSRC, "reward_terms.hpp"),
     os.path.join(_CSRC, "wave_io.hpp"),
     os.path.join(_HERE, "..", "include", "upkie_hip.h"),
 ]
@@ -155,6 +156,10 @@ def _abi_table():
         ("upkie_pipeline_shape_action", status, pipeline + [vp] * 5, "upkie_pipeline_observe"),
         ("upkie_pipeline_observe", status, pipeline + [vp] * 10, "upkie_pipeline_observe"),
         ("upkie_pipeline_reset", status, pipeline + [vp] * 6, "upkie_pipeline_observe"),
+        # the reward terms
+        ("upkie_reward_terms_params", C.c_int64, [i32, i32, i32, f64] + [vp] * 8 + [f64, f64, vp], "upkie_reward_terms_step"),
+        ("upkie_reward_terms_step", status, [i32] * 4 + [vp] * 12, "upkie_reward_terms_step"),
+        ("upkie_reward_terms_reset", status, [i32] * 3 + [vp] * 4, "upkie_reward_terms_step"),
     )
 
 

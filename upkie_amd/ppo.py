@@ -487,7 +487,8 @@ class Ppo:
     `RunningNormalizer` (``normalize``), the `EpisodeStatistics`, the `PpoTrainer` and the rollout's `GraphedLoop`, and
     runs them in the order examples/ppo_mlp_train_time_limits.py establishes. One rollout step is: store the episode
     starts; ``policy.act`` (normalised observation, action, value and log-prob straight into the buffer); ``env.step``;
-    the reward (``reward_fn(next_obs, info)``, default the env's own); ``episodes.step`` on the raw reward;
+    the reward (``reward_fn(next_obs, info)``, or ``reward``, a `upkie_amd.rewards.RewardTerms` stepped on the raw
+    observation, the applied action and ``info["final_obs"]``, one launch; default the env's own); ``episodes.step`` on the raw reward;
     ``normalizer.step`` (normalised reward and the next episode starts); the time-limit bootstrap
     (``bootstrap_time_limits``). With ``graph=True`` an iteration is two graph replays (the ``n_steps`` rollout steps,
     the update) around GAE and ``trainer.prepare``; capturing the rollout runs ONE real warm-up step first, as
@@ -500,21 +501,29 @@ class Ppo:
     the update; every ``log_interval`` iterations one `PpoTrainer.log` (one device-to-host copy) plus
     ``rollout/ep_rew_mean``, ``rollout/ep_len_mean``, ``time/total_timesteps`` and ``time/iterations`` make a record,
     appended to ``records`` and given to ``callback(model, record)`` (called every iteration, ``record`` None off the
-    interval); a callback that returns False ends training, as SB3's does. ``learning_rate``, ``clip_range`` and
+    interval; with ``reward`` it also carries ``rollout/ep_rew_<name>_mean`` of every term); a callback that returns False ends training, as SB3's does. ``learning_rate``, ``clip_range`` and
     ``clip_range_vf`` take floats or callables of ``progress_remaining``; ``target_kl`` as SB3.
 
     `save` / `load` carry everything the next iteration reads -- packed weights, Adam's moments and control block, the
-    trainer's generator, the policy's per-env noise counters, the normaliser, the episode statistics, the episode
+    trainer's generator, the policy's per-env noise counters, the normaliser, the episode statistics, the reward's state (``reward.*``, when one is given), the episode
     starts, the counters and the env (the simulation's state block, its observation and step outputs) -- so a run
-    resumed in fresh objects continues bit for bit. Schedules and ``reward_fn`` are code: give them to `load` again."""
+    resumed in fresh objects continues bit for bit. Schedules, ``reward_fn`` and ``reward`` are code: give them to `load` again."""
 
     def __init__(self, env, policy, n_steps: int = 128, gamma: float = 0.99, gae_lambda: float = 0.95, n_epochs: int = 10, batch_size: int = 64,
                  learning_rate: Schedule = 3e-4, clip_range: Schedule = 0.2, clip_range_vf: Optional[Schedule] = None,
                  normalize_advantage: bool = True, ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5,
                  target_kl: Optional[float] = None, normalize: bool = True, bootstrap_time_limits: bool = True, stats_window_size: int = 100,
-                 reward_fn: Optional[Callable] = None, graph: bool = True, seed: int = 0, process_group=None, pipeline=None):
+                 reward_fn: Optional[Callable] = None, graph: bool = True, seed: int = 0, process_group=None, pipeline=None, reward=None):
         if int(n_steps) < 1:
             raise ValueError("n_steps must be positive")
+        if reward is not None:
+            if reward_fn is not None:
+                raise ValueError("give reward (a RewardTerms) or reward_fn (a callable), not both")
+            raw = pipeline.obs_dim if pipeline is not None else int(policy.shape.obs_dim)
+            if reward.num_envs != int(env.num_envs) or reward.act_dim != int(policy.shape.act_dim) or reward.obs_dim != raw:
+                raise ValueError(f"the reward serves {reward.num_envs} envs, {reward.obs_dim} observation words and {reward.act_dim} actions, the "
+                                 f"rollout has {int(env.num_envs)}, {raw} (raw) and {int(policy.shape.act_dim)}")
+        self.reward = reward
         if pipeline is not None:
             words = int(policy.shape.obs_dim)
             if words != pipeline.stacked_dim:
@@ -596,6 +605,8 @@ class Ppo:
             self._obs = next_obs
         if self.reward_fn is not None:
             reward = self.reward_fn(next_obs, info)
+        elif self.reward is not None:
+            reward = self.reward.step(next_obs, self._env_action, terminated, truncated, final_obs=info.get("final_obs") if hasattr(info, "get") else None)
         self.episodes.step(reward, terminated, truncated)  # Monitor: the raw reward
         if self.normalizer is not None:
             self.normalizer.step(next_obs, reward, terminated, truncated, out={"reward": buf.rewards[t], "episode_starts": starts})
@@ -622,14 +633,17 @@ class Ppo:
         else:
             buf.observations[t].copy_(pipe.observation)
         pol.act(pipe.observation, out=out)
-        stepped = self.env.step(pipe.shape_action(self._env_action))
+        command = pipe.shape_action(self._env_action)
+        stepped = self.env.step(command)
         next_obs, reward, terminated, truncated = stepped[:4]
         info = stepped[4] if len(stepped) > 4 else {}
         self._obs = next_obs
+        final_obs = info.get("final_obs") if hasattr(info, "get") else None
         if self.reward_fn is not None:
             reward = self.reward_fn(next_obs, info)
+        elif self.reward is not None:  # (the RAW observation and the command the env received)
+            reward = self.reward.step(next_obs, command, terminated, truncated, final_obs=final_obs)
         self.episodes.step(reward, terminated, truncated)  # Monitor: the raw reward
-        final_obs = info.get("final_obs") if hasattr(info, "get") else None
         if self.bootstrap and final_obs is None:
             raise UpkieRuntimeError("bootstrap_time_limits needs info['final_obs'] (an env with autoreset_mode='same_step'); "
                                     "or build Ppo with bootstrap_time_limits=False")
@@ -697,6 +711,8 @@ class Ppo:
                 record = {f"train/{k}": v for k, v in self.trainer.log().items()}
                 record.update({"rollout/ep_rew_mean": self.episodes.ep_rew_mean(), "rollout/ep_len_mean": self.episodes.ep_len_mean(),
                                "time/total_timesteps": self.num_timesteps, "time/iterations": self.iterations})
+                if self.reward is not None:
+                    record.update({f"rollout/ep_rew_{name}_mean": mean for name, mean in self.reward.term_means().items()})
                 self.records.append(record)
             if callback is not None and callback(self, record) is False:
                 break
@@ -718,6 +734,8 @@ class Ppo:
         named.update({f"env.{k}": v for k, v in self._env_tensors().items()})
         if self.pipeline is not None:
             named.update({f"pipeline.{k}": v for k, v in self.pipeline.state_tensors().items()})
+        if self.reward is not None:
+            named.update({f"reward.{k}": v for k, v in self.reward.state_tensors().items()})
         return {k: v for k, v in named.items() if v is not None}
 
     def save(self, path) -> None:
