@@ -24,7 +24,8 @@ class OracleSim:
         B = self.num_envs
         self.obs4 = torch.zeros((B, 4))
         self.obs6 = torch.zeros((B, 6))
-        self.obs_servos = torch.zeros((B, 6, 5))
+        self.obs_servos = None  # (like the handle's: allocated by the first method that needs it, or by the env's reset)
+        self.obs3 = None
         self.reward = torch.zeros(B)
         self.terminated = torch.zeros(B, dtype=torch.uint8)
         self.truncated = torch.zeros(B, dtype=torch.uint8)
@@ -67,8 +68,8 @@ class OracleSim:
             raise UpkieHipError(abi.ERR_INVALID_ARGUMENT, "init_quat is not normalized")
         self._o.config = self.config
 
-    def randomize_inertias(self, variation):
-        self._o.body_inertials = self._o.sample_body_inertials(variation)
+    def randomize_inertias(self, inertia_variation):
+        self._o.body_inertials = self._o.sample_body_inertials(inertia_variation)
         self.body_inertials = torch.from_numpy(self._o.body_inertials.astype(np.float32))
         self.link_scale = torch.from_numpy(self._o.link_scale.astype(np.float32))
         return self.body_inertials
@@ -106,10 +107,22 @@ class OracleSim:
         self.obs6.copy_(torch.from_numpy(self._o.reset(m).astype(np.float32)))  # (the same buffer every time, like the handle's)
         return self.obs6
 
+    @property
+    def lanes_per_env(self):
+        return 1
+
+    def _scratch(self, name, shape):
+        """`BatchedSim._scratch`: the buffer ``self.<name>``, allocated by the first method that needs it."""
+        buf = getattr(self, name)
+        if buf is None:
+            buf = torch.zeros((self.num_envs,) + tuple(shape))
+            setattr(self, name, buf)
+        return buf
+
     def _out(self, obs, rew, term, trunc, holder):
         obs = torch.from_numpy(np.asarray(obs, dtype=np.float32))
-        getattr(self, holder).copy_(obs)
-        # (persistent buffers, rewritten in place, like the handle's: `UpkieVecEnv._fast_step` returns them as one cached tuple)
+        self._scratch(holder, obs.shape[1:]).copy_(obs)
+        # (persistent buffers, rewritten in place, like the handle's: `UpkieVecEnv._step_output` returns them as one cached tuple)
         self.reward.copy_(torch.from_numpy(rew.astype(np.float32)))
         self.terminated.copy_(torch.from_numpy(term))
         self.truncated.copy_(torch.from_numpy(trunc))
@@ -137,6 +150,53 @@ class OracleSim:
 
     def step_pendulum_agent(self):
         return self._out(*self._o.step_pendulum_agent(self.obs4.double().numpy()), "obs4")
+
+    def step_servos_policy(self, policy):
+        """`BatchedSim.step_servos_policy`: the servo-level law on the state the step starts from, then the Servos step."""
+        o = self._o
+        action, fallen = servo_policy_action(policy, o.state, float(self.model.left_sign) * float(self.model.wheel_radius))
+        o.state[abi.S_DONE] = np.where(fallen, 1.0, o.state[abi.S_DONE])
+        if self.ext_force is not None:
+            o.ext_force = np.ascontiguousarray(self.ext_force.double().numpy())
+        return self._out(*o.step_servos(action.astype(np.float32).astype(np.float64)), "obs_servos")
+
+    def step_base_velocity(self, act, commanded_velocity, mpc_x0, mpc_contact):
+        """`BatchedSim.step_base_velocity` (upkie_sim_step_base_velocity; UpkieBaseVelocity.step, upkie_base_velocity.py:
+        164-202, behind the balancer): the Gyropod step with `commanded_velocity` as ground velocity; the dead-reckoned
+        pose lives in the state words S_SE2_X / S_SE2_Y, zeroed for an env this step re-initialises, integrated with
+        the TARGET linear velocity and the new yaw otherwise (:197-199); the balancer's next inputs refreshed in place."""
+        o, B = self._o, self.num_envs
+        a = torch.as_tensor(act).double().numpy().reshape(B, 2)
+        reinitialised = (o.state[abi.S_DONE] != 0) if self.config.autoreset_mode else np.zeros(B, dtype=bool)
+        obs6, rew, term, trunc = o.step_gyropod(np.stack([commanded_velocity.double().numpy(), a[:, 1]], axis=1))
+        mpc_x0.copy_(torch.from_numpy(obs6[:, [0, 1, 3, 4]].astype(np.float32)))
+        mpc_contact.copy_(torch.from_numpy((o.state[abi.S_CONTACT] != 0).astype(np.uint8)))
+        yaw, dt = obs6[:, 2], float(self.config.dt)
+        x = np.where(reinitialised, 0.0, o.state[abi.S_SE2_X] + a[:, 0] * np.cos(yaw) * dt)
+        y = np.where(reinitialised, 0.0, o.state[abi.S_SE2_Y] + a[:, 0] * np.sin(yaw) * dt)
+        o.state[abi.S_SE2_X], o.state[abi.S_SE2_Y] = x, y
+        return self._out(np.stack([x, y, yaw], axis=1), rew, term, trunc, "obs3")
+
+    def step_base_velocity_mpc(self, mpc, act, mpc_x0, mpc_contact):
+        """`BatchedSim.step_base_velocity_mpc`: `mpc.step_env` then `step_base_velocity`, as include/upkie_hip.h states it."""
+        done = self.state[abi.S_DONE] if self.config.autoreset_mode else None
+        commanded = mpc.step_env(mpc_x0, torch.as_tensor(act).reshape(self.num_envs, 2), mpc_contact, done, float(self.config.dt))
+        return self.step_base_velocity(act, commanded, mpc_x0, mpc_contact)
+
+    def step_pendulum_records_raw(self, prev_records_ptr, records_ptr):
+        """`step_pendulum_records` on the addresses of two ``[B, 8]`` fp32 record buffers (CPU tensors have addresses too)."""
+        B = self.num_envs
+        prev, records = (torch.from_numpy(_from_address(p, B * 8, C.c_float, np.float32).reshape(B, 8)) for p in (prev_records_ptr, records_ptr))
+        self.step_pendulum_records(prev, records)
+
+    def step_pendulum_packed(self, records, act=None):
+        """`BatchedSim.step_pendulum_packed`: one packed record per env; ``act=None``: the linear agent on the previous record."""
+        if act is None:
+            return self.step_pendulum_records(records, records)
+        obs, rew, term, trunc = self._o.step_pendulum(torch.as_tensor(act).double().numpy().reshape(-1))
+        columns = [np.asarray(obs, dtype=np.float32), rew[:, None], term[:, None], trunc[:, None], np.zeros((self.num_envs, 1))]
+        records.copy_(torch.from_numpy(np.concatenate(columns, axis=1).astype(np.float32)))
+        return records
 
     def step_pendulum_records(self, prev_records, records):
         """The on-device linear agent acting on the observation held in the
@@ -220,7 +280,6 @@ def _step_into_fn(self, kind, policy=None, mpc=None, mpc_x0=None, mpc_contact=No
     B = self.num_envs
     obs_words = {"pendulum": 4, "gyropod": 6, "servos": 30, "servos_policy": 30, "base_velocity": 3}[kind]
     act_words = {"pendulum": 1, "gyropod": 2, "servos": 36, "servos_policy": 0, "base_velocity": 2}[kind]
-    xy = np.zeros((B, 2))
 
     def step(act, obs, rew, term, trunc):
         o = self._o
@@ -232,26 +291,9 @@ def _step_into_fn(self, kind, policy=None, mpc=None, mpc_x0=None, mpc_contact=No
         elif kind == "servos":
             out = o.step_servos(a.reshape(B, 6, 6))
         elif kind == "servos_policy":
-            action, fallen = servo_policy_action(policy, o.state, float(self.model.left_sign) * float(self.model.wheel_radius))
-            o.state[abi.S_DONE] = np.where(fallen, 1.0, o.state[abi.S_DONE])
-            if self.ext_force is not None:
-                o.ext_force = np.ascontiguousarray(self.ext_force.double().numpy())
-            out = o.step_servos(action.astype(np.float32).astype(np.float64))
-        else:  # UpkieBaseVelocity.step, upkie_base_velocity.py:164-202 (the generic composition of UpkieBaseVelocityVecEnv)
-            a = a.reshape(B, 2)
-            autoreset = (o.state[abi.S_DONE] != 0) if self.config.autoreset_mode else np.zeros(B, dtype=bool)
-            v, _ = mpc.step(mpc_x0, torch.from_numpy(a[:, 0].copy()), mpc_contact, float(self.config.dt))
-            obs6, r, t, tr = o.step_gyropod(np.stack([v.double().numpy(), a[:, 1]], axis=1))
-            mpc_x0.copy_(torch.from_numpy(obs6[:, [0, 1, 3, 4]].astype(np.float32)))
-            mpc_contact.copy_(torch.from_numpy((o.state[abi.S_CONTACT] != 0).astype(np.uint8)))
-            if autoreset.any():
-                mpc.reset(torch.from_numpy(autoreset.astype(np.uint8)))
-                xy[autoreset] = 0.0
-            live = ~autoreset
-            dt = float(self.config.dt)
-            xy[live, 0] += (a[:, 0] * np.cos(obs6[:, 2]) * dt)[live]
-            xy[live, 1] += (a[:, 0] * np.sin(obs6[:, 2]) * dt)[live]
-            out = (np.concatenate([xy, obs6[:, 2:3]], axis=1), r, t, tr)
+            out = [t.numpy() for t in self.step_servos_policy(policy)]
+        else:
+            out = [t.numpy() for t in self.step_base_velocity_mpc(mpc, torch.from_numpy(a.reshape(B, 2)), mpc_x0, mpc_contact)]
         o_, r_, t_, tr_ = out
         _from_address(obs, B * obs_words, C.c_float, np.float32)[:] = np.asarray(o_, dtype=np.float32).reshape(-1)
         _from_address(rew, B, C.c_float, np.float32)[:] = r_.astype(np.float32)
@@ -266,6 +308,8 @@ OracleSim.step_into_fn = _step_into_fn
 
 def _stepper(self, kind):
     """`BatchedSim.stepper` on the oracle: ``step(action_address)`` writing the double's persistent output buffers."""
+    if kind == "pendulum_agent":  # (no action buffer: the linear agent acts on the observation held in `obs4`)
+        return self.step_pendulum_agent
     B = self.num_envs
     words = {"pendulum": 1, "gyropod": 2, "servos": 36}[kind]
     call = {"pendulum": self.step_pendulum, "gyropod": self.step_gyropod, "servos": self.step_servos}[kind]
@@ -308,6 +352,15 @@ class OracleMpc:
         ct = np.ascontiguousarray(contact.to(torch.uint8).numpy())
         O.lib().oracle_mpc_step(C.byref(self.config), p(self._ws), p(x), p(vt), p(ct), C.c_double(dt), p(self._v), p(self._first))
         return torch.from_numpy(self._v.astype(np.float32)), torch.from_numpy(self._first.astype(np.float32))
+
+    def step_env(self, x0, act, contact, done, dt):
+        """`BatchedMpc.step_env` (upkie_mpc_step_env, include/upkie_hip.h): the target velocity of env e is ``act[e, 0]``;
+        an env whose `done` word is set gets `reset` INSTEAD of a solve (the env step that follows re-initialises it).
+        Envs are independent, so solving all of them and resetting the flagged ones afterwards leaves the same state."""
+        self.step(x0, act[:, 0].contiguous(), contact, dt)
+        if done is not None:
+            self.reset(done != 0)
+        return self.commanded_velocity
 
     def close(self):
         pass

@@ -86,13 +86,13 @@ def test_base_velocity_env_gpu_matches_cpu_double():
 
 
 def test_base_velocity_fused_path_with_autoreset():
-    """Fused MPC + Gyropod launches (the GPU path) vs the generic composition
-    on the CPU doubles, with falls and NEXT_STEP autoresets in the loop."""
+    """Balancer and step in one call (the GPU path at this batch) vs the two
+    calls on the CPU doubles, with falls and NEXT_STEP autoresets in the loop."""
     kw = dict(num_envs=48, frequency=200.0, nb_timesteps=16, fall_pitch=0.12, seed=3,
               init_state=RobotState(randomization=RobotStateRandomization(pitch=0.1)))
     gpu = envs.make("Upkie-HIP-BaseVelocity-Vec", **kw)
     cpu = envs.make("Upkie-HIP-BaseVelocity-Vec", sim_factory=oracle_sim_factory, mpc_factory=OracleMpc, **kw)
-    assert hasattr(gpu.sim, "step_base_velocity") and not hasattr(cpu.sim, "step_base_velocity")
+    assert gpu.fuse_mpc and not cpu.fuse_mpc
     gpu.reset()
     cpu.reset()
     act = torch.zeros(48, 2)

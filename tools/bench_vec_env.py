@@ -4,7 +4,10 @@ the device; the same recorded into a hipGraph (`GraphedEnvStep`, 1 / 4 / 16
 steps per graph launch).
 With --policy one_launch the same policy is ONE kernel (`upkie_amd.policies.LinearPolicy`), with --policy in_launch it is
 evaluated inside the step's launch (`env.step_linear_policy`, NEXT_STEP only).
-Usage: python tools/bench_vec_env.py [B] [steps] [modes, e.g. next_step,same_step] [--no-graph] [--limit] [--policy torch|one_launch|in_launch]"""
+With --kind gyropod | servos the loop steps that env kind (torch policy: the same gains on the Gyropod observation; the
+neutral action for Servos).
+Usage: python tools/bench_vec_env.py [B] [steps] [modes, e.g. next_step,same_step] [--no-graph] [--limit] [--policy torch|one_launch|in_launch]
+       [--kind pendulum|gyropod|servos]"""
 import os
 import sys
 import time
@@ -22,6 +25,11 @@ policy_kind = "torch"
 if "--policy" in sys.argv:
     i = sys.argv.index("--policy")
     policy_kind = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
+kind = "pendulum"
+if "--kind" in sys.argv:
+    i = sys.argv.index("--kind")
+    kind = sys.argv[i + 1]
     del sys.argv[i:i + 2]
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 B = int(args[0]) if len(args) > 0 else 4096
@@ -41,11 +49,17 @@ def timed(fn, n):
 
 for mode in modes:
     for limit in limits:
-        env = envs.make("Upkie-HIP-Pendulum-Vec", num_envs=B, frequency=200.0, autoreset_mode=mode, max_episode_steps=limit,
+        env = envs.make(f"Upkie-HIP-{kind.capitalize()}-Vec", num_envs=B, frequency=200.0, autoreset_mode=mode, max_episode_steps=limit,
                         init_state=RobotState(randomization=RobotStateRandomization(pitch=0.1, x=0.05, omega_y=0.1)))
         obs, _ = env.reset(seed=0)
         gain = torch.tensor([10.0, 1.0, 0.0, 0.1], device=env.device)
         policy = lambda o: (o @ gain).clamp(-0.99, 0.99).unsqueeze(1)
+        if kind == "gyropod":
+            gain6 = torch.tensor([[1.0, 0.0], [10.0, 0.0], [0.0, 0.0], [0.1, 0.0], [0.0, 0.0], [0.0, 0.0]], device=env.device)
+            policy = lambda o: (o @ gain6).clamp(-0.99, 0.99)
+        elif kind == "servos":
+            neutral = env.get_neutral_action()
+            policy = lambda o: neutral
         if policy_kind == "one_launch":
             from upkie_amd.policies import LinearPolicy
 
@@ -61,7 +75,7 @@ for mode in modes:
 
         timed(eager, 200)
         us = timed(eager, steps)
-        print(f"B={B} autoreset={mode} max_episode_steps={limit} policy={policy_kind}: {us:.2f} us per env.step() from Python, {B / us * 1e6:.3e} env-steps/s")
+        print(f"{kind} B={B} autoreset={mode} max_episode_steps={limit} policy={policy_kind}: {us:.2f} us per env.step() from Python, {B / us * 1e6:.3e} env-steps/s")
         # where the loop's time goes: the policy's kernels alone (same ops, result dropped), and the host side alone
         us_policy = timed(lambda: policy(state["obs"]), steps)
         t0 = time.perf_counter()

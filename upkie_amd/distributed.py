@@ -225,72 +225,9 @@ class RolloutGather:
         return self.records(self._step - 1 - steps_back)
 
 
-class ShardedPendulum:
-    """This rank's shard of a batch of Upkie-Pendulum envs plus the pipelined
-    gather of per-step records into rank 0's rollout buffer."""
-
-    def __init__(self, config, device: str, rank: int = 0, world_size: int = 1, model=None, horizon: int = 128, chunk: int = 8, sim_factory=None,
-                 collectives: Optional[bool] = None):
-        from .sim import BatchedSim
-
-        self.rank, self.world_size = rank, world_size
-        # (sim_factory: test doubles only; the product always builds a BatchedSim)
-        self.sim = sim_factory(config, model, device) if sim_factory is not None else BatchedSim(config, model, device=device)
-        self.gather = RolloutGather(self.sim.num_envs, rank, world_size, self.sim.device, horizon=horizon, chunk=chunk, collectives=collectives)
-        self._collectives = self.gather.collectives
-        self._device = self.sim.device
-
-    def reset(self) -> None:
-        obs6 = self.sim.reset()
-        self.gather.flush()
-        if self.gather.staging is not None:
-            self.gather.staging.zero_()
-        self.gather.previous.zero_()
-        # the agent's first input: the reset observation, upkie_pendulum.py:17
-        self.gather.previous[:, :4] = obs6[:, [1, 0, 4, 3]]
-
-    @property
-    def lanes_per_env(self) -> int:
-        return int(getattr(self.sim, "lanes_per_env", 1))
-
-    @property
-    def fused_rollouts(self) -> bool:
-        """True when `rollout_agent(n)` is ONE launch (the multi-lane mappings of small and medium batches)."""
-        return self.lanes_per_env > 1
-
-    @property
-    def kernel_name(self) -> str:
-        lanes = self.lanes_per_env
-        return {1: "step_kernel<MODE_PENDULUM_AGENT> (one env per lane)", 2: "step_kernel_pair<MODE_PENDULUM_AGENT / _ROLLOUT> (two lanes per env)",
-                8: "step_kernel_octet<MODE_PENDULUM_AGENT / _ROLLOUT> (eight lanes per env: one quad per leg, one lane per body)"}.get(
-            lanes, f"step kernel, {lanes} lanes per env")
-
-    def step_agent(self) -> None:
-        """One env.step() of every local env with the on-device linear agent;
-        the records of this step travel to rank 0 while the next step runs."""
-        g = self.gather
-        raw = getattr(self.sim, "step_pendulum_records_raw", None)
-        if raw is None:  # (test doubles)
-            out = g.begin_step()
-            self.sim.step_pendulum_records(g.previous, out)
-        else:
-            g.begin_step()
-            raw(*g.slot_pointers())
-        g.end_step()
-
-    def rollout_agent(self, n: int) -> None:
-        """`n` env.step() with the on-device agent in one launch (two lanes per
-        env; `n` launches beyond 32768 envs): same records as `n` calls of
-        `step_agent`. The steps must stay inside one gather chunk."""
-        prev = self.gather.previous
-        out = self.gather.begin_steps(n)
-        self.sim.rollout_pendulum_records(prev, out)
-        self.gather.end_steps(n)
-
-    def step(self, act: torch.Tensor) -> None:
-        out = self.gather.begin_step()
-        self.sim.step_pendulum_packed(out, act)
-        self.gather.end_step()
+class _Sharded:
+    """What the two sharded classes share: the subclass sets `sim` (the handle), `gather` (its `RolloutGather`),
+    `_collectives` and `_device`; here are the calls every rank of the group makes together."""
 
     def flush(self) -> None:
         self.gather.flush()
@@ -315,12 +252,78 @@ class ShardedPendulum:
             dist.all_reduce(n, op=dist.ReduceOp.SUM)
         return int(n.item())
 
+    @property
+    def lanes_per_env(self) -> int:
+        return self.sim.lanes_per_env
+
+    def _leave_group(self, destroy_group: bool) -> None:
+        if destroy_group and self._collectives and dist.is_initialized():
+            dist.destroy_process_group()
+
+
+class ShardedPendulum(_Sharded):
+    """This rank's shard of a batch of Upkie-Pendulum envs plus the pipelined
+    gather of per-step records into rank 0's rollout buffer."""
+
+    def __init__(self, config, device: str, rank: int = 0, world_size: int = 1, model=None, horizon: int = 128, chunk: int = 8, sim_factory=None,
+                 collectives: Optional[bool] = None):
+        from .sim import BatchedSim
+
+        self.rank, self.world_size = rank, world_size
+        # (sim_factory: the seam for a CPU double of the handle, `upkie_amd.sim.HANDLE_METHODS`; the product always builds a BatchedSim)
+        self.sim = sim_factory(config, model, device) if sim_factory is not None else BatchedSim(config, model, device=device)
+        self.gather = RolloutGather(self.sim.num_envs, rank, world_size, self.sim.device, horizon=horizon, chunk=chunk, collectives=collectives)
+        self._collectives = self.gather.collectives
+        self._device = self.sim.device
+
+    def reset(self) -> None:
+        obs6 = self.sim.reset()
+        self.gather.flush()
+        if self.gather.staging is not None:
+            self.gather.staging.zero_()
+        self.gather.previous.zero_()
+        # the agent's first input: the reset observation, upkie_pendulum.py:17
+        self.gather.previous[:, :4] = obs6[:, [1, 0, 4, 3]]
+
+    @property
+    def fused_rollouts(self) -> bool:
+        """True when `rollout_agent(n)` is ONE launch (the multi-lane mappings of small and medium batches)."""
+        return self.lanes_per_env > 1
+
+    @property
+    def kernel_name(self) -> str:
+        lanes = self.lanes_per_env
+        return {1: "step_kernel<MODE_PENDULUM_AGENT> (one env per lane)", 2: "step_kernel_pair<MODE_PENDULUM_AGENT / _ROLLOUT> (two lanes per env)",
+                8: "step_kernel_octet<MODE_PENDULUM_AGENT / _ROLLOUT> (eight lanes per env: one quad per leg, one lane per body)"}.get(
+            lanes, f"step kernel, {lanes} lanes per env")
+
+    def step_agent(self) -> None:
+        """One env.step() of every local env with the on-device linear agent;
+        the records of this step travel to rank 0 while the next step runs."""
+        g = self.gather
+        g.begin_step()
+        self.sim.step_pendulum_records_raw(*g.slot_pointers())
+        g.end_step()
+
+    def rollout_agent(self, n: int) -> None:
+        """`n` env.step() with the on-device agent in one launch (two lanes per
+        env; `n` launches beyond 32768 envs): same records as `n` calls of
+        `step_agent`. The steps must stay inside one gather chunk."""
+        prev = self.gather.previous
+        out = self.gather.begin_steps(n)
+        self.sim.rollout_pendulum_records(prev, out)
+        self.gather.end_steps(n)
+
+    def step(self, act: torch.Tensor) -> None:
+        out = self.gather.begin_step()
+        self.sim.step_pendulum_packed(out, act)
+        self.gather.end_step()
+
     def shutdown(self, destroy_group: bool = True) -> None:
         """Close the handle; leave the process group (`destroy_group=False`: another sharded env of this process follows)."""
         self.gather.flush()
         self.sim.close()
-        if destroy_group and self._collectives and dist.is_initialized():
-            dist.destroy_process_group()
+        self._leave_group(destroy_group)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -379,7 +382,7 @@ class StepBlob:
         return base + self.obs_offset, base + self.reward_offset, base + self.terminated_offset, base + self.truncated_offset
 
 
-class ShardedVecEnv:
+class ShardedVecEnv(_Sharded):
     """This rank's shard of a batch of envs of ANY kind ("pendulum" |
     "gyropod" | "servos" | "base_velocity") with the same pipelined gather of
     per-step outputs into rank 0's rollout ring as `ShardedPendulum`, and the
@@ -416,7 +419,7 @@ class ShardedVecEnv:
         self.obs_shape, self.act_shape = ENV_KINDS[kind]
         # `sim`: an existing handle (e.g. the `.sim` of a vector env built with this rank's `env_id_offset`, its
         # inertia randomisation and joint properties already applied) instead of a new one from `config`
-        # (sim_factory / mpc_factory: test doubles only; the product always builds a BatchedSim / BatchedMpc)
+        # (sim_factory / mpc_factory: the seam for CPU doubles; the product always builds a BatchedSim / BatchedMpc)
         self._owns_sim = sim is None  # (a caller's handle stays the caller's to close: `shutdown` leaves it open)
         self._stale_primed, self._stale_scatter = False, None  # `step_from_root(policy, stale=1)`
         if sim is not None:
@@ -469,9 +472,7 @@ class ShardedVecEnv:
         """Reset every local env; returns this rank's first observation ``[B, *obs_shape]``."""
         from . import abi
 
-        if self._stale_scatter is not None and self._stale_scatter[0] is not None:
-            self._stale_scatter[0].wait()  # (a lagged exchange still in flight: its actions die with the episode)
-        self._stale_primed, self._stale_scatter = False, None
+        self._drop_stale_exchange()  # (a lagged exchange still in flight: its actions die with the episode)
         obs6 = self.sim.reset()
         self.gather.flush()
         if self.kind == "pendulum":
@@ -514,34 +515,55 @@ class ShardedVecEnv:
         return views
 
     # -------------------------------------------------- a policy on rank 0
+    # Each collective has an issue half (asynchronous: returns at once) and a collect half (the wait, on the stream with
+    # RCCL: the host does not block); `slot` names the half of both double buffers an exchange uses.
+    def _issue_gather(self, slot: int):
+        obs = self.last[0]
+        if not self._collectives:
+            return None, obs
+        out = list(self._root_obs[slot].unbind(0)) if self.rank == 0 else None
+        return dist.gather(obs.contiguous(), out, dst=0, async_op=True), obs
+
+    def _collect_gather(self, issued, slot: int) -> Optional[torch.Tensor]:
+        work, obs = issued
+        if work is None:
+            return obs.reshape((self.num_envs,) + self.obs_shape)
+        work.wait()
+        return self._root_obs[slot].reshape((self.world_size * self.num_envs,) + self.obs_shape) if self.rank == 0 else None
+
+    def _issue_scatter(self, actions: Optional[torch.Tensor], slot: int):
+        mine = self.actions[slot]
+        if not self._collectives:
+            mine.copy_(actions.reshape(mine.shape))
+            return None
+        chunks = None
+        if self.rank == 0:
+            chunks = list(actions.to(torch.float32).reshape((self.world_size, self.num_envs) + self.act_shape).contiguous().unbind(0))
+        return dist.scatter(mine, chunks, src=0, async_op=True)
+
+    @staticmethod
+    def _collect_scatter(work) -> None:
+        if work is not None:
+            work.wait()
+
+    def _drop_stale_exchange(self) -> None:
+        """Finish and forget the exchange a `step_from_root(policy, stale=1)` call left in flight."""
+        if self._stale_scatter is not None:
+            self._collect_scatter(self._stale_scatter[0])
+        self._stale_primed, self._stale_scatter = False, None
+
     def gather_observations(self) -> Optional[torch.Tensor]:
         """Collective: the latest observation of every rank to rank 0,
         ``[world * B, *obs_shape]`` there (a persistent double buffer), None elsewhere."""
-        obs = self.last[0]
-        if not self._collectives:
-            return obs.reshape((self.num_envs,) + self.obs_shape)
         slot = self._action_slot
-        out = None
-        if self.rank == 0:
-            out = list(self._root_obs[slot].unbind(0))
-        work = dist.gather(obs.contiguous(), out, dst=0, async_op=True)
-        work.wait()  # (RCCL: a stream dependency, the host does not block)
-        return self._root_obs[slot].reshape((self.world_size * self.num_envs,) + self.obs_shape) if self.rank == 0 else None
+        return self._collect_gather(self._issue_gather(slot), slot)
 
     def scatter_actions(self, actions: Optional[torch.Tensor]) -> torch.Tensor:
         """Collective: rank 0 hands over the actions of ALL envs ``[world * B, *act_shape]``
         (None elsewhere); every rank receives its block into the action buffer the next `step()` reads."""
         self._action_slot ^= 1
-        mine = self.actions[self._action_slot]
-        if not self._collectives:
-            mine.copy_(actions.reshape(mine.shape))
-            return mine
-        chunks = None
-        if self.rank == 0:
-            chunks = list(actions.to(torch.float32).reshape((self.world_size, self.num_envs) + self.act_shape).contiguous().unbind(0))
-        work = dist.scatter(mine, chunks, src=0, async_op=True)
-        work.wait()
-        return mine
+        self._collect_scatter(self._issue_scatter(actions, self._action_slot))
+        return self.actions[self._action_slot]
 
     def step_from_root(self, policy, stale: int = 0):
         """``obs -> policy (rank 0) -> actions -> step`` with the policy on rank 0
@@ -559,55 +581,28 @@ class ShardedVecEnv:
         k + 2 waits for. What is left between two steps is the policy and one
         scatter; an on-policy learner must know that its actions are one step
         late (asynchronous / "lagged" actors accept exactly this)."""
-        if not stale:
-            if self._stale_scatter is not None:  # (a lagged exchange left in flight by an earlier stale=1 call: finished and dropped)
-                if self._stale_scatter[0] is not None:
-                    self._stale_scatter[0].wait()
-                self._stale_primed, self._stale_scatter = False, None
-            obs_all = self.gather_observations()
-            self.scatter_actions(policy(obs_all) if self.rank == 0 else None)
-            return self.step(None)
-        if stale != 1:
+        if stale and stale != 1:
             raise ValueError("stale must be 0 or 1")
-        if not self._stale_primed:
-            # the first step: nothing older than the reset observation exists; its actions also serve the second step
+        if not stale or not self._stale_primed:
+            # stale=1, first step: nothing older than the reset observation exists; its actions also serve the second step
+            if self._stale_scatter is not None:  # (stale=0 behind stale=1 calls: the lagged exchange left in flight is finished and dropped)
+                self._drop_stale_exchange()
             obs_all = self.gather_observations()
             self.scatter_actions(policy(obs_all) if self.rank == 0 else None)
-            self._stale_primed = True
-            self._stale_scatter = None
+            self._stale_primed = self._stale_primed or bool(stale)
             return self.step(None)
         # the scatter issued behind the previous step delivers this step's actions, policy(o_{k-1})
         if self._stale_scatter is not None:
-            work, ready_slot = self._stale_scatter
-            if work is not None:
-                work.wait()
-            self._action_slot = ready_slot
+            work, self._action_slot = self._stale_scatter
+            self._collect_scatter(work)
             self._stale_scatter = None
         # gather of the latest observation o_k: issued now, collected behind the step
-        obs = self.last[0]
         slot = self._action_slot ^ 1  # (the exchange in flight uses the OTHER half of both double buffers: this step reads `_action_slot`'s)
-        gather_work = None
-        if self._collectives:
-            out = list(self._root_obs[slot].unbind(0)) if self.rank == 0 else None
-            gather_work = dist.gather(obs.contiguous(), out, dst=0, async_op=True)
+        issued = self._issue_gather(slot)
         views = self.step(None)
         # rank 0: policy on o_k (which the gather has delivered meanwhile), scatter for the step after the next call's
-        if gather_work is not None:
-            gather_work.wait()
-        obs_all = None
-        if self.rank == 0:
-            obs_all = (self._root_obs[slot].reshape((self.world_size * self.num_envs,) + self.obs_shape) if self._collectives
-                       else obs.reshape((self.num_envs,) + self.obs_shape))
-        actions = policy(obs_all) if self.rank == 0 else None
-        mine = self.actions[slot]
-        if not self._collectives:
-            mine.copy_(actions.reshape(mine.shape))
-            self._stale_scatter = (None, slot)
-        else:
-            chunks = None
-            if self.rank == 0:
-                chunks = list(actions.to(torch.float32).reshape((self.world_size, self.num_envs) + self.act_shape).contiguous().unbind(0))
-            self._stale_scatter = (dist.scatter(mine, chunks, src=0, async_op=True), slot)
+        obs_all = self._collect_gather(issued, slot)
+        self._stale_scatter = (self._issue_scatter(policy(obs_all) if self.rank == 0 else None, slot), slot)
         return views
 
     # ------------------------------------------------------------ rank 0 reads
@@ -619,40 +614,13 @@ class ShardedVecEnv:
             return None
         return self.blob.views(blob[:, 0])
 
-    def flush(self) -> None:
-        self.gather.flush()
-
-    def barrier(self) -> None:
-        if self._collectives:
-            dist.barrier()
-
-    def max_over_ranks(self, value: float) -> float:
-        if not self._collectives:
-            return value
-        t = torch.tensor([value], dtype=torch.float64, device=self._device)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        return float(t.item())
-
-    def total_resets(self) -> int:
-        from . import abi
-
-        n = self.sim.state[abi.S_EPISODE].sum().to(torch.float64).reshape(1)
-        if self._collectives:
-            dist.all_reduce(n, op=dist.ReduceOp.SUM)
-        return int(n.item())
-
-    @property
-    def lanes_per_env(self) -> int:
-        return int(getattr(self.sim, "lanes_per_env", 1))
-
     def shutdown(self, destroy_group: bool = True) -> None:
         self.gather.flush()
         if self.mpc is not None:
             self.mpc.close()
         if self._owns_sim:
             self.sim.close()
-        if destroy_group and self._collectives and dist.is_initialized():
-            dist.destroy_process_group()
+        self._leave_group(destroy_group)
 
 
 class SlotExchange:

@@ -246,10 +246,16 @@ class UpkieVecEnv:
         """The persistent device buffer `reset()` and `step()` return as `obs`
         (rewritten in place by every step): what a graph-captured policy reads
         (`upkie_amd.graphs.GraphedEnvStep`)."""
-        sim = self.sim
-        if self._stepper_kind == "servos" and sim.obs_servos is None:
-            sim.obs_servos = torch.zeros((self.num_envs, 6, 5), dtype=torch.float32, device=self.device)
-        return {"pendulum": sim.obs4, "gyropod": sim.obs6, "servos": sim.obs_servos}.get(self._stepper_kind, getattr(sim, "obs3", None))
+        sim, kind = self.sim, self._stepper_kind
+        if kind == "pendulum":
+            return sim.obs4
+        if kind == "gyropod":
+            return sim.obs6
+        if kind == "servos":
+            if sim.obs_servos is None:  # (the handle allocates it lazily: here, so that it holds the reset observation from the start)
+                sim.obs_servos = torch.zeros((self.num_envs, 6, 5), dtype=torch.float32, device=self.device)
+            return sim.obs_servos
+        return sim.obs3  # (BaseVelocity: None until its first step)
 
     def close(self) -> None:
         if self._observers is not None:
@@ -260,7 +266,7 @@ class UpkieVecEnv:
     def _disarm_same_step(self) -> None:
         """Switch the in-step SAME_STEP autoreset off again (it is armed on `sim`, which other wrappers -- `HipSpine`,
         a `Backend` around the same handle, direct `sim.step_*` calls -- may keep using after this env)."""
-        if self._final_obs is not None and hasattr(self.sim, "set_final_observation"):
+        if self._final_obs is not None:
             self.sim.set_final_observation(None)
         self._final_obs = None
         self._step_out = None
@@ -285,41 +291,46 @@ class UpkieVecEnv:
             self._spine.materialize()
         return {"spine_observation": self._spine}
 
-    #: kind of `BatchedSim.stepper` behind `step()` (None: the wrapper composes its step from several calls)
+    #: kind of `BatchedSim.stepper` behind `step()` (None: the wrapper composes its step from several calls), the
+    #: shape of one env's action and its number of words
     _stepper_kind = None
+    _action_shape, _action_words = None, 0
     _stepper = None
+    _step_obs = None
     _step_out = None
 
-    def _fast_step(self, action, shape):
+    def step(self, action):
         """`step()` of the fused env kinds: one ctypes call on cached addresses
         (`BatchedSim.stepper`), the outputs returned as ONE cached tuple of the
-        handle's persistent buffers -- `obs`, `reward`, `terminated`, `truncated`
-        are rewritten in place by every step, `info` is one dictionary whose
-        ``spine_observation`` materialises on first access (a rollout buffer
-        copies what it keeps, as with any vector env that reuses its buffers)."""
+        handle's persistent buffers (`_step_output`)."""
         step = self._stepper
         if step is None:
-            if not hasattr(self.sim, "stepper"):  # (test doubles)
-                return None
             step = self._stepper = self.sim.stepper(self._stepper_kind)
+            self._step_obs = self.observation
         if not (type(action) is torch.Tensor and action.dtype is torch.float32 and action.device == self.device and action.is_contiguous()
                 and action.numel() == self.num_envs * self._action_words):
-            action = torch.as_tensor(action, dtype=torch.float32, device=self.device).reshape(shape).contiguous()
+            action = torch.as_tensor(action, dtype=torch.float32, device=self.device).reshape((self.num_envs,) + self._action_shape).contiguous()
         step(action.data_ptr())
+        return self._step_output(self._step_obs)
+
+    def _step_output(self, obs):
+        """What a step call returns once its launch has written `obs` and the handle's `reward`, `terminated`,
+        `truncated`: ONE cached tuple of these persistent buffers, rewritten in place by every step; `info` is one
+        dictionary whose ``spine_observation`` materialises on first access (a rollout buffer copies what it keeps,
+        as with any vector env that reuses its buffers). The tuple is built anew -- and not kept -- while something
+        has to happen per step: observers or `eager_spine_observation` materialise the spine observation, a SAME_STEP
+        env arms its final-observation buffer on its first step."""
         out = self._step_out
-        if out is None or self._observers is not None or self.eager_spine_observation or (self.autoreset_mode == "same_step" and self._final_obs is None):
-            sim = self.sim
-            obs = {"pendulum": sim.obs4, "gyropod": sim.obs6, "servos": sim.obs_servos}[self._stepper_kind]
-            out = self._finish_step(obs, sim.reward, sim.terminated, sim.truncated)
-            if self._observers is None and not self.eager_spine_observation and (self.autoreset_mode != "same_step" or self._final_obs is not None):
-                if self.autoreset_mode == "same_step":
-                    if self._same_step_layout is None or not hasattr(self.sim, "set_final_observation"):
-                        return out  # (composed through reset(mask): nothing to cache)
-                    info = _SameStepInfo(out[2], out[3], spine_observation=self._spine, final_obs=self._final_obs)
-                    out = (out[0], out[1], out[2], out[3], info)
-                self._step_out = out
+        if (out is not None and out[0] is obs and self._observers is None and not self.eager_spine_observation
+                and (self.autoreset_mode != "same_step" or self._final_obs is not None)):
+            self._spine._fresh = False
             return out
-        self._spine._fresh = False
+        sim = self.sim
+        out = self._finish_step(obs, sim.reward, sim.terminated, sim.truncated)
+        if self._observers is None and not self.eager_spine_observation:
+            if self.autoreset_mode == "same_step":  # (armed by `_finish_step`: from now on the mask is computed when it is read)
+                out = out[:4] + (_SameStepInfo(out[2], out[3], spine_observation=self._spine, final_obs=self._final_obs),)
+            self._step_out = out
         return out
 
     def _finish_step(self, obs, reward, terminated, truncated):
@@ -330,7 +341,7 @@ class UpkieVecEnv:
         if self.autoreset_mode != "same_step":
             return obs, reward, terminated, truncated, self._info()
         done = terminated | truncated
-        if self._same_step_layout is not None and hasattr(self.sim, "set_final_observation"):
+        if self._same_step_layout is not None:
             # the step call itself restarted the envs whose DONE word it set and kept every env's last observation
             # aside (inside the same launch up to 8192 envs): armed on the first step, see below
             if self._final_obs is None:
@@ -443,16 +454,9 @@ class UpkiePendulumVecEnv(UpkieVecEnv):
         torch.index_select(obs6, 1, self._pendulum_obs_indices, out=self.sim.obs4)  # upkie_pendulum.py:17,122
         return self.sim.obs4, self._info()  # (the buffer step() rewrites: `obs = env.step(policy(obs))[0]` stays on one tensor)
 
-    _stepper_kind, _action_words = "pendulum", 1
+    _stepper_kind, _action_shape, _action_words = "pendulum", (), 1
     _linear_policy_gains = None
     _agent_stepper = None
-
-    def step(self, action):
-        out = self._fast_step(action, (self.num_envs,))
-        if out is not None:
-            return out
-        obs, reward, terminated, truncated = self.sim.step_pendulum(action)  # (converted / reshaped to [B] there)
-        return self._finish_step(obs, reward, terminated, truncated)
 
     def step_linear_policy(self, gains=None, clip: Optional[float] = None):
         """``env.step(clamp(gains . obs, -clip, clip))`` with the policy evaluated INSIDE the step's launch, on the
@@ -465,7 +469,7 @@ class UpkiePendulumVecEnv(UpkieVecEnv):
         only when it is a different object from the previous call's (the identity shortcut: write new gains into a new
         tensor, or hand over host numbers). Same return value as `step`. NEXT_STEP or disabled autoreset (a SAME_STEP
         env steps with `step(policy(obs))`)."""
-        if self.autoreset_mode == "same_step" or not hasattr(self.sim, "step_pendulum_agent"):
+        if self.autoreset_mode == "same_step":
             raise UpkieException("step_linear_policy runs under NEXT_STEP or disabled autoreset; use step(policy(obs))")
         cfg, changed = self.sim.config, False
         on_device = isinstance(gains, torch.Tensor) and gains.device.type != "cpu"
@@ -486,25 +490,10 @@ class UpkiePendulumVecEnv(UpkieVecEnv):
             self.sim.push_config()
         self._linear_policy_gains = remember  # (only once the gains were validated and handed over)
         agent_step = self._agent_stepper
-        if agent_step is None and hasattr(self.sim, "stepper"):
-            try:
-                agent_step = self._agent_stepper = self.sim.stepper("pendulum_agent")  # one ctypes call on cached addresses
-            except KeyError:  # (test doubles without this kind)
-                agent_step = self._agent_stepper = False
-        if agent_step:
-            agent_step()
-            sim = self.sim
-            obs, reward, terminated, truncated = sim.obs4, sim.reward, sim.terminated, sim.truncated
-        else:
-            obs, reward, terminated, truncated = self.sim.step_pendulum_agent()
-        out = self._step_out
-        if out is None or self._observers is not None or self.eager_spine_observation:
-            out = self._finish_step(obs, reward, terminated, truncated)
-            if self._observers is None and not self.eager_spine_observation:
-                self._step_out = out  # (the same persistent buffers `step` returns)
-            return out
-        self._spine._fresh = False
-        return out
+        if agent_step is None:
+            agent_step = self._agent_stepper = self.sim.stepper("pendulum_agent")  # one ctypes call on cached addresses
+        agent_step()
+        return self._step_output(self.sim.obs4)  # (the same persistent buffers `step` returns)
 
 
 class UpkieGyropodVecEnv(UpkieVecEnv):
@@ -557,17 +546,7 @@ class UpkieGyropodVecEnv(UpkieVecEnv):
         obs6 = self._reset_sim(seed, mask)
         return obs6, self._info()
 
-    def _gyropod_step(self, action):
-        act = torch.as_tensor(action, dtype=torch.float32, device=self.device).reshape(self.num_envs, 2)
-        return self.sim.step_gyropod(act)
-
-    _stepper_kind, _action_words = "gyropod", 2
-
-    def step(self, action):
-        out = self._fast_step(action, (self.num_envs, 2)) if self._stepper_kind is not None else None
-        if out is not None:
-            return out
-        return self._finish_step(*self._gyropod_step(action))
+    _stepper_kind, _action_shape, _action_words = "gyropod", (2,), 2
 
 
 class UpkieServosVecEnv(UpkieVecEnv):
@@ -616,24 +595,11 @@ class UpkieServosVecEnv(UpkieVecEnv):
 
     def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None, mask: Optional[torch.Tensor] = None):
         self._reset_sim(seed, mask)
-        obs = self._servo_obs()
-        if hasattr(self.sim, "obs_servos"):
-            if self.sim.obs_servos is None:  # (allocated here, not by the first step: `env.observation` holds the reset observation from the start)
-                self.sim.obs_servos = torch.zeros((self.num_envs, 6, 5), dtype=torch.float32, device=self.device)
-            if self.sim.obs_servos.shape == obs.shape:
-                self.sim.obs_servos.copy_(obs)
-                obs = self.sim.obs_servos  # (the buffer step() rewrites)
+        obs = self.observation  # (the buffer step() rewrites)
+        obs.copy_(self._servo_obs())
         return obs, self._info()
 
-    _stepper_kind, _action_words = "servos", 36
-
-    def step(self, action):
-        out = self._fast_step(action, (self.num_envs, 6, 6))
-        if out is not None:
-            return out
-        act = torch.as_tensor(action, dtype=torch.float32, device=self.device).reshape(self.num_envs, 6, 6)
-        obs, reward, terminated, truncated = self.sim.step_servos(act)
-        return self._finish_step(obs, reward, terminated, truncated)
+    _stepper_kind, _action_shape, _action_words = "servos", (6, 6), 36
 
     def step_servo_policy(self, policy: "abi.UpkieServoPolicy"):
         """`step` with the action computed on the device by a servo-level law (`abi.torque_balancing_policy`:
@@ -641,17 +607,9 @@ class UpkieServosVecEnv(UpkieVecEnv):
         wheels' velocity loop) from the state the step starts from -- inside the step's own launch on eight lanes per
         env (`upkie_sim_step_servos_policy`), a launch in front of it otherwise. The law flags robots that fell past
         its `fall_pitch` for the NEXT_STEP autoreset. Same return value as `step`; NEXT_STEP or disabled autoreset."""
-        if self.autoreset_mode == "same_step" or not hasattr(self.sim, "step_servos_policy"):
+        if self.autoreset_mode == "same_step":
             raise UpkieException("step_servo_policy runs under NEXT_STEP or disabled autoreset; use step(action)")
-        obs, reward, terminated, truncated = self.sim.step_servos_policy(policy)
-        out = self._step_out
-        if out is None or out[0] is not obs or self._observers is not None or self.eager_spine_observation:
-            out = self._finish_step(obs, reward, terminated, truncated)
-            if self._observers is None and not self.eager_spine_observation:
-                self._step_out = out
-            return out
-        self._spine._fresh = False
-        return out
+        return self._step_output(self.sim.step_servos_policy(policy)[0])
 
 
 class UpkieBaseVelocityVecEnv(UpkieGyropodVecEnv):
@@ -697,13 +655,12 @@ class UpkieBaseVelocityVecEnv(UpkieGyropodVecEnv):
         B = self.num_envs
         self._x0 = torch.zeros((B, 4), dtype=torch.float32, device=self.device)
         self._contact = torch.zeros(B, dtype=torch.uint8, device=self.device)
-        self._xy = torch.zeros((B, 2), dtype=torch.float32, device=self.device)
         # balancer and step in ONE launch (upkie_sim_step_base_velocity_mpc) instead of two, same bits: on by default where
         # the eight-lane kernel steps the batch (up to 16384 envs: a wavefront solves the QPs of its eight envs as one
         # half-filled MFMA tile in front of their step); off on the two-lane mapping, where it measured SLOWER (37.9 vs
         # 35.6 us at 16384 envs: a wavefront that steps 32 envs solves two tiles one after the other, the separate kernel
         # spreads them over twice as many wavefronts; profiles/r02_secondary_configs_c.jsonl)
-        self.fuse_mpc = getattr(self.sim, "lanes_per_env", 0) == 8
+        self.fuse_mpc = self.sim.lanes_per_env == 8
 
     def _remember(self, obs6: torch.Tensor) -> None:
         # MPC state [ground position, pitch, ground velocity, pitch rate] of the
@@ -715,48 +672,19 @@ class UpkieBaseVelocityVecEnv(UpkieGyropodVecEnv):
         obs6, info = super().reset(seed=seed, options=options, mask=mask)
         self._remember(obs6)
         self.mpc_balancer.reset(mask)  # upkie_base_velocity.py:158
-        if hasattr(self.sim, "step_base_velocity") and hasattr(self.mpc_balancer, "step_env"):
-            # fused path (the condition step() takes it on): the dead-reckoned pose lives in the state words (the
-            # reset branch of the kernel has just zeroed them for the reset envs); the generic composition below
-            # dead-reckons in `_xy` and never touches those words
-            self._xy.copy_(self.sim.state[abi.S_SE2_X : abi.S_SE2_Y + 1].t())
-        elif mask is None:
-            self._xy.zero_()
-        else:
-            self._xy.masked_fill_(mask.to(self.device).bool()[:, None], 0.0)
-        # reset envs start at the origin (upkie_base_velocity.py:160-162);
-        # untouched ones report their current dead-reckoned pose
-        obs = torch.cat([self._xy, obs6[:, 2:3].to(self._xy.dtype)], dim=1)
-        return obs, info
+        # the dead-reckoned pose lives in the state words: the reset has just zeroed them for the reset envs, which
+        # start at the origin (upkie_base_velocity.py:160-162); untouched ones report their current pose
+        pose = self.sim.state[abi.S_SE2_X : abi.S_SE2_Y + 1].t()
+        return torch.cat([pose, obs6[:, 2:3]], dim=1), info
 
     def step(self, action):
         act = torch.as_tensor(action, dtype=torch.float32, device=self.device).reshape(self.num_envs, 2).contiguous()
-        if self.fuse_mpc and hasattr(self.sim, "step_base_velocity_mpc") and hasattr(self.mpc_balancer, "_handle"):
+        if self.fuse_mpc:
             # balancer and step in one call (one launch with two lanes per env and a horizon <= 16), everything on device
-            obs, reward, terminated, truncated = self.sim.step_base_velocity_mpc(self.mpc_balancer, act, self._x0, self._contact)
-            return self._finish_step(obs, reward, terminated, truncated)
-        if hasattr(self.sim, "step_base_velocity") and hasattr(self.mpc_balancer, "step_env"):
-            # fused path: two launches per env.step(), everything stays on device
+            out = self.sim.step_base_velocity_mpc(self.mpc_balancer, act, self._x0, self._contact)
+        else:
+            # two launches per env.step(), everything stays on device
             done = self.sim.state[abi.S_DONE] if self.config.autoreset_mode else None
             commanded = self.mpc_balancer.step_env(self._x0, act, self._contact, done, self.dt)
-            obs, reward, terminated, truncated = self.sim.step_base_velocity(act, commanded, self._x0, self._contact)
-            return self._finish_step(obs, reward, terminated, truncated)
-        # generic composition (used with the CPU test doubles)
-        linear_velocity, yaw_velocity = act[:, 0].contiguous(), act[:, 1]
-        autoreset = (self.sim.state[abi.S_DONE] != 0) if self.config.autoreset_mode else None
-        ground_velocity, _ = self.mpc_balancer.step(self._x0, linear_velocity, self._contact, self.dt)
-        gyropod_action = torch.stack([ground_velocity, yaw_velocity], dim=1)
-        obs6, reward, terminated, truncated = self._gyropod_step(gyropod_action)
-        self._remember(obs6)
-        yaw = obs6[:, 2]
-        if autoreset is not None and bool(autoreset.any()):
-            self.mpc_balancer.reset(autoreset.to(torch.uint8))
-            self._xy[autoreset] = 0.0
-            live = ~autoreset
-            self._xy[live, 0] += (linear_velocity * torch.cos(yaw) * self.dt)[live]  # :197-199
-            self._xy[live, 1] += (linear_velocity * torch.sin(yaw) * self.dt)[live]
-        else:
-            self._xy[:, 0] += linear_velocity * torch.cos(yaw) * self.dt  # :197-199
-            self._xy[:, 1] += linear_velocity * torch.sin(yaw) * self.dt
-        obs = torch.cat([self._xy, yaw[:, None]], dim=1)
-        return self._finish_step(obs, reward, terminated, truncated)
+            out = self.sim.step_base_velocity(act, commanded, self._x0, self._contact)
+        return self._finish_step(*out)

@@ -11,6 +11,11 @@ from .exceptions import UpkieRuntimeError
 from .launch import launcher, ptr
 
 
+# What an MPC balancer is to `UpkieBaseVelocityVecEnv` (its `mpc_factory=` parameter is the seam for a CPU double): these
+# methods and `commanded_velocity`; `workspace` and `_handle` too for the one-call path (`BatchedSim.step_base_velocity_mpc`).
+BALANCER_METHODS = ("reset", "step_env", "close")
+
+
 class BatchedMpc:
     """One condensed box-QP per env, solved every step by fixed-iteration
     ADMM on the matrix cores; warm start and commanded velocity stay on the

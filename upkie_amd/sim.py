@@ -27,6 +27,19 @@ _STEPS = {
 }
 
 
+# What a simulation handle is to its wrappers (`UpkieVecEnv` and its subclasses, `ShardedPendulum`, `ShardedVecEnv`,
+# `GraphedEnvStep`, `Ppo._env_tensors`): the persistent buffers and the members below, nothing else. `BatchedSim` is the
+# product's only handle; the `sim_factory=` parameter of the wrappers is the seam through which tests inject a CPU double,
+# which has to provide every one of these names with the same parameters (tests/test_handle_contract.py).
+HANDLE_BUFFERS = ("state", "reward", "terminated", "truncated", "obs4", "obs6", "obs_servos", "obs3")
+HANDLE_METHODS = (
+    "reset", "push_config", "restart_random_streams", "stepper", "step_into_fn", "step_pendulum_records", "step_pendulum_records_raw",
+    "rollout_pendulum_records", "step_pendulum_packed", "step_servos_policy", "step_base_velocity", "step_base_velocity_mpc",
+    "set_final_observation", "autoreset_done", "lanes_per_env", "attach_observers", "observe", "contact_points",
+    "use_bullet_like_contacts", "randomize_inertias", "set_external_forces", "close",
+)  # `stepper(kind)`: "pendulum" | "gyropod" | "servos" | "pendulum_agent"; `lanes_per_env` is a property
+
+
 class BatchedSim:
     """B robots stepped by one HIP kernel launch per ``env.step()``."""
 
@@ -66,7 +79,8 @@ class BatchedSim:
         self.truncated = torch.zeros(B, dtype=torch.uint8, device=self.device)
         self.obs4 = torch.zeros((B, 4), dtype=torch.float32, device=self.device)
         self.obs6 = torch.zeros((B, 6), dtype=torch.float32, device=self.device)
-        self.obs_servos = None
+        self.obs_servos = None  # (this one and `obs3`: allocated by the first method that needs them, `_scratch`)
+        self.obs3 = None
         self.body_inertials = None  # [70, B] per-env inertial records (randomize_inertias)
         self.link_scale = None  # [MAX_LINKS, B] the factors drawn per URDF link
         self.ext_force = None
