@@ -271,7 +271,7 @@ def test_ppo_checks_the_pipeline_against_the_policy_and_the_env():
 
 
 def test_ppo_rollout_step_with_a_pipeline_on_the_cpu_env():
-    """`Ppo._rollout_step_pipeline` on the CPU oracle env (tests/fake_sim.py), a recording policy and the twins: the
+    """`Ppo._rollout_step` with a pipeline on the CPU oracle env (tests/fake_sim.py), a recording policy and the twins: the
     order of the calls, what each one is given, and the buffer's rows."""
     import upkie_amd.envs as envs
     from tests.fake_sim import oracle_sim_factory
@@ -325,7 +325,7 @@ def test_ppo_rollout_step_with_a_pipeline_on_the_cpu_env():
         ended = 0
         for t in range(T):
             del log[:]
-            model._rollout_step_pipeline()
+            model._rollout_step()
             assert log == ["act", "shape_action", "reward", "episodes", "observe", "bootstrap"], log
             ended += int(model._starts.sum())
         assert ended >= N, "every env hit its time limit at least once"

@@ -8,7 +8,8 @@ import pytest
 import torch
 
 from upkie_amd import abi, launch, lib
-from upkie_amd.launch import launcher, ptr
+from upkie_amd.exceptions import UpkieRuntimeError
+from upkie_amd.launch import device_tensor, launcher, ptr
 from upkie_amd.sim import BatchedSim
 
 RAW, OBJECT = 0x7000, 0x9000  # stream handles: what the raw getter / a `Stream` object's `cuda_stream` give for device 0
@@ -65,6 +66,26 @@ class FakeCuda:
 def test_ptr_is_a_plain_address_or_none():
     t = torch.zeros(3)
     assert ptr(t) == t.data_ptr() and type(ptr(t)) is int and ptr(None) is None
+
+
+def test_device_tensor_passes_none_when_not_required_and_refuses_host_tensors():
+    """What a host-only run reaches of `device_tensor` (the checks of a device tensor: tests/test_launch_gpu.py)."""
+    dev = torch.device("cuda:0")
+    assert device_tensor(None, "mask", dev, (8,), (torch.bool, torch.uint8), required=False) is None
+    with pytest.raises(ValueError, match="^reward is required$"):
+        device_tensor(None, "reward", dev, (8,))
+    for host in (torch.zeros(8), [0.0] * 8):
+        with pytest.raises(UpkieRuntimeError, match=r"^reward must be a device tensor \(there is no CPU fallback\)$"):
+            device_tensor(host, "reward", dev, (8,), required=False)
+
+
+def test_require_names_the_symbol_and_the_hint():
+    library = types.SimpleNamespace(upkie_episodes_step=object())
+    assert lib.require(library, "upkie_episodes_step") is None
+    with pytest.raises(UpkieRuntimeError, match="^this build of libupkie_hip.so has no upkie_vecnorm_merge: rebuild it$"):
+        lib.require(library, "upkie_vecnorm_merge")
+    with pytest.raises(UpkieRuntimeError, match="^this build of libupkie_hip.so has no upkie_vecnorm_merge: rebuild it for a process group$"):
+        lib.require(library, "upkie_vecnorm_merge", "for a process group")
 
 
 def test_handle_first_stream_last_arguments_untouched(monkeypatch):

@@ -66,3 +66,26 @@ def test_every_family_launches_on_torchs_current_stream(monkeypatch):
     torch.cuda.synchronize(sim.device)
     for handle in (sim, mpc, observers):
         handle.close()
+
+
+@pytest.mark.gpu
+def test_device_tensor_checks_device_dtype_size_and_layout():
+    from upkie_amd.launch import device_tensor
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    good = torch.zeros(8, device=dev)
+    assert device_tensor(good, "reward", dev, (8,)) is good and device_tensor(good, "obs", dev, (2, 4)) is good  # (the element count, not the shape)
+    flags = torch.zeros(8, dtype=torch.uint8, device=dev)
+    assert device_tensor(flags, "mask", dev, (8,), (torch.bool, torch.uint8), required=False) is flags
+    wrong = {"dtype": torch.zeros(8, dtype=torch.float64, device=dev), "size": torch.zeros(9, device=dev),
+             "layout": torch.zeros(8, 2, device=dev)[:, 0], "flag dtype": good}
+    for what, t in wrong.items():
+        dtypes = (torch.bool, torch.uint8) if what == "flag dtype" else (torch.float32,)
+        with pytest.raises(ValueError, match="reward must be a contiguous") as info:
+            device_tensor(t, "reward", dev, (8,), dtypes)
+        assert str(info.value) == f"reward must be a contiguous [8] tensor of {' or '.join(map(str, dtypes))} on {dev}", what
+    if torch.cuda.device_count() > 1:
+        with pytest.raises(ValueError, match="reward must be a contiguous"):
+            device_tensor(good, "reward", torch.device("cuda", (dev.index + 1) % torch.cuda.device_count()), (8,))
+    with pytest.raises(ValueError, match="reward must be a contiguous"):
+        device_tensor(good, "reward", torch.device("cpu"), (8,))  # (a stage on another device than the tensor)

@@ -277,7 +277,7 @@ def _warm_up_as_the_capture_does(model):
     """A graphed `Ppo` runs one real rollout step into the last slot before it captures; the same by hand."""
     model._setup()
     model._slot = model.n_steps - 1
-    (model._rollout_step if model.pipeline is None else model._rollout_step_pipeline)()
+    model._rollout_step()
 
 
 def _snapshot(model, policy):

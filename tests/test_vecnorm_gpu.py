@@ -2,6 +2,7 @@
 outputs against the fp64 twin of tests/vecnorm_reference.py, the modes, determinism and hipGraph replay, the coupling to
 the MLP policy, a closed PPO loop, the example."""
 
+import gc
 import os
 import subprocess
 import sys
@@ -281,6 +282,7 @@ def test_closed_loop_eager_against_the_twin_and_graphed_bit_equal():
                     t = slot["t"]
                     body()
                     if i == 2:
+                        gc.collect()  # (cyclic garbage of earlier tests holds device memory until a collection: not during the count)
                         torch.cuda.synchronize()
                         allocated = torch.cuda.memory_allocated(dev)
                     o, r, te, tr = (x.cpu().numpy() for x in last["step"])

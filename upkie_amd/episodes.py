@@ -12,7 +12,7 @@ import torch
 
 from . import lib
 from .exceptions import UpkieRuntimeError
-from .launch import check, launcher, ptr
+from .launch import check, device_tensor, launcher, ptr
 
 
 class EpisodeStatistics:
@@ -47,8 +47,7 @@ class EpisodeStatistics:
         if self.device.type != "cuda":
             raise UpkieRuntimeError("EpisodeStatistics runs on the HIP device only (there is no CPU fallback): give device='cuda:0'")
         self._lib = lib.load()
-        if not hasattr(self._lib, "upkie_episodes_step"):
-            raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_episodes_step: rebuild it")
+        lib.require(self._lib, "upkie_episodes_step")
         nbytes = int(self._lib.upkie_episodes_workspace_bytes(self.num_envs))
         check(nbytes)
         self._launcher = launcher(self.device)
@@ -61,23 +60,13 @@ class EpisodeStatistics:
         self.means = torch.zeros(2, dtype=torch.float64, device=self.device)  # mean return, mean length over the ring
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)  # (its ticket starts, and stays, at zero)
 
-    def _vector(self, t, what, dtypes, required=False):
-        if t is None:
-            if required:
-                raise ValueError(f"{what} is required")
-            return None
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise UpkieRuntimeError(f"{what} must be a device tensor (there is no CPU fallback)")
-        if t.device != self.device or t.dtype not in dtypes or not t.is_contiguous() or t.numel() != self.num_envs:
-            raise ValueError(f"{what} must be a contiguous tensor of {self.num_envs} {' or '.join(map(str, dtypes))} on {self.device}")
-        return t
-
     def step(self, reward: torch.Tensor, terminated: Optional[torch.Tensor] = None, truncated: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One env step: ``reward`` [N] float32 (the raw reward, before any normalisation), ``terminated`` /
         ``truncated`` [N] bool or uint8 (None: none ended). Returns ``means``."""
-        reward = self._vector(reward, "reward", (torch.float32,), required=True)
-        terminated = self._vector(terminated, "terminated", (torch.bool, torch.uint8))
-        truncated = self._vector(truncated, "truncated", (torch.bool, torch.uint8))
+        N, dev, flags = (self.num_envs,), self.device, (torch.bool, torch.uint8)
+        reward = device_tensor(reward, "reward", dev, N)
+        terminated = device_tensor(terminated, "terminated", dev, N, flags, required=False)
+        truncated = device_tensor(truncated, "truncated", dev, N, flags, required=False)
         self._launcher(self._lib.upkie_episodes_step, self.num_envs, self.window, reward.data_ptr(), ptr(terminated), ptr(truncated),
                        self.ep_return.data_ptr(), self.ep_length.data_ptr(), self.ring_return.data_ptr(), self.ring_length.data_ptr(),
                        self.counters.data_ptr(), self.means.data_ptr(), self.workspace.data_ptr())
@@ -86,8 +75,13 @@ class EpisodeStatistics:
     def reset(self, mask: Optional[torch.Tensor] = None) -> None:
         """Discard the running episodes of the envs with ``mask`` set ([N] bool or uint8; None: every env) without
         recording them (``Monitor.reset``). The ring and the means are kept."""
-        mask = self._vector(mask, "mask", (torch.bool, torch.uint8))
+        mask = device_tensor(mask, "mask", self.device, (self.num_envs,), (torch.bool, torch.uint8), required=False)
         self._launcher(self._lib.upkie_episodes_reset, self.num_envs, ptr(mask), self.ep_return.data_ptr(), self.ep_length.data_ptr())
+
+    def state_tensors(self) -> dict:
+        """The running episodes, the ring, its counters and its means (what `Ppo.save` carries)."""
+        return {"ep_return": self.ep_return, "ep_length": self.ep_length, "ring_return": self.ring_return, "ring_length": self.ring_length,
+                "counters": self.counters, "means": self.means}
 
     # ---- host reads (each synchronises with the device)
     @property

@@ -7,6 +7,7 @@ from typing import Optional
 import torch
 
 from . import lib
+from .exceptions import UpkieRuntimeError
 
 # the raw handle of torch's current stream on a device without building a torch.cuda.Stream object per call
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -15,6 +16,23 @@ _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 def ptr(t: Optional[torch.Tensor]):
     # (a plain integer: ctypes turns it into the c_void_p the argtypes ask for, without an object per argument)
     return t.data_ptr() if t is not None else None
+
+
+def device_tensor(t, what: str, device, shape, dtypes=(torch.float32,), required: bool = True):
+    """`t` as an argument of a launch: a contiguous tensor of ``shape``'s element count and one of ``dtypes`` on
+    ``device``, returned as it is; None passes when not ``required``. ``what`` names it in the messages."""
+    if t is None:
+        if required:
+            raise ValueError(f"{what} is required")
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise UpkieRuntimeError(f"{what} must be a device tensor (there is no CPU fallback)")
+    n = 1
+    for s in shape:
+        n *= s
+    if t.device != device or t.dtype not in dtypes or not t.is_contiguous() or t.numel() != n:
+        raise ValueError(f"{what} must be a contiguous {list(shape)} tensor of {' or '.join(map(str, dtypes))} on {device}")
+    return t
 
 
 def check(status: int, last_error=None, handle=None) -> None:

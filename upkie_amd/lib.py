@@ -259,6 +259,13 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
 _lib = None
 
 
+def require(library, symbol: str, hint=None) -> None:
+    """Refuse a build of the library that lacks ``symbol`` (an older one, loaded through UPKIE_HIP_LIBRARY); ``hint``
+    says what the symbol is needed for."""
+    if not hasattr(library, symbol):
+        raise UpkieRuntimeError(f"this build of libupkie_hip.so has no {symbol}: rebuild it" + (f" {hint}" if hint else ""))
+
+
 def _check_struct_sizes(lib) -> None:
     """The structs this package writes (`abi.py`) must be the structs the library reads: a build of another version of
     the header, loaded through UPKIE_HIP_LIBRARY for an A/B run, may have shorter or longer config structs (they grow

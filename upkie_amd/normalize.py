@@ -63,8 +63,7 @@ class RunningNormalizer:
         self.gamma, self.epsilon, self.clip_obs, self.clip_reward = float(gamma), float(epsilon), float(clip_obs), float(clip_reward)
         self.norm_obs, self.norm_reward, self.training = bool(norm_obs), bool(norm_reward), bool(training)
         self._lib = lib.load()
-        if not hasattr(self._lib, "upkie_vecnorm_step"):
-            raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_vecnorm_step")
+        lib.require(self._lib, "upkie_vecnorm_step")
         nbytes = int(self._lib.upkie_vecnorm_workspace_bytes(self.num_envs, self.obs_dim))
         check(nbytes)
         self._launcher = launcher(self.device)
@@ -84,8 +83,7 @@ class RunningNormalizer:
         if process_group is not None:
             from .distributed import SlotExchange
 
-            if not hasattr(self._lib, "upkie_vecnorm_merge"):
-                raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_vecnorm_merge: rebuild it for a process group")
+            lib.require(self._lib, "upkie_vecnorm_merge", "for a process group")
             words = int(self._lib.upkie_vecnorm_slot_bytes(D)) // 4
             self._exchange = SlotExchange(words, self.device, process_group)
         self.obs_stats[D:2 * D] = 1.0

@@ -16,7 +16,7 @@ import torch
 
 from . import lib
 from .exceptions import UpkieRuntimeError
-from .launch import check, launcher, ptr
+from .launch import check, device_tensor, launcher, ptr
 
 # enum UpkiePipelineFlag
 ACTION_IN_OBSERVATION, INTEGRATE_ACTION, ACTION_NOISE, ACTION_LAG, OBSERVATION_NOISE = 1, 2, 4, 8, 16
@@ -109,8 +109,7 @@ class AgentPipeline:
         if self.device.type != "cuda":
             raise UpkieRuntimeError("AgentPipeline runs on the HIP device only (there is no CPU fallback): give device='cuda:0'")
         self._lib = lib.load()
-        if not hasattr(self._lib, "upkie_pipeline_observe"):
-            raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_pipeline_observe: rebuild it")
+        lib.require(self._lib, "upkie_pipeline_observe")
         self._launcher = launcher(self.device)
         self.params = torch.from_numpy(self.packed_params()).to(self.device)
         N, A, S = self.num_envs, self.act_dim, self.stacked_dim
@@ -134,27 +133,12 @@ class AgentPipeline:
         check(words)
         return out
 
-    # ---- arguments
-    def _tensor(self, t, what, shape, dtypes=(torch.float32,), required=True):
-        if t is None:
-            if required:
-                raise ValueError(f"{what} is required")
-            return None
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise UpkieRuntimeError(f"{what} must be a device tensor (there is no CPU fallback)")
-        n = 1
-        for s in shape:
-            n *= s
-        if t.device != self.device or t.dtype not in dtypes or not t.is_contiguous() or t.numel() != n:
-            raise ValueError(f"{what} must be a contiguous {list(shape)} tensor of {' or '.join(map(str, dtypes))} on {self.device}")
-        return t
-
     def _settings(self):
         return (self.num_envs, self.obs_dim, self.act_dim, self.stack, self.flags, self.dt, self.action_lag or 0.0, self.params.data_ptr(), self.seed)
 
     def shape_action(self, env_action: torch.Tensor) -> torch.Tensor:
         """``env_action`` [N, A] float32 (the policy's clamped output) into `command`, which is returned."""
-        a = self._tensor(env_action, "env_action", (self.num_envs, self.act_dim))
+        a = device_tensor(env_action, "env_action", self.device, (self.num_envs, self.act_dim))
         self._launcher(self._lib.upkie_pipeline_shape_action, *self._settings(), a.data_ptr(), self.prev_command.data_ptr(), self.calls.data_ptr(),
                        self.command.data_ptr())
         return self.command
@@ -163,11 +147,11 @@ class AgentPipeline:
                 final_obs: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One env step: ``next_obs`` [N, D] float32, ``terminated`` / ``truncated`` [N] bool or uint8 (None: none ended),
         ``final_obs`` [N, D] (None: no `final_observation`). Returns `observation`."""
-        N, D = self.num_envs, self.obs_dim
-        obs = self._tensor(next_obs, "next_obs", (N, D))
-        term = self._tensor(terminated, "terminated", (N,), (torch.bool, torch.uint8), required=False)
-        trunc = self._tensor(truncated, "truncated", (N,), (torch.bool, torch.uint8), required=False)
-        final = self._tensor(final_obs, "final_obs", (N, D), required=False)
+        N, D, dev, flags = self.num_envs, self.obs_dim, self.device, (torch.bool, torch.uint8)
+        obs = device_tensor(next_obs, "next_obs", dev, (N, D))
+        term = device_tensor(terminated, "terminated", dev, (N,), flags, required=False)
+        trunc = device_tensor(truncated, "truncated", dev, (N,), flags, required=False)
+        final = device_tensor(final_obs, "final_obs", dev, (N, D), required=False)
         self._launcher(self._lib.upkie_pipeline_observe, *self._settings(), obs.data_ptr(), ptr(term), ptr(trunc), ptr(final),
                        self.command.data_ptr(), self.prev_command.data_ptr(), self.calls.data_ptr(), self.observation.data_ptr(),
                        self.final_observation.data_ptr())
@@ -176,8 +160,8 @@ class AgentPipeline:
     def reset(self, obs: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Restart the envs with ``mask`` set ([N] bool or uint8; None: every env) from ``obs`` [N, D]: a zero stack
         with the frame of ``obs`` (noised, zero command) last, ``prev_command`` zero. Returns `observation`."""
-        obs = self._tensor(obs, "obs", (self.num_envs, self.obs_dim))
-        mask = self._tensor(mask, "mask", (self.num_envs,), (torch.bool, torch.uint8), required=False)
+        obs = device_tensor(obs, "obs", self.device, (self.num_envs, self.obs_dim))
+        mask = device_tensor(mask, "mask", self.device, (self.num_envs,), (torch.bool, torch.uint8), required=False)
         self._launcher(self._lib.upkie_pipeline_reset, *self._settings(), obs.data_ptr(), ptr(mask), self.prev_command.data_ptr(),
                        self.calls.data_ptr(), self.observation.data_ptr())
         return self.observation

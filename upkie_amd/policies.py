@@ -53,8 +53,7 @@ class LinearPolicy:
         if self._act is None or self._act.shape[0] != n or self._act.device != obs.device:
             self._act = torch.empty((n, self.act_dim), dtype=torch.float32, device=obs.device)
             self._lib = lib.load()
-            if not hasattr(self._lib, "upkie_linear_policy"):
-                raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_linear_policy")
+            lib.require(self._lib, "upkie_linear_policy")
             self._launcher = launcher(obs.device)  # (the observations' device, as the action buffer)
         self._launcher(self._lib.upkie_linear_policy, n, self.obs_dim, self.act_dim, obs.data_ptr(), self.weights.data_ptr(), ptr(self.bias),
                        self.clip, self._act.data_ptr())
@@ -265,8 +264,7 @@ class MlpActorCritic:
         self.activation = activation
         self.clip_obs, self.eps = float(clip_obs), float(eps)
         self._lib = lib.load()
-        if not hasattr(self._lib, "upkie_mlp_actor_critic"):
-            raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_mlp_actor_critic")
+        lib.require(self._lib, "upkie_mlp_actor_critic")
         words = int(self._lib.upkie_mlp_packed_words(C.byref(shape)))
         check(words)
         self._launcher = launcher(self.device)
@@ -382,6 +380,11 @@ class MlpActorCritic:
         if self.calls is not None:
             self.calls.zero_()
 
+    def state_tensors(self) -> dict:
+        """The packed weights and the per-env call counters of the noise (None before the first call): what `Ppo.save`
+        carries."""
+        return {"packed": self.packed, "calls": self.calls}
+
     # ---- calls
     def _obs(self, obs: torch.Tensor) -> torch.Tensor:
         if not isinstance(obs, torch.Tensor) or not obs.is_cuda:
@@ -477,8 +480,7 @@ class MlpActorCritic:
         gamma = float(gamma)
         if not 0.0 <= gamma <= 1.0:
             raise ValueError("gamma must be in [0, 1]")
-        if not hasattr(self._lib, "upkie_mlp_bootstrap_time_limits"):
-            raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_mlp_bootstrap_time_limits: rebuild it")
+        lib.require(self._lib, "upkie_mlp_bootstrap_time_limits")
         self._launcher(self._lib.upkie_mlp_bootstrap_time_limits, n, C.byref(self.shape), self.packed.data_ptr(), final_obs.data_ptr(),
                        flags[0].data_ptr(), flags[1].data_ptr(), gamma, reward.data_ptr())
         return reward

@@ -121,16 +121,14 @@ class PpoTrainer:
         cfg.obs_normalized = int(self.obs_normalized)
         self.config = cfg
         self._lib = lib.load()
-        if not hasattr(self._lib, "upkie_ppo_minibatch_update"):
-            raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_ppo_minibatch_update")
+        lib.require(self._lib, "upkie_ppo_minibatch_update")
         self._launcher = launcher(self.device)
         words = policy.packed.numel()
         f32 = dict(dtype=torch.float32, device=self.device)
         self.m = torch.zeros(words, **f32)
         self.v = torch.zeros(words, **f32)
-        if self.controlled and not hasattr(self._lib, "upkie_ppo_minibatch_update_controlled"):
-            raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_ppo_minibatch_update_controlled: rebuild it for target_kl "
-                                    "and schedules")
+        if self.controlled:
+            lib.require(self._lib, "upkie_ppo_minibatch_update_controlled", "for target_kl and schedules")
         # the control block (include/upkie_hip.h: UPKIE_PPO_CTRL_*); `scalars` (lr, t) is its first two words
         self.control = torch.zeros(abi.PPO_CTRL_WORDS, dtype=torch.float64, device=self.device)
         self.control[abi.PPO_CTRL_LR] = float(lr)
@@ -153,8 +151,7 @@ class PpoTrainer:
         if process_group is not None:
             from .distributed import SlotExchange
 
-            if not hasattr(self._lib, "upkie_ppo_minibatch_apply"):
-                raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_ppo_minibatch_apply: rebuild it for a process group")
+            lib.require(self._lib, "upkie_ppo_minibatch_apply", "for a process group")
             self._grad_exchange = SlotExchange(int(self._lib.upkie_ppo_slot_bytes(C.byref(policy.shape))) // 4, self.device, process_group)
             self._ev_exchange = SlotExchange(8, self.device, process_group)  # (4 doubles per rank)
 
@@ -261,64 +258,56 @@ class PpoTrainer:
             raise UpkieRuntimeError("call prepare(buffer) first: it copies the advantages and returns update() reads")
         if self._addresses(buffer) != self._buffer:
             raise ValueError("this trainer serves one rollout buffer (a captured update reads its tensors): build another trainer")
-        lb, launch, shape, cfg = self._lib, self._launcher, C.byref(self.policy.shape), C.byref(self.config)
-        obs, act = ptr(buffer.observations), ptr(buffer.actions)
-        vals, logp, adv, ret = ptr(buffer.values), ptr(buffer.log_probs), ptr(self.advantages), ptr(self.returns)
-        if self.process_group is not None:
-            if torch.cuda.is_current_stream_capturing():
-                raise UpkieRuntimeError("a PpoTrainer with a process group cannot be captured in a graph (every minibatch exchanges the "
-                                        "gradients through a collective)")
-            self._update_shared(total, shape, cfg, obs, act, vals, logp, adv, ret)
-            if sync:
-                self.sync_modules()
-            return self.stats
-        # (the controlled entry point has upkie_ppo_minibatch_update's signature, the control block where adam_scalars is)
-        minibatch = lb.upkie_ppo_minibatch_update_controlled if self.controlled else lb.upkie_ppo_minibatch_update
-        with torch.cuda.device(self.device):  # (around the whole block: every launch then takes the launcher's fast path)
+        if self.process_group is not None and torch.cuda.is_current_stream_capturing():
+            raise UpkieRuntimeError("a PpoTrainer with a process group cannot be captured in a graph (every minibatch exchanges the "
+                                    "gradients through a collective)")
+        mb = self._mb
+        # what every minibatch launch begins with, and the six sample arrays it reads
+        head = (C.byref(self.policy.shape), C.byref(self.config))
+        data = tuple(ptr(t) for t in (buffer.observations, buffer.actions, buffer.values, buffer.log_probs, self.advantages, self.returns))
+        with torch.cuda.device(self.device):  # (around the whole block: every launch takes the launcher's fast path, and the collectives rely on it)
             if self.controlled:
-                launch(lb.upkie_ppo_update_begin, ptr(self.control))
+                self._launcher(self._lib.upkie_ppo_update_begin, ptr(self.control))
             for e in range(self.n_epochs):
-                perm = self.perm[e]
-                launch(lb.upkie_ppo_advantage_stats, total, self._mb, ptr(perm), adv, int(self.normalize_advantage), ptr(self.adv_stats[e]))
+                perm = ptr(self.perm[e])
+                self._advantage_stats(e, total, perm, data[4])
                 for j in range(self.n_minibatches):
-                    start = j * self._mb
-                    launch(minibatch, shape, cfg, total, start, min(self._mb, total - start), self._mb, ptr(perm), obs, act, vals, logp, adv, ret,
-                           ptr(self.adv_stats[e, j]), ptr(self.policy.packed), ptr(self.m), ptr(self.v), ptr(self.control), ptr(self.workspace),
-                           ptr(self.stats[e, j]))
+                    start = j * mb
+                    self._minibatch(e, j, head, total, start, min(mb, total - start), perm, data)
         if sync:
             self.sync_modules()
         return self.stats
 
-    def _update_shared(self, total, shape, cfg, obs, act, vals, logp, adv, ret) -> None:
-        """`update`'s epochs and minibatches in the data-parallel form: the same launches split around the exchanges."""
-        lb, launch, gx, ax = self._lib, self._launcher, self._grad_exchange, self._adv_exchange
-        W, mb = gx.world, self._mb
+    def _advantage_stats(self, e: int, total: int, perm, adv) -> None:
+        """Epoch ``e``'s per-minibatch advantage statistics: one launch, or with a process group two exchanges of
+        per-minibatch sums (the means, then the squared deviations) and the finish."""
+        lb, launch, ax, norm, out = self._lib, self._launcher, self._adv_exchange, int(self.normalize_advantage), ptr(self.adv_stats[e])
+        if ax is None:
+            launch(lb.upkie_ppo_advantage_stats, total, self._mb, perm, adv, norm, out)
+            return
+        launch(lb.upkie_ppo_advantage_partials, total, self._mb, perm, adv, 0, None, ax.world, ptr(ax.mine))
+        ax.exchange()
+        launch(lb.upkie_ppo_advantage_partials, total, self._mb, perm, adv, 1, ptr(ax.slots), ax.world, ptr(ax.mine))
+        ax.exchange()
+        launch(lb.upkie_ppo_advantage_finish, total, self._mb, norm, ptr(ax.slots), ax.world, out)
 
-        with torch.cuda.device(self.device):  # (around the whole block: the collectives between the launches rely on it)
-            if self.controlled:
-                launch(lb.upkie_ppo_update_begin, ptr(self.control))
-            for e in range(self.n_epochs):
-                perm = ptr(self.perm[e])
-                launch(lb.upkie_ppo_advantage_partials, total, mb, perm, adv, 0, None, W, ptr(ax.mine))
-                ax.exchange()
-                launch(lb.upkie_ppo_advantage_partials, total, mb, perm, adv, 1, ptr(ax.slots), W, ptr(ax.mine))
-                ax.exchange()
-                launch(lb.upkie_ppo_advantage_finish, total, mb, int(self.normalize_advantage), ptr(ax.slots), W, ptr(self.adv_stats[e]))
-                for j in range(self.n_minibatches):
-                    start = j * mb
-                    size = min(mb, total - start)
-                    if self.controlled:
-                        launch(lb.upkie_ppo_minibatch_gradient_controlled, shape, cfg, total, start, size, W * size, mb, perm, obs, act, vals, logp,
-                               adv, ret, ptr(self.adv_stats[e, j]), ptr(self.policy.packed), ptr(self.workspace), ptr(gx.mine), ptr(self.control))
-                        gx.exchange()  # (after a stop: still a collective every rank joins; the apply half ignores it)
-                        launch(lb.upkie_ppo_minibatch_apply_controlled, shape, cfg, start, W * size, mb, ptr(gx.slots), W, ptr(self.policy.packed),
-                               ptr(self.m), ptr(self.v), ptr(self.control), ptr(self.workspace), ptr(self.stats[e, j]))
-                        continue
-                    launch(lb.upkie_ppo_minibatch_gradient, shape, cfg, total, start, size, W * size, mb, perm, obs, act, vals, logp, adv, ret,
-                           ptr(self.adv_stats[e, j]), ptr(self.policy.packed), ptr(self.workspace), ptr(gx.mine))
-                    gx.exchange()
-                    launch(lb.upkie_ppo_minibatch_apply, shape, cfg, W * size, mb, ptr(gx.slots), W, ptr(self.policy.packed), ptr(self.m),
-                           ptr(self.v), ptr(self.scalars), ptr(self.workspace), ptr(self.stats[e, j]))
+    def _minibatch(self, e: int, j: int, head, total: int, start: int, size: int, perm, data) -> None:
+        """Minibatch ``j`` of epoch ``e``: gradient, clip and Adam in one launch, or with a process group the gradient
+        half, the exchange of the ranks' slots and the apply half. The controlled entry points have the plain ones'
+        signatures with the control block where ``adam_scalars`` is (the fused one), after it (the gradient half), and
+        with ``minibatch_start`` first (the apply half)."""
+        lb, launch, gx, ctl, mb = self._lib, self._launcher, self._grad_exchange, self.controlled, self._mb
+        adv_stats, packed, work, stats = ptr(self.adv_stats[e, j]), ptr(self.policy.packed), ptr(self.workspace), ptr(self.stats[e, j])
+        if gx is None:
+            launch(lb.upkie_ppo_minibatch_update_controlled if ctl else lb.upkie_ppo_minibatch_update, *head, total, start, size, mb, perm, *data,
+                   adv_stats, packed, ptr(self.m), ptr(self.v), ptr(self.control), work, stats)
+            return
+        W = gx.world
+        launch(lb.upkie_ppo_minibatch_gradient_controlled if ctl else lb.upkie_ppo_minibatch_gradient, *head, total, start, size, W * size, mb, perm,
+               *data, adv_stats, packed, work, ptr(gx.mine), *((ptr(self.control),) if ctl else ()))
+        gx.exchange()  # (after a stop: still a collective every rank joins; the apply half ignores it)
+        launch(lb.upkie_ppo_minibatch_apply_controlled if ctl else lb.upkie_ppo_minibatch_apply, *head, *((start,) if ctl else ()), W * size, mb,
+               ptr(gx.slots), W, packed, ptr(self.m), ptr(self.v), ptr(self.control if ctl else self.scalars), work, stats)
 
     def train(self, buffer, sync: bool = True) -> torch.Tensor:
         """`prepare` then `update`: SB3's ``PPO.train`` on one full rollout buffer. Returns ``[n_epochs, n_minibatches, 7]``
@@ -388,8 +377,7 @@ class PpoTrainer:
         with a process group over every rank's samples: two exchanges, so every rank calls it)."""
         if self._values is None:
             raise UpkieRuntimeError("call prepare(buffer) first")
-        if not hasattr(self._lib, "upkie_ppo_explained_variance"):
-            raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_ppo_explained_variance: rebuild it")
+        lib.require(self._lib, "upkie_ppo_explained_variance")
         lb, ret, val, out, ex = self._lib, self.returns.data_ptr(), self._values.data_ptr(), self._log_words.data_ptr(), self._ev_exchange
         with torch.cuda.device(self.device):  # (around the whole block: the collectives between the launches rely on it)
             if ex is None:
@@ -450,6 +438,19 @@ class PpoTrainer:
                 start += n
 
     # ---- state
+    def state_tensors(self) -> dict:
+        """Adam's moments and the control block (what `Ppo.save` carries)."""
+        return {"m": self.m, "v": self.v, "control": self.control}
+
+    def host_state(self) -> dict:
+        """The host's copies of what the control block holds: the values the setters and the schedules wrote last."""
+        return {"clip_range": self._clip_range, "clip_range_vf": self._clip_range_vf, "target_kl": self._target_kl, "lr": self._current_lr()}
+
+    def load_host_state(self, state: dict, progress_remaining: float) -> None:
+        """`host_state` of a saved run, and where its schedules stood (the control block itself is a tensor)."""
+        self._clip_range, self._clip_range_vf, self._target_kl, self._lr = (state[k] for k in ("clip_range", "clip_range_vf", "target_kl", "lr"))
+        self.progress_remaining = progress_remaining
+
     def _unpack(self, packed: torch.Tensor):
         flat = torch.zeros(sum(self._sizes) + 1, dtype=torch.float32, device=self.device)
         flat.index_copy_(0, self.policy._index, packed)
@@ -576,85 +577,59 @@ class Ppo:
         self._obs = getattr(env, "observation", None)
         if self._obs is None:
             self._obs = reset[0] if isinstance(reset, tuple) else reset
-        self._policy_obs = self._obs if self.pipeline is None else self.pipeline.reset(self._obs)
+        if self.pipeline is not None:
+            self.pipeline.reset(self._obs)
         if self.normalizer is not None:
-            self.normalizer.reset(self._policy_obs)
+            self.normalizer.reset(self._policy_observation())
         self._env_action = torch.empty(N, A, device=dev)
         self._starts = torch.ones(N, dtype=torch.uint8, device=dev)
         self._slot = self.n_steps - 1 if self.graph else 0  # (the capture's warm-up step takes the last slot)
         if self.graph:
             from .graphs import GraphedLoop
 
-            step = self._rollout_step if self.pipeline is None else self._rollout_step_pipeline
-            self._loop = GraphedLoop(step, unroll=T, warmup=1, device=dev)
+            self._loop = GraphedLoop(self._rollout_step, unroll=T, warmup=1, device=dev)
+
+    def _policy_observation(self) -> torch.Tensor:
+        """The observation the policy reads: the env's, or with a pipeline the stack of frames it keeps."""
+        return self._obs if self.pipeline is None else self.pipeline.observation
 
     def _rollout_step(self) -> None:
-        t, buf, pol, starts = self._slot, self.buffer, self.policy, self._starts
-        obs = self._obs
+        """One step of every env into slot ``_slot``. With an `AgentPipeline` between the policy and the env the policy
+        reads the stacked observation, the env receives the shaped command, the reward still sees the RAW observation,
+        and the normaliser and the bootstrap see the stack and its terminal form."""
+        t, buf, pol, starts, pipe = self._slot, self.buffer, self.policy, self._starts, self.pipeline
+        obs = self._policy_observation()
         buf.episode_starts[t].copy_(starts)
         out = {"action": buf.actions[t], "value": buf.values[t], "log_prob": buf.log_probs[t], "env_action": self._env_action}
         if self.normalizer is not None:
             out["norm_obs"] = buf.observations[t]
         else:
             buf.observations[t].copy_(obs)
-        action = pol.act(obs, out=out)[0]
+        pol.act(obs, out=out)
+        action = self._env_action if pipe is None else pipe.shape_action(self._env_action)  # (what the env receives)
         stepped = self.env.step(action)
         next_obs, reward, terminated, truncated = stepped[:4]
         info = stepped[4] if len(stepped) > 4 else {}
-        if next_obs is not obs:  # (an env without a persistent observation buffer)
-            self._obs = next_obs
+        self._obs = next_obs  # (an env without a persistent observation buffer hands out a new one)
+        final_obs = info.get("final_obs") if hasattr(info, "get") else None
         if self.reward_fn is not None:
             reward = self.reward_fn(next_obs, info)
         elif self.reward is not None:
-            reward = self.reward.step(next_obs, self._env_action, terminated, truncated, final_obs=info.get("final_obs") if hasattr(info, "get") else None)
+            reward = self.reward.step(next_obs, action, terminated, truncated, final_obs=final_obs)
         self.episodes.step(reward, terminated, truncated)  # Monitor: the raw reward
+        if self.bootstrap and final_obs is None:
+            raise UpkieRuntimeError("bootstrap_time_limits needs info['final_obs'] (an env with autoreset_mode='same_step'); "
+                                    "or build Ppo with bootstrap_time_limits=False")
+        if pipe is not None:
+            pipe.observe(next_obs, terminated, truncated, final_obs=final_obs)
+            next_obs, final_obs = pipe.observation, pipe.final_observation  # (what the normaliser and the bootstrap read)
         if self.normalizer is not None:
             self.normalizer.step(next_obs, reward, terminated, truncated, out={"reward": buf.rewards[t], "episode_starts": starts})
         else:
             buf.rewards[t].copy_(reward)
             torch.bitwise_or(terminated, truncated, out=starts)
         if self.bootstrap:
-            final_obs = info.get("final_obs") if hasattr(info, "get") else None
-            if final_obs is None:
-                raise UpkieRuntimeError("bootstrap_time_limits needs info['final_obs'] (an env with autoreset_mode='same_step'); "
-                                        "or build Ppo with bootstrap_time_limits=False")
             pol.bootstrap_time_limits(final_obs, terminated, truncated, buf.rewards[t], self.gamma)
-        self._slot = (t + 1) % self.n_steps
-
-    def _rollout_step_pipeline(self) -> None:
-        """`_rollout_step` with an `AgentPipeline` between the policy and the env: the policy reads the stacked
-        observation, the env receives the shaped command, the reward is the user's function of the RAW observation,
-        and the normaliser and the bootstrap see the stack and its terminal form."""
-        t, buf, pol, starts, pipe = self._slot, self.buffer, self.policy, self._starts, self.pipeline
-        buf.episode_starts[t].copy_(starts)
-        out = {"action": buf.actions[t], "value": buf.values[t], "log_prob": buf.log_probs[t], "env_action": self._env_action}
-        if self.normalizer is not None:
-            out["norm_obs"] = buf.observations[t]
-        else:
-            buf.observations[t].copy_(pipe.observation)
-        pol.act(pipe.observation, out=out)
-        command = pipe.shape_action(self._env_action)
-        stepped = self.env.step(command)
-        next_obs, reward, terminated, truncated = stepped[:4]
-        info = stepped[4] if len(stepped) > 4 else {}
-        self._obs = next_obs
-        final_obs = info.get("final_obs") if hasattr(info, "get") else None
-        if self.reward_fn is not None:
-            reward = self.reward_fn(next_obs, info)
-        elif self.reward is not None:  # (the RAW observation and the command the env received)
-            reward = self.reward.step(next_obs, command, terminated, truncated, final_obs=final_obs)
-        self.episodes.step(reward, terminated, truncated)  # Monitor: the raw reward
-        if self.bootstrap and final_obs is None:
-            raise UpkieRuntimeError("bootstrap_time_limits needs info['final_obs'] (an env with autoreset_mode='same_step'); "
-                                    "or build Ppo with bootstrap_time_limits=False")
-        pipe.observe(next_obs, terminated, truncated, final_obs=final_obs)
-        if self.normalizer is not None:
-            self.normalizer.step(pipe.observation, reward, terminated, truncated, out={"reward": buf.rewards[t], "episode_starts": starts})
-        else:
-            buf.rewards[t].copy_(reward)
-            torch.bitwise_or(terminated, truncated, out=starts)
-        if self.bootstrap:
-            pol.bootstrap_time_limits(pipe.final_observation, terminated, truncated, buf.rewards[t], self.gamma)
         self._slot = (t + 1) % self.n_steps
 
     def collect_rollouts(self) -> None:
@@ -662,14 +637,12 @@ class Ppo:
         if self._loop is not None:
             self._loop.replay()
         else:
-            step = self._rollout_step if self.pipeline is None else self._rollout_step_pipeline
             for _ in range(self.n_steps):
-                step()
+                self._rollout_step()
         self.num_timesteps += self.n_steps * self.n_envs
         buf = self.buffer
         buf.pos, buf.full = self.n_steps, True
-        last_obs = self._obs if self.pipeline is None else self.pipeline.observation
-        buf.compute_returns_and_advantage(last_values=self.policy.value(last_obs), dones=self._starts)
+        buf.compute_returns_and_advantage(last_values=self.policy.value(self._policy_observation()), dones=self._starts)
 
     def train(self) -> None:
         """SB3's ``PPO.train`` on the collected rollout: `PpoTrainer.prepare`, then the update (a graph replay when
@@ -726,16 +699,16 @@ class Ppo:
         named["final_obs"] = getattr(self.env, "_final_obs", None)
         return {k: v for k, v in named.items() if isinstance(v, torch.Tensor)}
 
+    # where a stage's `state_tensors` go under "tensors" in the file: stage -> (prefix, the names that differ from the stage's own)
+    _FILE_NAMES = {"policy": ("", {}), "trainer": ("", {}), "episodes": ("", {"counters": "ep_counters", "means": "ep_means"}),
+                   "pipeline": ("pipeline.", {}), "reward": ("reward.", {})}
+
     def _state_tensors(self):
-        tr, ep = self.trainer, self.episodes
-        named = {"packed": self.policy.packed, "m": tr.m, "v": tr.v, "control": tr.control, "calls": self.policy.calls, "starts": self._starts,
-                 "ep_return": ep.ep_return, "ep_length": ep.ep_length, "ring_return": ep.ring_return, "ring_length": ep.ring_length,
-                 "ep_counters": ep.counters, "ep_means": ep.means}
+        named = {"starts": self._starts}
         named.update({f"env.{k}": v for k, v in self._env_tensors().items()})
-        if self.pipeline is not None:
-            named.update({f"pipeline.{k}": v for k, v in self.pipeline.state_tensors().items()})
-        if self.reward is not None:
-            named.update({f"reward.{k}": v for k, v in self.reward.state_tensors().items()})
+        for stage, (prefix, renamed) in self._FILE_NAMES.items():
+            if getattr(self, stage) is not None:
+                named.update({renamed.get(k, prefix + k): v for k, v in getattr(self, stage).state_tensors().items()})
         return {k: v for k, v in named.items() if v is not None}
 
     def save(self, path) -> None:
@@ -747,7 +720,7 @@ class Ppo:
               "normalizer": self.normalizer.state_dict() if self.normalizer is not None else None,
               "counters": {"num_timesteps": self.num_timesteps, "iterations": self.iterations, "total_timesteps": self.total_timesteps,
                            "progress_remaining": self.progress_remaining, "policy_seed": int(self.policy.seed)},
-              "trainer": {"clip_range": tr._clip_range, "clip_range_vf": tr._clip_range_vf, "target_kl": tr._target_kl, "lr": tr._current_lr()},
+              "trainer": tr.host_state(),
               "sizes": {"n_envs": self.n_envs, "n_steps": self.n_steps}}
         torch.save(sd, path)
 
@@ -772,8 +745,6 @@ class Ppo:
         c = sd["counters"]
         model.num_timesteps, model.iterations, model.total_timesteps = c["num_timesteps"], c["iterations"], c["total_timesteps"]
         model.progress_remaining = c["progress_remaining"]
-        t = sd["trainer"]
-        tr._clip_range, tr._clip_range_vf, tr._target_kl, tr._lr = t["clip_range"], t["clip_range_vf"], t["target_kl"], t["lr"]
-        tr.progress_remaining = model.progress_remaining
+        tr.load_host_state(sd["trainer"], model.progress_remaining)
         tr.sync_modules()
         return model

@@ -17,7 +17,7 @@ import torch
 
 from . import abi, lib
 from .exceptions import UpkieRuntimeError
-from .launch import check, launcher, ptr
+from .launch import check, device_tensor, launcher, ptr
 
 Tap = namedtuple("Tap", ("source", "index", "fn", "coef"))
 _FNS = {None: abi.REWARD_FN_ID, "id": abi.REWARD_FN_ID, "sin": abi.REWARD_FN_SIN, "cos": abi.REWARD_FN_COS}
@@ -112,8 +112,7 @@ def pack_terms(obs_dim: int, act_dim: int, dt: float, terms, clip: Optional[Tupl
         shapes.append(SHAPES[term.shape]), weights.append(float(term.weight)), counts.append(len(term.taps))
         scales.append(float(term.scale) if term.shape in _SCALED else 1.0)
     library = lib.load()
-    if not hasattr(library, "upkie_reward_terms_step"):
-        raise UpkieRuntimeError("this build of libupkie_hip.so has no upkie_reward_terms_step: rebuild it")
+    lib.require(library, "upkie_reward_terms_step")
     ints = lambda v: (C.c_int32 * len(v))(*v)  # noqa: E731
     floats = lambda v: (C.c_float * len(v))(*v)  # noqa: E731
     out = C.create_string_buffer(abi.REWARD_PARAMS_BYTES)
@@ -164,33 +163,19 @@ class RewardTerms:
         self.finished = torch.zeros(N, dtype=torch.int32, device=self.device)
         self.reward = torch.zeros(N, dtype=torch.float32, device=self.device)
 
-    def _tensor(self, t, what, shape, dtypes=(torch.float32,), required=True):
-        if t is None:
-            if required:
-                raise ValueError(f"{what} is required")
-            return None
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise UpkieRuntimeError(f"{what} must be a device tensor (there is no CPU fallback)")
-        n = 1
-        for s in shape:
-            n *= s
-        if t.device != self.device or t.dtype not in dtypes or not t.is_contiguous() or t.numel() != n:
-            raise ValueError(f"{what} must be a contiguous {list(shape)} tensor of {' or '.join(map(str, dtypes))} on {self.device}")
-        return t
-
     def step(self, next_obs: torch.Tensor, action: torch.Tensor, terminated: Optional[torch.Tensor] = None,
              truncated: Optional[torch.Tensor] = None, final_obs: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One env step: ``next_obs`` / ``final_obs`` [N, D] float32 (``final_obs`` None: ``next_obs`` everywhere),
         ``action`` [N, A] float32, ``terminated`` / ``truncated`` [N] bool or uint8 (None: none). Returns the reward
         [N] float32, written into ``out`` when given (a rollout buffer's slot), else into `reward`."""
-        N, D, A = self.num_envs, self.obs_dim, self.act_dim
+        N, D, A, dev = self.num_envs, self.obs_dim, self.act_dim, self.device
         flags = (torch.bool, torch.uint8)
-        obs_ = self._tensor(next_obs, "next_obs", (N, D))
-        action = self._tensor(action, "action", (N, A))
-        term = self._tensor(terminated, "terminated", (N,), flags, required=False)
-        trunc = self._tensor(truncated, "truncated", (N,), flags, required=False)
-        final = self._tensor(final_obs, "final_obs", (N, D), required=False)
-        out = self.reward if out is None else self._tensor(out, "out", (N,))
+        obs_ = device_tensor(next_obs, "next_obs", dev, (N, D))
+        action = device_tensor(action, "action", dev, (N, A))
+        term = device_tensor(terminated, "terminated", dev, (N,), flags, required=False)
+        trunc = device_tensor(truncated, "truncated", dev, (N,), flags, required=False)
+        final = device_tensor(final_obs, "final_obs", dev, (N, D), required=False)
+        out = self.reward if out is None else device_tensor(out, "out", dev, (N,))
         self._launcher(self._lib.upkie_reward_terms_step, N, D, A, self.num_terms, self.params.data_ptr(), obs_.data_ptr(), action.data_ptr(),
                        ptr(term), ptr(trunc), ptr(final), self.prev_action.data_ptr(), self.term_sum.data_ptr(), self.term_last.data_ptr(),
                        self.finished.data_ptr(), out.data_ptr())
@@ -199,7 +184,7 @@ class RewardTerms:
     def reset(self, mask: Optional[torch.Tensor] = None) -> None:
         """Forget the running episodes of the envs with ``mask`` set ([N] bool or uint8; None: every env): their
         `term_sum` and `prev_action` go back to zero. `term_last` and `finished` are kept."""
-        mask = self._tensor(mask, "mask", (self.num_envs,), (torch.bool, torch.uint8), required=False)
+        mask = device_tensor(mask, "mask", self.device, (self.num_envs,), (torch.bool, torch.uint8), required=False)
         self._launcher(self._lib.upkie_reward_terms_reset, self.num_envs, self.act_dim, self.num_terms, ptr(mask), self.prev_action.data_ptr(),
                        self.term_sum.data_ptr())
 
