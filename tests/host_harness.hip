@@ -1,7 +1,8 @@
 // Test-only: runs the product's device functions on the HOST so that a single
 // physics substep can be compared with the oracle without a GPU.
-// (step_kernels.hpp + host_setup.hpp, not the C-ABI's units: no launch and none of their template kernels is instantiated, so this
-// builds in seconds; agent_pipeline.hpp, read for its two host inline functions, brings its one non-template kernel into the device pass)
+// (step_dispatch.hpp, which brings step_kernels.hpp, + host_setup.hpp, not the C-ABI's units: no launch and none of their template
+// kernels is instantiated, so this builds in seconds; agent_pipeline.hpp, read for its two host inline functions, brings random.hpp
+// and its one non-template kernel into the device pass, and nothing of the simulator)
 #include <string>
 
 #include "../upkie_amd/csrc/agent_pipeline.hpp"
@@ -284,4 +285,11 @@ extern "C" void harness_select_step_instances(int count, const int* facts, int* 
     out[0] = k.family, out[1] = k.rand, out[2] = k.waves, out[3] = k.spine, out[4] = k.bullet, out[5] = k.default_scalars;
     out[6] = k.in_place, out[7] = k.done_pass_follows, out[8] = k.refused;
   }
+}
+
+// The Philox4x32-10 rounds (csrc/random.hpp) on the host, for tests/test_device_arithmetic_on_host.py: counter [4], key [2], out [4].
+extern "C" void harness_philox4x32_10(const uint32_t* counter, const uint32_t* key, uint32_t* out) {
+  unsigned r[4];
+  upkie::philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1], r);
+  for (int i = 0; i < 4; ++i) out[i] = r[i];
 }

@@ -130,6 +130,32 @@ def test_the_build_watches_every_source_of_the_library():
     assert any(s.endswith("upkie_hip.h") for s in watched)
 
 
+SIMULATOR_HEADERS = ("step_kernels.hpp", "dynamics.hpp", "bullet_like.hpp", "mpc.hpp", "observers.hpp", "pair.hpp", "octet.hpp")
+
+
+@pytest.mark.parametrize("unit", ["trainer_abi.hip", "ppo_abi.hip"])
+def test_the_trainer_units_include_nothing_of_the_simulator(unit):
+    """the trainer's units share the device primitives (random.hpp, block_reduce.hpp) and the error
+    message with the simulator's unit, and none of its headers."""
+    source = os.path.join(ROOT, "upkie_amd", "csrc", unit)
+    made = subprocess.run(["hipcc", "--offload-arch=gfx950", "-std=c++17", "-M", source], check=True, capture_output=True, text=True).stdout
+    named = {os.path.basename(word) for word in made.replace("\\\n", " ").split()}
+    assert "random.hpp" in named and "abi_host.hpp" in named, sorted(n for n in named if n.endswith(".hpp"))
+    assert not named & set(SIMULATOR_HEADERS), sorted(named & set(SIMULATOR_HEADERS))
+
+
+@pytest.mark.parametrize("header", ["random.hpp", "block_reduce.hpp"])
+def test_the_shared_device_primitives_stand_alone(header):
+    """A file that includes one of the two headers and nothing else compiles: neither leans on what its includers bring."""
+    csrc = os.path.join(ROOT, "upkie_amd", "csrc")
+    with tempfile.TemporaryDirectory() as tmp:
+        source = os.path.join(tmp, "alone.hip")
+        with open(source, "w") as f:
+            f.write(f'#include "{header}"\nint main() {{ return 0; }}\n')
+        result = subprocess.run(["hipcc", "--offload-arch=gfx950", "-std=c++17", "-I", csrc, "-fsyntax-only", source], capture_output=True, text=True)
+    assert result.returncode == 0, result.stderr
+
+
 def test_observer_filter_error_is_reported_without_a_gpu(library):
     """low_pass_filter throws FilterError when cutoff <= 2 dt
     (upkie/cpp/utils/low_pass_filter.h:22-30): the C-ABI reports it at create,

@@ -34,6 +34,21 @@ def harness():
     return C.CDLL(LIB)
 
 
+def test_philox_rounds_known_answer(harness):
+    """The product's Philox4x32-10 rounds (csrc/random.hpp), compiled for the host, give the Random123 known-answer
+    vectors the oracle's are held to (tests/test_oracle_golden.py::test_philox_known_answer): the integers, exactly."""
+
+    def philox(counter, key):
+        out = (C.c_uint32 * 4)()
+        harness.harness_philox4x32_10((C.c_uint32 * 4)(*counter), (C.c_uint32 * 2)(*key), out)
+        return list(out)
+
+    assert philox([0, 0, 0, 0], [0, 0]) == [0x6627E8D5, 0xE169C58D, 0xBC57AC4C, 0x9B00DBD8]
+    assert philox([0xFFFFFFFF] * 4, [0xFFFFFFFF] * 2) == [0x408F276D, 0x41C83B0E, 0xA20BC7C6, 0x6D5451FD]
+    assert philox([0x243F6A88, 0x85A308D3, 0x13198A2E, 0x03707344], [0xA4093822, 0x299F31D0]) == [
+        0xD16CFE09, 0x94FDCCEB, 0x5001E420, 0x24126EA1]
+
+
 def random_state(rng, on_floor: bool):
     s = np.zeros(abi.STATE_WORDS)
     pitch = rng.uniform(-0.3, 0.3)

@@ -16,8 +16,8 @@
 // captured graph). shape_action gives a wavefront floor(64 / A) envs, one lane per command word, for the same reason:
 // the lane that advances an env's counter shares a wavefront with every lane that reads it.
 //
-// Noise: Philox4x32-10 with counter (env, call, 0, STREAM_PIPELINE << 24 | block) under the pipeline's seed, Box-Muller
-// as policy_mlp.hpp's mlp_normal4 (four normals per block). shape_action draws action a from element a & 3 of block
+// Noise: Philox4x32-10 with counter (env, call, 0, STREAM_PIPELINE << 24 | block) under the pipeline's seed, random.hpp's
+// box_muller (four normals per block). shape_action draws action a from element a & 3 of block
 // a >> 2; observe draws column d of the new frame from element d & 3 of block d >> 2 and column d of the terminal
 // frame from block 64 + (d >> 2). Every noisy call of an env uses the env's counter once and advances it, so no two
 // calls share a block; without noise no Philox round is executed and the counters stay.
@@ -27,12 +27,9 @@
 
 #include <cstdint>
 
-#include "step_kernels.hpp"  // philox4x32_10
+#include "random.hpp"
 
 namespace upkie {
-
-// Tag of the pipeline's Philox draws (the step kernels use tags 0-3, the MLP policy 4).
-enum { STREAM_PIPELINE = 5 };
 
 enum { PIPELINE_THREADS = 256, PIPELINE_WAVE_WORDS = 256, PIPELINE_FINAL_BLOCK = 64 };
 
@@ -65,18 +62,14 @@ inline int pipeline_blocks(int num_envs, int group) {
 
 #if defined(__HIPCC__)
 
-// Element `elem` of the four standard normals of one Philox block (the arithmetic of mlp_normal4).
+// Element `elem` of the four standard normals of one Philox block (box_muller on words 0-1 or 2-3, the pair that holds it).
 __device__ __forceinline__ float pipeline_normal(unsigned env, unsigned call, unsigned block, unsigned elem, unsigned k0, unsigned k1) {
   unsigned r[4];
   philox4x32_10(env, call, 0u, ((unsigned)STREAM_PIPELINE << 24) | block, k0, k1, r);
   const unsigned p = elem >> 1;
-  const unsigned ra = p ? r[2] : r[0], rb = p ? r[3] : r[1];
-  const float u1 = ((float)(ra >> 8) + 1.0f) * (1.0f / 16777216.0f);
-  const float u2 = (float)(rb >> 8) * (1.0f / 16777216.0f);
-  const float radius = sqrtf(-2.0f * logf(u1));
-  float sn, cs;
-  sincosf(6.283185307179586f * u2, &sn, &cs);
-  return radius * ((elem & 1u) ? sn : cs);
+  float z_cos, z_sin;
+  box_muller(p ? r[2] : r[0], p ? r[3] : r[1], z_cos, z_sin);
+  return (elem & 1u) ? z_sin : z_cos;
 }
 
 __device__ __forceinline__ float pipeline_clip(float v, float low, float high) { return fminf(fmaxf(v, low), high); }

@@ -6,16 +6,15 @@
 // One launch per env step. Block b owns envs [b R, (b + 1) R) and walks them 256 at a time in env order: every env adds
 // (double)reward and 1 to its accumulators; an env with terminated | truncated set finishes its episode, zeroes its
 // accumulators and appends (return, length) to the block's segment of the workspace, in env order (a wave ballot and
-// a prefix over the block's four waves), and the block writes its count of finished episodes. Then the ticket of
-// vecnorm.hpp (cdna_hip_programming.md, "In-launch split-K reduction"): every wave drains its stores, lane 0 releases
-// at agent scope and draws a ticket; the block that draws blocks - 1 acquires and does the ordered work alone: an
+// a prefix over the block's four waves), and the block writes its count of finished episodes. Then the ticket
+// (block_reduce.hpp): the block that arrives last does the ordered work alone: an
 // exclusive prefix of the blocks' counts (in LDS) gives every finished episode of the step its index g in env order;
 // of the `total` finished, the last keep = min(total, window) enter the ring at head, head + 1, ... (a deque of
 // maxlen window: what more than `window` finishers push out of it never lands), each found by a binary search of the
 // prefix; the means are recomputed in ring order, oldest to newest (the ring staged through LDS by the whole block, 1024
-// entries at a time, then summed by one thread: the return sum sequential in fp64, the length sum exact in int64), and the
-// ticket goes back to 0. The last block reads one count per block and at most `window`
-// finished episodes. No block waits on another, no float atomics: the same bits every call and under graph replay.
+// entries at a time, then summed by one thread: the return sum sequential in fp64, the length sum exact in int64). The
+// last block reads one count per block and at most `window` finished episodes: the same bits every call and under
+// graph replay.
 //
 // Launch R (reset): the accumulators of the masked envs (all without a mask) back to zero; no episode is recorded and
 // the ring is kept (Monitor.reset).
@@ -24,6 +23,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "block_reduce.hpp"
 
 namespace upkie {
 
@@ -101,25 +102,8 @@ __global__ __launch_bounds__(EPISODES_THREADS) void episodes_step_kernel(const E
   }
   if (tid == 0) P.counts[blockIdx.x] = done_in_block;
 
-  // publish and draw a ticket: agent-scope release before the fetch_add, acquire in the last arriver
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned ticket = __hip_atomic_fetch_add(P.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool last = ticket == (unsigned)(P.blocks - 1);
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    wave_n[EPISODES_THREADS / 64] = last ? 1 : 0;
-  }
-  __syncthreads();
-  if (wave_n[EPISODES_THREADS / 64] == 0) return;
-
-  // the last arriver: every block's count and segment is visible
-  if (tid == 0) __hip_atomic_store(P.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // publish and draw a ticket (block_reduce.hpp); the last arriver goes on, with every block's count and segment visible
+  if (!ticket_last_block(P.ticket, P.blocks, &wave_n[EPISODES_THREADS / 64])) return;
   constexpr int PER = EPISODES_MAX_BLOCKS / EPISODES_THREADS;  // blocks per thread in the prefix
   int own[PER], sum = 0;
 #pragma unroll

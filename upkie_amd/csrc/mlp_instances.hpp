@@ -4,9 +4,6 @@
 
 #include <type_traits>
 
-// (policy_mlp.hpp reads the Philox rounds of step_kernels.hpp, which brings the MPC and observer headers with it: their
-// non-template kernels are defined by upkie_hip.hip alone)
-#define UPKIE_STEP_INSTANCES_ONLY 1
 #include "policy_mlp.hpp"
 
 // The instantiation of a kernel template <int W, int ACT> that runs `shape`: launch(width class, activation), both as

@@ -35,12 +35,9 @@
 #include <cstdint>
 
 #include "../../include/upkie_hip.h"
-#include "step_kernels.hpp"  // philox4x32_10
+#include "random.hpp"
 
 namespace upkie {
-
-// Tag of the policy's Philox draws (top byte of counter word 3; the step kernels use tags 0-3).
-enum { STREAM_POLICY = 4 };
 
 struct MlpLayerDev {
   int w_off, b_off;  // words into the packed buffer
@@ -245,20 +242,12 @@ __device__ __forceinline__ void mlp_tower(const float* __restrict__ packed, cons
   else mlp_dense<WT, ACT, false, false>(packed, T.head, obs_dim, h, out, lane);
 }
 
-// Box-Muller on one Philox4x32-10 block: four standard normals. u1 = (r0 >> 8) + 1 over 2^24 lies in (0, 1] (never 0).
+// The four standard normals of one Philox4x32-10 block of the policy's stream (random.hpp: box_muller on words 0-1, 2-3).
 __device__ __forceinline__ void mlp_normal4(unsigned env, unsigned call, unsigned block, unsigned k0, unsigned k1, float (&z)[4]) {
   unsigned r[4];
   philox4x32_10(env, call, 0u, ((unsigned)STREAM_POLICY << 24) | block, k0, k1, r);
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const float u1 = ((float)(r[2 * p] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    const float u2 = (float)(r[2 * p + 1] >> 8) * (1.0f / 16777216.0f);
-    const float radius = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincosf(6.283185307179586f * u2, &sn, &cs);
-    z[2 * p] = radius * cs;
-    z[2 * p + 1] = radius * sn;
-  }
+  box_muller(r[0], r[1], z[0], z[1]);
+  box_muller(r[2], r[3], z[2], z[3]);
 }
 
 template <int W, int ACT>

@@ -23,9 +23,9 @@
 // per lane, then a fixed shuffle tree and wave order) go to a per-block stats partial.
 //
 // Launch B, fold: thread i sums word i of the G partials in block order (+ the entropy term of log_std), writes the
-// minibatch gradient and its square; a fixed LDS tree gives one sum of squares per block; the vecnorm ticket
-// (agent-scope release / acquire, last arriver, counter reset in-kernel) lets the last block form ||g||, the clip
-// coefficient, the statistics row, t += 1 and Adam's bias corrections, all in a fixed order.
+// minibatch gradient and its square; a fixed LDS tree gives one sum of squares per block; the ticket (block_reduce.hpp)
+// lets the last block form ||g||, the clip coefficient, the statistics row, t += 1 and Adam's bias corrections, all in
+// a fixed order.
 //
 // Launch C, Adam: element-wise over the trainable words (log_std_off on; the fixed obs_mean / obs_std / action bounds
 // before it are never written; padding words have a zero gradient, so m, v and the word stay 0).
@@ -60,6 +60,7 @@
 #include <cstdint>
 
 #include "../../include/upkie_hip.h"
+#include "block_reduce.hpp"
 #include "policy_mlp.hpp"
 
 namespace upkie {
@@ -538,37 +539,17 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fold_kernel(const PpoDev P) {
   }
   double sq = 0.0;
   if (i < P.train_words) {
-    float s = 0.f;
-    const float* p = P.partials + i;
-    int b = 0;
-    for (; b + 32 <= P.grid; b += 32) {  // (32 loads in flight, added in block order)
-      float x[32];
-#pragma unroll
-      for (int k = 0; k < 32; ++k) x[k] = p[(size_t)(b + k) * P.part_stride];
-#pragma unroll
-      for (int k = 0; k < 32; ++k) s += x[k];
-    }
-    for (; b < P.grid; ++b) s += p[(size_t)b * P.part_stride];
+    float s = fold_in_block_order(P.partials + i, P.grid, P.part_stride);
     if (i < P.net.act_dim) s -= P.ent_coef;  // d(ent_coef * entropy_loss) / d log_std_a
     P.grad[i] = s;
     sq = (double)s * (double)s;
   }
   lds[tid] = sq;
-  for (int h = PPO_THREADS / 2; h > 0; h >>= 1) {
-    __syncthreads();
-    if (tid < h) lds[tid] += lds[tid + h];
-  }
-  __syncthreads();
+  lds_tree_sum<PPO_THREADS>(tid, lds);
   if (tid == 0) P.sq_partials[blockIdx.x] = lds[0];
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (tid != 0) return;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const unsigned ticket = __hip_atomic_fetch_add(P.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (ticket != (unsigned)(P.fold_blocks - 1)) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (tid != 0 || !ticket_draw(P.ticket, P.fold_blocks)) return;  // (block_reduce.hpp; thread 0 of the last block goes on alone)
   __hip_atomic_store(P.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   double total = 0.0;
   for (int b = 0; b < P.fold_blocks; ++b) total += P.sq_partials[b];
@@ -614,20 +595,7 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fold_kernel(const PpoDev P) {
 __global__ __launch_bounds__(PPO_THREADS) void ppo_local_fold_kernel(const PpoDev P) {
   const int tid = threadIdx.x, i = blockIdx.x * PPO_THREADS + tid;
   if (P.ctrl && P.ctrl[PPO_CTRL_STOPPED] != 0.0) return;  // (the slot keeps its last contents: launch B ignores them)
-  if (i < P.train_words) {
-    float s = 0.f;
-    const float* p = P.partials + i;
-    int b = 0;
-    for (; b + 32 <= P.grid; b += 32) {
-      float x[32];
-#pragma unroll
-      for (int k = 0; k < 32; ++k) x[k] = p[(size_t)(b + k) * P.part_stride];
-#pragma unroll
-      for (int k = 0; k < 32; ++k) s += x[k];
-    }
-    for (; b < P.grid; ++b) s += p[(size_t)b * P.part_stride];
-    P.slot[i] = s;
-  }
+  if (i < P.train_words) P.slot[i] = fold_in_block_order(P.partials + i, P.grid, P.part_stride);
   if (blockIdx.x != 0) return;
   const int at = (P.train_words + 1) & ~1;
   if (tid < PPO_STATS) {
@@ -670,11 +638,7 @@ __device__ __forceinline__ double ppo_adv_pass(double* lds, int n, int start, co
     for (int k = 0; k < 8; ++k) s += square ? x[k] * x[k] : x[k];
   }
   lds[tid] = s;
-  for (int h = PPO_ADV_THREADS / 2; h > 0; h >>= 1) {
-    __syncthreads();
-    if (tid < h) lds[tid] += lds[tid + h];
-  }
-  __syncthreads();
+  lds_tree_sum<PPO_ADV_THREADS>(tid, lds);
   const double r = lds[0];
   __syncthreads();
   return r;
@@ -768,11 +732,7 @@ __device__ __forceinline__ void ppo_ev_pass(double (*lds)[PPO_ADV_THREADS], int 
     for (int k = 0; k < 8; ++k) sy += square ? y[k] * y[k] : y[k], sd += square ? d[k] * d[k] : d[k];
   }
   lds[0][tid] = sy, lds[1][tid] = sd;
-  for (int h = PPO_ADV_THREADS / 2; h > 0; h >>= 1) {
-    __syncthreads();
-    if (tid < h) lds[0][tid] += lds[0][tid + h], lds[1][tid] += lds[1][tid + h];
-  }
-  __syncthreads();
+  lds_tree_sum<PPO_ADV_THREADS>(tid, lds[0], lds[1]);
   *sum_y = lds[0][0], *sum_d = lds[1][0];
   __syncthreads();
 }

@@ -1,8 +1,8 @@
 // step_kernels.hpp -- the fused env.step() kernels (one, two and eight lanes per env) and what they share: the
-// settings blocks, Philox streams, the servo torque law, the action and observation maps. Included by upkie_hip.hip (the
-// simulator's unit of the C-ABI, which only DECLARES the instantiations it launches: step_instances.hpp), by
-// step_instances.hip (which defines them, one group per translation unit so that the library builds on all cores) and,
-// for the Philox rounds alone, by policy_mlp.hpp.
+// settings blocks, the servo torque law, the action and observation maps. Included by upkie_hip.hip (the simulator's
+// unit of the C-ABI, which only DECLARES the instantiations it launches: step_instances.hpp) and by step_instances.hip
+// (which defines them, one group per translation unit so that the library builds on all cores). The Philox streams are
+// random.hpp's, which the trainer's kernels include without this file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 #include "bullet_like.hpp"
 #include "mpc.hpp"
 #include "observers.hpp"
+#include "random.hpp"
 #include "wave_io.hpp"
 
 namespace upkie {
@@ -83,62 +84,6 @@ struct BaseVelocityPtrs {
   float* mpc_ws = nullptr;
   float* mpc_commanded = nullptr;
 };
-
-// ------------------------------------------------------------------ Philox
-// Philox4x32-10 (Salmon et al., SC'11): counter = (env id lo/hi, episode,
-// stream<<24 | block), key = seed: results do not depend on how envs are sharded.
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned (&out)[4]) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    unsigned n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-enum { STREAM_RESET = 0, STREAM_NOISE = 1, STREAM_INERTIA = 2, STREAM_PUSH = 3 };
-
-template <class ConfigT>
-__device__ __forceinline__ void philox_uniform4(const ConfigT& C, unsigned env_local, unsigned episode, unsigned stream,
-                                                unsigned block, float (&u)[4]) {
-  unsigned lo = C.env_lo + env_local;
-  unsigned hi = C.env_hi + (lo < C.env_lo ? 1u : 0u);
-  unsigned r[4];
-  philox4x32_10(lo, hi, episode, (stream << 24) | block, C.seed_lo, C.seed_hi, r);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) u[i] = (float)(r[i] >> 8) * (1.0f / 16777216.0f);
-}
-
-// Six standard normals for (env, step, slot): Box-Muller on two Philox blocks.
-// slot = substep index (control noise) or NOISE_SLOT_MEASUREMENT.
-#define NOISE_SLOT_MEASUREMENT 0x7fffu
-template <class ConfigT>
-__device__ __forceinline__ void philox_normal6(const ConfigT& C, unsigned env_local, unsigned step, unsigned slot, float (&z)[6]) {
-  unsigned lo = C.env_lo + env_local;
-  unsigned hi = C.env_hi + (lo < C.env_lo ? 1u : 0u);
-  unsigned r[8];
-#pragma unroll
-  for (unsigned k = 0; k < 2; ++k) {
-    unsigned q[4];
-    philox4x32_10(lo, hi, step, ((unsigned)STREAM_NOISE << 24) | (slot * 2u + k), C.seed_lo, C.seed_hi, q);
-    r[4 * k] = q[0]; r[4 * k + 1] = q[1]; r[4 * k + 2] = q[2]; r[4 * k + 3] = q[3];
-  }
-#pragma unroll
-  for (int p = 0; p < 3; ++p) {
-    float u1 = ((float)(r[2 * p] >> 8) + 1.0f) * (1.0f / 16777216.0f);  // (0, 1]
-    float u2 = (float)(r[2 * p + 1] >> 8) * (1.0f / 16777216.0f);
-    float radius = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincosf(6.283185307179586f * u2, &sn, &cs);
-    z[2 * p] = radius * cs;
-    z[2 * p + 1] = radius * sn;
-  }
-}
 
 __device__ __forceinline__ float uniform(float low, float high, float u) { return fmaf(high - low, u, low); }
 

@@ -11,12 +11,9 @@
 // row). A returns lane also updates the env's return in place
 // (returns = returns * gamma + reward, then 0 when the env is done). The lanes of a column are merged by Chan's formula
 // in a fixed binary tree in LDS, and the block writes one partial (mean[cols], M2[cols]; its count is its number of
-// envs) to the workspace. Then the ticket (cdna_hip_programming.md, "In-launch split-K reduction"): every wave drains
-// its stores, lane 0 releases at agent scope and draws a ticket; the block that draws blocks - 1 acquires, merges all
-// partials (the same fixed order every call), folds the batch into the running statistics by RunningMeanStd's update,
-// writes them in place with their fp32 mirrors (and a policy's packed obs_mean / obs_std words, csrc/policy_mlp.hpp),
-// and puts the ticket back to 0 for the next launch. No block ever waits on another: a block that is not last just
-// exits. No float atomics: the result does not depend on arrival order, so it is bit-for-bit deterministic.
+// envs) to the workspace. Then the ticket (block_reduce.hpp): the block that arrives last merges all partials (the same
+// fixed order every call), folds the batch into the running statistics by RunningMeanStd's update and writes them in
+// place with their fp32 mirrors (and a policy's packed obs_mean / obs_std words, csrc/policy_mlp.hpp).
 //
 // Launch B, apply (when a per-env output needs the NEW statistics: a normalised reward or normalised observations, or
 // when no statistic moves). Grid-stride over envs and over observation words: reward / sqrt(ret_var + eps) in fp64,
@@ -39,6 +36,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "block_reduce.hpp"
 
 namespace upkie {
 
@@ -223,25 +222,8 @@ __global__ __launch_bounds__(VECNORM_THREADS) void vecnorm_moments_kernel(const 
     for (int r = r0 + tid; r < r1; r += VECNORM_THREADS) vecnorm_env(P, r, ret_std);
   }
 
-  // publish the partial and draw a ticket: agent-scope release before the fetch_add, acquire in the last arriver
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned ticket = __hip_atomic_fetch_add(P.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool last = ticket == (unsigned)(P.blocks - 1);
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    lds[3 * VECNORM_THREADS] = last ? 1.0 : 0.0;
-  }
-  __syncthreads();
-  if (lds[3 * VECNORM_THREADS] == 0.0) return;
-
-  // the last arriver: every partial is visible; the ticket goes back to 0 for the next launch
-  if (tid == 0) __hip_atomic_store(P.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // publish the partial and draw a ticket (block_reduce.hpp); the last arriver goes on, with every partial visible
+  if (!ticket_last_block(P.ticket, P.blocks, &lds[3 * VECNORM_THREADS])) return;
   const int D = P.obs_dim;
   for (int c0 = 0; c0 < cols; c0 += VECNORM_THREADS) {
     const int g = min(cols - c0, (int)VECNORM_THREADS), slots = min(P.blocks, VECNORM_THREADS / g);

@@ -39,6 +39,8 @@ SOURCES = [
     os.path.join(_CSRC, "pair.hpp"),
     os.path.join(_CSRC, "octet.hpp"),
     os.path.join(_CSRC, "observers.hpp"),
+    os.path.join(_CSRC, "random.hpp"),
+    os.path.join(_CSRC, "block_reduce.hpp"),
     os.path.join(_CSRC, "rollout.hpp"),
     os.path.join(_CSRC, "policy_mlp.hpp"),
     os.path.join(_CSRC, "vecnorm.hpp"),
@@ -214,7 +216,7 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
         os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
         tag = f"{LIB_PATH}.{os.getpid()}"
         # (the heaviest units first, so that the build ends when the total work does, not when a late-started heavy unit
-        # does. Alone on one core: the PPO unit 112 s and the trainer unit 58 s -- thirty MFMA template kernels between them,
+        # does. Alone on one core: the PPO unit 107 s and the trainer unit 58 s -- thirty MFMA template kernels between them,
         # the build is as long as the first of the two --, a one-lane group, 0-7, 19 s, the simulator's unit 11 s)
         units = [(PPO_ABI_SOURCE, [], f"{tag}.ppo.o"), (TRAINER_ABI_SOURCE, [], f"{tag}.trainer.o")]
         units += [(INSTANCES_SOURCE, [f"-DUPKIE_INSTANCE_GROUP={g}"], f"{tag}.g{g}.o") for g in range(8)]
