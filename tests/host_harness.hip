@@ -2,12 +2,15 @@
 // physics substep can be compared with the oracle without a GPU.
 // (step_dispatch.hpp, which brings step_kernels.hpp, + host_setup.hpp, not the C-ABI's units: no launch and none of their template
 // kernels is instantiated, so this builds in seconds; agent_pipeline.hpp, read for its two host inline functions, brings random.hpp
-// and its one non-template kernel into the device pass, and nothing of the simulator)
+// and its one non-template kernel into the device pass, and nothing of the simulator; episodes.hpp and vecnorm.hpp, read for
+// their host inline launch plans, bring their five kernels)
 #include <string>
 
 #include "../upkie_amd/csrc/agent_pipeline.hpp"
+#include "../upkie_amd/csrc/episodes.hpp"
 #include "../upkie_amd/csrc/host_setup.hpp"
 #include "../upkie_amd/csrc/step_dispatch.hpp"
+#include "../upkie_amd/csrc/vecnorm.hpp"
 
 extern "C" int harness_substep(const UpkieModel* model, float* st, const float* tau, float h, const float* records,
                                const float* ext_forces, const UpkieExternalForces* ext_slots) {
@@ -272,6 +275,12 @@ extern "C" int harness_pipeline_sizes(int obs_dim, int act_dim, int stack, int a
   return 1;
 }
 extern "C" int harness_pipeline_blocks(int num_envs, int group) { return upkie::pipeline_blocks(num_envs, group); }
+
+// The launch plans of the two ticketed reductions of the rollout side (csrc/episodes.hpp, csrc/vecnorm.hpp: host inline
+// functions), for tests/test_reduction_matrix.py: the grid, and the envs per block in *rows.
+extern "C" int harness_episodes_blocks(int num_envs, int* rows) { return upkie::episodes_blocks(num_envs, rows); }
+extern "C" int64_t harness_episodes_workspace_bytes(int num_envs) { return upkie::episodes_workspace_bytes(num_envs); }
+extern "C" int harness_vecnorm_blocks(int num_envs, int obs_dim, int* rows) { return upkie::vecnorm_blocks(num_envs, obs_dim, rows); }
 
 // The choice of the step kernel (csrc/step_dispatch.hpp), for tests/test_step_dispatch.py: `count` rows, facts [count][13] =
 // the fields of StepFacts in their order, out [count][9] = the fields of StepInstance in theirs.
