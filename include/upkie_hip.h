@@ -1250,6 +1250,63 @@ int upkie_episodes_step(int32_t num_envs, int32_t window, const float* reward, c
 
 int upkie_episodes_reset(int32_t num_envs, const uint8_t* mask, double* ep_return, int32_t* ep_length, void* stream);
 
+/* ---- Evaluation tally (SB3 evaluate_policy's bookkeeping) ---------------
+ * N = num_envs envs give E = n_eval_episodes episodes between them, E at most
+ * `capacity`, the length of the record buffers (csrc/eval_episodes.hpp).
+ * State, device buffers:
+ *   ep_return [N] fp64, ep_length [N] int32: the running episode of each env
+ *   count [N] int32: episodes the env has given
+ *   target [N] int32: its quota, target[n] = (E + n) / N (integer division;
+ *     the quotas sum to E; with N > E only the last E envs count, as in SB3)
+ *   rec_return [capacity] fp64, rec_length, rec_env [capacity] int32,
+ *   rec_truncated [capacity] bytes: the records, E of them when full
+ *   counters [2] int64: filled (records so far), steps (steps begun with
+ *     filled < E: what the evaluation took)
+ *   summary [7] fp64, see below
+ * upkie_eval_reset (one launch): ep_return, ep_length, count, counters and
+ * summary to 0, target written for E. The records are not cleared: those
+ * behind `filled` mean nothing.
+ * One step (one launch), for every env n with count[n] < target[n] (an env at
+ * its quota is left alone), term = terminated[n] != 0, trunc = truncated[n]
+ * != 0 (bytes, NULL: none):
+ *   ep_return[n] += (double)reward[n];  ep_length[n] += 1   (the fp64 sum in
+ *     step order, as Python's sum over the episode's rewards)
+ *   with term | trunc: the record (ep_return[n], ep_length[n], n,
+ *     trunc & !term) is appended, count[n] += 1 and the accumulators go back
+ *     to 0.
+ *   The step's records are appended at `filled` in increasing n, so that the
+ *   list is step-major and env-minor: the order SB3's loop appends in. The
+ *   list cannot overflow (the quotas sum to E); every store is bounded by E
+ *   all the same.
+ * In the step in which filled reaches E, and in no other, summary is written
+ * from the records r_k, l_k, t_k, k = 0 .. E - 1, in that order:
+ *   [0] mean_r = (r_0 + r_1 + ... + r_{E-1}) / E, fp64, summed sequentially
+ *   [1] ((r_0 - mean_r)^2 + ... + (r_{E-1} - mean_r)^2) / E, a second pass,
+ *       sequential, every difference, square and sum rounded (no fused
+ *       multiply-add): the population variance (numpy's std squared)
+ *   [2] mean_l = (l_0 + ... + l_{E-1}) / E (integer sum, one rounding)
+ *   [3] the same second pass over (double)l_k - mean_l
+ *   [4] min r_k, [5] max r_k (x < min and x > max from r_0)
+ *   [6] (t_0 + ... + t_{E-1}) / E: the share of episodes the time limit ended
+ * Square roots are the host's. numpy sums pairwise, so np.mean of the same
+ * records may differ in the last bits.
+ * workspace: upkie_eval_workspace_bytes(N) bytes, zeroed once before the
+ * first step (every step leaves its counter at zero again). No block waits
+ * on another, no float atomics, no allocation, no host synchronisation, no
+ * host argument that changes between steps: the same bits every call, and the
+ * step can be captured in a hipGraph. Bad sizes and NULL buffers are refused
+ * before any device use. No CPU fallback: UPKIE_ERR_NO_DEVICE without a HIP
+ * device. Errors are reported through upkie_sim_last_error(NULL). */
+int64_t upkie_eval_workspace_bytes(int32_t num_envs);
+
+int upkie_eval_reset(int32_t num_envs, int32_t capacity, int32_t n_eval_episodes, double* ep_return, int32_t* ep_length,
+                     int32_t* count, int32_t* target, int64_t* counters, double* summary, void* stream);
+
+int upkie_eval_step(int32_t num_envs, int32_t capacity, int32_t n_eval_episodes, const float* reward, const uint8_t* terminated,
+                    const uint8_t* truncated, double* ep_return, int32_t* ep_length, int32_t* count, const int32_t* target,
+                    double* rec_return, int32_t* rec_length, int32_t* rec_env, uint8_t* rec_truncated, int64_t* counters,
+                    double* summary, void* workspace, void* stream);
+
 /* ---- Agent pipeline (action shaping, noise, VecFrameStack) --------------
  * What an agent wraps around the env before PPO sees it, csrc/
  * agent_pipeline.hpp: N = num_envs envs, D = obs_dim words per env

@@ -1,5 +1,5 @@
 // trainer_abi.hip -- handle-free entry points of include/upkie_hip.h around a rollout: the MLP actor-critic policy, the
-// time-limit bootstrap, episode statistics, the agent pipeline, the reward terms, VecNormalize, the linear policy and GAE. Host code around the kernels of the
+// time-limit bootstrap, episode statistics, the evaluation tally, the agent pipeline, the reward terms, VecNormalize, the linear policy and GAE. Host code around the kernels of the
 // headers below; nothing here takes or touches a simulator, MPC or observer handle (upkie_hip.hip). The PPO update, the
 // other heavy set of kernel instantiations, is ppo_abi.hip's.
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include "vecnorm.hpp"
 #include "time_limits.hpp"
 #include "episodes.hpp"
+#include "eval_episodes.hpp"
 #include "agent_pipeline.hpp"
 #include "reward_terms.hpp"
 
@@ -120,6 +121,59 @@ extern "C" int upkie_episodes_reset(int32_t num_envs, const uint8_t* mask, doubl
   const int grid = std::min((num_envs + upkie::EPISODES_THREADS - 1) / upkie::EPISODES_THREADS, 1024);
   hipLaunchKernelGGL(upkie::episodes_reset_kernel, dim3((unsigned)grid), dim3(upkie::EPISODES_THREADS), 0, (hipStream_t)stream, num_envs, mask,
                      ep_return, ep_length);
+  return launch_status();
+}
+
+// ============================================================ evaluation tally (SB3 evaluate_policy's bookkeeping)
+static int check_eval_shape(int32_t num_envs, int32_t capacity, int32_t n_eval_episodes) {
+  if (num_envs <= 0 || capacity < 1) return fail(UPKIE_ERR_INVALID_ARGUMENT, "eval: num_envs and capacity must be positive");
+  if (n_eval_episodes < 1 || n_eval_episodes > capacity)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "eval: n_eval_episodes must be in 1-capacity (the record buffers hold `capacity` entries)");
+  return UPKIE_OK;
+}
+
+extern "C" int64_t upkie_eval_workspace_bytes(int32_t num_envs) {
+  if (check_eval_shape(num_envs, 1, 1)) return UPKIE_ERR_INVALID_ARGUMENT;
+  return upkie::eval_workspace_bytes(num_envs);
+}
+
+extern "C" int upkie_eval_reset(int32_t num_envs, int32_t capacity, int32_t n_eval_episodes, double* ep_return, int32_t* ep_length,
+                                int32_t* count, int32_t* target, int64_t* counters, double* summary, void* stream) {
+  if (check_eval_shape(num_envs, capacity, n_eval_episodes)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!ep_return || !ep_length || !count || !target || !counters || !summary) return fail(UPKIE_ERR_INVALID_ARGUMENT, "eval: null state buffer");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  const int grid = std::min((num_envs + upkie::EPISODES_THREADS - 1) / upkie::EPISODES_THREADS, 1024);
+  hipLaunchKernelGGL(upkie::eval_reset_kernel, dim3((unsigned)grid), dim3(upkie::EPISODES_THREADS), 0, (hipStream_t)stream, num_envs,
+                     n_eval_episodes, ep_return, ep_length, count, target, counters, summary);
+  return launch_status();
+}
+
+extern "C" int upkie_eval_step(int32_t num_envs, int32_t capacity, int32_t n_eval_episodes, const float* reward, const uint8_t* terminated,
+                               const uint8_t* truncated, double* ep_return, int32_t* ep_length, int32_t* count, const int32_t* target,
+                               double* rec_return, int32_t* rec_length, int32_t* rec_env, uint8_t* rec_truncated, int64_t* counters,
+                               double* summary, void* workspace, void* stream) {
+  if (check_eval_shape(num_envs, capacity, n_eval_episodes)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!reward || !ep_return || !ep_length || !count || !target || !rec_return || !rec_length || !rec_env || !rec_truncated || !counters ||
+      !summary || !workspace)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "eval: null argument (only terminated and truncated may be NULL)");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  upkie::EvalDev P{};
+  P.num_envs = num_envs;
+  P.episodes = n_eval_episodes;
+  P.blocks = upkie::episodes_blocks(num_envs, &P.rows);
+  P.reward = reward, P.terminated = terminated, P.truncated = truncated;
+  P.ep_return = ep_return, P.ep_length = ep_length, P.count = count, P.target = target;
+  P.rec_return = rec_return, P.rec_length = rec_length, P.rec_env = rec_env, P.rec_truncated = rec_truncated;
+  P.counters = counters, P.summary = summary;
+  char* ws = (char*)workspace;
+  P.ticket = (unsigned*)ws;
+  P.counts = (int32_t*)(ws + upkie::EPISODES_COUNTS_OFFSET);
+  char* fin = ws + upkie::EPISODES_COUNTS_OFFSET + upkie::EPISODES_MAX_BLOCKS * 4;
+  P.fin_return = (double*)fin;
+  P.fin_length = (int32_t*)(fin + (int64_t)num_envs * 8);
+  P.fin_env = (int32_t*)(fin + (int64_t)num_envs * 12);
+  P.fin_truncated = (uint8_t*)(fin + (int64_t)num_envs * 16);
+  hipLaunchKernelGGL(upkie::eval_step_kernel, dim3((unsigned)P.blocks), dim3(upkie::EPISODES_THREADS), 0, (hipStream_t)stream, P);
   return launch_status();
 }
 

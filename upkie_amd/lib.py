@@ -47,6 +47,7 @@ SOURCES = [
     os.path.join(_CSRC, "ppo.hpp"),
     os.path.join(_CSRC, "time_limits.hpp"),
     os.path.join(_CSRC, "episodes.hpp"),
+    os.path.join(_CSRC, "eval_episodes.hpp"),
     os.path.join(_CSRC, "agent_pipeline.hpp"),
     os.path.join(_CSRC, "reward_terms.hpp"),
     os.path.join(_CSRC, "wave_io.hpp"),
@@ -153,6 +154,10 @@ def _abi_table():
         ("upkie_episodes_workspace_bytes", C.c_int64, [i32], "upkie_episodes_step"),
         ("upkie_episodes_step", status, [i32, i32] + [vp] * 11, "upkie_episodes_step"),
         ("upkie_episodes_reset", status, [i32, vp, vp, vp, vp], "upkie_episodes_step"),
+        # the evaluation tally
+        ("upkie_eval_workspace_bytes", C.c_int64, [i32], "upkie_eval_step"),
+        ("upkie_eval_reset", status, [i32] * 3 + [vp] * 7, "upkie_eval_step"),
+        ("upkie_eval_step", status, [i32] * 3 + [vp] * 15, "upkie_eval_step"),
         # the agent pipeline
         ("upkie_pipeline_params", C.c_int64, [i32, i32, vp, vp, vp, vp, vp], "upkie_pipeline_observe"),
         ("upkie_pipeline_shape_action", status, pipeline + [vp] * 5, "upkie_pipeline_observe"),

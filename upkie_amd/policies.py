@@ -439,6 +439,18 @@ class MlpActorCritic:
         self._launch(obs, deterministic, outs)
         return outs["env_action"], outs["action"], outs["value"], outs["log_prob"]
 
+    def mean_action(self, obs: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """The deterministic action (the Gaussian's mean, clamped to the action bounds) of a batch of ANY size into the
+        caller's ``out`` ``[N, act_dim]``, which is returned: bit for bit the ``env_action`` of ``act(obs,
+        deterministic=True)``. The launch is handed no call counters and writes nothing but ``out``: neither the
+        persistent output buffers nor `calls` are touched (or allocated), so a policy that trains on one batch size can
+        be evaluated on an env of another (`upkie_amd.evaluation`) without a bit of its training changing."""
+        obs = self._obs(obs)
+        out = self._check_out("env_action", out, obs.shape[0])
+        self._launcher(self._lib.upkie_mlp_actor_critic, obs.shape[0], C.byref(self.shape), self.packed.data_ptr(), obs.data_ptr(), None, self.seed, 1,
+                       None, None, None, out.data_ptr(), None, None)
+        return out
+
     def value(self, obs: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The critic alone (e.g. the bootstrap values of the observations after a rollout's last step)."""
         if self.shape.critic_layers == 0:
