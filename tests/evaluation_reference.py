@@ -8,7 +8,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from tests.reduction_shapes import episodes_blocks
+from tests.reduction_shapes import episodes_blocks, ordered_append
 
 F32, F64 = np.float32, np.float64
 EVAL_STAGE = 1024  # enum value of csrc/eval_episodes.hpp
@@ -174,9 +174,9 @@ EVAL_MUTATIONS = ("last_env_dropped", "quota_compared_with_le", "appended_at_zer
 
 class EvalOrderModel:
     """eval_step_kernel in numpy, with its workspace: every block's finished episodes appended to its segment (what an
-    earlier step left behind a segment's end stays there), the exclusive prefix of the counts, the binary search of the
-    last block with offsets[b] <= g, the record written at filled + g under the bound E, the summary in the step that
-    fills the list. `mutation`: one of `EVAL_MUTATIONS`, the same with one index mistake."""
+    earlier step left behind a segment's end stays there) and found again in env order (`ordered_append`), the record
+    written at filled + g under the bound E, the summary in the step that fills the list. `mutation`: one of
+    `EVAL_MUTATIONS`, the same with one index mistake."""
 
     def __init__(self, N, E, mutation=None):
         assert mutation is None or mutation in EVAL_MUTATIONS
@@ -206,19 +206,10 @@ class EvalOrderModel:
         self.ep_return = np.where(live, np.where(done, 0.0, ret), self.ep_return)
         self.ep_length = np.where(live, np.where(done, 0, length), self.ep_length).astype(np.int32)
         self.count = self.count + done
-        idx = np.flatnonzero(done)
-        block = idx // rows
-        counts = np.bincount(block, minlength=blocks)
-        offsets = np.concatenate([[0], np.cumsum(counts)])
-        at = block * rows + (np.arange(idx.size) - offsets[block])
+        idx, at, _, total, src_of = ordered_append(done, rows, blocks, self.mutation)
         self.fin_return[at], self.fin_length[at], self.fin_env[at], self.fin_truncated[at] = ret[idx], length[idx], idx, limit[idx]
-        total = int(offsets[blocks])
         g = np.arange(total)
-        lo = np.searchsorted(offsets[:blocks], g, side="right") - 1  # the last block with offsets[b] <= g
-        if self.mutation == "neighbour_of_an_empty_block":  # the first block with offsets[b] == g: an empty one, where there is one
-            left = np.minimum(np.searchsorted(offsets[:blocks], g, side="left"), blocks - 1)
-            lo = np.where(offsets[left] == g, left, lo)
-        src = lo * rows + (g - offsets[lo])
+        src = src_of(g)
         filled = self.filled
         slot = g if self.mutation == "appended_at_zero" else filled + g
         keep = slot < E

@@ -280,6 +280,12 @@ extern "C" int harness_pipeline_blocks(int num_envs, int group) { return upkie::
 // functions), for tests/test_reduction_matrix.py: the grid, and the envs per block in *rows.
 extern "C" int harness_episodes_blocks(int num_envs, int* rows) { return upkie::episodes_blocks(num_envs, rows); }
 extern "C" int64_t harness_episodes_workspace_bytes(int num_envs) { return upkie::episodes_workspace_bytes(num_envs); }
+// The layout of csrc/episode_append.hpp's workspace, as the byte offsets its carve adds: out [6] = the counts, the segments, the tally's four.
+extern "C" void harness_episode_append_offsets(int num_envs, int64_t* out) {
+  out[0] = upkie::EPISODES_COUNTS_OFFSET, out[1] = upkie::EPISODES_SEGMENTS_OFFSET;
+  const int before[4] = {0, 8, 8 + 4, 8 + 4 + 4};  // (a double, an int32, an int32 ahead of the flag)
+  for (int k = 0; k < 4; ++k) out[2 + k] = upkie::episode_append_bytes(num_envs, before[k]);
+}
 extern "C" int harness_vecnorm_blocks(int num_envs, int obs_dim, int* rows) { return upkie::vecnorm_blocks(num_envs, obs_dim, rows); }
 
 // The choice of the step kernel (csrc/step_dispatch.hpp), for tests/test_step_dispatch.py: `count` rows, facts [count][13] =

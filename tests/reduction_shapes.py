@@ -165,14 +165,32 @@ def monitor_twin(row):
     return (BatchMonitorTwin if row.N > 5000 else MonitorTwin)(row.N, window=row.window)
 
 
+def ordered_append(done, rows, blocks, mutation=None):
+    """csrc/episode_append.hpp in numpy, for both order models: the finished envs `idx` in env order, their places `at` in the
+    segment arrays, the exclusive prefix `offsets` of the blocks' counts, its end `total`, and `src(g)`, the place of
+    finished episodes g (an array): in the last block with offsets[b] <= g, unless `mutation` is the search's mistake."""
+    idx = np.flatnonzero(done)
+    block = idx // rows
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(block, minlength=blocks))])
+    at = block * rows + (np.arange(idx.size) - offsets[block])
+
+    def src(g):
+        lo = np.searchsorted(offsets[:blocks], g, side="right") - 1
+        if mutation == "neighbour_of_an_empty_block":  # the first block with offsets[b] == g: an empty one, where there is one
+            left = np.minimum(np.searchsorted(offsets[:blocks], g, side="left"), blocks - 1)
+            lo = np.where(offsets[left] == g, left, lo)
+        return lo * rows + (g - offsets[lo])
+    return idx, at, offsets, int(offsets[blocks]), src
+
+
 EPISODE_MUTATIONS = ("last_row_dropped", "neighbour_of_an_empty_block", "first_window_kept", "slot_without_the_wrap")
 
 
 class EpisodesOrderModel:
     """episodes_step_kernel in numpy, with its workspace: every block's finished episodes appended to its segment (what an
-    earlier step left behind a segment's end stays there), the exclusive prefix of the counts, the binary search of the
-    last block with offsets[b] <= g, the ring written at head + j wrapped, the means from the oldest entry. `mutation`:
-    one of `EPISODE_MUTATIONS`, the same with one index mistake."""
+    earlier step left behind a segment's end stays there) and found again in env order (`ordered_append`), the ring written
+    at head + j wrapped, the means from the oldest entry. `mutation`: one of `EPISODE_MUTATIONS`, the same with one index
+    mistake."""
 
     def __init__(self, N, window, mutation=None):
         assert mutation is None or mutation in EPISODE_MUTATIONS
@@ -197,26 +215,16 @@ class EpisodesOrderModel:
         length = self.ep_length + 1
         self.ep_return[:live] = np.where(done, 0.0, ret)[:live]
         self.ep_length[:live] = np.where(done, 0, length)[:live]
-        idx = np.flatnonzero(done)
-        block = idx // rows
-        counts = np.bincount(block, minlength=blocks)
-        offsets = np.concatenate([[0], np.cumsum(counts)])
-        at = block * rows + (np.arange(idx.size) - offsets[block])
+        idx, at, offsets, total, src_of = ordered_append(done, rows, blocks, self.mutation)
         self.fin_return[at], self.fin_length[at] = ret[idx], length[idx]
-        total = int(offsets[blocks])
         keep = min(total, window)
         first = 0 if self.mutation == "first_window_kept" else total - keep
-        g = first + np.arange(keep)
-        lo = np.searchsorted(offsets[:blocks], g, side="right") - 1  # the last block with offsets[b] <= g
-        if self.mutation == "neighbour_of_an_empty_block":  # the first block with offsets[b] == g: an empty one, where there is one
-            left = np.minimum(np.searchsorted(offsets[:blocks], g, side="left"), blocks - 1)
-            lo = np.where(offsets[left] == g, left, lo)
-        src = lo * rows + (g - offsets[lo])
+        src = src_of(first + np.arange(keep))
         slot = self.head + np.arange(keep)
         if self.mutation != "slot_without_the_wrap":
             slot = np.where(slot < window, slot, slot - window)
         self.ring_return[slot], self.ring_length[slot] = self.fin_return[src], self.fin_length[src]
-        self.last = {"total": total, "keep": keep, "head": self.head, "counts": counts}
+        self.last = {"total": total, "keep": keep, "head": self.head, "counts": np.diff(offsets)}
         self.fill = min(self.fill + keep, window)
         self.head = (self.head + keep) % window
         self.total += total

@@ -144,9 +144,9 @@ def test_the_trainer_units_include_nothing_of_the_simulator(unit):
     assert not named & set(SIMULATOR_HEADERS), sorted(named & set(SIMULATOR_HEADERS))
 
 
-@pytest.mark.parametrize("header", ["random.hpp", "block_reduce.hpp"])
+@pytest.mark.parametrize("header", ["random.hpp", "block_reduce.hpp", "episode_append.hpp"])
 def test_the_shared_device_primitives_stand_alone(header):
-    """A file that includes one of the two headers and nothing else compiles: neither leans on what its includers bring."""
+    """A file that includes one of these headers and nothing else compiles: neither leans on what its includers bring."""
     csrc = os.path.join(ROOT, "upkie_amd", "csrc")
     with tempfile.TemporaryDirectory() as tmp:
         source = os.path.join(tmp, "alone.hip")

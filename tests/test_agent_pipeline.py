@@ -175,8 +175,9 @@ def test_library_refuses_every_listed_limit_without_a_gpu(library):
 
     def shape(**change):
         a = dict(ok, **change)
+        action, prev_command, calls, command = a.get("buffers", (buf,) * 4)
         return library.upkie_pipeline_shape_action(a["num_envs"], a["obs_dim"], a["act_dim"], a["stack"], a["flags"], a["dt"], a["lag"], a["params"], 0,
-                                                   buf, buf, buf, buf, None)
+                                                   action, prev_command, calls, command, None)
 
     def observe(**change):
         a = dict(ok, **change)
@@ -196,9 +197,18 @@ def test_library_refuses_every_listed_limit_without_a_gpu(library):
         for change, word in cases:
             assert call(**change) == abi.ERR_INVALID_ARGUMENT, (call.__name__, change)
             assert word in err(), (call.__name__, change, err())
-    assert shape(stack=51) != abi.ERR_INVALID_ARGUMENT, "51 * 5 = 255 words fit"
-    assert shape(stack=64, flags=flags_all & ~1) != abi.ERR_INVALID_ARGUMENT, "without the command a frame is 4 words: 256 fit"
-    assert shape(lag=0.01, flags=flags_all & ~8) != abi.ERR_INVALID_ARGUMENT, "the lag is read with its flag only"
+    if library.upkie_hip_device_count() > 0:
+        # an accepted call launches: params, action, prev_command, calls and command are device memory of 1024 words each
+        dev = [torch.zeros(1024, dtype=torch.float32, device="cuda") for _ in range(5)]
+        on_device = dict(params=dev[0].data_ptr(), buffers=tuple(t.data_ptr() for t in dev[1:]))
+        assert shape(stack=51, **on_device) == abi.OK, "51 * 5 = 255 words fit"
+        assert shape(stack=64, flags=flags_all & ~1, **on_device) == abi.OK, "without the command a frame is 4 words: 256 fit"
+        assert shape(lag=0.01, flags=flags_all & ~8, **on_device) == abi.OK, "the lag is read with its flag only"
+        torch.cuda.synchronize()
+    else:
+        assert shape(stack=51) != abi.ERR_INVALID_ARGUMENT, "51 * 5 = 255 words fit"
+        assert shape(stack=64, flags=flags_all & ~1) != abi.ERR_INVALID_ARGUMENT, "without the command a frame is 4 words: 256 fit"
+        assert shape(lag=0.01, flags=flags_all & ~8) != abi.ERR_INVALID_ARGUMENT, "the lag is read with its flag only"
     assert observe(final_obs=buf, final_observation=None) == abi.ERR_INVALID_ARGUMENT and b"final_observation" in err()
     # the host arrays behind params
     f = lambda *v: (C.c_float * len(v))(*v)  # noqa: E731

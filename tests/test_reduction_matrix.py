@@ -42,6 +42,9 @@ def test_plans_are_the_headers(harness):  # noqa: F811
         assert harness.harness_episodes_workspace_bytes(n) == S.episodes_workspace_bytes(n) == library.upkie_episodes_workspace_bytes(n)
         blocks, per = S.episodes_blocks(n)
         assert blocks <= S.EPISODES_MAX_BLOCKS and (blocks - 1) * per < n <= blocks * per, "every block owns at least one env"
+        carve = (C.c_int64 * 6)()
+        harness.harness_episode_append_offsets(n, carve)
+        assert list(carve) == [256, 256 + 4096] + [256 + 4096 + k * n for k in (0, 8, 12, 16)], n
     for n, d in [(r.N, r.D) for r in S.VECNORM_ROWS] + SIZES + [(sum(shards), d) for d, shards in S.SHARDED]:
         blocks, per, cap = S.vecnorm_blocks(n, d)
         assert (harness.harness_vecnorm_blocks(n, d, C.byref(rows)), rows.value) == (blocks, per), (n, d)

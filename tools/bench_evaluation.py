@@ -1,5 +1,5 @@
-"""What on-device evaluation (`upkie_amd.evaluation`) costs at 4096 envs and 4096 episodes on the pendulum env with a
-[64, 64] tanh policy. Time per step, device events around whole graph replays of 128 steps, of
+"""What on-device evaluation (`upkie_amd.evaluation`) costs at 4096 envs and 4096 episodes (`--num-envs N`: at N and N)
+on the pendulum env with a [64, 64] tanh policy. Time per step, device events around whole graph replays of 128 steps, of
 
   tally      `EpisodeTally.step` alone on a [128, 4096] stream of flags in which 31 OTHER envs end on every step (a
              random permutation of the envs, 31 at a time, alternately terminated and truncated), so that every step of a
@@ -25,7 +25,9 @@ process (the program to put behind ``rocprofv3 --kernel-trace --stats --`` for t
 `--replays` counts graph replays of 128 steps for the per-step variants (400: a quarter of a second of tally launches) and
 a tenth as many whole evaluations for `evaluate` / `torch`; every result line records the count it used.
 
-usage: python tools/bench_evaluation.py [--rounds 5] [--replays 400] [--variant NAME] [--out profiles/evaluation_bench.jsonl]"""
+`--num-envs N` takes every measurement at N envs and N episodes instead (262145: 1021 blocks in the bookkeeping kernels).
+
+usage: python tools/bench_evaluation.py [--rounds 5] [--replays 400] [--variant NAME] [--num-envs 4096] [--out profiles/evaluation_bench.jsonl]"""
 import argparse
 import json
 import os
@@ -37,7 +39,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-N, E, T, LIMIT = 4096, 4096, 128, 400
+DEFAULT_ENVS, T, LIMIT = 4096, 128, 400  # (N envs and E = N episodes: every measurement takes `n`)
 PER_STEP = 31  # envs that end on each step of the tally's stream: T x PER_STEP < E, so the list never fills
 VARIANTS = ("tally", "idle", "episodes", "step", "no_tally", "evaluate", "torch")
 UNITS = {"evaluate": "ms_per_evaluation", "torch": "ms_per_evaluation"}
@@ -58,7 +60,8 @@ def _time_replays(replay, replays):
     return start.elapsed_time(end) * 1e3 / (replays * T)
 
 
-def _bookkeeping(variant, replays):
+def _bookkeeping(variant, replays, n):
+    N = E = n
     import torch
 
     from upkie_amd.episodes import EpisodeStatistics
@@ -111,7 +114,8 @@ def _reward(obs, info):
     return torch.abs(obs[:, 0]).neg_().add_(1.0)
 
 
-def _setup():
+def _setup(n):
+    N = n
     import torch
     import torch.nn as nn
 
@@ -129,11 +133,12 @@ def _setup():
     return env, policy
 
 
-def _eval_step(variant, replays):
+def _eval_step(variant, replays, n):
+    E = n
     from upkie_amd.evaluation import PolicyEvaluator
     from upkie_amd.graphs import GraphedLoop
 
-    env, policy = _setup()
+    env, policy = _setup(n)
     with env:
         runner = PolicyEvaluator(policy, env, E, reward_fn=_reward, graph=False)
         runner.begin(E, 0)
@@ -142,12 +147,13 @@ def _eval_step(variant, replays):
         return _time_replays(loop.replay, replays)
 
 
-def _evaluate(replays):
+def _evaluate(replays, n):
+    E = n
     import torch
 
     from upkie_amd.evaluation import PolicyEvaluator
 
-    env, policy = _setup()
+    env, policy = _setup(n)
     with env:
         runner = PolicyEvaluator(policy, env, E, reward_fn=_reward, chunk=32, graph=True)
         runner.run(E, seed=0)  # (captures)
@@ -159,12 +165,13 @@ def _evaluate(replays):
         return (time.perf_counter() - begin) * 1e3 / replays, result
 
 
-def _torch_loop(replays):
+def _torch_loop(replays, n):
     """SB3's loop with the env, the policy and the reward on the device and the bookkeeping as torch ops: the finished
     envs under quota are gathered on the host every step."""
+    N = E = n
     import torch
 
-    env, policy = _setup()
+    env, policy = _setup(n)
     with env:
         dev = env.device
         action = torch.empty(N, 1, device=dev)
@@ -199,14 +206,15 @@ def _torch_loop(replays):
         return (time.perf_counter() - begin) * 1e3 / replays, {"episode_rewards": rewards, "episode_lengths": ep_lengths}
 
 
-def measure(variant, replays):
-    line = {"variant": variant, "num_envs": N, "n_eval_episodes": E, "replays": replays}
+def measure(variant, replays, n):
+    E = n
+    line = {"variant": variant, "num_envs": n, "n_eval_episodes": E, "replays": replays}
     if variant in ("tally", "idle", "episodes"):
-        line["us_per_step"] = round(_bookkeeping(variant, replays), 3)
+        line["us_per_step"] = round(_bookkeeping(variant, replays, n), 3)
     elif variant in ("step", "no_tally"):
-        line["us_per_step"] = round(_eval_step(variant, replays), 3)
+        line["us_per_step"] = round(_eval_step(variant, replays, n), 3)
     else:
-        ms, result = _evaluate(replays) if variant == "evaluate" else _torch_loop(replays)
+        ms, result = _evaluate(replays, n) if variant == "evaluate" else _torch_loop(replays, n)
         line["ms_per_evaluation"] = round(ms, 3)
         line["mean_ep_length"] = sum(result["episode_lengths"]) / E
         line["mean_reward"] = sum(result["episode_rewards"]) / E
@@ -219,16 +227,20 @@ def main():
     parser.add_argument("--replays", type=int, default=400)
     parser.add_argument("--variant", choices=VARIANTS)
     parser.add_argument("--out", help="append the result lines to this file")
+    parser.add_argument("--num-envs", type=int, default=DEFAULT_ENVS, help="envs, and episodes asked for")
     args = parser.parse_args()
+    N = args.num_envs
+    if N <= T * PER_STEP:
+        parser.error(f"--num-envs must be above {T * PER_STEP}: the tally's stream ends {PER_STEP} other envs on each of {T} steps and must not fill the list")
     if args.variant:
-        measure(args.variant, args.replays)
+        measure(args.variant, args.replays, N)
         return
     samples = {v: [] for v in VARIANTS}
     used = {v: args.replays if v not in UNITS else max(1, args.replays // 10) for v in VARIANTS}
     for _ in range(args.rounds):
         for variant in VARIANTS:
             replays = used[variant]
-            cmd = [sys.executable, os.path.abspath(__file__), "--variant", variant, "--replays", str(replays)]
+            cmd = [sys.executable, os.path.abspath(__file__), "--variant", variant, "--replays", str(replays), "--num-envs", str(N)]
             result = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
             if result.returncode != 0:
                 sys.exit(f"{variant} failed ({result.returncode}):\n{result.stderr[-2000:]}")
@@ -237,7 +249,7 @@ def main():
     for variant, values in samples.items():
         unit = UNITS.get(variant, "us_per_step")
         lines.append({"variant": variant, f"{unit}_median": round(statistics.median(values), 3), "min": min(values), "max": max(values),
-                      "rounds": args.rounds, "replays": used[variant], "num_envs": N, "n_eval_episodes": E})
+                      "rounds": args.rounds, "replays": used[variant], "num_envs": N, "n_eval_episodes": N})
     for line in lines:
         print(json.dumps(line), flush=True)
     if args.out:

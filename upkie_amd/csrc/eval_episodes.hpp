@@ -4,20 +4,16 @@
 // whether the time limit ended it) with its fill count; once the list is full, its summary (include/upkie_hip.h states
 // the arithmetic; Python: upkie_amd/evaluation.py).
 //
-// One launch per env step, the structure of episodes_step_kernel (episodes.hpp). Block b owns envs [b R, (b + 1) R) and
-// walks them 256 at a time in env order: an env below its quota adds (double)reward and 1 to its accumulators; with
-// terminated | truncated set it finishes its episode, counts it, zeroes its accumulators and appends (return, length,
-// env, truncated & !terminated) to the block's segment of the workspace, in env order (a wave ballot and a prefix over
-// the block's four waves); an env at its quota is neither read further nor written. The block writes its count of
-// finished episodes. Then the ticket (block_reduce.hpp): the block that arrives last does the ordered work alone: an
-// exclusive prefix of the blocks' counts (in LDS) gives every finished episode of the step its index g in env order;
-// episode g, found by a binary search of the prefix, becomes record filled + g (the quotas sum to E, so filled + g < E;
-// the store is bounded by E all the same): records are step-major and env-minor, the order SB3's loop appends in. In the
-// step in which filled reaches E the last block goes on to the summary: the records staged through LDS by the whole block,
-// 1024 at a time, and added by one thread in record order -- the return sum sequential in fp64, the length sum exact
-// in int64, the smallest and largest return, the count of time-limit records; then a second pass in the same order for
-// sum((x - mean)^2) of the returns and of the lengths, each term rounded (no fused multiply-add). The last block reads
-// one count per block and at most E records: the same bits every call and under graph replay.
+// One launch per env step, the ordered append of episode_append.hpp. Only an env below its quota counts: it adds
+// (double)reward and 1 to its accumulators, and with terminated | truncated set it finishes its episode, counts it and
+// zeroes them; an env at its quota is neither read further nor written. The payload: (return, length, env,
+// truncated & !terminated). The last block keeps a list: episode g becomes record filled + g (the quotas sum to E, so
+// filled + g < E; the store is bounded by E all the same): records are step-major and env-minor, the order SB3's loop
+// appends in. In the step in which filled reaches E it goes on to the summary: the records staged through LDS by the
+// whole block, 1024 at a time, and added by one thread in record order -- the return sum sequential in fp64, the length
+// sum exact in int64, the smallest and largest return, the count of time-limit records; then a second pass in the same
+// order for sum((x - mean)^2) of the returns and of the lengths, each term rounded (no fused multiply-add). It reads at
+// most E records.
 //
 // Launch R (reset): accumulators, counts, filled, steps and the summary back to zero, the targets written for E.
 #pragma once
@@ -27,7 +23,7 @@
 #include <cstdint>
 
 #include "block_reduce.hpp"
-#include "episodes.hpp"  // the grid (episodes_blocks) and its constants: the two kernels share one geometry
+#include "episode_append.hpp"
 
 namespace upkie {
 
@@ -57,18 +53,15 @@ struct EvalDev {
   uint8_t* fin_truncated;  // [num_envs]
 };
 
-// Workspace bytes: the ticket, the per-block counts, then the finished returns, lengths, envs and time-limit flags.
-inline int64_t eval_workspace_bytes(int num_envs) {
-  const int64_t counts = (int64_t)EPISODES_MAX_BLOCKS * 4;
-  return EPISODES_COUNTS_OFFSET + counts + (int64_t)num_envs * (8 + 4 + 4 + 1);
-}
+// Workspace bytes: the head of episode_append.hpp, then the finished returns, lengths, envs and time-limit flags.
+inline int64_t eval_workspace_bytes(int num_envs) { return episode_append_bytes(num_envs, 8 + 4 + 4 + 1); }
 
 #if defined(__HIPCC__)
 
 __global__ __launch_bounds__(EPISODES_THREADS) void eval_step_kernel(const EvalDev P) {
   __shared__ int32_t offsets[EPISODES_MAX_BLOCKS + 1];  // last block: exclusive prefix of the counts, then the total
   __shared__ int32_t wave_n[EPISODES_THREADS / 64 + 1];  // finished per wave of a chunk; [4]: "last block" flag
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
   const int r0 = blockIdx.x * P.rows, r1 = min(P.num_envs, r0 + P.rows);
 
   // every env below its quota: its accumulators; the finished ones appended to the block's segment in env order
@@ -91,21 +84,13 @@ __global__ __launch_bounds__(EPISODES_THREADS) void eval_step_kernel(const EvalD
         if (done) P.count[i] = given + 1;
       }
     }
-    const unsigned long long ballot = __ballot(done);
-    const int before = __popcll(ballot & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_n[wave] = __popcll(ballot);
-    __syncthreads();
-    int base = done_in_block;
-    for (int w = 0; w < wave; ++w) base += wave_n[w];
+    const int at = r0 + episode_append_index(done, done_in_block, wave_n);  // (< r1: at most one per env of the block)
     if (done) {
-      const int at = r0 + base + before;  // (< r1: at most one per env of the block)
       P.fin_return[at] = ret;
       P.fin_length[at] = len;
       P.fin_env[at] = i;
       P.fin_truncated[at] = limit ? 1 : 0;
     }
-    for (int w = 0; w < EPISODES_THREADS / 64; ++w) done_in_block += wave_n[w];
-    __syncthreads();
   }
   if (tid == 0) P.counts[blockIdx.x] = done_in_block;
 
@@ -114,42 +99,10 @@ __global__ __launch_bounds__(EPISODES_THREADS) void eval_step_kernel(const EvalD
   const int E = P.episodes;
   const int64_t filled64 = P.counters[0];  // (read by every thread ahead of the scan's barriers; thread 0 writes it behind them)
   const int filled = filled64 < 0 ? 0 : filled64 < E ? (int)filled64 : E;
-  constexpr int PER = EPISODES_MAX_BLOCKS / EPISODES_THREADS;  // blocks per thread in the prefix
-  int own[PER], sum = 0;
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int b = tid * PER + k;
-    own[k] = b < P.blocks ? P.counts[b] : 0;
-    sum += own[k];
-  }
-  // inclusive scan of the threads' sums (Hillis-Steele in LDS), then each thread's blocks
   __shared__ int32_t scan[EPISODES_THREADS];
-  scan[tid] = sum;
-  __syncthreads();
-  for (int d = 1; d < EPISODES_THREADS; d <<= 1) {
-    const int add = tid >= d ? scan[tid - d] : 0;
-    __syncthreads();
-    scan[tid] += add;
-    __syncthreads();
-  }
-  int run = scan[tid] - sum;
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    offsets[tid * PER + k] = run;
-    run += own[k];
-  }
-  if (tid == EPISODES_THREADS - 1) offsets[EPISODES_MAX_BLOCKS] = run;
-  __syncthreads();
-
-  const int total = offsets[EPISODES_MAX_BLOCKS];
+  const int total = episode_append_offsets(P.counts, P.blocks, scan, offsets);
   for (int g = tid; g < total; g += EPISODES_THREADS) {
-    int lo = 0, hi = P.blocks - 1;  // the block b with offsets[b] <= g < offsets[b + 1] (the last such: empty blocks share offsets)
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (offsets[mid] <= g) lo = mid;
-      else hi = mid - 1;
-    }
-    const int src = lo * P.rows + (g - offsets[lo]);
+    const int src = episode_append_source(g, offsets, P.blocks, P.rows);
     if (g < E - filled) {  // (always, by the quotas: no store ever lands behind the list)
       const int slot = filled + g;
       P.rec_return[slot] = P.fin_return[src];

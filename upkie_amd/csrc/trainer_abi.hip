@@ -99,17 +99,13 @@ extern "C" int upkie_episodes_step(int32_t num_envs, int32_t window, const float
     return fail(UPKIE_ERR_INVALID_ARGUMENT, "null argument (only terminated and truncated may be NULL)");
   if (no_device()) return UPKIE_ERR_NO_DEVICE;
   upkie::EpisodesDev P{};
-  P.num_envs = num_envs;
-  P.window = window;
+  P.num_envs = num_envs, P.window = window;
   P.blocks = upkie::episodes_blocks(num_envs, &P.rows);
   P.reward = reward, P.terminated = terminated, P.truncated = truncated;
   P.ep_return = ep_return, P.ep_length = ep_length, P.ring_return = ring_return, P.ring_length = ring_length;
   P.counters = counters, P.means = means;
-  char* ws = (char*)workspace;
-  P.ticket = (unsigned*)ws;
-  P.counts = (int32_t*)(ws + upkie::EPISODES_COUNTS_OFFSET);
-  P.fin_return = (double*)(ws + upkie::EPISODES_COUNTS_OFFSET + upkie::EPISODES_MAX_BLOCKS * 4);
-  P.fin_length = (int32_t*)(ws + upkie::EPISODES_COUNTS_OFFSET + upkie::EPISODES_MAX_BLOCKS * 4 + (int64_t)num_envs * 8);
+  const upkie::EpisodeAppendWorkspace ws = upkie::episode_append_carve(workspace, num_envs);
+  P.ticket = ws.ticket, P.counts = ws.counts, P.fin_return = ws.segment<double>(0), P.fin_length = ws.segment<int32_t>(8);
   hipLaunchKernelGGL(upkie::episodes_step_kernel, dim3((unsigned)P.blocks), dim3(upkie::EPISODES_THREADS), 0, (hipStream_t)stream, P);
   return launch_status();
 }
@@ -118,7 +114,7 @@ extern "C" int upkie_episodes_reset(int32_t num_envs, const uint8_t* mask, doubl
   if (check_episodes_shape(num_envs, 1)) return UPKIE_ERR_INVALID_ARGUMENT;
   if (!ep_return || !ep_length) return fail(UPKIE_ERR_INVALID_ARGUMENT, "null accumulator buffer");
   if (no_device()) return UPKIE_ERR_NO_DEVICE;
-  const int grid = std::min((num_envs + upkie::EPISODES_THREADS - 1) / upkie::EPISODES_THREADS, 1024);
+  const int grid = upkie::episodes_reset_blocks(num_envs);
   hipLaunchKernelGGL(upkie::episodes_reset_kernel, dim3((unsigned)grid), dim3(upkie::EPISODES_THREADS), 0, (hipStream_t)stream, num_envs, mask,
                      ep_return, ep_length);
   return launch_status();
@@ -142,7 +138,7 @@ extern "C" int upkie_eval_reset(int32_t num_envs, int32_t capacity, int32_t n_ev
   if (check_eval_shape(num_envs, capacity, n_eval_episodes)) return UPKIE_ERR_INVALID_ARGUMENT;
   if (!ep_return || !ep_length || !count || !target || !counters || !summary) return fail(UPKIE_ERR_INVALID_ARGUMENT, "eval: null state buffer");
   if (no_device()) return UPKIE_ERR_NO_DEVICE;
-  const int grid = std::min((num_envs + upkie::EPISODES_THREADS - 1) / upkie::EPISODES_THREADS, 1024);
+  const int grid = upkie::episodes_reset_blocks(num_envs);
   hipLaunchKernelGGL(upkie::eval_reset_kernel, dim3((unsigned)grid), dim3(upkie::EPISODES_THREADS), 0, (hipStream_t)stream, num_envs,
                      n_eval_episodes, ep_return, ep_length, count, target, counters, summary);
   return launch_status();
@@ -158,21 +154,15 @@ extern "C" int upkie_eval_step(int32_t num_envs, int32_t capacity, int32_t n_eva
     return fail(UPKIE_ERR_INVALID_ARGUMENT, "eval: null argument (only terminated and truncated may be NULL)");
   if (no_device()) return UPKIE_ERR_NO_DEVICE;
   upkie::EvalDev P{};
-  P.num_envs = num_envs;
-  P.episodes = n_eval_episodes;
+  P.num_envs = num_envs, P.episodes = n_eval_episodes;
   P.blocks = upkie::episodes_blocks(num_envs, &P.rows);
   P.reward = reward, P.terminated = terminated, P.truncated = truncated;
   P.ep_return = ep_return, P.ep_length = ep_length, P.count = count, P.target = target;
   P.rec_return = rec_return, P.rec_length = rec_length, P.rec_env = rec_env, P.rec_truncated = rec_truncated;
   P.counters = counters, P.summary = summary;
-  char* ws = (char*)workspace;
-  P.ticket = (unsigned*)ws;
-  P.counts = (int32_t*)(ws + upkie::EPISODES_COUNTS_OFFSET);
-  char* fin = ws + upkie::EPISODES_COUNTS_OFFSET + upkie::EPISODES_MAX_BLOCKS * 4;
-  P.fin_return = (double*)fin;
-  P.fin_length = (int32_t*)(fin + (int64_t)num_envs * 8);
-  P.fin_env = (int32_t*)(fin + (int64_t)num_envs * 12);
-  P.fin_truncated = (uint8_t*)(fin + (int64_t)num_envs * 16);
+  const upkie::EpisodeAppendWorkspace ws = upkie::episode_append_carve(workspace, num_envs);
+  P.ticket = ws.ticket, P.counts = ws.counts, P.fin_return = ws.segment<double>(0), P.fin_length = ws.segment<int32_t>(8);
+  P.fin_env = ws.segment<int32_t>(12), P.fin_truncated = ws.segment<uint8_t>(16);
   hipLaunchKernelGGL(upkie::eval_step_kernel, dim3((unsigned)P.blocks), dim3(upkie::EPISODES_THREADS), 0, (hipStream_t)stream, P);
   return launch_status();
 }

@@ -12,7 +12,7 @@ import torch
 
 from . import lib
 from .exceptions import UpkieRuntimeError
-from .launch import check, device_tensor, launcher, ptr
+from .launch import check, device_tensor, end_flags, launcher, ptr
 
 
 class EpisodeStatistics:
@@ -63,10 +63,8 @@ class EpisodeStatistics:
     def step(self, reward: torch.Tensor, terminated: Optional[torch.Tensor] = None, truncated: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One env step: ``reward`` [N] float32 (the raw reward, before any normalisation), ``terminated`` /
         ``truncated`` [N] bool or uint8 (None: none ended). Returns ``means``."""
-        N, dev, flags = (self.num_envs,), self.device, (torch.bool, torch.uint8)
-        reward = device_tensor(reward, "reward", dev, N)
-        terminated = device_tensor(terminated, "terminated", dev, N, flags, required=False)
-        truncated = device_tensor(truncated, "truncated", dev, N, flags, required=False)
+        reward = device_tensor(reward, "reward", self.device, (self.num_envs,))
+        terminated, truncated = end_flags(terminated, truncated, self.device, self.num_envs)
         self._launcher(self._lib.upkie_episodes_step, self.num_envs, self.window, reward.data_ptr(), ptr(terminated), ptr(truncated),
                        self.ep_return.data_ptr(), self.ep_length.data_ptr(), self.ring_return.data_ptr(), self.ring_length.data_ptr(),
                        self.counters.data_ptr(), self.means.data_ptr(), self.workspace.data_ptr())

@@ -15,7 +15,7 @@ import torch
 
 from . import lib
 from .exceptions import UpkieRuntimeError
-from .launch import check, device_tensor, launcher, ptr
+from .launch import check, device_tensor, end_flags, launcher, ptr
 
 SUMMARY_NAMES = ("mean_reward", "var_reward", "mean_ep_length", "var_ep_length", "min_reward", "max_reward", "time_limit_frac")
 
@@ -85,10 +85,8 @@ class EpisodeTally:
         (None: none ended)."""
         if self.n_eval_episodes < 1:
             raise UpkieRuntimeError("EpisodeTally.step before reset(n_eval_episodes)")
-        N, dev, flags = (self.num_envs,), self.device, (torch.bool, torch.uint8)
-        reward = device_tensor(reward, "reward", dev, N)
-        terminated = device_tensor(terminated, "terminated", dev, N, flags, required=False)
-        truncated = device_tensor(truncated, "truncated", dev, N, flags, required=False)
+        reward = device_tensor(reward, "reward", self.device, (self.num_envs,))
+        terminated, truncated = end_flags(terminated, truncated, self.device, self.num_envs)
         self._launcher(self._lib.upkie_eval_step, self.num_envs, self.capacity, self.n_eval_episodes, reward.data_ptr(), ptr(terminated),
                        ptr(truncated), self.ep_return.data_ptr(), self.ep_length.data_ptr(), self.count.data_ptr(), self.target.data_ptr(),
                        self.rec_return.data_ptr(), self.rec_length.data_ptr(), self.rec_env.data_ptr(), self.rec_truncated.data_ptr(),

@@ -35,6 +35,13 @@ def device_tensor(t, what: str, device, shape, dtypes=(torch.float32,), required
     return t
 
 
+def end_flags(terminated, truncated, device, num_envs: int):
+    """``(terminated, truncated)`` of an env step as arguments of a launch: each [num_envs] bool or uint8, or None."""
+    flags = (torch.bool, torch.uint8)
+    return (device_tensor(terminated, "terminated", device, (num_envs,), flags, required=False),
+            device_tensor(truncated, "truncated", device, (num_envs,), flags, required=False))
+
+
 def check(status: int, last_error=None, handle=None) -> None:
     """Raise `UpkieHipError` on a negative status, also of a call that is no launch (a setter, a creator, a size), with
     the message of ``last_error(handle)``: a handle family's ``upkie_*_last_error``, or ``upkie_sim_last_error(NULL)``

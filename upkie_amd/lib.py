@@ -46,6 +46,7 @@ SOURCES = [
     os.path.join(_CSRC, "vecnorm.hpp"),
     os.path.join(_CSRC, "ppo.hpp"),
     os.path.join(_CSRC, "time_limits.hpp"),
+    os.path.join(_CSRC, "episode_append.hpp"),
     os.path.join(_CSRC, "episodes.hpp"),
     os.path.join(_CSRC, "eval_episodes.hpp"),
     os.path.join(_CSRC, "agent_pipeline.hpp"),

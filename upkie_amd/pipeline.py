@@ -16,7 +16,7 @@ import torch
 
 from . import lib
 from .exceptions import UpkieRuntimeError
-from .launch import check, device_tensor, launcher, ptr
+from .launch import check, device_tensor, end_flags, launcher, ptr
 
 # enum UpkiePipelineFlag
 ACTION_IN_OBSERVATION, INTEGRATE_ACTION, ACTION_NOISE, ACTION_LAG, OBSERVATION_NOISE = 1, 2, 4, 8, 16
@@ -147,10 +147,9 @@ class AgentPipeline:
                 final_obs: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One env step: ``next_obs`` [N, D] float32, ``terminated`` / ``truncated`` [N] bool or uint8 (None: none ended),
         ``final_obs`` [N, D] (None: no `final_observation`). Returns `observation`."""
-        N, D, dev, flags = self.num_envs, self.obs_dim, self.device, (torch.bool, torch.uint8)
+        N, D, dev = self.num_envs, self.obs_dim, self.device
         obs = device_tensor(next_obs, "next_obs", dev, (N, D))
-        term = device_tensor(terminated, "terminated", dev, (N,), flags, required=False)
-        trunc = device_tensor(truncated, "truncated", dev, (N,), flags, required=False)
+        term, trunc = end_flags(terminated, truncated, dev, N)
         final = device_tensor(final_obs, "final_obs", dev, (N, D), required=False)
         self._launcher(self._lib.upkie_pipeline_observe, *self._settings(), obs.data_ptr(), ptr(term), ptr(trunc), ptr(final),
                        self.command.data_ptr(), self.prev_command.data_ptr(), self.calls.data_ptr(), self.observation.data_ptr(),

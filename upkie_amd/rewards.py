@@ -17,7 +17,7 @@ import torch
 
 from . import abi, lib
 from .exceptions import UpkieRuntimeError
-from .launch import check, device_tensor, launcher, ptr
+from .launch import check, device_tensor, end_flags, launcher, ptr
 
 Tap = namedtuple("Tap", ("source", "index", "fn", "coef"))
 _FNS = {None: abi.REWARD_FN_ID, "id": abi.REWARD_FN_ID, "sin": abi.REWARD_FN_SIN, "cos": abi.REWARD_FN_COS}
@@ -169,11 +169,9 @@ class RewardTerms:
         ``action`` [N, A] float32, ``terminated`` / ``truncated`` [N] bool or uint8 (None: none). Returns the reward
         [N] float32, written into ``out`` when given (a rollout buffer's slot), else into `reward`."""
         N, D, A, dev = self.num_envs, self.obs_dim, self.act_dim, self.device
-        flags = (torch.bool, torch.uint8)
         obs_ = device_tensor(next_obs, "next_obs", dev, (N, D))
         action = device_tensor(action, "action", dev, (N, A))
-        term = device_tensor(terminated, "terminated", dev, (N,), flags, required=False)
-        trunc = device_tensor(truncated, "truncated", dev, (N,), flags, required=False)
+        term, trunc = end_flags(terminated, truncated, dev, N)
         final = device_tensor(final_obs, "final_obs", dev, (N, D), required=False)
         out = self.reward if out is None else device_tensor(out, "out", dev, (N,))
         self._launcher(self._lib.upkie_reward_terms_step, N, D, A, self.num_terms, self.params.data_ptr(), obs_.data_ptr(), action.data_ptr(),
