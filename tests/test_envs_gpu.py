@@ -515,3 +515,37 @@ def test_graphed_env_step_starts_from_the_reset_state(env_id):
         GraphedEnvStep(bv, lambda o: torch.zeros(64, 2, device="cuda:0"))
     for e in (eager, graphed, bv):
         e.close()
+
+
+@pytest.mark.parametrize("bullet_like", (False, True))
+def test_state_tensors_is_all_that_the_next_steps_read(bullet_like):
+    """`UpkieVecEnv.state_tensors()` is complete: put back after three more steps (a truncation and the in-step reset
+    among them), the same three steps give the same bits. 65 envs: one full wavefront and one env more."""
+    B = 65
+    env = envs.make("Upkie-HIP-Pendulum-Vec", num_envs=B, frequency=200.0, init_state=RobotState(randomization=RobotStateRandomization(pitch=0.2)),
+                    autoreset_mode="same_step", max_episode_steps=4)
+    with env:
+        if bullet_like:
+            env.sim.use_bullet_like_contacts(True)
+        env.reset(seed=3)
+        action = torch.linspace(-0.9, 0.9, B, device=env.device).reshape(B, 1)
+
+        def three_steps():
+            outputs = []
+            for _ in range(3):
+                obs, reward, terminated, truncated, info = env.step(action)
+                outputs.append([x.clone() for x in (obs, reward, terminated, truncated, info["final_obs"])])
+            return outputs
+
+        three_steps()
+        tensors = env.state_tensors()
+        assert set(tensors) == {"state", "reward", "terminated", "truncated", "observation", "final_obs"} | ({"contact_manifold"} if bullet_like else set())
+        saved = {name: x.clone() for name, x in tensors.items()}
+        first = three_steps()
+        assert first[0][3].all() and not first[1][3].any(), "the fourth step truncates every env, the fifth begins the next episodes"
+        assert env.state_tensors().keys() == saved.keys() and any(not torch.equal(x, saved[name]) for name, x in env.state_tensors().items())
+        for name, x in env.state_tensors().items():
+            x.copy_(saved[name])
+        again = three_steps()
+    for want, got in zip(first, again):
+        assert all(torch.equal(a, b) for a, b in zip(want, got))

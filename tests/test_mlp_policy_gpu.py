@@ -204,10 +204,7 @@ def test_graph_replay_is_bit_equal_to_the_eager_loop():
                 buf.rewards[t].copy_(reward)
                 slot["t"] = (t + 1) % T
 
-            sim = env.sim
-            keep = [x for x in (getattr(sim, n, None) for n in ("state", "reward", "terminated", "truncated")) if x is not None] + [obs]
-            if getattr(env, "_final_obs", None) is not None:
-                keep.append(env._final_obs)
+            keep = list(env.state_tensors().values())  # (`obs` among them)
             saved = [x.clone() for x in keep]
             if graphed:
                 loop = GraphedLoop(body, unroll=T, warmup=1)  # (warm-up and capture advance the state: restored below)

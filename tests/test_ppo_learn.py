@@ -308,6 +308,7 @@ def _saved_parts(scale, pipeline, reward):
     f = lambda *shape, dtype=torch.float32: torch.full(shape, next(fill) * scale, dtype=dtype)  # noqa: E731
     sim = types.SimpleNamespace(state=f(3, 2), reward=f(2), terminated=f(2, dtype=torch.uint8), truncated=f(2, dtype=torch.uint8))
     env = types.SimpleNamespace(num_envs=2, sim=sim, _final_obs=f(2, 4), scale=scale)
+    env.state_tensors = lambda: dict(vars(sim), final_obs=env._final_obs)  # (no persistent observation buffer: `Ppo` supplies its own)
     policy = _stage(MlpActorCritic, shape=_shape(4, [8], 1), packed=f(6), calls=f(2, dtype=torch.int32), seed=7 * scale)
     kwargs = {}
     if pipeline:

@@ -8,101 +8,14 @@ import pytest
 import torch
 
 import upkie_amd.envs as envs
+from tests.agent_step_doubles import A, D, N, T, Calls, Env, Episodes, Normalizer, Pipeline, Policy, Reward, reward_fn
 from tests.fake_sim import oracle_sim_factory
 from upkie_amd.exceptions import UpkieRuntimeError
 from upkie_amd.ppo import Ppo
 from upkie_amd.utils.robot_state import RobotState
 from upkie_amd.utils.robot_state_randomization import RobotStateRandomization
 
-N, T, K, D, A = 3, 5, 2, 4, 1  # envs, steps, stacked frames, raw observation words, action words
 FIRST_SLOT = 2  # the window starts here, so that the slot wraps inside it: 2, 3, 4, 0, 1
-
-
-class Calls:
-    """The log of the doubles: the names in call order, and per name the arguments of every call."""
-
-    def __init__(self):
-        self.names, self.args = [], {}
-
-    def add(self, name, **args):
-        self.names.append(name)
-        self.args.setdefault(name, []).append(args)
-
-
-class Env:
-    """The oracle env behind a recorder of what `step` is given and what it returns."""
-
-    def __init__(self, env, calls):
-        self._env, self.calls, self.num_envs = env, calls, env.num_envs
-
-    def step(self, action):
-        out = self._env.step(action)
-        self.calls.add("env.step", action=action, out=out, ended=out[2].clone() | out[3].clone(), truncated=out[3].clone(), reward=out[1].clone())
-        return out
-
-
-class Policy:
-    def __init__(self, obs_dim, calls):
-        self.shape, self.calls = types.SimpleNamespace(obs_dim=obs_dim, act_dim=A), calls
-
-    def act(self, obs, out):
-        self.calls.add("act", obs=obs, out=out, seen=obs.clone())
-        out["env_action"].fill_(0.5)
-        out["action"].fill_(0.5)
-        return out["env_action"], out["action"], out["value"], out["log_prob"]
-
-    def bootstrap_time_limits(self, final_obs, terminated, truncated, reward, gamma):
-        self.calls.add("bootstrap", final_obs=final_obs, terminated=terminated, truncated=truncated, reward=reward, gamma=gamma)
-
-    def value(self, obs):
-        self.calls.add("value", obs=obs)
-        return torch.zeros(N)
-
-
-class Pipeline:
-    def __init__(self, calls):
-        self.num_envs, self.obs_dim, self.act_dim, self.stack = N, D, A, K
-        self.frame_dim, self.stacked_dim = D + A, K * (D + A)
-        self.observation, self.final_observation, self.command = torch.zeros(N, self.stacked_dim), torch.zeros(N, self.stacked_dim), torch.zeros(N, A)
-        self.calls = calls
-
-    def shape_action(self, env_action):
-        self.calls.add("shape_action", env_action=env_action)
-        self.command.copy_(env_action).mul_(0.5)
-        return self.command
-
-    def observe(self, next_obs, terminated, truncated, final_obs=None):
-        self.calls.add("observe", next_obs=next_obs, terminated=terminated, truncated=truncated, final_obs=final_obs)
-        self.observation[:, :D] = next_obs
-        return self.observation
-
-
-class Normalizer:
-    def __init__(self, calls):
-        self.calls = calls
-
-    def step(self, obs, reward, terminated, truncated, out):
-        self.calls.add("normalizer", obs=obs, reward=reward, terminated=terminated, truncated=truncated, out=out)
-        out["reward"].copy_(reward).mul_(0.5)
-        torch.bitwise_or(terminated, truncated, out=out["episode_starts"])
-
-
-class Episodes:
-    def __init__(self, calls):
-        self.calls = calls
-
-    def step(self, reward, terminated, truncated):
-        self.calls.add("episodes", reward=reward, terminated=terminated, truncated=truncated, seen=reward.clone())
-
-
-class Reward:
-    def __init__(self, obs_dim, calls):
-        self.num_envs, self.obs_dim, self.act_dim, self.calls, self.reward = N, obs_dim, A, calls, torch.zeros(N)
-
-    def step(self, next_obs, action, terminated, truncated, final_obs=None):
-        self.calls.add("reward.step", next_obs=next_obs, action=action, terminated=terminated, truncated=truncated, final_obs=final_obs)
-        self.reward.copy_(1.0 - next_obs[:, 0].abs())
-        return self.reward
 
 
 def _model(env, calls, pipeline, normalizer, reward, **kw):
@@ -110,12 +23,7 @@ def _model(env, calls, pipeline, normalizer, reward, **kw):
     pipe = Pipeline(calls) if pipeline else None
     words = pipe.stacked_dim if pipeline else D
     if reward == "fn":
-        def reward_fn(next_obs, info):
-            result = 1.0 - next_obs[:, 0].abs()
-            calls.add("reward_fn", next_obs=next_obs, info=info, result=result)
-            return result
-
-        kw["reward_fn"] = reward_fn
+        kw["reward_fn"] = reward_fn(calls)
     elif reward == "terms":
         kw["reward"] = Reward(D, calls)
     model = Ppo(env, Policy(words, calls), n_steps=T, pipeline=pipe, normalize=normalizer, graph=False, **kw)

@@ -263,10 +263,7 @@ def test_closed_loop_eager_against_the_twin_and_graphed_bit_equal():
                 last["step"] = (next_obs, reward, terminated, truncated)
                 slot["t"] = (t + 1) % T
 
-            sim = env.sim
-            keep = [x for x in (getattr(sim, n, None) for n in ("state", "reward", "terminated", "truncated")) if x is not None] + [obs]
-            if getattr(env, "_final_obs", None) is not None:
-                keep.append(env._final_obs)
+            keep = list(env.state_tensors().values())  # (`obs` among them)
             keep += [norm.obs_stats, norm.ret_stats, norm.returns, norm.obs_mean_f32, norm.obs_std_f32, policy.packed, starts]
             saved = [x.clone() for x in keep]
             if graphed:

@@ -257,6 +257,14 @@ class UpkieVecEnv:
             return sim.obs_servos
         return sim.obs3  # (BaseVelocity: None until its first step)
 
+    def state_tensors(self) -> dict:
+        """The tensors the next `step()` reads or rewrites, by name (what `upkie_amd.ppo.Ppo.save` carries under
+        ``env.`` and `upkie_amd.graphs.GraphedEnvStep` snapshots): the handle's, the `observation` buffer where the kind
+        has one, and ``final_obs`` once the same-step autoreset is armed."""
+        named = {n: getattr(self.sim, n, None) for n in ("state", "reward", "terminated", "truncated", "contact_manifold", "observer_state")}
+        named.update(observation=self.observation, final_obs=self._final_obs)
+        return {k: v for k, v in named.items() if v is not None}
+
     def close(self) -> None:
         if self._observers is not None:
             self._observers.close()

@@ -28,10 +28,10 @@ class EpisodeStatistics:
 
     Differences from SB3: Monitor's ``round(r, 6)`` is not applied, and there is no ``"t"`` (wall-clock) entry.
 
-    Order inside a rollout step, as in SB3 (Monitor sits under VecNormalize): 1. ``policy.act``; 2. ``env.step``;
-    3. the user's reward; 4. ``EpisodeStatistics.step`` on the RAW reward; 5. ``RunningNormalizer.step`` into
-    ``buffer.rewards[t]``; 6. ``policy.bootstrap_time_limits(info["final_obs"], terminated, truncated,
-    buffer.rewards[t], buffer.gamma)`` on the normalised slot.
+    Order inside a rollout step, as in SB3 (Monitor sits under VecNormalize): ``EpisodeStatistics.step`` on the RAW
+    reward comes between the two halves of `upkie_amd.agent_step.AgentStep` (after ``env.step`` and the user's reward),
+    so before ``RunningNormalizer.step`` into ``buffer.rewards[t]`` and ``policy.bootstrap_time_limits(info["final_obs"],
+    terminated, truncated, buffer.rewards[t], buffer.gamma)`` on the normalised slot.
 
     All state is allocated at construction; a step allocates nothing and has no host argument that changes between
     steps, so it can be captured in a hipGraph (`GraphedLoop`). Statistics are per process (per rank of a sharded

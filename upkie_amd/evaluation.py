@@ -14,6 +14,7 @@ from typing import Callable, Optional
 import torch
 
 from . import lib
+from .agent_step import AgentStep
 from .exceptions import UpkieRuntimeError
 from .launch import check, device_tensor, end_flags, launcher, ptr
 
@@ -129,39 +130,23 @@ class PolicyEvaluator:
         if mode != "same_step":
             raise ValueError(f"evaluation needs an env with autoreset_mode='same_step' (SB3's VecEnv semantics, and the terminal observation "
                              f"the reward terms read), this one has {mode!r}")
-        if reward is not None and reward_fn is not None:
-            raise ValueError("give reward (a RewardTerms) or reward_fn (a callable), not both")
-        N, D, A = int(env.num_envs), int(policy.shape.obs_dim), int(policy.shape.act_dim)
-        if pipeline is not None:
-            if D != pipeline.stacked_dim or A != pipeline.act_dim or N != pipeline.num_envs:
-                raise ValueError(f"the pipeline serves {pipeline.num_envs} envs, {pipeline.act_dim} actions and stacks {pipeline.stacked_dim} "
-                                 f"words, the env has {N} and the policy takes {D} and gives {A}")
-        if reward is not None:
-            raw = pipeline.obs_dim if pipeline is not None else D
-            if reward.num_envs != N or reward.act_dim != A or reward.obs_dim != raw:
-                raise ValueError(f"the reward serves {reward.num_envs} envs, {reward.obs_dim} observation words and {reward.act_dim} actions, "
-                                 f"the evaluation has {N}, {raw} (raw) and {A}")
+        self._agent = AgentStep(env, policy, pipeline, reward, reward_fn, noun="evaluation")  # (checks the sizes)
         if int(chunk) < 1:
             raise ValueError("chunk must be positive")
         self.policy, self.env, self.pipeline, self.reward, self.reward_fn = policy, env, pipeline, reward, reward_fn
         self.deterministic, self.chunk, self.graph = bool(deterministic), int(chunk), bool(graph)
         self.device = env.device
+        N, A = int(env.num_envs), int(policy.shape.act_dim)
         self.tally = EpisodeTally(N, capacity, device=self.device)
         self._action = torch.empty(N, A, dtype=torch.float32, device=self.device)
-        self._obs = None
         self._loop, self._captured_for = None, None
 
     def begin(self, n_eval_episodes: int, seed: Optional[int] = None) -> None:
-        """Start an evaluation over: the env reset (``reset(seed=seed)``), the pipeline's noise counters zeroed and its stack
-        restarted, the reward's running episodes forgotten, the tally reset for ``n_eval_episodes``."""
-        env, pipe = self.env, self.pipeline
-        reset = env.reset(seed=seed) if seed is not None else env.reset()
-        self._obs = getattr(env, "observation", None)
-        if self._obs is None:
-            self._obs = reset[0] if isinstance(reset, tuple) else reset
-        if pipe is not None:
-            pipe.calls.zero_()  # (its noise starts over, so that two evaluations from one seed draw the same)
-            pipe.reset(self._obs)
+        """Start an evaluation over: the pipeline's noise counters zeroed, the env reset (``reset(seed=seed)``) and the
+        pipeline's stack restarted, the reward's running episodes forgotten, the tally reset for ``n_eval_episodes``."""
+        if self.pipeline is not None:
+            self.pipeline.calls.zero_()  # (its noise starts over, so that two evaluations from one seed draw the same)
+        self._agent.reset(seed)
         if self.reward is not None:
             self.reward.reset()
         self.tally.reset(n_eval_episodes)
@@ -169,24 +154,13 @@ class PolicyEvaluator:
     def step(self, record: bool = True) -> None:
         """One evaluation step (`evaluate_policy` lists its stages); ``record=False`` leaves the tally's launch out (what
         tools/bench_evaluation.py times the tally against)."""
-        pol, pipe = self.policy, self.pipeline
-        obs = self._obs if pipe is None else pipe.observation
+        pol, agent = self.policy, self._agent
         if self.deterministic:
-            pol.mean_action(obs, self._action)
+            pol.mean_action(agent.observation, self._action)
         else:
-            pol.act(obs, out={"env_action": self._action})
-        action = self._action if pipe is None else pipe.shape_action(self._action)  # (what the env receives)
-        stepped = self.env.step(action)
-        next_obs, reward, terminated, truncated = stepped[:4]
-        info = stepped[4] if len(stepped) > 4 else {}
-        self._obs = next_obs
-        final_obs = info.get("final_obs") if hasattr(info, "get") else None
-        if self.reward_fn is not None:
-            reward = self.reward_fn(next_obs, info)
-        elif self.reward is not None:
-            reward = self.reward.step(next_obs, action, terminated, truncated, final_obs=final_obs)
-        if pipe is not None:
-            pipe.observe(next_obs, terminated, truncated, final_obs=final_obs)
+            pol.act(agent.observation, out={"env_action": self._action})
+        _, reward, terminated, truncated, _, _ = agent.apply(self._action)
+        agent.observe()
         if record:
             self.tally.step(reward, terminated, truncated)  # the raw reward
 
@@ -233,10 +207,10 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
     ``(mean_reward, std_reward)``, or ``(episode_rewards, episode_lengths)`` with ``return_episode_rewards``.
 
     One evaluation step is: 1. the policy's action from the observation it reads (the env's, or the ``pipeline``'s
-    stack): `MlpActorCritic.mean_action`, which serves any batch size and touches nothing of the policy; 2.
-    ``pipeline.shape_action``; 3. ``env.step``; 4. the reward (``reward``, a `upkie_amd.rewards.RewardTerms` stepped
-    with ``info["final_obs"]``, or ``reward_fn(next_obs, info)``, or the env's own; always raw, never normalised); 5.
-    ``pipeline.observe``; 6. `EpisodeTally.step`. The policy normalises observations with its own packed statistics,
+    stack): `MlpActorCritic.mean_action`, which serves any batch size and touches nothing of the policy; 2. to 5. the
+    two halves of `upkie_amd.agent_step.AgentStep`, back to back: ``pipeline.shape_action``, ``env.step``, the reward
+    (``reward``, ``reward_fn`` or the env's own; always raw, never normalised), ``pipeline.observe``; 6.
+    `EpisodeTally.step`. The policy normalises observations with its own packed statistics,
     which `RunningNormalizer.attach` keeps live: the evaluation env needs no normaliser and is always in sync with
     training (SB3's ``sync_envs_normalization``). ``pipeline`` and ``reward`` are the evaluation's own instances (sized
     for ``env``), reset when it begins.

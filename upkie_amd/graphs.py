@@ -83,19 +83,15 @@ class GraphedEnvStep:
         def body():
             holder["out"] = env.step(policy(obs))
 
-        sim = env.sim
-        keep = [t for t in (getattr(sim, n, None) for n in ("state", "reward", "terminated", "truncated", "contact_manifold", "observer_state")) if t is not None]
-        keep.append(obs)
-        if getattr(env, "_final_obs", None) is not None:
-            keep.append(env._final_obs)
-        saved = [t.clone() for t in keep] if restore_state else []
+        keep = env.state_tensors() if restore_state else {}
+        saved = [t.clone() for t in keep.values()]
         self._loop = GraphedLoop(body, unroll=unroll, warmup=warmup, device=env.device)
         if restore_state:
-            final_obs = getattr(env, "_final_obs", None)  # (a SAME_STEP env arms this buffer on its first step: not among the saved ones then)
-            for t, s in zip(keep, saved):
+            for t, s in zip(keep.values(), saved):
                 t.copy_(s)
-            if final_obs is not None and all(final_obs is not t for t in keep):
-                final_obs.copy_(obs)
+            armed = env.state_tensors().get("final_obs")  # (a SAME_STEP env arms this buffer on its first step: not among the saved ones then)
+            if armed is not None and "final_obs" not in keep:
+                armed.copy_(obs)
         self.out = holder["out"]
         self.steps_per_call = self._loop.unroll
 

@@ -10,6 +10,7 @@ from typing import Callable, Optional, Union
 import torch
 
 from . import abi, lib
+from .agent_step import AgentStep
 from .exceptions import UpkieRuntimeError
 from .launch import check, launcher, ptr
 
@@ -487,10 +488,10 @@ class Ppo:
     """Stable-Baselines3's ``PPO(...).learn(...)`` on the device: the driver that owns the `RolloutBuffer`, the
     `RunningNormalizer` (``normalize``), the `EpisodeStatistics`, the `PpoTrainer` and the rollout's `GraphedLoop`, and
     runs them in the order examples/ppo_mlp_train_time_limits.py establishes. One rollout step is: store the episode
-    starts; ``policy.act`` (normalised observation, action, value and log-prob straight into the buffer); ``env.step``;
-    the reward (``reward_fn(next_obs, info)``, or ``reward``, a `upkie_amd.rewards.RewardTerms` stepped on the raw
-    observation, the applied action and ``info["final_obs"]``, one launch; default the env's own); ``episodes.step`` on the raw reward;
-    ``normalizer.step`` (normalised reward and the next episode starts); the time-limit bootstrap
+    starts; ``policy.act`` (normalised observation, action, value and log-prob straight into the buffer); the env's step
+    and the reward (``reward_fn``, ``reward`` or the env's own) as `upkie_amd.agent_step` states them; ``episodes.step``
+    on the raw reward; the pipeline's observation (same module); ``normalizer.step`` (normalised reward and the next
+    episode starts); the time-limit bootstrap
     (``bootstrap_time_limits``). With ``graph=True`` an iteration is two graph replays (the ``n_steps`` rollout steps,
     the update) around GAE and ``trainer.prepare``; capturing the rollout runs ONE real warm-up step first, as
     `GraphedLoop` does, which is not counted in ``num_timesteps``. With a ``process_group`` (data-parallel: every rank
@@ -517,23 +518,8 @@ class Ppo:
                  reward_fn: Optional[Callable] = None, graph: bool = True, seed: int = 0, process_group=None, pipeline=None, reward=None):
         if int(n_steps) < 1:
             raise ValueError("n_steps must be positive")
-        if reward is not None:
-            if reward_fn is not None:
-                raise ValueError("give reward (a RewardTerms) or reward_fn (a callable), not both")
-            raw = pipeline.obs_dim if pipeline is not None else int(policy.shape.obs_dim)
-            if reward.num_envs != int(env.num_envs) or reward.act_dim != int(policy.shape.act_dim) or reward.obs_dim != raw:
-                raise ValueError(f"the reward serves {reward.num_envs} envs, {reward.obs_dim} observation words and {reward.act_dim} actions, the "
-                                 f"rollout has {int(env.num_envs)}, {raw} (raw) and {int(policy.shape.act_dim)}")
-        self.reward = reward
-        if pipeline is not None:
-            words = int(policy.shape.obs_dim)
-            if words != pipeline.stacked_dim:
-                raise ValueError(f"the policy reads {words} observation words, the pipeline stacks {pipeline.stack} frames of "
-                                 f"{pipeline.frame_dim} = {pipeline.stacked_dim}")
-            if int(policy.shape.act_dim) != pipeline.act_dim or int(env.num_envs) != pipeline.num_envs:
-                raise ValueError(f"the pipeline serves {pipeline.num_envs} envs and {pipeline.act_dim} actions, the env has {int(env.num_envs)} "
-                                 f"and the policy {int(policy.shape.act_dim)}")
-        self.pipeline = pipeline
+        self._agent = AgentStep(env, policy, pipeline, reward, reward_fn, noun="rollout")  # (checks the sizes)
+        self.reward, self.pipeline = reward, pipeline
         self.env, self.policy = env, policy
         self.n_envs = int(env.num_envs)
         self.n_steps, self.gamma, self.gae_lambda = int(n_steps), float(gamma), float(gae_lambda)
@@ -573,14 +559,9 @@ class Ppo:
             if self.normalizer is not None:
                 self.normalizer.broadcast_statistics(0)
         self.buffer = RolloutBuffer(T, N, obs_shape=(D,), action_shape=(A,), device=dev, gamma=self.gamma, gae_lambda=self.gae_lambda)
-        reset = env.reset(seed=self.seed) if self.process_group is None else env.reset()
-        self._obs = getattr(env, "observation", None)
-        if self._obs is None:
-            self._obs = reset[0] if isinstance(reset, tuple) else reset
-        if self.pipeline is not None:
-            self.pipeline.reset(self._obs)
+        self._agent.reset(seed=self.seed if self.process_group is None else None)
         if self.normalizer is not None:
-            self.normalizer.reset(self._policy_observation())
+            self.normalizer.reset(self._agent.observation)
         self._env_action = torch.empty(N, A, device=dev)
         self._starts = torch.ones(N, dtype=torch.uint8, device=dev)
         self._slot = self.n_steps - 1 if self.graph else 0  # (the capture's warm-up step takes the last slot)
@@ -589,16 +570,14 @@ class Ppo:
 
             self._loop = GraphedLoop(self._rollout_step, unroll=T, warmup=1, device=dev)
 
-    def _policy_observation(self) -> torch.Tensor:
-        """The observation the policy reads: the env's, or with a pipeline the stack of frames it keeps."""
-        return self._obs if self.pipeline is None else self.pipeline.observation
+    # the env's latest (raw) observation: the agent step's
+    _obs = property(lambda self: self._agent.raw_observation, lambda self, obs: setattr(self._agent, "raw_observation", obs))
 
     def _rollout_step(self) -> None:
-        """One step of every env into slot ``_slot``. With an `AgentPipeline` between the policy and the env the policy
-        reads the stacked observation, the env receives the shaped command, the reward still sees the RAW observation,
-        and the normaliser and the bootstrap see the stack and its terminal form."""
-        t, buf, pol, starts, pipe = self._slot, self.buffer, self.policy, self._starts, self.pipeline
-        obs = self._policy_observation()
+        """One step of every env into slot ``_slot``: `Ppo`'s own stages around the two halves of `AgentStep`. With an
+        `AgentPipeline` the normaliser and the bootstrap see the stack and its terminal form."""
+        t, buf, pol, starts, agent = self._slot, self.buffer, self.policy, self._starts, self._agent
+        obs = agent.observation
         buf.episode_starts[t].copy_(starts)
         out = {"action": buf.actions[t], "value": buf.values[t], "log_prob": buf.log_probs[t], "env_action": self._env_action}
         if self.normalizer is not None:
@@ -606,23 +585,12 @@ class Ppo:
         else:
             buf.observations[t].copy_(obs)
         pol.act(obs, out=out)
-        action = self._env_action if pipe is None else pipe.shape_action(self._env_action)  # (what the env receives)
-        stepped = self.env.step(action)
-        next_obs, reward, terminated, truncated = stepped[:4]
-        info = stepped[4] if len(stepped) > 4 else {}
-        self._obs = next_obs  # (an env without a persistent observation buffer hands out a new one)
-        final_obs = info.get("final_obs") if hasattr(info, "get") else None
-        if self.reward_fn is not None:
-            reward = self.reward_fn(next_obs, info)
-        elif self.reward is not None:
-            reward = self.reward.step(next_obs, action, terminated, truncated, final_obs=final_obs)
+        _, reward, terminated, truncated, final_obs, _ = agent.apply(self._env_action)
         self.episodes.step(reward, terminated, truncated)  # Monitor: the raw reward
         if self.bootstrap and final_obs is None:
             raise UpkieRuntimeError("bootstrap_time_limits needs info['final_obs'] (an env with autoreset_mode='same_step'); "
                                     "or build Ppo with bootstrap_time_limits=False")
-        if pipe is not None:
-            pipe.observe(next_obs, terminated, truncated, final_obs=final_obs)
-            next_obs, final_obs = pipe.observation, pipe.final_observation  # (what the normaliser and the bootstrap read)
+        next_obs, final_obs = agent.observe()  # (what the normaliser and the bootstrap read)
         if self.normalizer is not None:
             self.normalizer.step(next_obs, reward, terminated, truncated, out={"reward": buf.rewards[t], "episode_starts": starts})
         else:
@@ -642,7 +610,7 @@ class Ppo:
         self.num_timesteps += self.n_steps * self.n_envs
         buf = self.buffer
         buf.pos, buf.full = self.n_steps, True
-        buf.compute_returns_and_advantage(last_values=self.policy.value(self._policy_observation()), dones=self._starts)
+        buf.compute_returns_and_advantage(last_values=self.policy.value(self._agent.observation), dones=self._starts)
 
     def train(self) -> None:
         """SB3's ``PPO.train`` on the collected rollout: `PpoTrainer.prepare`, then the update (a graph replay when
@@ -693,10 +661,8 @@ class Ppo:
 
     # ---- saving and loading
     def _env_tensors(self):
-        sim = getattr(self.env, "sim", None)
-        named = {n: getattr(sim, n, None) for n in ("state", "reward", "terminated", "truncated", "contact_manifold", "observer_state")}
-        named["observation"] = self._obs
-        named["final_obs"] = getattr(self.env, "_final_obs", None)
+        named = dict(self.env.state_tensors())
+        named.setdefault("observation", self._obs)  # (an env without a persistent buffer: the one its latest step handed out)
         return {k: v for k, v in named.items() if isinstance(v, torch.Tensor)}
 
     # where a stage's `state_tensors` go under "tensors" in the file: stage -> (prefix, the names that differ from the stage's own)

@@ -28,7 +28,7 @@ _STEPS = {
 
 
 # What a simulation handle is to its wrappers (`UpkieVecEnv` and its subclasses, `ShardedPendulum`, `ShardedVecEnv`,
-# `GraphedEnvStep`, `Ppo._env_tensors`): the persistent buffers and the members below, nothing else. `BatchedSim` is the
+# `GraphedEnvStep` and `Ppo.save` through `UpkieVecEnv.state_tensors`): the persistent buffers and the members below, nothing else. `BatchedSim` is the
 # product's only handle; the `sim_factory=` parameter of the wrappers is the seam through which tests inject a CPU double,
 # which has to provide every one of these names with the same parameters (tests/test_handle_contract.py).
 HANDLE_BUFFERS = ("state", "reward", "terminated", "truncated", "obs4", "obs6", "obs_servos", "obs3")
