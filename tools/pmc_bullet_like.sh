@@ -15,7 +15,9 @@ for C in "FETCH_SIZE" "WRITE_SIZE" \
   "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_SALU SQ_WAVES GRBM_GUI_ACTIVE" \
   "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_INSTS_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_THREAD_CYCLES_VALU"; do
   i=$((i+1))
-  timeout 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pass$i -o pmc -- python $R/tools/profile_bullet_like.py c2 > $OUT/pass$i.log 2>&1
+  # (the first pass that fails ends the script: nothing more is started on that GPU)
+  timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pass$i -o pmc -- python $R/tools/profile_bullet_like.py c2 > $OUT/pass$i.log 2>&1 \
+    || { rc=$?; tail -20 $OUT/pass$i.log; echo "pass $i ($C) ended with status $rc"; exit $rc; }
 done
 find $OUT -name "*kernel_trace.csv" -size +8M -delete
 ls $OUT

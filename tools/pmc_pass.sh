@@ -19,7 +19,9 @@ for C in "FETCH_SIZE" "WRITE_SIZE" \
   "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_INSTS_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_THREAD_CYCLES_VALU" \
   "SQ_INSTS_VALU_MFMA_F32 SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INST_CYCLES_VMEM SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS"; do
   i=$((i+1))
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pass$i -o pmc -- \
-    python $R/bench.py --steps 128 --warmup 64 --no-cpu-baseline --no-fused --no-steady-state --no-secondary "$@" > $OUT/pass$i.log 2>&1
+  # (every pass under its own time limit; the first pass that fails ends the script: nothing more is started on that GPU)
+  timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pass$i -o pmc -- \
+    python $R/bench.py --steps 128 --warmup 64 --no-cpu-baseline --no-fused --no-steady-state --no-secondary "$@" > $OUT/pass$i.log 2>&1 \
+    || { rc=$?; tail -20 $OUT/pass$i.log; echo "pass $i ($C) ended with status $rc"; exit $rc; }
 done
 ls -R $OUT | head -40

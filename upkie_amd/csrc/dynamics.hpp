@@ -295,6 +295,9 @@ UPKIE_HD BaseFrame base_frame(float qw, float qx, float qy, float qz, V3 linvel,
 // dq = (cos(half), sin(half) w / |w|) with sin(half) / |w| = h/2 sinc(half); half
 // is a few 1e-3 at most in practice: series to x^8 (exact to fp32 below 0.5 rad),
 // libm beyond; q <- dq * q (world-frame angular velocity), renormalised.
+// WAVE_UNIFORM_LIBM (the eight-lane kernels): every lane evaluates the series and the libm arm sits behind ONE scalar test
+// of the whole wavefront, which the common path falls through; a lane beyond 0.5 rad takes libm's values as before.
+template <bool WAVE_UNIFORM_LIBM = false>
 UPKIE_HD void integrate_base(const BaseFrame& f, float n0, float n1, float n2, float n3, float n4, float n5, float h, V3& pos, float& qw,
                              float& qx, float& qy, float& qz, V3& linvel, V3& angvel) {
   linvel = v3(f.r00 * n0 + f.r01 * n1 + f.r02 * n2, f.r10 * n0 + f.r11 * n1 + f.r12 * n2, f.r20 * n0 + f.r21 * n1 + f.r22 * n2);
@@ -303,7 +306,24 @@ UPKIE_HD void integrate_base(const BaseFrame& f, float n0, float n1, float n2, f
   const float wn = fast_sqrt(dot(angvel, angvel));
   const float half = 0.5f * h * wn;
   float ch, k;
-  if (half < 0.5f) {
+  if constexpr (WAVE_UNIFORM_LIBM) {
+    const float x2 = half * half;
+    k = 0.5f * h * (1.f + x2 * (-1.f / 6.f + x2 * (1.f / 120.f + x2 * (-1.f / 5040.f + x2 * (1.f / 362880.f)))));
+    ch = 1.f + x2 * (-0.5f + x2 * (1.f / 24.f + x2 * (-1.f / 720.f + x2 * (1.f / 40320.f))));
+    const bool beyond = !(half < 0.5f);
+#if defined(__HIP_DEVICE_COMPILE__)
+    const bool some_lane_beyond = __builtin_amdgcn_ballot_w64(beyond) != 0;
+#else
+    const bool some_lane_beyond = beyond;
+#endif
+    if (__builtin_expect(some_lane_beyond, 0)) {
+      if (beyond) {
+        float sh;
+        sincosf(half, &sh, &ch);
+        k = sh * fast_rcp(wn);
+      }
+    }
+  } else if (half < 0.5f) {
     const float x2 = half * half;
     k = 0.5f * h * (1.f + x2 * (-1.f / 6.f + x2 * (1.f / 120.f + x2 * (-1.f / 5040.f + x2 * (1.f / 362880.f)))));
     ch = 1.f + x2 * (-0.5f + x2 * (1.f / 24.f + x2 * (-1.f / 720.f + x2 * (1.f / 40320.f))));

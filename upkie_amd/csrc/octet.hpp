@@ -508,8 +508,44 @@ UPKIE_HD void ldl6_solve_planar(const Ldl6Planar& f, float (&x)[6]) {
 // symmetric positive definite (a tire's own Delassus block or its Schur
 // complement): no pivoting. The trunk lane carries zeros along (its reciprocal
 // pivot is that of a unit diagonal).
+#define OCT_GJ(x, f, k) "v_fmac_f32_dpp " x ", -" x ", " f OCT_Q(k)
 template <int NE>
 UPKIE_HD void oct_gauss_jordan(const OctLane& L, float (&D)[3], float (&E)[NE]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (NE == 4) {
+    // The three eliminations of the direct solve's [D | X rhs] as ONE block: x -= f qb<k>(x) is v_fmac_f32_dpp x, -x, f (left to
+    // the compiler, a v_mov_b32_dpp and a v_fma_f32 each: fifteen lane moves), the same operations on the same values in the
+    // same order. Inside the block a register is read through DPP at least two instructions after it was written (D1 / D2 are
+    // eliminated first and their reciprocals taken two multiply-adds later), a reciprocal is used two instructions after it
+    // was issued or behind a wait state.
+    const float w1 = 1.f - L.e[0], w2 = 1.f - L.e[1], w3 = 1.f - L.e[2];
+    float ip, iq, f, g;
+    asm("s_nop 1\n\t"
+        "v_rcp_f32_dpp %[ip], %[d0]" OCT_Q(1)
+        "s_nop 0\n\t"
+        "v_mul_f32_e32 %[f], %[d0], %[ip]\n\t"
+        "v_mul_f32_e32 %[f], %[w1], %[f]\n\t"
+        OCT_GJ("%[d1]", "%[f]", 1) OCT_GJ("%[d2]", "%[f]", 1) OCT_GJ("%[e0]", "%[f]", 1)
+        "v_rcp_f32_dpp %[iq], %[d1]" OCT_Q(2)
+        OCT_GJ("%[e1]", "%[f]", 1) OCT_GJ("%[e2]", "%[f]", 1) OCT_GJ("%[e3]", "%[f]", 1)
+        "v_mul_f32_e32 %[g], %[d1], %[iq]\n\t"
+        "v_mul_f32_e32 %[g], %[w2], %[g]\n\t"
+        OCT_GJ("%[d2]", "%[g]", 2) OCT_GJ("%[e0]", "%[g]", 2) OCT_GJ("%[e1]", "%[g]", 2)
+        "v_rcp_f32_dpp %[ip], %[d2]" OCT_Q(3)
+        OCT_GJ("%[e2]", "%[g]", 2) OCT_GJ("%[e3]", "%[g]", 2)
+        "v_mul_f32_e32 %[f], %[d2], %[ip]\n\t"
+        "v_mul_f32_e32 %[f], %[w3], %[f]\n\t"
+        OCT_GJ("%[e0]", "%[f]", 3) OCT_GJ("%[e1]", "%[f]", 3) OCT_GJ("%[e2]", "%[f]", 3) OCT_GJ("%[e3]", "%[f]", 3)
+        : [d1] "+v"(D[1]), [d2] "+v"(D[2]), [e0] "+v"(E[0]), [e1] "+v"(E[1]), [e2] "+v"(E[2]), [e3] "+v"(E[3]), [ip] "=&v"(ip), [iq] "=&v"(iq),
+          [f] "=&v"(f), [g] "=&v"(g)
+        : [d0] "v"(D[0]), [w1] "v"(w1), [w2] "v"(w2), [w3] "v"(w3));
+    const float diag = L.e[0] * D[0] + L.e[1] * D[1] + L.e[2] * D[2] + L.w0;
+    const float id = fast_rcp(diag);
+#pragma unroll
+    for (int i = 0; i < NE; ++i) E[i] *= id;
+    return;
+  }
+#endif
   // pivot 0 (lane 1)
   {
     const float ip = fast_rcp(oct_qb<1>(D[0]));
@@ -1121,12 +1157,14 @@ UPKIE_HD int physics_substep_octet(const ModelT& M, const LimitsT& Lm, const Oct
   // ---- a joint at its stop (rare): its row joins the contact rows in the general solve below
   // (L.bounded carries the handle's `enforce` switch: read from the settings block here, `if (Lm.enforce)` was a scalar
   // load and a wait for it in every substep, 86-160 cycles of a lone wavefront each)
+  // (the own joint's test without a branch: joint_limit_near's `&&` / `||` were two nested exec-mask regions in every substep)
   bool at_a_stop = false;
   {
 #if defined(UPKIE_AB_OLD_LIMITS)
     const bool own_limit = L.bounded && (s.q <= L.lower || s.q >= L.upper);
 #else
-    const bool own_limit = joint_limit_near(L.bounded, s.q, L.lower, L.upper, joint_limit_reach(s.qd, OCT_HOT(max_joint_velocity), h));
+    const float zone = joint_limit_reach(s.qd, OCT_HOT(max_joint_velocity), h);
+    const bool own_limit = (int)L.bounded & ((int)(s.q - L.lower <= zone) | (int)(L.upper - s.q <= zone));  // = joint_limit_near
 #endif
     if (__builtin_expect(oct_wave_any(own_limit), 0)) at_a_stop = oct_env_any(own_limit);
   }
@@ -1289,6 +1327,10 @@ UPKIE_HD int physics_substep_octet(const ModelT& M, const LimitsT& Lm, const Oct
   float xl = 0.f;  // own joint velocity change
   int swept_now = 0;
   float lam_now = 0.f;
+  // ---- a joint at its stop (the envs of the wavefront that are not get their answer below: the two write disjoint lanes).
+  // In line, skipped by one taken s_cbranch_execz: behind a scalar test of the whole wavefront the path moves out of the loop
+  // and the skip is not taken -- and every eight-lane kernel then allocates 256 registers (the headline: 241 this way, 248
+  // before) for 0.08 us of a 13.7 us launch, less than two windows of one build differ (profiles/octet_common_path_ab.txt)
   if (__builtin_expect(at_a_stop, 0)) {
     if (census) census->path = OCT_NOT_MINE_LIMIT;
     if (LIMITS_IN_REGISTERS && !BULLET_LIKE) {
@@ -1301,7 +1343,9 @@ UPKIE_HD int physics_substep_octet(const ModelT& M, const LimitsT& Lm, const Oct
       octet_limit_path_scratch<BULLET_LIKE>(M, L, fac, Dc, hv0, hv1, hv2, o, Pc, nB, iun, vB, wB, dist, active, active_partner, s.qd, tl, rt, cfm, erp, ih,
                                             lim_sign, lim_bias, xb, xl, ws[oct_env_slot()], &bf, &s.bl_applied);
     }
-  } else if (__builtin_expect(active || active_partner, 1)) {
+  }
+  if (__builtin_expect(!at_a_stop, 1)) {
+  if (__builtin_expect(active || active_partner, 1)) {
     const float sa = oct_qb<3>(L.sg);
     const V3 t1 = (sa * iun) * v3(nB.z, 0.f, -nB.x);
     const V3 t2 = cross(nB, t1);
@@ -1385,7 +1429,8 @@ UPKIE_HD int physics_substep_octet(const ModelT& M, const LimitsT& Lm, const Oct
     // on it (contact_pgs6: same rows, same order), every lane of the env in lockstep on identical data
     {
       const float lam_n = oct_qb<1>(lam);
-      const bool bad = L.l == 1 ? lam < 0.f : (L.l != 0 && fabsf(lam) > OCT_HOT(friction_mu) * lam_n);
+      // (bitwise: as `?:` / `&&` it was three nested exec-mask regions in every substep)
+      const bool bad = ((int)(L.l == 1) & (int)(lam < 0.f)) | ((int)(L.l > 1) & (int)(fabsf(lam) > OCT_HOT(friction_mu) * lam_n));
       if (__builtin_expect(oct_wave_any(bad), 0)) {
         if (oct_env_any(bad)) {
           if (census) census->path = OCT_NOT_MINE_INFEASIBLE;
@@ -1455,11 +1500,10 @@ UPKIE_HD int physics_substep_octet(const ModelT& M, const LimitsT& Lm, const Oct
     if (BULLET_LIKE) s.bl_applied = 0.f;
   }
 
-  // ---- joint velocity change: Hinv t - D' xb ------------------------------------
-  if (__builtin_expect(!at_a_stop, 1)) {
-    xl = oct_sumj(0.f, tlc, hv0, hv1, hv2);
-    xl -= Dc[0] * xb[0] + Dc[2] * xb[2] + Dc[3] * xb[3] + Dc[4] * xb[4] + Dc[5] * xb[5];
-  }
+  // ---- joint velocity change: Hinv t - D' xb (inside the region of the lanes that are not at a stop: one exec mask) ----
+  xl = oct_sumj(0.f, tlc, hv0, hv1, hv2);
+  xl -= Dc[0] * xb[0] + Dc[2] * xb[2] + Dc[3] * xb[3] + Dc[4] * xb[4] + Dc[5] * xb[5];
+  }  // !at_a_stop
 
   // ---- integrate --------------------------------------------------------------------
   {
@@ -1495,7 +1539,7 @@ UPKIE_HD int physics_substep_octet(const ModelT& M, const LimitsT& Lm, const Oct
   }
   const float n0 = vB.x + xb[0], n1 = vB.y + xb[1], n2 = vB.z + xb[2];
   const float n3 = wB.x + xb[3], n4 = wB.y + xb[4], n5 = wB.z + xb[5];
-  integrate_base(bf, n0, n1, n2, n3, n4, n5, h, s.pos, s.qw, s.qx, s.qy, s.qz, s.linvel, s.angvel);
+  integrate_base<true>(bf, n0, n1, n2, n3, n4, n5, h, s.pos, s.qw, s.qx, s.qy, s.qz, s.linvel, s.angvel);
   return (active || active_partner) ? OCT_CONTACT : OCT_NO_CONTACT;
 }
 
@@ -1922,15 +1966,22 @@ next_step:
   float tau = 0.f;
   bool contact = false;
   const int nsub = do_reset ? 1 : nb_substeps;
+  // control noise is a setting of the launch: whether any lane of the wavefront draws it is asked once, here, and the
+  // substeps test that scalar -- a branch the common path falls through, the draws sit behind the loop
+  const bool wave_control_noise = oct_wave_any(any_control_noise && !do_reset);
   for (int sub = 0; sub < nb_substeps; ++sub) {
     if (sub >= nsub) break;
     float noise = 0.f;
-    if (any_control_noise && !do_reset) {
-      float zn[6];
-      philox_normal6(C, (unsigned)e, step_count, (unsigned)sub, zn);
-      noise = L.control_noise * pick6(joint, zn);
+    if (__builtin_expect(wave_control_noise, 0)) {
+      if (any_control_noise && !do_reset) {
+        float zn[6];
+        philox_normal6(C, (unsigned)e, step_count, (unsigned)sub, zn);
+        noise = L.control_noise * pick6(joint, zn);
+      }
     }
-    tau = jointed ? joint_torque(s.q, s.qd, cmd, kp_gain, kd_gain, L.friction, noise) : 0.f;
+    // (every lane: the trunk lane's servo is all zeros, its torque is dropped -- a select, not a branch around the law)
+    const float servo_torque = joint_torque(s.q, s.qd, cmd, kp_gain, kd_gain, L.friction, noise);
+    tau = jointed ? servo_torque : 0.f;
     ConstModelPtr mp = (ConstModelPtr)Mp;
     asm volatile("" : "+s"(mp));
     const bool forces = RAND && ext.force && !do_reset;  // the reset substep runs without external forces
