@@ -206,7 +206,8 @@ enum UpkieStructId {
   UPKIE_STRUCT_OBSERVER_OUTPUT = 8,
   UPKIE_STRUCT_MLP_SHAPE = 9,
   UPKIE_STRUCT_PPO_CONFIG = 10,
-  UPKIE_STRUCT_COUNT = 11
+  UPKIE_STRUCT_EPISODE_EVENTS = 11,
+  UPKIE_STRUCT_COUNT = 12
 };
 int64_t upkie_hip_struct_bytes(int which);
 
@@ -442,6 +443,76 @@ int upkie_sim_sample_body_inertials(UpkieSim* sim, float* body_inertials,
  * substep. Zero the buffer to end the push. */
 int upkie_sim_sample_pushes(UpkieSim* sim, float* force, uint32_t push_index,
                             double max_norm, void* stream);
+
+/* ---- Episode events (random pushes, per-episode inertias) ----------------
+ * The two perturbations a balancing policy is trained with, decided on the
+ * device between two env steps, in ONE launch per env step
+ * (csrc/episode_events.hpp), so that they can live inside a captured rollout:
+ * pushes that start at random per env and are held a random number of steps
+ * (what a RandomPush-style wrapper around the reference's
+ * set_external_forces does, pybullet_backend.py:603-658), and link inertias
+ * drawn again for every episode (randomize_inertias, :571-601, once per reset
+ * of the reference's backend). The step kernels are not involved: `force` is
+ * the [1][3][N] buffer upkie_sim_set_external_forces installed and
+ * `body_inertials` the records upkie_sim_set_randomization installed; the
+ * caller installs both once. State, device buffers of N = the handle's
+ * num_envs words each, zero before the first call:
+ *   calls uint32: calls so far;  remaining int32: steps the current force is
+ *   still held, the coming one included;  pushes uint32: pushes started so
+ *   far;  episodes uint32: episodes ended so far.
+ * upkie_sim_episode_events_step, per env n, in this order:
+ *   1. r = Philox4x32-10, counter (global env id lo, hi, calls[n],
+ *      STREAM_EVENTS << 24 | 0) with STREAM_EVENTS = 6, key = the handle's
+ *      seed; calls[n] += 1. Every env, every call: an env's draws depend
+ *      neither on the batch, nor on the sharding, nor on other envs.
+ *   2. if terminated[n] | truncated[n] (bytes; either may be NULL: 0):
+ *      episodes[n] += 1, remaining[n] = 0 (a push does not outlive its
+ *      episode) and, with inertia_variation > 0, the env's link factors are
+ *      drawn as upkie_sim_sample_body_inertials draws them but with counter
+ *      word 2 = episodes[n] (0 there), fused into the env's
+ *      UPKIE_NB * UPKIE_INERTIAL_WORDS words of body_inertials and written to
+ *      its column of link_scale [UPKIE_MAX_LINKS][N]. Other envs' words are
+ *      not written.
+ *   3. if remaining[n] > 0: remaining[n] -= 1.
+ *   4. if remaining[n] == 0 the coming step is free: a push starts iff
+ *      (r[0] >> 8) < llround(push_prob * 2^24). At a start, with
+ *      k = pushes[n], the force is push number k of env n as
+ *      upkie_sim_sample_pushes(push_index = k) defines it, but for its norm
+ *      fma(push_norm_max - push_norm_min, u0, push_norm_min) (float32;
+ *      push_norm_min = 0: the same value); pushes[n] += 1; remaining[n] =
+ *      push_steps_min + (r[3] >> 8) % (push_steps_max - push_steps_min + 1).
+ *      Without a start the three force words are +0.
+ *   5. otherwise (a force is held) the force words are not written.
+ * upkie_sim_episode_events_reset, for the envs with mask[n] != 0 (all when
+ * mask is NULL): the four counters and the force back to 0 and, with
+ * inertia_variation > 0, the records and factors of episode 0, which are
+ * upkie_sim_sample_body_inertials'.
+ * Refused with UPKIE_ERR_INVALID_ARGUMENT before anything else, with or
+ * without a device: push_prob outside [0, 1], norms that are not finite with
+ * 0 <= min <= max, steps outside 1 <= min <= max <= 65535, inertia_variation
+ * outside [0, 1), push_prob == 0 with inertia_variation == 0 (nothing to do),
+ * a NULL handle or state buffer, body_inertials / link_scale not given
+ * exactly when inertia_variation > 0. No allocation, no host synchronisation,
+ * no host argument that changes between calls: a step can be captured in a
+ * hipGraph; the handle's seed and env_id_offset are read when the launch is
+ * recorded. */
+typedef struct UpkieEpisodeEvents {
+  double push_prob;         /* per free env step */
+  double push_norm_min;     /* N */
+  double push_norm_max;
+  double inertia_variation; /* 0: the records are left alone */
+  int32_t push_steps_min;   /* env steps a push is held */
+  int32_t push_steps_max;
+} UpkieEpisodeEvents;
+
+int upkie_sim_episode_events_step(UpkieSim* sim, const UpkieEpisodeEvents* params, const uint8_t* terminated,
+                                  const uint8_t* truncated, uint32_t* calls, int32_t* remaining, uint32_t* pushes,
+                                  uint32_t* episodes, float* force, float* body_inertials, float* link_scale,
+                                  void* stream);
+
+int upkie_sim_episode_events_reset(UpkieSim* sim, const UpkieEpisodeEvents* params, const uint8_t* mask, uint32_t* calls,
+                                   int32_t* remaining, uint32_t* pushes, uint32_t* episodes, float* force,
+                                   float* body_inertials, float* link_scale, void* stream);
 
 /* Diagnostic: the projected Gauss-Seidel sweeps the step kernels run when the
  * direct contact solution leaves its friction cone (what Bullet's

@@ -314,6 +314,19 @@ class UpkiePpoConfig(C.Structure):
     ]
 
 
+class UpkieEpisodeEvents(C.Structure):
+    """The settings of `upkie_sim_episode_events_step` (include/upkie_hip.h, "Episode events")."""
+
+    _fields_ = [
+        ("push_prob", C.c_double),
+        ("push_norm_min", C.c_double),
+        ("push_norm_max", C.c_double),
+        ("inertia_variation", C.c_double),
+        ("push_steps_min", C.c_int32),
+        ("push_steps_max", C.c_int32),
+    ]
+
+
 # enum UpkieStructId -> the mirror of that struct here (`upkie_hip_struct_bytes`: lib.load() compares sizes)
 STRUCT_IDS = {
     0: UpkieModel,
@@ -327,10 +340,11 @@ STRUCT_IDS = {
     8: UpkieObserverOutput,
     9: UpkieMlpShape,
     10: UpkiePpoConfig,
+    11: UpkieEpisodeEvents,
 }
 # structs that only newer, optional entry points read: a build without that entry point (an older library loaded through
 # UPKIE_HIP_LIBRARY for an A/B run) answers -1 for them, and lib.load() still accepts it
-OPTIONAL_STRUCTS = {9: "upkie_mlp_actor_critic", 10: "upkie_ppo_minibatch_update"}
+OPTIONAL_STRUCTS = {9: "upkie_mlp_actor_critic", 10: "upkie_ppo_minibatch_update", 11: "upkie_sim_episode_events_step"}
 MAX_GRAPH_CAPTURES = 8  # UPKIE_MAX_GRAPH_CAPTURES
 
 # the PPO control block's fp64 words (enum UPKIE_PPO_CTRL_*)

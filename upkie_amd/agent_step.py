@@ -8,6 +8,8 @@ The caller takes the policy's action from `observation` (the env's, or the ``pip
    observation, the APPLIED action and ``info["final_obs"]`` (one launch), or by default the env's own. Always raw,
    never normalised: what a Monitor and an evaluation count.
 2. the caller's stages that read the raw reward before the stack moves (`Ppo`: the episode statistics);
+   Last, ``events.step(terminated, truncated)`` (a `upkie_amd.events.EpisodeEvents`: random pushes, per-episode
+   inertias), so that what it decides after step k acts during step k + 1.
 3. `observe`: ``pipeline.observe`` on the raw next observation and ``info["final_obs"]``; it returns what a normaliser
    and a time-limit bootstrap read: the stack and its terminal form, or without a pipeline the env's two.
 
@@ -17,7 +19,8 @@ from typing import Callable, Optional
 
 
 class AgentStep:
-    def __init__(self, env, policy, pipeline=None, reward=None, reward_fn: Optional[Callable] = None, noun: str = "rollout"):
+    def __init__(self, env, policy, pipeline=None, reward=None, reward_fn: Optional[Callable] = None, noun: str = "rollout",
+                 events=None):
         """Checks the stages' sizes against each other once; ``noun`` names the caller in the messages."""
         if reward is not None and reward_fn is not None:
             raise ValueError("give reward (a RewardTerms) or reward_fn (a callable), not both")
@@ -32,12 +35,14 @@ class AgentStep:
                                  f"{pipeline.frame_dim} = {pipeline.stacked_dim}")
             if pipeline is not None and (A != pipeline.act_dim or N != pipeline.num_envs):
                 raise ValueError(f"the pipeline serves {pipeline.num_envs} envs and {pipeline.act_dim} actions, the env has {N} and the policy {A}")
-        self.env, self.pipeline, self.reward, self.reward_fn = env, pipeline, reward, reward_fn
+        if events is not None and int(events.num_envs) != int(env.num_envs):
+            raise ValueError(f"the events serve {events.num_envs} envs, the {noun} has {int(env.num_envs)}")
+        self.env, self.pipeline, self.reward, self.reward_fn, self.events = env, pipeline, reward, reward_fn, events
         self.raw_observation = None  # the env's latest observation (an env without a persistent buffer hands out a new one per step)
         self._stepped = None  # what the latest `apply` returned
 
     def reset(self, seed: Optional[int] = None):
-        """``env.reset``, then the pipeline's stack restarted on the first observation."""
+        """``env.reset``, then the pipeline's stack restarted on the first observation, then ``events.reset``."""
         reset = self.env.reset(seed=seed) if seed is not None else self.env.reset()
         obs = getattr(self.env, "observation", None)
         if obs is None:
@@ -45,6 +50,8 @@ class AgentStep:
         self.raw_observation = obs
         if self.pipeline is not None:
             self.pipeline.reset(obs)
+        if self.events is not None:
+            self.events.reset()
 
     @property
     def observation(self):
@@ -63,6 +70,8 @@ class AgentStep:
             reward = self.reward_fn(next_obs, info)
         elif self.reward is not None:
             reward = self.reward.step(next_obs, action, terminated, truncated, final_obs=final_obs)
+        if self.events is not None:
+            self.events.step(terminated, truncated)
         self._stepped = stepped = (next_obs, reward, terminated, truncated, final_obs, info)
         return stepped
 

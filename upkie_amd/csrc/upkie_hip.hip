@@ -17,6 +17,7 @@
 #include "step_instances.hpp"  // (the step kernels this unit launches are compiled elsewhere, by groups: declarations only)
 #include "step_dispatch.hpp"
 #include "host_setup.hpp"
+#include "episode_events.hpp"
 #include "abi_host.hpp"
 
 namespace upkie {
@@ -330,6 +331,7 @@ extern "C" int64_t upkie_hip_struct_bytes(int which) {
     case UPKIE_STRUCT_OBSERVER_OUTPUT: return (int64_t)sizeof(UpkieObserverOutput);
     case UPKIE_STRUCT_MLP_SHAPE: return (int64_t)sizeof(UpkieMlpShape);
     case UPKIE_STRUCT_PPO_CONFIG: return (int64_t)sizeof(UpkiePpoConfig);
+    case UPKIE_STRUCT_EPISODE_EVENTS: return (int64_t)sizeof(UpkieEpisodeEvents);
     default: return -1;
   }
 }
@@ -483,6 +485,55 @@ extern "C" int upkie_sim_sample_pushes(UpkieSim* sim, float* force, uint32_t pus
   hipLaunchKernelGGL(push_kernel, grid_for(sim->config.num_envs), dim3(block_lanes()), 0, (hipStream_t)stream, sim->config, force,
                      (unsigned)push_index, (float)max_norm);
   return check_hip(sim, hipGetLastError(), "push_kernel");
+}
+
+// Episode events (include/upkie_hip.h): the settings checked and converted; every refusal comes before any device use.
+static int events_params(UpkieSim* sim, const UpkieEpisodeEvents* p, const void* calls, const void* remaining, const void* pushes,
+                         const void* episodes, const void* force, const void* body_inertials, const void* link_scale, EventsParams* out) {
+  if (!p) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  if (!(p->push_prob >= 0.0 && p->push_prob <= 1.0)) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "push_prob must be in [0, 1]");
+  if (!(std::isfinite(p->push_norm_min) && std::isfinite(p->push_norm_max) && p->push_norm_min >= 0.0 && p->push_norm_min <= p->push_norm_max))
+    return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "push_norm must be finite with 0 <= min <= max");
+  if (!(p->push_steps_min >= 1 && p->push_steps_min <= p->push_steps_max && p->push_steps_max <= 65535))
+    return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "push_steps must hold 1 <= min <= max <= 65535");
+  if (!(p->inertia_variation >= 0.0 && p->inertia_variation < 1.0)) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "inertia_variation must be in [0, 1)");
+  if (p->push_prob == 0.0 && p->inertia_variation == 0.0)
+    return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "push_prob and inertia_variation are both 0: nothing to do");
+  if (!sim || !calls || !remaining || !pushes || !episodes || !force) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  const bool inertia = p->inertia_variation > 0.0;
+  if (inertia != (body_inertials != nullptr) || inertia != (link_scale != nullptr))
+    return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "body_inertials and link_scale are given exactly when inertia_variation > 0");
+  out->threshold = (unsigned)std::llround(p->push_prob * 16777216.0);
+  out->steps_min = p->push_steps_min;
+  out->steps_span = (unsigned)(p->push_steps_max - p->push_steps_min + 1);
+  out->norm_min = (float)p->push_norm_min;
+  out->norm_max = (float)p->push_norm_max;
+  out->variation = (float)p->inertia_variation;
+  return UPKIE_OK;
+}
+
+extern "C" int upkie_sim_episode_events_step(UpkieSim* sim, const UpkieEpisodeEvents* params, const uint8_t* terminated,
+                                             const uint8_t* truncated, uint32_t* calls, int32_t* remaining, uint32_t* pushes,
+                                             uint32_t* episodes, float* force, float* body_inertials, float* link_scale, void* stream) {
+  EventsParams P;
+  const int status = events_params(sim, params, calls, remaining, pushes, episodes, force, body_inertials, link_scale, &P);
+  if (status != UPKIE_OK) return status;
+  hipLaunchKernelGGL(episode_events_kernel, grid_for(sim->config.num_envs), dim3(block_lanes()), 0, (hipStream_t)stream, sim->config, sim->links,
+                     P, terminated, truncated, (unsigned*)calls, (int*)remaining, (unsigned*)pushes, (unsigned*)episodes, force, body_inertials,
+                     link_scale);
+  return check_hip(sim, hipGetLastError(), "episode_events_kernel");
+}
+
+extern "C" int upkie_sim_episode_events_reset(UpkieSim* sim, const UpkieEpisodeEvents* params, const uint8_t* mask, uint32_t* calls,
+                                              int32_t* remaining, uint32_t* pushes, uint32_t* episodes, float* force,
+                                              float* body_inertials, float* link_scale, void* stream) {
+  EventsParams P;
+  const int status = events_params(sim, params, calls, remaining, pushes, episodes, force, body_inertials, link_scale, &P);
+  if (status != UPKIE_OK) return status;
+  hipLaunchKernelGGL(episode_events_reset_kernel, grid_for(sim->config.num_envs), dim3(block_lanes()), 0, (hipStream_t)stream, sim->config,
+                     sim->links, P, mask, (unsigned*)calls, (int*)remaining, (unsigned*)pushes, (unsigned*)episodes, force, body_inertials,
+                     link_scale);
+  return check_hip(sim, hipGetLastError(), "episode_events_reset_kernel");
 }
 
 // What the choice of a step kernel (step_dispatch.hpp) reads from the handle, for an entry point that launches `mode`.

@@ -51,6 +51,7 @@ SOURCES = [
     os.path.join(_CSRC, "eval_episodes.hpp"),
     os.path.join(_CSRC, "agent_pipeline.hpp"),
     os.path.join(_CSRC, "reward_terms.hpp"),
+    os.path.join(_CSRC, "episode_events.hpp"),
     os.path.join(_CSRC, "wave_io.hpp"),
     os.path.join(_HERE, "..", "include", "upkie_hip.h"),
 ]
@@ -93,6 +94,9 @@ def _abi_table():
         ("upkie_sim_sample_body_inertials", status, [vp, vp, vp, f64, vp], None),
         ("upkie_sim_contact_sweeps", status, [vp, i32, vp, vp, vp, vp, vp, vp], None),
         ("upkie_sim_sample_pushes", status, [vp, vp, C.c_uint32, f64, vp], None),
+        # the episode events (random pushes, per-episode inertias)
+        ("upkie_sim_episode_events_step", status, [vp, P(abi.UpkieEpisodeEvents)] + [vp] * 10, "upkie_sim_episode_events_step"),
+        ("upkie_sim_episode_events_reset", status, [vp, P(abi.UpkieEpisodeEvents)] + [vp] * 9, "upkie_sim_episode_events_step"),
         ("upkie_sim_reset", status, [vp, vp, vp, vp, vp], None),
         ("upkie_sim_step_pendulum", status, step, None),
         ("upkie_sim_step_gyropod", status, step, None),

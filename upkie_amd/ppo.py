@@ -507,19 +507,23 @@ class Ppo:
     ``clip_range_vf`` take floats or callables of ``progress_remaining``; ``target_kl`` as SB3.
 
     `save` / `load` carry everything the next iteration reads -- packed weights, Adam's moments and control block, the
-    trainer's generator, the policy's per-env noise counters, the normaliser, the episode statistics, the reward's state (``reward.*``, when one is given), the episode
+    trainer's generator, the policy's per-env noise counters, the normaliser, the episode statistics, the reward's state (``reward.*``, when one is given), the episode events' (``events.*``: counters, force, inertial records), the episode
     starts, the counters and the env (the simulation's state block, its observation and step outputs) -- so a run
-    resumed in fresh objects continues bit for bit. Schedules, ``reward_fn`` and ``reward`` are code: give them to `load` again."""
+    resumed in fresh objects continues bit for bit. Schedules, ``reward_fn``, ``reward`` and ``events`` are code: give them to `load` again.
+
+    ``events`` (a `upkie_amd.events.EpisodeEvents` built on ``env``) perturbs the rollout: random pushes and per-episode
+    inertias, one more launch per step, after the reward (`AgentStep`)."""
 
     def __init__(self, env, policy, n_steps: int = 128, gamma: float = 0.99, gae_lambda: float = 0.95, n_epochs: int = 10, batch_size: int = 64,
                  learning_rate: Schedule = 3e-4, clip_range: Schedule = 0.2, clip_range_vf: Optional[Schedule] = None,
                  normalize_advantage: bool = True, ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5,
                  target_kl: Optional[float] = None, normalize: bool = True, bootstrap_time_limits: bool = True, stats_window_size: int = 100,
-                 reward_fn: Optional[Callable] = None, graph: bool = True, seed: int = 0, process_group=None, pipeline=None, reward=None):
+                 reward_fn: Optional[Callable] = None, graph: bool = True, seed: int = 0, process_group=None, pipeline=None, reward=None,
+                 events=None):
         if int(n_steps) < 1:
             raise ValueError("n_steps must be positive")
-        self._agent = AgentStep(env, policy, pipeline, reward, reward_fn, noun="rollout")  # (checks the sizes)
-        self.reward, self.pipeline = reward, pipeline
+        self._agent = AgentStep(env, policy, pipeline, reward, reward_fn, noun="rollout", events=events)  # (checks the sizes)
+        self.reward, self.pipeline, self.events = reward, pipeline, events
         self.env, self.policy = env, policy
         self.n_envs = int(env.num_envs)
         self.n_steps, self.gamma, self.gae_lambda = int(n_steps), float(gamma), float(gae_lambda)
@@ -667,7 +671,7 @@ class Ppo:
 
     # where a stage's `state_tensors` go under "tensors" in the file: stage -> (prefix, the names that differ from the stage's own)
     _FILE_NAMES = {"policy": ("", {}), "trainer": ("", {}), "episodes": ("", {"counters": "ep_counters", "means": "ep_means"}),
-                   "pipeline": ("pipeline.", {}), "reward": ("reward.", {})}
+                   "pipeline": ("pipeline.", {}), "reward": ("reward.", {}), "events": ("events.", {})}
 
     def _state_tensors(self):
         named = {"starts": self._starts}
