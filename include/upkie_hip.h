@@ -920,6 +920,7 @@ typedef struct {
   int32_t critic_widths[UPKIE_MLP_MAX_LAYERS];
   int32_t normalize; /* 1: observation normalisation with the packed obs_mean / obs_std */
   float clip_obs;    /* VecNormalize's clip_obs (> 0 when normalize) */
+  int32_t critic_obs_dim; /* 0: the critic reads obs; 1-256: a row of its own (asymmetric, needs critic_layers >= 1) */
 } UpkieMlpShape;
 
 /* Words of the packed weight buffer of `shape`, or -1 (with the reason in
@@ -937,6 +938,66 @@ int64_t upkie_mlp_packed_words(const UpkieMlpShape* shape);
 int upkie_mlp_actor_critic(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* obs,
                            uint32_t* calls, uint64_t seed, int32_t deterministic, float* norm_obs, float* mean,
                            float* action, float* env_action, float* value, float* log_prob, void* stream);
+
+/* Asymmetric actor-critic ("privileged observations"): with
+ * shape->critic_obs_dim = Dc in 1-256 the critic reads a row of its own,
+ *   xc    = clamp((critic_obs - critic_obs_mean) / critic_obs_std, -clip_obs, clip_obs)
+ *           (xc = critic_obs when normalize == 0)
+ *   value = critic(xc)
+ * and everything of the actor is as above, on obs. The critic's first layer
+ * takes Dc inputs; its statistics are one more fixed block of the packed
+ * buffer, critic_obs_mean[Dcp], critic_obs_std[Dcp] (Dcp = Dc rounded up to
+ * 4, std directly after mean: a pointer to the block serves as
+ * upkie_vecnorm_step's packed_stats for a normaliser of Dc columns), after
+ * action_high and before log_std, so the PPO update never writes it. With
+ * critic_obs_dim == 0 every offset, upkie_mlp_packed_words and every output
+ * are what they are without the field.
+ * upkie_mlp_actor_critic_asym is upkie_mlp_actor_critic plus critic_obs
+ * [num_envs][Dc] and the output norm_critic_obs [num_envs][Dc] (may be NULL;
+ * written even when value is NULL); the same single launch: the critic's wave
+ * reads its own pointer, width and statistics. It takes symmetric shapes too
+ * (critic_obs is then [num_envs][obs_dim]). upkie_mlp_actor_critic refuses an
+ * asymmetric shape (UPKIE_ERR_INVALID_ARGUMENT). */
+int upkie_mlp_actor_critic_asym(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* obs,
+                                const float* critic_obs, uint32_t* calls, uint64_t seed, int32_t deterministic,
+                                float* norm_obs, float* norm_critic_obs, float* mean, float* action, float* env_action,
+                                float* value, float* log_prob, void* stream);
+
+/* ---- Privileged observation (the asymmetric critic's row) ---------------
+ * One launch per env step that assembles, for every env n < num_envs, the row
+ * the critic of an asymmetric actor-critic reads (csrc/privileged_obs.hpp).
+ * The row is the concatenation of up to UPKIE_PRIVILEGED_MAX_SEGMENTS
+ * segments, in the caller's order: segment k is kinds[k] with counts[k] words,
+ *   UPKIE_PRIVILEGED_OBSERVATION: next_obs[n][0 .. count)   (the raw observation)
+ *   UPKIE_PRIVILEGED_COMMAND:     command[n][0 .. count)    (what the env receives)
+ *   UPKIE_PRIVILEGED_PUSH_FORCE:  force[c][n], c < count    ([count][num_envs]: the force the next step applies)
+ *   UPKIE_PRIVILEGED_LINK_SCALE:  link_scale[links[c]][n]   ([*][num_envs]; links: count device int32 rows)
+ * row_dim = the sum of the counts, 1-256. Pure data movement:
+ *   new[n] = the row from the sources as they are at the call;
+ *   final_observation[n] = new[n] where the episode goes on (done[n] ==
+ *     terminated[n] | truncated[n] == 0); where it ended, the OBSERVATION
+ *     words come from final_obs[n] (next_obs when final_obs is NULL) and every
+ *     other word is the OLD observation[n] word: the command, force and scales
+ *     that were current during the ended step (the sources already hold the
+ *     next episode's). The old word is read before the new one is written, by
+ *     the thread that writes it;
+ *   observation[n] = new[n].
+ * reset != 0: observation[n] = new[n] for the envs with mask[n] (done is the
+ * mask; NULL: all), final_observation untouched. No allocation, no host
+ * argument that changes between steps: capturable in a hipGraph. */
+#define UPKIE_PRIVILEGED_MAX_SEGMENTS 8
+enum UpkiePrivilegedKind {
+  UPKIE_PRIVILEGED_OBSERVATION = 0,
+  UPKIE_PRIVILEGED_COMMAND = 1,
+  UPKIE_PRIVILEGED_PUSH_FORCE = 2,
+  UPKIE_PRIVILEGED_LINK_SCALE = 3
+};
+int upkie_privileged_observation(int32_t num_envs, int32_t obs_dim, int32_t act_dim, int32_t num_segments,
+                                 const int32_t* kinds, const int32_t* counts, const float* next_obs,
+                                 const float* final_obs, const float* command, const float* force,
+                                 const float* link_scale, const int32_t* links, const uint8_t* terminated,
+                                 const uint8_t* truncated, int32_t reset, float* observation, float* final_observation,
+                                 void* stream);
 
 /* ---- Running observation / reward normalisation (VecNormalize) ----------
  * Stable-Baselines3's VecNormalize in training mode, on the device
@@ -1244,6 +1305,34 @@ int upkie_ppo_minibatch_apply_controlled(const UpkieMlpShape* shape, const Upkie
                                          const void* slots, int32_t world, float* packed, float* adam_m, float* adam_v,
                                          double* control, void* workspace, float* stats, void* stream);
 
+/* The gradient launch for an asymmetric shape (critic_obs_dim > 0; a
+ * symmetric one is taken too): the existing signatures plus critic_obs
+ * [total][Dc], the critic's rows of the same samples, and a nullable control
+ * block (NULL: upkie_ppo_minibatch_update / _gradient, otherwise their
+ * controlled forms). The actor's forward, loss and gradient read obs as
+ * before; the critic's read critic_obs, normalised with critic_obs_mean /
+ * critic_obs_std unless config->obs_normalized (which then holds for both
+ * tensors). No term of the loss couples the towers before the norm clip, so
+ * every gradient word is the symmetric arithmetic on its tower's own input.
+ * upkie_ppo_workspace_bytes, the fold, apply, Adam and advantage-statistics
+ * entry points serve both kinds of shape. The entry points without critic_obs
+ * refuse an asymmetric shape. */
+int upkie_ppo_minibatch_update_asym(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total,
+                                    int32_t minibatch_start, int32_t minibatch_size, int32_t max_minibatch,
+                                    const int32_t* perm, const float* obs, const float* critic_obs, const float* actions,
+                                    const float* old_values, const float* old_log_prob, const float* advantages,
+                                    const float* returns, const double* adv_stats, float* packed, float* adam_m,
+                                    float* adam_v, double* adam_scalars, double* control, void* workspace, float* stats,
+                                    void* stream);
+
+int upkie_ppo_minibatch_gradient_asym(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total,
+                                      int32_t minibatch_start, int32_t minibatch_size, int32_t global_minibatch_size,
+                                      int32_t max_minibatch, const int32_t* perm, const float* obs,
+                                      const float* critic_obs, const float* actions, const float* old_values,
+                                      const float* old_log_prob, const float* advantages, const float* returns,
+                                      const double* adv_stats, float* packed, void* workspace, void* slot,
+                                      double* control, void* stream);
+
 /* SB3's train/explained_variance of the critic over the `total` samples of a
  * rollout: out[0] = 1 - Var(returns - values) / Var(returns), population
  * variances, NaN when Var(returns) == 0. fp64, two passes (means, then
@@ -1276,7 +1365,10 @@ int upkie_ppo_explained_variance(int32_t total, const float* returns, const floa
  * rollout step: the Monitor statistics on the raw reward, VecNormalize, then
  * this on the normalised reward with the statistics after that update; its
  * semantics assume same-step autoreset (final_obs: the observation the
- * ended episode stopped in). No CPU fallback: UPKIE_ERR_NO_DEVICE without a
+ * ended episode stopped in). Only the critic runs: for an asymmetric shape
+ * (critic_obs_dim = Dc > 0) final_obs is the critic's final row
+ * [num_envs][Dc], normalised with critic_obs_mean / critic_obs_std. No CPU
+ * fallback: UPKIE_ERR_NO_DEVICE without a
  * HIP device. Errors are reported through upkie_sim_last_error(NULL). */
 int upkie_mlp_bootstrap_time_limits(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* final_obs,
                                     const uint8_t* terminated, const uint8_t* truncated, double gamma, float* reward,

@@ -296,7 +296,13 @@ class UpkieMlpShape(C.Structure):
         ("critic_widths", C.c_int32 * MLP_MAX_LAYERS),
         ("normalize", C.c_int32),
         ("clip_obs", C.c_float),
+        ("critic_obs_dim", C.c_int32),  # 0: the critic reads the actor's observation
     ]
+
+
+# the privileged observation's segments (enum UpkiePrivilegedKind)
+PRIVILEGED_MAX_SEGMENTS = 8  # UPKIE_PRIVILEGED_MAX_SEGMENTS
+PRIVILEGED_OBSERVATION, PRIVILEGED_COMMAND, PRIVILEGED_PUSH_FORCE, PRIVILEGED_LINK_SCALE = 0, 1, 2, 3
 
 
 class UpkiePpoConfig(C.Structure):

@@ -27,6 +27,12 @@
 //   critic: per hidden layer as above; head: weights[in_tiles][16], bias[4]
 // Weight word (o, t, lane l, step s) of a layer is W[16o + (l & 15)][k], k = 16t + 4s + (l >> 4) in the first layer,
 // 16t + 4(l >> 4) + s after it; zero where the unit or k is past the layer's width.
+//
+// Asymmetric shape (shape.critic_obs_dim = Dc > 0, the critic reads a row of its own; include/upkie_hip.h): W also
+// covers Dc, the critic's first layer has tiles(Dc) input tiles in the first-layer order of its own width, and one more
+// fixed block, critic_obs_mean[Dcp], critic_obs_std[Dcp] (Dcp = Dc rounded up to 4), sits between action_high and
+// log_std. Wave 1 then loads critic_obs with that width and those statistics; with Dc = 0 MlpDev's critic fields repeat
+// the actor's and the kernel's arithmetic is word for word the symmetric one.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -55,6 +61,7 @@ struct MlpDev {
   int num_envs, obs_dim, act_dim, act_tiles, normalize;
   float clip_obs;
   int mean_off, std_off, low_off, high_off, log_std_off;
+  int critic_obs_dim, critic_mean_off, critic_std_off;  // the critic's input: the actor's (obs_dim, mean_off, std_off) for a symmetric shape
   MlpTowerDev actor, critic;
   int run_actor, run_critic, sample;
   unsigned seed_lo, seed_hi;
@@ -62,6 +69,7 @@ struct MlpDev {
 
 struct MlpOutputs {
   float* norm_obs;
+  float* norm_critic_obs;  // asymmetric shapes: the critic's normalised row (written by wave 1)
   float* mean;
   float* action;
   float* env_action;
@@ -72,6 +80,7 @@ struct MlpOutputs {
 // Width class of a shape (the template argument W), 0 when a dimension is out of range.
 inline int mlp_width_class(const UpkieMlpShape& s) {
   int w = s.obs_dim > s.act_dim ? s.obs_dim : s.act_dim;
+  w = s.critic_obs_dim > w ? s.critic_obs_dim : w;
   for (int i = 0; i < s.actor_layers && i < UPKIE_MLP_MAX_LAYERS; ++i) w = s.actor_widths[i] > w ? s.actor_widths[i] : w;
   for (int i = 0; i < s.critic_layers && i < UPKIE_MLP_MAX_LAYERS; ++i) w = s.critic_widths[i] > w ? s.critic_widths[i] : w;
   for (int c = 16; c <= 256; c *= 2)
@@ -89,6 +98,7 @@ inline int64_t mlp_layout(const UpkieMlpShape& s, MlpDev* dev) {
   for (int i = 0; i < s.critic_layers; ++i)
     if (s.critic_widths[i] < 1 || s.critic_widths[i] > 256) return -1;
   if (s.normalize && !(s.clip_obs > 0.f)) return -1;
+  if (s.critic_obs_dim < 0 || s.critic_obs_dim > 256 || (s.critic_obs_dim > 0 && s.critic_layers < 1)) return -1;
   const int W = mlp_width_class(s);
   if (W == 0) return -1;
   const int pair = W >= 32 ? 2 : 1;
@@ -101,6 +111,13 @@ inline int64_t mlp_layout(const UpkieMlpShape& s, MlpDev* dev) {
   d.std_off = (int)off, off += dp;
   d.low_off = (int)off, off += 16 * at;
   d.high_off = (int)off, off += 16 * at;
+  const int dc = s.critic_obs_dim > 0 ? s.critic_obs_dim : s.obs_dim;
+  d.critic_obs_dim = dc, d.critic_mean_off = d.mean_off, d.critic_std_off = d.std_off;
+  if (s.critic_obs_dim > 0) {
+    const int dcp = (dc + 3) / 4 * 4;
+    d.critic_mean_off = (int)off, off += dcp;
+    d.critic_std_off = (int)off, off += dcp;
+  }
   d.log_std_off = (int)off, off += 16 * at;
   auto mfma_layer = [&](int in_tiles, int width) {
     MlpLayerDev L{};
@@ -117,9 +134,9 @@ inline int64_t mlp_layout(const UpkieMlpShape& s, MlpDev* dev) {
     L.b_off = (int)off, off += 4;
     return L;
   };
-  auto tower = [&](MlpTowerDev& T, int layers, const int32_t* widths, int outputs) {
+  auto tower = [&](MlpTowerDev& T, int inputs, int layers, const int32_t* widths, int outputs) {
     T.layers = layers;
-    int in_tiles = tiles(s.obs_dim);
+    int in_tiles = tiles(inputs);
     for (int i = 0; i < layers; ++i) {
       T.hidden[i] = mfma_layer(in_tiles, widths[i]);
       in_tiles = tiles(widths[i]);
@@ -127,8 +144,8 @@ inline int64_t mlp_layout(const UpkieMlpShape& s, MlpDev* dev) {
     T.head_dot = outputs == 1;
     T.head = T.head_dot ? dot_layer(in_tiles) : mfma_layer(in_tiles, outputs);
   };
-  tower(d.actor, s.actor_layers, s.actor_widths, s.act_dim);
-  if (s.critic_layers > 0) tower(d.critic, s.critic_layers, s.critic_widths, 1);
+  tower(d.actor, s.obs_dim, s.actor_layers, s.actor_widths, s.act_dim);
+  if (s.critic_layers > 0) tower(d.critic, dc, s.critic_layers, s.critic_widths, 1);
   d.obs_dim = s.obs_dim;
   d.act_dim = s.act_dim;
   d.act_tiles = at;
@@ -252,35 +269,42 @@ __device__ __forceinline__ void mlp_normal4(unsigned env, unsigned call, unsigne
 
 template <int W, int ACT>
 __global__ __launch_bounds__(128) void mlp_actor_critic_kernel(const MlpDev P, const float* __restrict__ packed, const float* __restrict__ obs,
-                                                               uint32_t* __restrict__ counters, const MlpOutputs out) {
+                                                               const float* __restrict__ critic_obs, uint32_t* __restrict__ counters,
+                                                               const MlpOutputs out) {
   constexpr int WT = W / 16;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, q = lane >> 4;
   const int env = blockIdx.x * 16 + (lane & 15);
   const bool valid = env < P.num_envs;
-  if (wave == 0 ? !(P.run_actor || out.norm_obs) : !P.run_critic) return;
+  if (wave == 0 ? !(P.run_actor || out.norm_obs) : !(P.run_critic || out.norm_critic_obs)) return;
+  // this wave's input (wave-uniform): the actor's, or the critic's own row, width and statistics (the same for a symmetric shape)
+  const bool actor_wave = __builtin_amdgcn_readfirstlane(wave) == 0;  // (scalar: the selections below stay in scalar registers)
+  const float* __restrict__ in = actor_wave ? obs : critic_obs;
+  const int in_dim = actor_wave ? P.obs_dim : P.critic_obs_dim;
+  const int mean_off = actor_wave ? P.mean_off : P.critic_mean_off, std_off = actor_wave ? P.std_off : P.critic_std_off;
+  float* __restrict__ norm_out = actor_wave ? out.norm_obs : out.norm_critic_obs;
 
-  // observation (normalised): x[t][s] = element 16t + 4s + q of this lane's env, 0 past obs_dim or num_envs
+  // observation (normalised): x[t][s] = element 16t + 4s + q of this lane's env, 0 past in_dim or num_envs
   float x[WT][4] = {};
   const int env_c = valid ? env : P.num_envs - 1;  // (loads clamped into the buffers and issued together; values past the batch discarded)
 #pragma unroll
   for (int t = 0; t < WT; ++t) {
-    if (16 * t < P.obs_dim) {
+    if (16 * t < in_dim) {
       float v[4], m[4], sd[4];
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        const int k = 16 * t + 4 * s + q, kc = k < P.obs_dim ? k : P.obs_dim - 1;
-        v[s] = obs[(size_t)env_c * P.obs_dim + kc];
-        m[s] = packed[P.mean_off + kc];
-        sd[s] = packed[P.std_off + kc];
+        const int k = 16 * t + 4 * s + q, kc = k < in_dim ? k : in_dim - 1;
+        v[s] = in[(size_t)env_c * in_dim + kc];
+        m[s] = packed[mean_off + kc];
+        sd[s] = packed[std_off + kc];
       }
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         const int k = 16 * t + 4 * s + q;
-        if (valid && k < P.obs_dim) {
+        if (valid && k < in_dim) {
           float u = v[s];
           if (P.normalize) u = fminf(fmaxf((u - m[s]) / sd[s], -P.clip_obs), P.clip_obs);
           x[t][s] = u;
-          if (wave == 0 && out.norm_obs) out.norm_obs[(size_t)env * P.obs_dim + k] = u;
+          if (norm_out) norm_out[(size_t)env * in_dim + k] = u;
         }
       }
     }
@@ -288,8 +312,9 @@ __global__ __launch_bounds__(128) void mlp_actor_critic_kernel(const MlpDev P, c
 
   float head[WT][4] = {};
   if (wave == 1) {
+    if (!P.run_critic) return;
     float v = 0.f;
-    mlp_tower<WT, ACT>(packed, P.critic, P.obs_dim, x, head, &v, lane);
+    mlp_tower<WT, ACT>(packed, P.critic, in_dim, x, head, &v, lane);
     if (valid && q == 0) out.value[env] = v;
     return;
   }

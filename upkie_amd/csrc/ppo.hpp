@@ -39,6 +39,12 @@
 // global mean (launch 0a, phase 1), exchange, (mean, std + 1e-8) over the global count (launch 0b). With one rank every
 // output is the same bits as the fused form's.
 //
+// Asymmetric shape (critic_obs_dim = Dc > 0; PpoDev::critic_obs): the two towers read different rows of the same sample.
+// The critic's stage has its own x region of tiles(Dc) rows of 16 (the actor's tiles(obs_dim)), and between the towers
+// every wave restages x from critic_obs -- all 16 rows of each of its tiles(Dc) tiles, zeros past Dc, so nothing the actor
+// left in the stage is read as critic input -- normalised with the critic's statistics unless obs_normalized. One more
+// x load per sample per chunk; a symmetric shape takes no restage and computes word for word what it did.
+//
 // Every launch argument is constant for a given (epoch, minibatch) position: counters, t, lr and the permutation live
 // in device memory, so the whole sequence can be captured in a hipGraph and replayed.
 //
@@ -103,9 +109,11 @@ struct PpoDev {
   int count;                      // samples the loss means run over: mb_size, or the global minibatch size (all ranks)
   int part_stride, stat_stride;   // launch B: floats between two gradient partials, doubles between two loss-sum partials
   int obs_normalized, vf_clip;
+  int asym;  // the critic reads critic_obs (restaged between the towers)
   float clip_lo, clip_hi, clip_range, clip_vf, ent_coef, vf_coef, max_grad_norm, beta1, beta2, adam_eps;
   const int32_t* perm;
   const float* obs;
+  const float* critic_obs;  // [total][critic_obs_dim] when asym
   const float* actions;
   const float* old_values;
   const float* old_log_prob;
@@ -143,7 +151,7 @@ inline bool ppo_plan(const UpkieMlpShape& s, PpoPlan* plan) {
   PpoPlan p{};
   auto stage = [&](const MlpTowerDev& T, bool actor) {
     PpoStage st{};
-    int off = 16 * 16 * ppo_tiles(s.obs_dim);
+    int off = 16 * 16 * ppo_tiles(actor ? d.obs_dim : d.critic_obs_dim);  // (x: the tower's own input; the tile is sized by the larger stage)
     for (int l = 0; l < T.layers; ++l) st.h_off[l] = off, off += 16 * 16 * T.hidden[l].out_tiles;
     st.head_off = off, off += T.head_dot ? 16 : 16 * 16 * T.head.out_tiles;
     st.ls_off = off;
@@ -329,6 +337,7 @@ __device__ __forceinline__ void ppo_tower(const PpoDev& P, const PpoClip& K, flo
   const int q = lane >> 4, r = lane & 15, tid = wave * 64 + lane;
   const MlpTowerDev& T = ACTOR ? P.net.actor : P.net.critic;
   const PpoStage& S = P.stage[ACTOR ? 0 : 1];
+  const int in_dim = ACTOR ? P.net.obs_dim : P.net.critic_obs_dim;  // (the tower's input width)
   const float* __restrict__ packed = P.packed;
   float* my = stage + wave * P.tile_floats;
   const float inv_b = 1.f / (float)P.count;
@@ -339,14 +348,14 @@ __device__ __forceinline__ void ppo_tower(const PpoDev& P, const PpoClip& K, flo
     __syncthreads();  // (every wave is done reading the previous tower's stage)
 #pragma unroll
     for (int t = 0; t < WT; ++t)
-      if (16 * t < P.net.obs_dim)
+      if (16 * t < in_dim)
 #pragma unroll
         for (int s = 0; s < 4; ++s) x[t][s] = my[(16 * t + 4 * s + q) * 16 + r];
-    mlp_dense<WT, ACT, true, true>(packed, T.hidden[0], P.net.obs_dim, x, h, lane);
+    mlp_dense<WT, ACT, true, true>(packed, T.hidden[0], in_dim, x, h, lane);
     ppo_store<WT>(my, S.h_off[0], T.hidden[0].out_tiles, h, lane);
 #pragma unroll 1
     for (int l = 1; l < T.layers; ++l) {
-      mlp_dense<WT, ACT, false, true>(packed, T.hidden[l], P.net.obs_dim, h, x, lane);
+      mlp_dense<WT, ACT, false, true>(packed, T.hidden[l], in_dim, h, x, lane);
 #pragma unroll
       for (int t = 0; t < WT; ++t)
 #pragma unroll
@@ -357,7 +366,7 @@ __device__ __forceinline__ void ppo_tower(const PpoDev& P, const PpoClip& K, flo
       float head[WT][4] = {};
       float m1 = 0.f;
       if (T.head_dot) m1 = mlp_dot<WT>(packed, T.head, h, lane);
-      else mlp_dense<WT, ACT, false, false>(packed, T.head, P.net.obs_dim, h, head, lane);
+      else mlp_dense<WT, ACT, false, false>(packed, T.head, in_dim, h, head, lane);
       if (T.head_dot) head[0][0] = m1;
       constexpr float HALF_LOG_2PI = 0.91893853320467274f;
       float lp = 0.f, d[4][4] = {}, sig2[4][4] = {};
@@ -470,6 +479,29 @@ __device__ __forceinline__ void ppo_tower(const PpoDev& P, const PpoClip& K, flo
   if constexpr (ACTOR) ppo_row_sums(P, stage, S.ls_off, 16 * P.net.act_tiles, P.net.log_std_off - P.train_off, part, first, tid);
 }
 
+// The x rows of the wave's tile from `src` [total][dim]: element k of the sample, normalised as act() does (statistics at
+// mean_off / std_off) unless the buffer holds normalised observations; all 16 rows of every tile below dim, zeros past it.
+template <int WT>
+__device__ __forceinline__ void ppo_stage_x(const PpoDev& P, float* my, const float* __restrict__ src, int dim, int mean_off, int std_off, int sample,
+                                            int q, int r) {
+#pragma unroll
+  for (int t = 0; t < WT; ++t) {
+    if (16 * t < dim) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int k = 16 * t + 4 * s + q;
+        float u = 0.f;
+        if (k < dim) {
+          u = src[(size_t)sample * dim + k];
+          if (P.net.normalize && !P.obs_normalized)
+            u = fminf(fmaxf((u - P.packed[mean_off + k]) / P.packed[std_off + k], -P.net.clip_obs), P.net.clip_obs);
+        }
+        my[k * 16 + r] = u;
+      }
+    }
+  }
+}
+
 template <int W, int ACT>
 __global__ __launch_bounds__(256) void ppo_grad_kernel(const PpoDev P) {
   extern __shared__ float stage[];
@@ -493,24 +525,12 @@ __global__ __launch_bounds__(256) void ppo_grad_kernel(const PpoDev P) {
     const bool valid = j < P.mb_size;
     const int sample = P.perm[(int64_t)P.mb_start + (valid ? j : 0)];
     __syncthreads();  // (the previous chunk's critic is done reading x)
-    // x rows: element k of the sample, normalised as act() does unless the buffer holds normalised observations
-#pragma unroll
-    for (int t = 0; t < WT; ++t) {
-      if (16 * t < P.net.obs_dim) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int k = 16 * t + 4 * s + q;
-          float u = 0.f;
-          if (k < P.net.obs_dim) {
-            u = P.obs[(size_t)sample * P.net.obs_dim + k];
-            if (P.net.normalize && !P.obs_normalized)
-              u = fminf(fmaxf((u - P.packed[P.net.mean_off + k]) / P.packed[P.net.std_off + k], -P.net.clip_obs), P.net.clip_obs);
-          }
-          my[k * 16 + r] = u;
-        }
-      }
-    }
+    ppo_stage_x<WT>(P, my, P.obs, P.net.obs_dim, P.net.mean_off, P.net.std_off, sample, q, r);
     ppo_tower<WT, ACT, true>(P, K, stage, sample, valid, part, first, st, wave, lane);
+    if (P.asym) {
+      __syncthreads();  // (every wave is done reading the actor's x: its first-layer dW reads every wave's rows)
+      ppo_stage_x<WT>(P, my, P.critic_obs, P.net.critic_obs_dim, P.net.critic_mean_off, P.net.critic_std_off, sample, q, r);
+    }
     ppo_tower<WT, ACT, false>(P, K, stage, sample, valid, part, first, st, wave, lane);
   }
   // loss sums: a fixed shuffle tree per wave, then the waves in order

@@ -3,9 +3,11 @@
 // instantiations take as long to compile as everything else outside the step kernels.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdint>
+#include <string>
 
 #include "mlp_instances.hpp"
 #include "ppo.hpp"
@@ -77,17 +79,21 @@ static void ppo_fill(upkie::PpoDev& P, const UpkieMlpShape& shape, const upkie::
 // Checks and fields of the gradient launch (launch A) of minibatch [minibatch_start, + minibatch_size).
 static int ppo_gradient_setup(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
                               int32_t minibatch_size, int32_t count, int32_t max_minibatch, const int32_t* perm, const float* obs,
-                              const float* actions, const float* old_values, const float* old_log_prob, const float* advantages,
+                              const float* critic_obs, const float* actions, const float* old_values, const float* old_log_prob, const float* advantages,
                               const float* returns, const double* adv_stats, float* packed, void* workspace, upkie::PpoDev* out,
                               upkie::PpoPlan* plan) {
   if (check_ppo_shape(shape, plan)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!critic_obs && shape->critic_obs_dim != 0)  // (the entry points without critic_obs hand NULL down)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "the shape is asymmetric (critic_obs_dim " + std::to_string(shape->critic_obs_dim) + ", obs_dim " +
+                                                std::to_string(shape->obs_dim) +
+                                                "): the critic's rows go to upkie_ppo_minibatch_update_asym / upkie_ppo_minibatch_gradient_asym");
   if (check_ppo_config(config)) return UPKIE_ERR_INVALID_ARGUMENT;
   if (total < 1 || minibatch_size < 1 || max_minibatch < 1 || minibatch_start < 0 || minibatch_size > max_minibatch ||
       (int64_t)minibatch_start + minibatch_size > total || count < minibatch_size)
     return fail(UPKIE_ERR_INVALID_ARGUMENT,
                 "minibatch out of range: 0 <= minibatch_start, 1 <= minibatch_size <= max_minibatch, start + size <= total, global size >= size");
-  if ((int64_t)total * (shape->obs_dim > shape->act_dim ? shape->obs_dim : shape->act_dim) > INT_MAX)
-    return fail(UPKIE_ERR_INVALID_ARGUMENT, "total * obs_dim (or act_dim) must stay below 2^31");
+  if ((int64_t)total * std::max(std::max(shape->obs_dim, shape->act_dim), shape->critic_obs_dim) > INT_MAX)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "total * obs_dim (or act_dim, or critic_obs_dim) must stay below 2^31");
   if (!perm || !obs || !actions || !old_values || !old_log_prob || !advantages || !returns || !adv_stats || !packed || !workspace)
     return fail(UPKIE_ERR_INVALID_ARGUMENT, "null argument");
   if (no_device()) return UPKIE_ERR_NO_DEVICE;
@@ -95,7 +101,8 @@ static int ppo_gradient_setup(const UpkieMlpShape* shape, const UpkiePpoConfig* 
   ppo_fill(P, *shape, *plan, *config, max_minibatch, workspace);
   P.mb_start = minibatch_start, P.mb_size = minibatch_size, P.count = count;
   P.grid = upkie::ppo_grid(*plan, minibatch_size);
-  P.perm = perm, P.obs = obs, P.actions = actions, P.old_values = old_values, P.old_log_prob = old_log_prob;
+  P.asym = shape->critic_obs_dim != 0;
+  P.perm = perm, P.obs = obs, P.critic_obs = P.asym ? critic_obs : obs, P.actions = actions, P.old_values = old_values, P.old_log_prob = old_log_prob;
   P.advantages = advantages, P.returns = returns, P.adv_stats = adv_stats;
   P.packed = packed;
   *out = P;
@@ -127,14 +134,14 @@ static int check_ppo_control(const double* control) {
 
 // upkie_ppo_minibatch_update (control == nullptr) and upkie_ppo_minibatch_update_controlled.
 static int ppo_minibatch_update(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
-                                int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm, const float* obs, const float* actions,
-                                const float* old_values, const float* old_log_prob, const float* advantages, const float* returns,
+                                int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm, const float* obs, const float* critic_obs,
+                                const float* actions, const float* old_values, const float* old_log_prob, const float* advantages, const float* returns,
                                 const double* adv_stats, float* packed, float* adam_m, float* adam_v, double* adam_scalars, double* control,
                                 void* workspace, float* stats, void* stream) {
   upkie::PpoPlan plan;
   upkie::PpoDev P;
   if (!adam_m || !adam_v || !adam_scalars || !stats) return fail(UPKIE_ERR_INVALID_ARGUMENT, "null argument");
-  int status = ppo_gradient_setup(shape, config, total, minibatch_start, minibatch_size, minibatch_size, max_minibatch, perm, obs, actions,
+  int status = ppo_gradient_setup(shape, config, total, minibatch_start, minibatch_size, minibatch_size, max_minibatch, perm, obs, critic_obs, actions,
                                   old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, &P, &plan);
   if (status != UPKIE_OK) return status;
   P.m = adam_m, P.v = adam_v, P.scalars = adam_scalars, P.ctrl = control, P.stats = stats;
@@ -151,7 +158,7 @@ extern "C" int upkie_ppo_minibatch_update(const UpkieMlpShape* shape, const Upki
                                           const float* actions, const float* old_values, const float* old_log_prob, const float* advantages,
                                           const float* returns, const double* adv_stats, float* packed, float* adam_m, float* adam_v,
                                           double* adam_scalars, void* workspace, float* stats, void* stream) {
-  return ppo_minibatch_update(shape, config, total, minibatch_start, minibatch_size, max_minibatch, perm, obs, actions, old_values, old_log_prob,
+  return ppo_minibatch_update(shape, config, total, minibatch_start, minibatch_size, max_minibatch, perm, obs, nullptr, actions, old_values, old_log_prob,
                               advantages, returns, adv_stats, packed, adam_m, adam_v, adam_scalars, nullptr, workspace, stats, stream);
 }
 
@@ -162,7 +169,7 @@ extern "C" int upkie_ppo_minibatch_update_controlled(const UpkieMlpShape* shape,
                                                      const float* advantages, const float* returns, const double* adv_stats, float* packed,
                                                      float* adam_m, float* adam_v, double* control, void* workspace, float* stats, void* stream) {
   if (check_ppo_control(control)) return UPKIE_ERR_INVALID_ARGUMENT;
-  return ppo_minibatch_update(shape, config, total, minibatch_start, minibatch_size, max_minibatch, perm, obs, actions, old_values, old_log_prob,
+  return ppo_minibatch_update(shape, config, total, minibatch_start, minibatch_size, max_minibatch, perm, obs, nullptr, actions, old_values, old_log_prob,
                               advantages, returns, adv_stats, packed, adam_m, adam_v, control, control, workspace, stats, stream);
 }
 
@@ -206,13 +213,13 @@ extern "C" int64_t upkie_ppo_slot_bytes(const UpkieMlpShape* shape) {
 
 static int ppo_minibatch_gradient(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
                                   int32_t minibatch_size, int32_t global_minibatch_size, int32_t max_minibatch, const int32_t* perm,
-                                  const float* obs, const float* actions, const float* old_values, const float* old_log_prob,
+                                  const float* obs, const float* critic_obs, const float* actions, const float* old_values, const float* old_log_prob,
                                   const float* advantages, const float* returns, const double* adv_stats, float* packed, void* workspace,
                                   void* slot, double* control, void* stream) {
   upkie::PpoPlan plan;
   upkie::PpoDev P;
   if (!slot) return fail(UPKIE_ERR_INVALID_ARGUMENT, "null slot");
-  int status = ppo_gradient_setup(shape, config, total, minibatch_start, minibatch_size, global_minibatch_size, max_minibatch, perm, obs, actions,
+  int status = ppo_gradient_setup(shape, config, total, minibatch_start, minibatch_size, global_minibatch_size, max_minibatch, perm, obs, critic_obs, actions,
                                   old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, &P, &plan);
   if (status != UPKIE_OK) return status;
   P.slot = (float*)slot;
@@ -229,7 +236,7 @@ extern "C" int upkie_ppo_minibatch_gradient(const UpkieMlpShape* shape, const Up
                                             const float* obs, const float* actions, const float* old_values, const float* old_log_prob,
                                             const float* advantages, const float* returns, const double* adv_stats, float* packed, void* workspace,
                                             void* slot, void* stream) {
-  return ppo_minibatch_gradient(shape, config, total, minibatch_start, minibatch_size, global_minibatch_size, max_minibatch, perm, obs, actions,
+  return ppo_minibatch_gradient(shape, config, total, minibatch_start, minibatch_size, global_minibatch_size, max_minibatch, perm, obs, nullptr, actions,
                                 old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, slot, nullptr, stream);
 }
 
@@ -240,8 +247,35 @@ extern "C" int upkie_ppo_minibatch_gradient_controlled(const UpkieMlpShape* shap
                                                        const float* returns, const double* adv_stats, float* packed, void* workspace, void* slot,
                                                        double* control, void* stream) {
   if (check_ppo_control(control)) return UPKIE_ERR_INVALID_ARGUMENT;
-  return ppo_minibatch_gradient(shape, config, total, minibatch_start, minibatch_size, global_minibatch_size, max_minibatch, perm, obs, actions,
+  return ppo_minibatch_gradient(shape, config, total, minibatch_start, minibatch_size, global_minibatch_size, max_minibatch, perm, obs, nullptr, actions,
                                 old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, slot, control, stream);
+}
+
+// ---- asymmetric shapes: the critic's rows beside obs, a nullable control block (include/upkie_hip.h)
+extern "C" int upkie_ppo_minibatch_update_asym(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
+                                               int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm, const float* obs,
+                                               const float* critic_obs, const float* actions, const float* old_values, const float* old_log_prob,
+                                               const float* advantages, const float* returns, const double* adv_stats, float* packed,
+                                               float* adam_m, float* adam_v, double* adam_scalars, double* control, void* workspace, float* stats,
+                                               void* stream) {
+  if (!critic_obs) return fail(UPKIE_ERR_INVALID_ARGUMENT, "null critic_obs");
+  if (control && check_ppo_control(control)) return UPKIE_ERR_INVALID_ARGUMENT;
+  return ppo_minibatch_update(shape, config, total, minibatch_start, minibatch_size, max_minibatch, perm, obs, critic_obs, actions, old_values,
+                              old_log_prob, advantages, returns, adv_stats, packed, adam_m, adam_v, control ? control : adam_scalars, control,
+                              workspace, stats, stream);
+}
+
+extern "C" int upkie_ppo_minibatch_gradient_asym(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t total, int32_t minibatch_start,
+                                                 int32_t minibatch_size, int32_t global_minibatch_size, int32_t max_minibatch,
+                                                 const int32_t* perm, const float* obs, const float* critic_obs, const float* actions,
+                                                 const float* old_values, const float* old_log_prob, const float* advantages,
+                                                 const float* returns, const double* adv_stats, float* packed, void* workspace, void* slot,
+                                                 double* control, void* stream) {
+  if (!critic_obs) return fail(UPKIE_ERR_INVALID_ARGUMENT, "null critic_obs");
+  if (control && check_ppo_control(control)) return UPKIE_ERR_INVALID_ARGUMENT;
+  return ppo_minibatch_gradient(shape, config, total, minibatch_start, minibatch_size, global_minibatch_size, max_minibatch, perm, obs,
+                                critic_obs, actions, old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, slot, control,
+                                stream);
 }
 
 static int ppo_minibatch_apply(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t minibatch_start, int32_t global_minibatch_size,

@@ -1,7 +1,8 @@
 // trainer_abi.hip -- handle-free entry points of include/upkie_hip.h around a rollout: the MLP actor-critic policy, the
-// time-limit bootstrap, episode statistics, the evaluation tally, the agent pipeline, the reward terms, VecNormalize, the linear policy and GAE. Host code around the kernels of the
-// headers below; nothing here takes or touches a simulator, MPC or observer handle (upkie_hip.hip). The PPO update, the
-// other heavy set of kernel instantiations, is ppo_abi.hip's.
+// time-limit bootstrap, episode statistics, the evaluation tally, the agent pipeline, the reward terms, the privileged
+// observation, VecNormalize, the linear policy and GAE. Host code around the kernels of the headers below; nothing here
+// takes or touches a simulator, MPC or observer handle (upkie_hip.hip). The PPO update, the other heavy set of kernel
+// instantiations, is ppo_abi.hip's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +20,7 @@
 #include "eval_episodes.hpp"
 #include "agent_pipeline.hpp"
 #include "reward_terms.hpp"
+#include "privileged_obs.hpp"
 
 #include "abi_host.hpp"
 
@@ -28,14 +30,17 @@ extern "C" int64_t upkie_mlp_packed_words(const UpkieMlpShape* shape) {
   const int64_t words = upkie::mlp_layout(*shape, nullptr);
   if (words >= 0) return words;
   return fail(UPKIE_ERR_INVALID_ARGUMENT,
-              "MLP shape out of range (obs_dim 1-256, act_dim 1-64, 1-4 actor / 0-4 critic layers of 1-256 units, tanh or relu, clip_obs > 0)");
+              "MLP shape out of range (obs_dim 1-256, act_dim 1-64, 1-4 actor / 0-4 critic layers of 1-256 units, tanh or relu, clip_obs > 0, "
+              "critic_obs_dim 0 or 1-256 with a critic)");
 }
 
-extern "C" int upkie_mlp_actor_critic(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* obs, uint32_t* calls,
-                                      uint64_t seed, int32_t deterministic, float* norm_obs, float* mean, float* action, float* env_action,
-                                      float* value, float* log_prob, void* stream) {
+// upkie_mlp_actor_critic (critic_obs = obs, no norm_critic_obs) and upkie_mlp_actor_critic_asym: one launch.
+static int mlp_actor_critic(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* obs, const float* critic_obs,
+                            uint32_t* calls, uint64_t seed, int32_t deterministic, float* norm_obs, float* norm_critic_obs, float* mean,
+                            float* action, float* env_action, float* value, float* log_prob, void* stream) {
   if (num_envs <= 0) return fail(UPKIE_ERR_INVALID_ARGUMENT, "num_envs must be positive");
   if (!shape || !packed || !obs) return fail(UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  if (!critic_obs && (value || norm_critic_obs)) return fail(UPKIE_ERR_INVALID_ARGUMENT, "value and norm_critic_obs need critic_obs");
   upkie::MlpDev P;
   if (upkie::mlp_layout(*shape, &P) < 0)
     return (int)upkie_mlp_packed_words(shape);  // (sets the message)
@@ -48,13 +53,38 @@ extern "C" int upkie_mlp_actor_critic(int32_t num_envs, const UpkieMlpShape* sha
   P.seed_lo = (unsigned)(seed & 0xffffffffu);
   P.seed_hi = (unsigned)(seed >> 32);
   if (no_device()) return UPKIE_ERR_NO_DEVICE;
-  if (!P.run_actor && !P.run_critic && !norm_obs) return UPKIE_OK;
-  const upkie::MlpOutputs out{norm_obs, mean, action, env_action, value, log_prob};
+  if (!P.run_actor && !P.run_critic && !norm_obs && !norm_critic_obs) return UPKIE_OK;
+  const upkie::MlpOutputs out{norm_obs, norm_critic_obs, mean, action, env_action, value, log_prob};
   const dim3 grid((unsigned)((num_envs + 15) / 16));
   for_mlp_instance(*shape, [&](auto w, auto act) {
-    hipLaunchKernelGGL((upkie::mlp_actor_critic_kernel<w(), act()>), grid, dim3(128), 0, (hipStream_t)stream, P, packed, obs, calls, out);
+    hipLaunchKernelGGL((upkie::mlp_actor_critic_kernel<w(), act()>), grid, dim3(128), 0, (hipStream_t)stream, P, packed, obs, critic_obs, calls,
+                       out);
   });
   return launch_status();
+}
+
+static int refuse_asymmetric(const UpkieMlpShape* shape, const char* entry, const char* other) {
+  if (shape && shape->critic_obs_dim != 0)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, std::string(entry) + ": the shape is asymmetric (critic_obs_dim " +
+                                                std::to_string(shape->critic_obs_dim) + ", obs_dim " + std::to_string(shape->obs_dim) +
+                                                "): the critic's rows go to " + other);
+  return UPKIE_OK;
+}
+
+extern "C" int upkie_mlp_actor_critic(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* obs, uint32_t* calls,
+                                      uint64_t seed, int32_t deterministic, float* norm_obs, float* mean, float* action, float* env_action,
+                                      float* value, float* log_prob, void* stream) {
+  if (refuse_asymmetric(shape, "upkie_mlp_actor_critic", "upkie_mlp_actor_critic_asym")) return UPKIE_ERR_INVALID_ARGUMENT;
+  return mlp_actor_critic(num_envs, shape, packed, obs, obs, calls, seed, deterministic, norm_obs, nullptr, mean, action, env_action, value,
+                          log_prob, stream);
+}
+
+extern "C" int upkie_mlp_actor_critic_asym(int32_t num_envs, const UpkieMlpShape* shape, const float* packed, const float* obs,
+                                           const float* critic_obs, uint32_t* calls, uint64_t seed, int32_t deterministic, float* norm_obs,
+                                           float* norm_critic_obs, float* mean, float* action, float* env_action, float* value,
+                                           float* log_prob, void* stream) {
+  return mlp_actor_critic(num_envs, shape, packed, obs, critic_obs, calls, seed, deterministic, norm_obs, norm_critic_obs, mean, action,
+                          env_action, value, log_prob, stream);
 }
 
 // ============================================================ time-limit bootstrap (SB3 collect_rollouts)
@@ -500,5 +530,40 @@ extern "C" int upkie_rollout_gae(int32_t num_steps, int32_t num_envs, const floa
   if (no_device()) return UPKIE_ERR_NO_DEVICE;
   hipLaunchKernelGGL(upkie::gae_kernel, dim3((unsigned)((num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, num_steps, num_envs,
                      rewards, values, episode_starts, last_values, last_dones, (float)gamma, (float)gae_lambda, advantages, returns);
+  return launch_status();
+}
+
+// ============================================================ privileged observation (the asymmetric critic's row)
+extern "C" int upkie_privileged_observation(int32_t num_envs, int32_t obs_dim, int32_t act_dim, int32_t num_segments, const int32_t* kinds,
+                                            const int32_t* counts, const float* next_obs, const float* final_obs, const float* command,
+                                            const float* force, const float* link_scale, const int32_t* links, const uint8_t* terminated,
+                                            const uint8_t* truncated, int32_t reset, float* observation, float* final_observation,
+                                            void* stream) {
+  if (num_envs <= 0 || obs_dim < 1 || obs_dim > 256 || act_dim < 1 || act_dim > 64)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "privileged: num_envs must be positive, obs_dim in 1-256 and act_dim in 1-64");
+  if (!kinds || !counts) return fail(UPKIE_ERR_INVALID_ARGUMENT, "privileged: null segment arrays");
+  upkie::PrivilegedDev P{};
+  P.num_envs = num_envs, P.obs_dim = obs_dim, P.act_dim = act_dim, P.num_segments = num_segments, P.reset = reset ? 1 : 0;
+  for (int k = 0; k < num_segments && k < UPKIE_PRIVILEGED_MAX_SEGMENTS; ++k) P.kind[k] = kinds[k], P.count[k] = counts[k];
+  if (!upkie::privileged_layout(P))
+    return fail(UPKIE_ERR_INVALID_ARGUMENT,
+                "privileged: 1-8 segments of a known kind; observation words at most obs_dim, command words at most act_dim, 1-3 force words, "
+                "1-24 link scales; a row of at most 256 words, at most 32 of them force or scale words");
+  if ((int64_t)num_envs * P.row_dim > INT_MAX) return fail(UPKIE_ERR_INVALID_ARGUMENT, "privileged: num_envs * row_dim must stay below 2^31");
+  for (int k = 0; k < num_segments; ++k) {
+    const void* source = P.kind[k] == UPKIE_PRIVILEGED_OBSERVATION ? (const void*)next_obs
+                         : P.kind[k] == UPKIE_PRIVILEGED_COMMAND   ? (const void*)command
+                         : P.kind[k] == UPKIE_PRIVILEGED_PUSH_FORCE ? (const void*)force
+                                                                    : (const void*)link_scale;
+    if (!source || (P.kind[k] == UPKIE_PRIVILEGED_LINK_SCALE && !links))
+      return fail(UPKIE_ERR_INVALID_ARGUMENT, "privileged: segment " + std::to_string(k) + " has no source buffer (link scales also need links)");
+  }
+  if (!observation || (!P.reset && !final_observation))
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "privileged: null observation (or final_observation outside a reset)");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  P.next_obs = next_obs, P.final_obs = final_obs, P.command = command, P.force = force, P.link_scale = link_scale, P.links = links;
+  P.terminated = terminated, P.truncated = truncated, P.observation = observation, P.final_observation = final_observation;
+  const unsigned blocks = (unsigned)((num_envs + upkie::PRIVILEGED_ENVS - 1) / upkie::PRIVILEGED_ENVS);
+  hipLaunchKernelGGL(upkie::privileged_observation_kernel, dim3(blocks), dim3(upkie::PRIVILEGED_THREADS), 0, (hipStream_t)stream, P);
   return launch_status();
 }

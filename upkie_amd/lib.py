@@ -52,6 +52,7 @@ SOURCES = [
     os.path.join(_CSRC, "agent_pipeline.hpp"),
     os.path.join(_CSRC, "reward_terms.hpp"),
     os.path.join(_CSRC, "episode_events.hpp"),
+    os.path.join(_CSRC, "privileged_obs.hpp"),
     os.path.join(_CSRC, "wave_io.hpp"),
     os.path.join(_HERE, "..", "include", "upkie_hip.h"),
 ]
@@ -70,6 +71,7 @@ def _abi_table():
     vecnorm = [i32, i32] + [vp] * 8 + [i32] + [f64] * 4  # (the arguments every vecnorm launch begins with)
     pipeline = [i32] * 5 + [f64, f64, vp, C.c_uint64]  # (the settings every pipeline launch begins with)
     controlled = "upkie_ppo_minibatch_update_controlled"
+    asym = "upkie_mlp_actor_critic_asym"
     return (
         ("upkie_hip_device_count", status, None, None),
         ("upkie_hip_struct_bytes", C.c_int64, [C.c_int], "upkie_hip_struct_bytes"),  # (see _check_struct_sizes)
@@ -172,6 +174,11 @@ def _abi_table():
         ("upkie_reward_terms_params", C.c_int64, [i32, i32, i32, f64] + [vp] * 8 + [f64, f64, vp], "upkie_reward_terms_step"),
         ("upkie_reward_terms_step", status, [i32] * 4 + [vp] * 12, "upkie_reward_terms_step"),
         ("upkie_reward_terms_reset", status, [i32] * 3 + [vp] * 4, "upkie_reward_terms_step"),
+        # the asymmetric actor-critic: a critic observation of its own, and the stage that assembles it
+        ("upkie_mlp_actor_critic_asym", status, [i32, shape_p, vp, vp, vp, vp, C.c_uint64, i32] + [vp] * 8, asym),
+        ("upkie_ppo_minibatch_update_asym", status, [shape_p, cfg_p] + [i32] * 4 + [vp] * 17, asym),
+        ("upkie_ppo_minibatch_gradient_asym", status, [shape_p, cfg_p] + [i32] * 5 + [vp] * 14, asym),
+        ("upkie_privileged_observation", status, [i32] * 4 + [vp] * 10 + [i32, vp, vp, vp], asym),
     )
 
 

@@ -78,6 +78,7 @@ class RunningNormalizer:
         self._reward = torch.empty(N, dtype=torch.float32, device=self.device)
         self._norm_obs = torch.empty((N, D), dtype=torch.float32, device=self.device)
         self._policy = None
+        self._tower = "actor"  # which of the policy's statistics blocks `attach` feeds
         self.process_group = process_group
         self._exchange = None
         if process_group is not None:
@@ -175,7 +176,7 @@ class RunningNormalizer:
     def _launch(self, flags, obs=None, reward=None, terminated=None, truncated=None, norm_obs=None, norm_reward=None, starts=None) -> None:
         if self.device.type != "cuda":
             raise UpkieRuntimeError("RunningNormalizer runs on the HIP device only (there is no CPU fallback): build it with device='cuda:0'")
-        packed = None if self._policy is None else self._policy.packed
+        packed = self._packed_stats()
         training, reset = bool(flags & TRAINING), bool(flags & RESET)
         shared = self._exchange is not None and training and (bool(flags & NORM_OBS) or not reset)  # (a statistic moves)
         if shared and torch.cuda.is_current_stream_capturing():
@@ -245,16 +246,29 @@ class RunningNormalizer:
         return dst
 
     # ---- a policy reading the live statistics
-    def attach(self, policy) -> None:
+    def attach(self, policy, tower: str = "actor") -> None:
         """Make an `MlpActorCritic` / `MlpPolicy` normalise its observations with these statistics: every step that moves
         them also rewrites the policy's packed obs_mean / obs_std words, the fp32 mirrors become the tensors its
         `update_from` gathers them from (an optimiser step does not revert them), and its normalisation flag and
-        clip_obs follow the normalizer. Attach before the policy's first call (and before any capture)."""
+        clip_obs follow the normalizer. Attach before the policy's first call (and before any capture).
+
+        ``tower="critic"``: the statistics of the rows an asymmetric policy's critic reads (its critic_obs_mean /
+        critic_obs_std block and mirrors); this normalizer then has ``critic_obs_dim`` columns. The normalisation switch
+        and clip_obs are the policy's, shared by both towers: give both normalizers the same ``norm_obs``, ``clip_obs``
+        and ``epsilon``."""
         from .policies import MlpActorCritic
 
         if not isinstance(policy, MlpActorCritic):
             raise TypeError("attach takes an MlpActorCritic or MlpPolicy")
-        if int(policy.shape.obs_dim) != self.obs_dim:
+        if tower not in ("actor", "critic"):
+            raise ValueError("tower must be 'actor' or 'critic'")
+        if tower == "critic":
+            if not policy.asymmetric:
+                raise ValueError(f"tower='critic' needs an asymmetric policy: this critic reads the actor's {policy.shape.obs_dim}-word "
+                                 f"observation (the normalizer has {self.obs_dim} columns)")
+            if policy.critic_obs_dim != self.obs_dim:
+                raise ValueError(f"the policy's critic takes {policy.critic_obs_dim} observation words, the normalizer {self.obs_dim}")
+        elif int(policy.shape.obs_dim) != self.obs_dim:
             raise ValueError(f"the policy takes {policy.shape.obs_dim} observation words, the normalizer {self.obs_dim}")
         if policy.device != self.device:
             raise ValueError(f"the policy is on {policy.device}, the normalizer on {self.device}")
@@ -263,11 +277,22 @@ class RunningNormalizer:
                                     "and its launches keep the normalisation settings they were made with")
         if self._policy is not None and self._policy is not policy:
             raise UpkieRuntimeError("this normalizer already feeds another policy")
-        policy._fixed[0], policy._fixed[1] = self.obs_mean_f32, self.obs_std_f32
-        self._policy = policy
-        policy._normalizer = self  # (upkie_amd.ppo refuses raw observations for a policy reading live statistics)
+        at = 4 if tower == "critic" else 0  # (sources() order: the critic's block follows the action bounds)
+        policy._fixed[at], policy._fixed[at + 1] = self.obs_mean_f32, self.obs_std_f32
+        self._policy, self._tower = policy, tower
+        if tower == "critic":
+            policy._critic_normalizer = self
+        else:
+            policy._normalizer = self  # (upkie_amd.ppo refuses raw observations for a policy reading live statistics)
         self._sync_policy()
         policy.update_from()
+
+    def _packed_stats(self):
+        """``packed_stats`` of the launches: the attached policy's statistics block (mean, then std at the width rounded
+        up to 4) -- the head of its packed buffer, or an asymmetric policy's critic block."""
+        if self._policy is None:
+            return None
+        return self._policy.packed if self._tower == "actor" else self._policy.packed[self._policy.critic_stats_offset():]
 
     def _sync_policy(self) -> None:
         p = self._policy
@@ -277,6 +302,8 @@ class RunningNormalizer:
         p.shape.clip_obs = self.clip_obs
         p.clip_obs, p.eps = self.clip_obs, self.epsilon
         D, (mean_at, std_at) = self.obs_dim, packed_offsets(self.obs_dim)
+        if self._tower == "critic":
+            mean_at, std_at = (p.critic_stats_offset() + at for at in (mean_at, std_at))
         p.packed[mean_at: mean_at + D].copy_(self.obs_mean_f32)
         p.packed[std_at: std_at + D].copy_(self.obs_std_f32)
 

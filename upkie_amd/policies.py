@@ -68,6 +68,8 @@ class LinearPolicy:
 
 _ACTIVATIONS = {"tanh": 0, "relu": 1}  # enum UpkieMlpActivation
 OUTPUT_NAMES = ("norm_obs", "mean", "action", "env_action", "value", "log_prob")  # the kernel's outputs, in argument order
+# the outputs of `upkie_mlp_actor_critic_asym` (an asymmetric policy: the critic reads a row of its own), in argument order
+ASYM_OUTPUT_NAMES = ("norm_obs", "norm_critic_obs", "mean", "action", "env_action", "value", "log_prob")
 
 
 def _tiles(width: int) -> int:
@@ -75,7 +77,7 @@ def _tiles(width: int) -> int:
 
 
 def _width_class(shape) -> int:
-    w = max([shape.obs_dim, shape.act_dim] + list(shape.actor_widths[: shape.actor_layers]) + list(shape.critic_widths[: shape.critic_layers]))
+    w = max([shape.obs_dim, shape.act_dim, shape.critic_obs_dim] + list(shape.actor_widths[: shape.actor_layers]) + list(shape.critic_widths[: shape.critic_layers]))
     for c in (16, 32, 64, 128, 256):
         if w <= c:
             return c
@@ -85,7 +87,8 @@ def _width_class(shape) -> int:
 def pack_index(shape, sizes):
     """Gather map of the packed weight buffer (layout: csrc/policy_mlp.hpp): for each packed word, the index of its
     value in the concatenation of the flattened source tensors (`sizes`: their element counts, in the order of
-    `MlpActorCritic.sources()`), or ``sum(sizes)`` -- one zero word appended to the concatenation -- for padding."""
+    `MlpActorCritic.sources()`), or ``sum(sizes)`` -- one zero word appended to the concatenation -- for padding. An
+    asymmetric shape (``critic_obs_dim > 0``) has two more sources, critic_obs_mean and critic_obs_std, after action_high."""
     import numpy as np
 
     starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
@@ -117,8 +120,7 @@ def pack_index(shape, sizes):
         blocks.append(np.where(k < n_in, starts[wi] + k, zero))
         blocks.append(np.array([starts[bi], zero, zero, zero], dtype=np.int64))
 
-    def tower(layers, widths, outputs):
-        n_in = D
+    def tower(n_in, layers, widths, outputs):
         for i in range(layers):
             mfma_layer(n_in, int(widths[i]), i == 0)
             n_in = int(widths[i])
@@ -130,17 +132,23 @@ def pack_index(shape, sizes):
     dp = (D + 3) // 4 * 4
     vector(D, dp)  # obs_mean
     vector(D, dp)  # obs_std
-    for _ in range(3):  # action_low, action_high, log_std
+    for _ in range(2):  # action_low, action_high
         vector(A, 16 * _tiles(A))
-    tower(int(shape.actor_layers), shape.actor_widths, A)
+    Dc = int(shape.critic_obs_dim)
+    for _ in range(2 if Dc else 0):  # critic_obs_mean, critic_obs_std (an asymmetric shape only)
+        vector(Dc, (Dc + 3) // 4 * 4)
+    vector(A, 16 * _tiles(A))  # log_std
+    tower(D, int(shape.actor_layers), shape.actor_widths, A)
     if shape.critic_layers > 0:
-        tower(int(shape.critic_layers), shape.critic_widths, 1)
+        tower(Dc or D, int(shape.critic_layers), shape.critic_widths, 1)
     return np.concatenate(blocks)
 
 
 def mlp_shape(actor_dims, critic_dims, activation: str, normalize: bool = False, clip_obs: float = 10.0) -> abi.UpkieMlpShape:
     """`abi.UpkieMlpShape` of an actor (and critic) given as the ``[out, in]`` shapes of their Linear weights, head
-    last (``critic_dims`` empty: no critic)."""
+    last (``critic_dims`` empty: no critic). A critic whose first layer takes another number of inputs than the actor's
+    makes the shape asymmetric: ``critic_obs_dim`` is that number (`critic_obs_dim` of `asymmetric_shape` forces it for a
+    critic row as wide as the observation)."""
     if activation not in _ACTIVATIONS:
         raise ValueError(f"activation must be one of {sorted(_ACTIVATIONS)}")
     if not 2 <= len(actor_dims) <= abi.MLP_MAX_LAYERS + 1:
@@ -155,10 +163,14 @@ def mlp_shape(actor_dims, critic_dims, activation: str, normalize: bool = False,
                 raise ValueError(f"{what} layer {i} takes {d[1]} inputs, the layer before gives {dims[i - 1][0]}")
     shape = abi.UpkieMlpShape()
     shape.obs_dim, shape.act_dim = int(actor_dims[0][1]), int(actor_dims[-1][0])
-    if critic_dims and (critic_dims[0][1] != shape.obs_dim or critic_dims[-1][0] != 1):
-        raise ValueError(f"the critic must map {shape.obs_dim} inputs to 1 value")
+    if critic_dims and critic_dims[-1][0] != 1:
+        raise ValueError(f"the critic must map its {critic_dims[0][1]} inputs to 1 value")
     if not 1 <= shape.obs_dim <= 256 or not 1 <= shape.act_dim <= 64:
         raise ValueError("obs_dim must be in 1-256, act_dim in 1-64")
+    if critic_dims and critic_dims[0][1] != shape.obs_dim:
+        shape.critic_obs_dim = int(critic_dims[0][1])
+        if not 1 <= shape.critic_obs_dim <= 256:
+            raise ValueError(f"the critic's observation must have 1-256 words, got {shape.critic_obs_dim}")
     shape.activation = _ACTIVATIONS[activation]
     shape.actor_layers = len(actor_dims) - 1
     shape.critic_layers = max(len(critic_dims) - 1, 0)
@@ -172,6 +184,18 @@ def mlp_shape(actor_dims, critic_dims, activation: str, normalize: bool = False,
     if normalize and not shape.clip_obs > 0.0:
         raise ValueError("clip_obs must be positive")
     return shape
+
+
+def asymmetric_shape(shape: abi.UpkieMlpShape, critic_obs_dim: Optional[int] = None) -> abi.UpkieMlpShape:
+    """A copy of ``shape`` whose critic reads a row of its own of ``critic_obs_dim`` words (None: as many as the actor's
+    observation -- the degenerate asymmetric shape, which `mlp_shape` cannot tell from a symmetric one)."""
+    out = abi.UpkieMlpShape.from_buffer_copy(shape)
+    if int(out.critic_layers) < 1:
+        raise ValueError("an asymmetric shape needs a critic")
+    out.critic_obs_dim = int(shape.obs_dim if critic_obs_dim is None else critic_obs_dim)
+    if not 1 <= out.critic_obs_dim <= 256:
+        raise ValueError(f"the critic's observation must have 1-256 words, got {out.critic_obs_dim}")
+    return out
 
 
 def sb3_parameters(state_dict):
@@ -244,13 +268,28 @@ class MlpActorCritic:
     The first call fixes the batch size N (outputs and counters are allocated once; a call with another N raises).
     Observation normalisation uses VecNormalize statistics: frozen ones given here, or live ones kept by a
     `upkie_amd.normalize.RunningNormalizer` it is attached to (`attach`). Build with `from_modules` or
-    `from_sb3_state_dict`; after an optimiser step on those modules, `update_from` re-packs on the device."""
+    `from_sb3_state_dict`; after an optimiser step on those modules, `update_from` re-packs on the device.
+
+    Asymmetric actor-critic ("privileged observations"): a critic whose first layer takes another number of inputs than
+    the actor's (or ``asymmetric=True`` for one of the same width) reads a row of its own, ``critic_obs`` ``[N, Dc]``,
+    normalised with statistics of its own (``critic_obs_mean`` / ``critic_obs_var``, or a second `RunningNormalizer`
+    attached with ``tower="critic"``): ``act(obs, critic_obs=...)``, ``value(critic_obs)``,
+    ``bootstrap_time_limits(final_critic_obs, ...)``. `mean_action` and everything else of the actor are unchanged; the
+    observation normalisation switch and ``clip_obs`` are shared by both towers. `from_sb3_state_dict` stays symmetric."""
+
+    asymmetric = False  # (set per object by __init__: whether the critic reads a row of its own)
 
     def __init__(self, actor_weights, actor_biases, critic_weights, critic_biases, log_std, activation: str, action_low=None,
-                 action_high=None, obs_mean=None, obs_var=None, clip_obs: float = 10.0, eps: float = 1e-8, seed: int = 0, device=None):
+                 action_high=None, obs_mean=None, obs_var=None, clip_obs: float = 10.0, eps: float = 1e-8, seed: int = 0, device=None,
+                 critic_obs_mean=None, critic_obs_var=None, asymmetric: bool = False):
         critic_weights, critic_biases = list(critic_weights or []), list(critic_biases or [])
         shape = mlp_shape([tuple(w.shape) for w in actor_weights], [tuple(w.shape) for w in critic_weights], activation,
-                          obs_mean is not None or obs_var is not None, clip_obs)
+                          any(v is not None for v in (obs_mean, obs_var, critic_obs_mean, critic_obs_var)), clip_obs)
+        if asymmetric and not shape.critic_obs_dim:
+            shape = asymmetric_shape(shape)
+        if not shape.critic_obs_dim and (critic_obs_mean is not None or critic_obs_var is not None):
+            raise ValueError(f"critic_obs_mean / critic_obs_var are an asymmetric policy's: this critic reads the actor's "
+                             f"{shape.obs_dim}-word observation (asymmetric=True gives it a row of its own)")
         for w, b in zip(list(actor_weights) + critic_weights, list(actor_biases) + critic_biases):
             if tuple(b.shape) != (w.shape[0],):
                 raise ValueError(f"bias of shape {tuple(b.shape)} for a weight of shape {tuple(w.shape)}")
@@ -259,12 +298,14 @@ class MlpActorCritic:
         self.device = torch.device(device) if device is not None else actor_weights[0].device
         if self.device.type != "cuda":
             raise UpkieRuntimeError("MlpActorCritic runs on the HIP device only (there is no CPU fallback): give device='cuda:0'")
-        D, A = shape.obs_dim, shape.act_dim
+        D, A, Dc = shape.obs_dim, shape.act_dim, int(shape.critic_obs_dim)
         self.shape = shape
+        self.asymmetric = Dc > 0
+        self.critic_obs_dim = Dc if Dc else int(D)  # (words of the row the critic reads)
         self.activation = activation
         self.clip_obs, self.eps = float(clip_obs), float(eps)
         self._lib = lib.load()
-        lib.require(self._lib, "upkie_mlp_actor_critic")
+        lib.require(self._lib, "upkie_mlp_actor_critic_asym" if self.asymmetric else "upkie_mlp_actor_critic")
         words = int(self._lib.upkie_mlp_packed_words(C.byref(shape)))
         check(words)
         self._launcher = launcher(self.device)
@@ -283,6 +324,9 @@ class MlpActorCritic:
             raise ValueError("action_low must not exceed action_high")
         f32 = dict(dtype=torch.float32, device=self.device)
         self._fixed = [mean.to(**f32), std.to(**f32), low.to(**f32), high.to(**f32)]
+        if self.asymmetric:  # (the critic's statistics block: after action_high, before log_std)
+            cstd = torch.sqrt(vec(critic_obs_var, Dc, 1.0, "critic_obs_var") + self.eps)
+            self._fixed += [vec(critic_obs_mean, Dc, 0.0, "critic_obs_mean").to(**f32), cstd.to(**f32)]
         self.action_low, self.action_high = self._fixed[2], self._fixed[3]
         self._params = None
         self._set_params(actor_weights, actor_biases, critic_weights, critic_biases, log_std)
@@ -301,16 +345,17 @@ class MlpActorCritic:
     # ---- construction
     @classmethod
     def from_modules(cls, actor, critic, log_std, action_low, action_high, obs_mean=None, obs_var=None, clip_obs: float = 10.0,
-                     eps: float = 1e-8, seed: int = 0, device=None):
+                     eps: float = 1e-8, seed: int = 0, device=None, critic_obs_mean=None, critic_obs_var=None, asymmetric: bool = False):
         """``actor``: nn.Sequential(Linear, act, ..., Linear) to the action mean; ``critic``: the same to one value (or
         None); ``log_std``: [act_dim] tensor; act is Tanh or ReLU, the same in both. The modules stay referenced:
-        `update_from()` re-packs their current parameters."""
+        `update_from()` re-packs their current parameters. A critic with another input width than the actor's (or
+        ``asymmetric=True``) makes the policy asymmetric; ``critic_obs_mean`` / ``critic_obs_var`` are its statistics."""
         aw, ab, act = _linear_stack(actor, "actor")
         cw, cb, cact = ([], [], None) if critic is None else _linear_stack(critic, "critic")
         if act is not None and cact is not None and act != cact:
             raise ValueError("one activation for both towers")
         self = cls(aw, ab, cw, cb, log_std, act or cact or "tanh", action_low, action_high, obs_mean, obs_var, clip_obs, eps, seed,
-                   device if device is not None else aw[0].device)
+                   device if device is not None else aw[0].device, critic_obs_mean, critic_obs_var, asymmetric)
         self._modules = (actor, critic, log_std)
         return self
 
@@ -344,9 +389,22 @@ class MlpActorCritic:
 
     def sources(self):
         """The tensors the packed buffer is gathered from, in `pack_index` order: obs_mean, obs_std, action_low,
-        action_high, log_std, then (weight, bias) per layer of the actor (head last) and of the critic."""
+        action_high, (an asymmetric policy: critic_obs_mean, critic_obs_std,) log_std, then (weight, bias) per layer of
+        the actor (head last) and of the critic. The first `n_fixed` are never trained."""
         p = self._params
         return self._fixed + [p[-1]] + p[:-1]
+
+    @property
+    def n_fixed(self) -> int:
+        """How many of `sources()` are fixed (statistics and action bounds): 4, or 6 for an asymmetric policy."""
+        return len(self._fixed)
+
+    def critic_stats_offset(self) -> int:
+        """First word of critic_obs_mean in the packed buffer of an asymmetric policy (critic_obs_std follows it at the
+        width rounded up to 4): what a critic normaliser hands to ``upkie_vecnorm_step`` as ``packed_stats``."""
+        if not self.asymmetric:
+            raise UpkieRuntimeError("a symmetric policy has no critic statistics block")
+        return 2 * ((int(self.shape.obs_dim) + 3) // 4 * 4) + 2 * 16 * _tiles(self.shape.act_dim)
 
     def update_from(self, actor=None, critic=None, log_std=None) -> None:
         """Re-pack the weights -- of the given modules, or of the ones the policy was built from (`from_modules`),
@@ -386,13 +444,14 @@ class MlpActorCritic:
         return {"packed": self.packed, "calls": self.calls}
 
     # ---- calls
-    def _obs(self, obs: torch.Tensor) -> torch.Tensor:
+    def _obs(self, obs: torch.Tensor, critic: bool = False) -> torch.Tensor:
+        words, what = (self.critic_obs_dim, "critic observations") if critic else (int(self.shape.obs_dim), "observations")
         if not isinstance(obs, torch.Tensor) or not obs.is_cuda:
-            raise UpkieRuntimeError("MlpActorCritic runs on the HIP device only (there is no CPU fallback): observations must be device tensors")
+            raise UpkieRuntimeError(f"MlpActorCritic runs on the HIP device only (there is no CPU fallback): {what} must be device tensors")
         if obs.device != self.device:
-            raise ValueError(f"observations on {obs.device}, policy on {self.device}")
-        if obs.dim() < 1 or obs.shape[0] < 1 or obs[0].numel() != self.shape.obs_dim:
-            raise ValueError(f"observations must be [N, ...] with {self.shape.obs_dim} words per env, got {tuple(obs.shape)}")
+            raise ValueError(f"{what} on {obs.device}, policy on {self.device}")
+        if obs.dim() < 1 or obs.shape[0] < 1 or obs[0].numel() != words:
+            raise ValueError(f"{what} must be [N, ...] with {words} words per env, got {tuple(obs.shape)}")
         if obs.dtype is not torch.float32 or not obs.is_contiguous():
             obs = obs.to(torch.float32).contiguous()
         return obs
@@ -413,30 +472,54 @@ class MlpActorCritic:
         return self._out
 
     def _check_out(self, name: str, t: torch.Tensor, n: int) -> torch.Tensor:
-        words = {"norm_obs": self.shape.obs_dim, "value": 1, "log_prob": 1}.get(name, self.shape.act_dim) * n
-        if name not in OUTPUT_NAMES:
-            raise ValueError(f"unknown output {name!r} (one of {OUTPUT_NAMES})")
+        words = {"norm_obs": self.shape.obs_dim, "norm_critic_obs": self.critic_obs_dim, "value": 1, "log_prob": 1}.get(name, self.shape.act_dim) * n
+        names = ASYM_OUTPUT_NAMES if self.asymmetric else OUTPUT_NAMES
+        if name not in names:
+            raise ValueError(f"unknown output {name!r} (one of {names})")
         if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype is not torch.float32 or not t.is_contiguous() or t.numel() != words:
             raise ValueError(f"out[{name!r}] must be a contiguous float32 tensor of {words} words on {self.device}")
         return t
 
-    def _launch(self, obs, deterministic: bool, outs: dict) -> None:
-        self._launcher(self._lib.upkie_mlp_actor_critic, obs.shape[0], C.byref(self.shape), self.packed.data_ptr(), obs.data_ptr(),
-                       self.calls.data_ptr(), self.seed, int(bool(deterministic)), *[ptr(outs.get(name)) for name in OUTPUT_NAMES])
+    def _launch(self, obs, deterministic: bool, outs: dict, critic_obs=None) -> None:
+        """One launch: the symmetric entry point, or for an asymmetric policy the one that also takes the critic's rows
+        (``obs`` None: the critic alone; the actor's pointer is then the critic's rows, which no wave reads)."""
+        if not self.asymmetric:
+            self._launcher(self._lib.upkie_mlp_actor_critic, obs.shape[0], C.byref(self.shape), self.packed.data_ptr(), obs.data_ptr(),
+                           self.calls.data_ptr(), self.seed, int(bool(deterministic)), *[ptr(outs.get(name)) for name in OUTPUT_NAMES])
+            return
+        rows = obs if obs is not None else critic_obs
+        self._launcher(self._lib.upkie_mlp_actor_critic_asym, rows.shape[0], C.byref(self.shape), self.packed.data_ptr(), rows.data_ptr(),
+                       ptr(critic_obs), ptr(self.calls), self.seed, int(bool(deterministic)), *[ptr(outs.get(name)) for name in ASYM_OUTPUT_NAMES])
 
-    def act(self, obs: torch.Tensor, deterministic: bool = False, out: Optional[dict] = None):
+    def _critic_rows(self, critic_obs, n=None):
+        """The critic's rows of an asymmetric policy, checked (``n``: the actor's batch)."""
+        if critic_obs is None:
+            raise ValueError(f"this policy is asymmetric: its critic reads rows of {self.critic_obs_dim} words of its own, the actor "
+                             f"{int(self.shape.obs_dim)}; give critic_obs=")
+        critic_obs = self._obs(critic_obs, critic=True)
+        if n is not None and critic_obs.shape[0] != n:
+            raise ValueError(f"{n} observations but {critic_obs.shape[0]} critic observations")
+        return critic_obs
+
+    def act(self, obs: torch.Tensor, deterministic: bool = False, out: Optional[dict] = None, critic_obs: Optional[torch.Tensor] = None):
         """(env_action, action, value, log_prob) of a batch of observations ``[N, ...]``; value is None without a
         critic. ``out``: tensors to write instead of the persistent buffers (any of `OUTPUT_NAMES`; "norm_obs" and
-        "mean" are written only when given)."""
+        "mean" are written only when given). An asymmetric policy also takes ``critic_obs`` ``[N, Dc]``, the rows its
+        critic reads, and may write "norm_critic_obs"."""
         obs = self._obs(obs)
         n = obs.shape[0]
+        if self.asymmetric:
+            critic_obs = self._critic_rows(critic_obs, n)
+        elif critic_obs is not None:
+            raise ValueError(f"this policy is symmetric: its critic reads the actor's {int(self.shape.obs_dim)}-word observation, not a "
+                             f"critic_obs of {critic_obs[0].numel()} words")
         outs = dict(self._buffers(n))
         del outs["n"]
         if self.shape.critic_layers == 0:
             outs["value"] = None
         for name, t in (out or {}).items():
             outs[name] = self._check_out(name, t, n)
-        self._launch(obs, deterministic, outs)
+        self._launch(obs, deterministic, outs, critic_obs)
         return outs["env_action"], outs["action"], outs["value"], outs["log_prob"]
 
     def mean_action(self, obs: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
@@ -447,18 +530,26 @@ class MlpActorCritic:
         be evaluated on an env of another (`upkie_amd.evaluation`) without a bit of its training changing."""
         obs = self._obs(obs)
         out = self._check_out("env_action", out, obs.shape[0])
+        if self.asymmetric:  # (the actor alone: no critic rows, no counters)
+            self._launcher(self._lib.upkie_mlp_actor_critic_asym, obs.shape[0], C.byref(self.shape), self.packed.data_ptr(), obs.data_ptr(), None,
+                           None, self.seed, 1, None, None, None, None, out.data_ptr(), None, None)
+            return out
         self._launcher(self._lib.upkie_mlp_actor_critic, obs.shape[0], C.byref(self.shape), self.packed.data_ptr(), obs.data_ptr(), None, self.seed, 1,
                        None, None, None, out.data_ptr(), None, None)
         return out
 
     def value(self, obs: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The critic alone (e.g. the bootstrap values of the observations after a rollout's last step)."""
+        """The critic alone (e.g. the bootstrap values of the observations after a rollout's last step). An asymmetric
+        policy takes the critic's rows ``[N, Dc]``."""
         if self.shape.critic_layers == 0:
             raise UpkieRuntimeError("this policy has no critic")
-        obs = self._obs(obs)
+        obs = self._obs(obs, critic=self.asymmetric)
         n = obs.shape[0]
         v = self._buffers(n)["value"] if out is None else self._check_out("value", out, n)
-        self._launch(obs, True, {"value": v})
+        if self.asymmetric:
+            self._launch(None, True, {"value": v}, critic_obs=obs)
+        else:
+            self._launch(obs, True, {"value": v})
         return v
 
     def bootstrap_time_limits(self, final_obs: torch.Tensor, terminated: torch.Tensor, truncated: torch.Tensor, reward: torch.Tensor,
@@ -478,7 +569,7 @@ class MlpActorCritic:
         observation the ended episode stopped in)."""
         if self.shape.critic_layers == 0:
             raise UpkieRuntimeError("this policy has no critic: the time-limit bootstrap needs V(final_obs)")
-        final_obs = self._obs(final_obs)
+        final_obs = self._obs(final_obs, critic=self.asymmetric)  # (only the critic runs: an asymmetric policy's final critic rows)
         n = final_obs.shape[0]
         flags = []
         for name, t in (("terminated", terminated), ("truncated", truncated)):

@@ -27,10 +27,11 @@ def _at(schedule, progress: float) -> Optional[float]:
 
 def trainable_offset(shape) -> int:
     """First trainable word of the packed buffer (csrc/policy_mlp.hpp): log_std's. The words before it -- obs_mean,
-    obs_std, action_low, action_high -- are never written by the update; from it on every word is a parameter (log_std,
-    the towers' weights and biases) or padding, which stays zero."""
+    obs_std, action_low, action_high and an asymmetric shape's critic_obs_mean, critic_obs_std -- are never written by
+    the update; from it on every word is a parameter (log_std, the towers' weights and biases) or padding, which stays
+    zero."""
     at = 16 * ((int(shape.act_dim) + 15) // 16)
-    return 2 * ((int(shape.obs_dim) + 3) // 4 * 4) + 2 * at
+    return 2 * ((int(shape.obs_dim) + 3) // 4 * 4) + 2 * at + 2 * ((int(getattr(shape, "critic_obs_dim", 0)) + 3) // 4 * 4)
 
 
 class PpoTrainer:
@@ -50,6 +51,11 @@ class PpoTrainer:
     nothing. So a caller may capture ``update(buffer)`` once and replay it every iteration, calling ``prepare(buffer)``
     after ``compute_returns_and_advantage`` and before each replay. A trainer serves ONE buffer: `prepare` refuses
     another, whose tensors a captured update would not read.
+
+    An asymmetric policy (its critic reads rows of its own: `MlpActorCritic`) trains from a buffer built with
+    ``critic_obs_shape=(Dc,)``: the gradient launch reads ``buffer.critic_observations`` for the critic
+    (``upkie_ppo_minibatch_update_asym`` / ``upkie_ppo_minibatch_gradient_asym``); ``obs_normalized`` then says that BOTH
+    tensors hold normalised rows. A symmetric policy issues exactly the launches it always did.
 
     Speed: with [64, 64] towers an update is several times faster than the same SB3 minibatch as torch ops. With
     256-unit layers the gradient launch spills registers and runs few blocks, and the update is many times SLOWER than
@@ -82,6 +88,8 @@ class PpoTrainer:
     trainer issues exactly the launches it always did. With a process group every rank takes the same decision from
     the same exchanged bits; the collectives of the minibatches after a stop still run (the host cannot see the flag
     without a synchronisation) and change nothing. `log` returns SB3's ``train/*`` record with one device-to-host copy."""
+
+    asymmetric = False  # (set per object by __init__: whether the policy's critic reads rows of its own)
 
     def __init__(self, policy, lr: Schedule = 3e-4, n_epochs: int = 10, batch_size: int = 64, clip_range: Schedule = 0.2,
                  clip_range_vf: Optional[Schedule] = None, normalize_advantage: bool = True, ent_coef: float = 0.0, vf_coef: float = 0.5,
@@ -123,6 +131,9 @@ class PpoTrainer:
         self.config = cfg
         self._lib = lib.load()
         lib.require(self._lib, "upkie_ppo_minibatch_update")
+        self.asymmetric = bool(getattr(policy, "asymmetric", False))
+        if self.asymmetric:
+            lib.require(self._lib, "upkie_ppo_minibatch_update_asym", "for an asymmetric policy")
         self._launcher = launcher(self.device)
         words = policy.packed.numel()
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -190,7 +201,20 @@ class PpoTrainer:
         if buffer.observations[0, 0].numel() != D or buffer.actions[0, 0].numel() != A:
             raise ValueError(f"the buffer holds {buffer.observations[0, 0].numel()} observation and {buffer.actions[0, 0].numel()} action "
                              f"words per sample, the policy takes {D} and {A}")
-        if not self.obs_normalized and getattr(self.policy, "_normalizer", None) is not None:
+        critic_rows = getattr(buffer, "critic_observations", None)
+        Dc = int(getattr(self.policy, "critic_obs_dim", D))
+        if self.asymmetric and critic_rows is None:
+            raise ValueError(f"the policy is asymmetric (its critic reads {Dc} words, its actor {D}) but the buffer holds no "
+                             f"critic_observations: build it with critic_obs_shape=({Dc},)")
+        if not self.asymmetric and critic_rows is not None:
+            raise ValueError(f"the buffer holds critic_observations of {critic_rows[0, 0].numel()} words but the policy is symmetric (its "
+                             f"critic reads the actor's {D}-word observation)")
+        if self.asymmetric and critic_rows[0, 0].numel() != Dc:
+            raise ValueError(f"the buffer holds {critic_rows[0, 0].numel()} critic observation words per sample, the policy's critic takes {Dc}")
+        if self.asymmetric and (critic_rows.dtype is not torch.float32 or not critic_rows.is_contiguous()):
+            raise ValueError("the buffer's tensors must be contiguous float32")
+        live = getattr(self.policy, "_normalizer", None) is not None or getattr(self.policy, "_critic_normalizer", None) is not None
+        if not self.obs_normalized and live:
             raise UpkieRuntimeError("the policy reads a live RunningNormalizer: its statistics moved during the rollout, so train on the "
                                     "normalised observations the rollout stored (act(out={'norm_obs': ...})) with obs_normalized=True")
         for t in (buffer.observations, buffer.actions, buffer.values, buffer.log_probs, buffer.advantages, buffer.returns):
@@ -200,7 +224,8 @@ class PpoTrainer:
 
     @staticmethod
     def _addresses(buffer):
-        return tuple(t.data_ptr() for t in (buffer.observations, buffer.actions, buffer.values, buffer.log_probs))
+        tensors = (buffer.observations, buffer.actions, buffer.values, buffer.log_probs, getattr(buffer, "critic_observations", None))
+        return tuple(t.data_ptr() for t in tensors if t is not None)
 
     # ---- training
     def prepare(self, buffer) -> None:
@@ -266,12 +291,14 @@ class PpoTrainer:
         # what every minibatch launch begins with, and the six sample arrays it reads
         head = (C.byref(self.policy.shape), C.byref(self.config))
         data = tuple(ptr(t) for t in (buffer.observations, buffer.actions, buffer.values, buffer.log_probs, self.advantages, self.returns))
+        if self.asymmetric:  # (the critic's rows go after obs)
+            data = data[:1] + (ptr(buffer.critic_observations),) + data[1:]
         with torch.cuda.device(self.device):  # (around the whole block: every launch takes the launcher's fast path, and the collectives rely on it)
             if self.controlled:
                 self._launcher(self._lib.upkie_ppo_update_begin, ptr(self.control))
             for e in range(self.n_epochs):
                 perm = ptr(self.perm[e])
-                self._advantage_stats(e, total, perm, data[4])
+                self._advantage_stats(e, total, perm, data[-2])
                 for j in range(self.n_minibatches):
                     start = j * mb
                     self._minibatch(e, j, head, total, start, min(mb, total - start), perm, data)
@@ -299,6 +326,18 @@ class PpoTrainer:
         with ``minibatch_start`` first (the apply half)."""
         lb, launch, gx, ctl, mb = self._lib, self._launcher, self._grad_exchange, self.controlled, self._mb
         adv_stats, packed, work, stats = ptr(self.adv_stats[e, j]), ptr(self.policy.packed), ptr(self.workspace), ptr(self.stats[e, j])
+        if self.asymmetric:  # (one entry point per half serves the plain and the controlled form: a nullable control block)
+            control = ptr(self.control) if ctl else None
+            if gx is None:
+                launch(lb.upkie_ppo_minibatch_update_asym, *head, total, start, size, mb, perm, *data, adv_stats, packed, ptr(self.m), ptr(self.v),
+                       ptr(self.scalars), control, work, stats)
+                return
+            launch(lb.upkie_ppo_minibatch_gradient_asym, *head, total, start, size, gx.world * size, mb, perm, *data, adv_stats, packed, work,
+                   ptr(gx.mine), control)
+            gx.exchange()
+            launch(lb.upkie_ppo_minibatch_apply_controlled if ctl else lb.upkie_ppo_minibatch_apply, *head, *((start,) if ctl else ()), gx.world * size,
+                   mb, ptr(gx.slots), gx.world, packed, ptr(self.m), ptr(self.v), ptr(self.control if ctl else self.scalars), work, stats)
+            return
         if gx is None:
             launch(lb.upkie_ppo_minibatch_update_controlled if ctl else lb.upkie_ppo_minibatch_update, *head, total, start, size, mb, perm, *data,
                    adv_stats, packed, ptr(self.m), ptr(self.v), ptr(self.control), work, stats)
@@ -431,10 +470,11 @@ class PpoTrainer:
         pol = self.policy
         self._flat.index_copy_(0, pol._index, pol.packed)  # (padding words, all mapped to the last slot, are zero)
         params = pol._params
-        trainable = [params[-1]] + params[:-1]  # sources() order after the four fixed tensors
-        start = sum(self._sizes[:4])
+        trainable = [params[-1]] + params[:-1]  # sources() order after the fixed tensors
+        nf = getattr(pol, "n_fixed", 4)
+        start = sum(self._sizes[:nf])
         with torch.no_grad():
-            for t, n in zip(trainable, self._sizes[4:]):
+            for t, n in zip(trainable, self._sizes[nf:]):
                 t.detach().view(-1).copy_(self._flat[start:start + n])
                 start += n
 
@@ -455,13 +495,14 @@ class PpoTrainer:
     def _unpack(self, packed: torch.Tensor):
         flat = torch.zeros(sum(self._sizes) + 1, dtype=torch.float32, device=self.device)
         flat.index_copy_(0, self.policy._index, packed)
-        return [t.clone() for t in torch.split(flat[:-1], self._sizes)[4:]]
+        return [t.clone() for t in torch.split(flat[:-1], self._sizes)[getattr(self.policy, "n_fixed", 4):]]
 
     def _pack(self, tensors, into: torch.Tensor) -> None:
-        if len(tensors) != len(self._sizes) - 4:
-            raise ValueError(f"need {len(self._sizes) - 4} tensors (log_std, then weight and bias per layer)")
-        flat = [torch.zeros(n, dtype=torch.float32, device=self.device) for n in self._sizes[:4]]
-        for t, n in zip(tensors, self._sizes[4:]):
+        nf = getattr(self.policy, "n_fixed", 4)
+        if len(tensors) != len(self._sizes) - nf:
+            raise ValueError(f"need {len(self._sizes) - nf} tensors (log_std, then weight and bias per layer)")
+        flat = [torch.zeros(n, dtype=torch.float32, device=self.device) for n in self._sizes[:nf]]
+        for t, n in zip(tensors, self._sizes[nf:]):
             t = torch.as_tensor(t, dtype=torch.float32).to(self.device).reshape(-1)
             if t.numel() != n:
                 raise ValueError(f"a tensor of {t.numel()} values where {n} belong")
@@ -512,16 +553,37 @@ class Ppo:
     resumed in fresh objects continues bit for bit. Schedules, ``reward_fn``, ``reward`` and ``events`` are code: give them to `load` again.
 
     ``events`` (a `upkie_amd.events.EpisodeEvents` built on ``env``) perturbs the rollout: random pushes and per-episode
-    inertias, one more launch per step, after the reward (`AgentStep`)."""
+    inertias, one more launch per step, after the reward (`AgentStep`).
+
+    ``critic_observation`` (a `upkie_amd.privileged.PrivilegedObservation` built on ``env``, ``events`` and ``pipeline``)
+    trains an asymmetric ``policy``: the critic reads the privileged row, the actor what the robot will see. One more
+    launch per step after `AgentStep.apply` (so after ``events.step``); the row is normalised by a second
+    `RunningNormalizer` (``critic_normalizer``, ``norm_reward=False``, attached with ``tower="critic"``; its return
+    statistics are unused) into ``buffer.critic_observations``; the time-limit bootstrap reads the row's
+    ``final_observation`` and ``last_values`` the current row. `save` / `load` carry ``critic_observation.*`` and the
+    critic's normaliser. Evaluation never runs the critic and takes such a policy unchanged."""
 
     def __init__(self, env, policy, n_steps: int = 128, gamma: float = 0.99, gae_lambda: float = 0.95, n_epochs: int = 10, batch_size: int = 64,
                  learning_rate: Schedule = 3e-4, clip_range: Schedule = 0.2, clip_range_vf: Optional[Schedule] = None,
                  normalize_advantage: bool = True, ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5,
                  target_kl: Optional[float] = None, normalize: bool = True, bootstrap_time_limits: bool = True, stats_window_size: int = 100,
                  reward_fn: Optional[Callable] = None, graph: bool = True, seed: int = 0, process_group=None, pipeline=None, reward=None,
-                 events=None):
+                 events=None, critic_observation=None):
         if int(n_steps) < 1:
             raise ValueError("n_steps must be positive")
+        D = int(getattr(getattr(policy, "shape", None), "obs_dim", 0))
+        Dc = int(getattr(policy, "critic_obs_dim", D))
+        if getattr(policy, "asymmetric", False) and critic_observation is None:
+            raise ValueError(f"the policy is asymmetric (its critic reads {Dc} words, its actor {D}): give critic_observation= (a "
+                             f"PrivilegedObservation of {Dc} words)")
+        if critic_observation is not None and not getattr(policy, "asymmetric", False):
+            raise ValueError(f"critic_observation has {int(critic_observation.dim)} words but the policy is symmetric (its critic reads the "
+                             f"actor's {D}-word observation): build the critic on {int(critic_observation.dim)} inputs")
+        if critic_observation is not None and int(critic_observation.dim) != Dc:
+            raise ValueError(f"critic_observation has {int(critic_observation.dim)} words, the policy's critic takes {Dc}")
+        if critic_observation is not None and int(critic_observation.num_envs) != int(env.num_envs):
+            raise ValueError(f"critic_observation serves {int(critic_observation.num_envs)} envs, the env has {int(env.num_envs)}")
+        self.critic_observation = critic_observation
         self._agent = AgentStep(env, policy, pipeline, reward, reward_fn, noun="rollout", events=events)  # (checks the sizes)
         self.reward, self.pipeline, self.events = reward, pipeline, events
         self.env, self.policy = env, policy
@@ -535,7 +597,7 @@ class Ppo:
                                   target_kl=target_kl, obs_normalized=self.normalize, seed=seed, process_group=process_group)
         self.num_timesteps, self.iterations, self.total_timesteps, self.progress_remaining = 0, 0, 0, 1.0
         self.records = []
-        self.trainer = self.buffer = self.normalizer = self.episodes = None
+        self.trainer = self.buffer = self.normalizer = self.critic_normalizer = self.episodes = None
         self._loop = self._update_graph = None
 
     # ---- the objects, built by the first learn() (or by load())
@@ -556,16 +618,27 @@ class Ppo:
             else:  # (SB3: VecNormalize over VecFrameStack, so its columns are the stack's, not the env's)
                 self.normalizer = RunningNormalizer(N, D, gamma=self.gamma, device=dev, **kw)
             self.normalizer.attach(pol)
+            if self.critic_observation is not None:  # (the privileged rows' own statistics; the reward is the first one's)
+                self.critic_normalizer = RunningNormalizer(N, int(pol.critic_obs_dim), gamma=self.gamma, norm_reward=False, device=dev, **kw)
+                self.critic_normalizer.attach(pol, tower="critic")
         self.episodes = EpisodeStatistics(N, window=self.window, device=dev)
         self.trainer = PpoTrainer(pol, **self._trainer_args)
         if self.process_group is not None:
             self.trainer.broadcast_parameters(0)
             if self.normalizer is not None:
                 self.normalizer.broadcast_statistics(0)
-        self.buffer = RolloutBuffer(T, N, obs_shape=(D,), action_shape=(A,), device=dev, gamma=self.gamma, gae_lambda=self.gae_lambda)
+            if self.critic_normalizer is not None:
+                self.critic_normalizer.broadcast_statistics(0)
+        cobs = self.critic_observation
+        self.buffer = RolloutBuffer(T, N, obs_shape=(D,), action_shape=(A,), device=dev, gamma=self.gamma, gae_lambda=self.gae_lambda,
+                                    critic_obs_shape=None if cobs is None else (int(cobs.dim),))
         self._agent.reset(seed=self.seed if self.process_group is None else None)
+        if cobs is not None:
+            cobs.reset(self._agent.raw_observation)  # (after the pipeline's and the events' resets: their first command, force and scales)
         if self.normalizer is not None:
             self.normalizer.reset(self._agent.observation)
+        if self.critic_normalizer is not None:
+            self.critic_normalizer.reset(cobs.observation)
         self._env_action = torch.empty(N, A, device=dev)
         self._starts = torch.ones(N, dtype=torch.uint8, device=dev)
         self._slot = self.n_steps - 1 if self.graph else 0  # (the capture's warm-up step takes the last slot)
@@ -580,7 +653,7 @@ class Ppo:
     def _rollout_step(self) -> None:
         """One step of every env into slot ``_slot``: `Ppo`'s own stages around the two halves of `AgentStep`. With an
         `AgentPipeline` the normaliser and the bootstrap see the stack and its terminal form."""
-        t, buf, pol, starts, agent = self._slot, self.buffer, self.policy, self._starts, self._agent
+        t, buf, pol, starts, agent, cobs = self._slot, self.buffer, self.policy, self._starts, self._agent, self.critic_observation
         obs = agent.observation
         buf.episode_starts[t].copy_(starts)
         out = {"action": buf.actions[t], "value": buf.values[t], "log_prob": buf.log_probs[t], "env_action": self._env_action}
@@ -588,8 +661,17 @@ class Ppo:
             out["norm_obs"] = buf.observations[t]
         else:
             buf.observations[t].copy_(obs)
-        pol.act(obs, out=out)
-        _, reward, terminated, truncated, final_obs, _ = agent.apply(self._env_action)
+        if cobs is None:
+            pol.act(obs, out=out)
+        else:  # (the critic reads the privileged row; its normalised form is what the update trains on)
+            if self.critic_normalizer is not None:
+                out["norm_critic_obs"] = buf.critic_observations[t]
+            else:
+                buf.critic_observations[t].copy_(cobs.observation)
+            pol.act(obs, out=out, critic_obs=cobs.observation)
+        raw_next, reward, terminated, truncated, final_obs, _ = agent.apply(self._env_action)
+        if cobs is not None:  # (after events.step: the force the next step applies, the next episode's scales)
+            cobs.step(raw_next, terminated, truncated, final_obs=final_obs)
         self.episodes.step(reward, terminated, truncated)  # Monitor: the raw reward
         if self.bootstrap and final_obs is None:
             raise UpkieRuntimeError("bootstrap_time_limits needs info['final_obs'] (an env with autoreset_mode='same_step'); "
@@ -600,8 +682,10 @@ class Ppo:
         else:
             buf.rewards[t].copy_(reward)
             torch.bitwise_or(terminated, truncated, out=starts)
+        if self.critic_normalizer is not None:  # (the rows' statistics move as the observations' do; its returns are unused)
+            self.critic_normalizer.step(cobs.observation, reward, terminated, truncated)
         if self.bootstrap:
-            pol.bootstrap_time_limits(final_obs, terminated, truncated, buf.rewards[t], self.gamma)
+            pol.bootstrap_time_limits(final_obs if cobs is None else cobs.final_observation, terminated, truncated, buf.rewards[t], self.gamma)
         self._slot = (t + 1) % self.n_steps
 
     def collect_rollouts(self) -> None:
@@ -614,7 +698,8 @@ class Ppo:
         self.num_timesteps += self.n_steps * self.n_envs
         buf = self.buffer
         buf.pos, buf.full = self.n_steps, True
-        buf.compute_returns_and_advantage(last_values=self.policy.value(self._agent.observation), dones=self._starts)
+        last = self._agent.observation if self.critic_observation is None else self.critic_observation.observation
+        buf.compute_returns_and_advantage(last_values=self.policy.value(last), dones=self._starts)
 
     def train(self) -> None:
         """SB3's ``PPO.train`` on the collected rollout: `PpoTrainer.prepare`, then the update (a graph replay when
@@ -671,7 +756,8 @@ class Ppo:
 
     # where a stage's `state_tensors` go under "tensors" in the file: stage -> (prefix, the names that differ from the stage's own)
     _FILE_NAMES = {"policy": ("", {}), "trainer": ("", {}), "episodes": ("", {"counters": "ep_counters", "means": "ep_means"}),
-                   "pipeline": ("pipeline.", {}), "reward": ("reward.", {}), "events": ("events.", {})}
+                   "pipeline": ("pipeline.", {}), "reward": ("reward.", {}), "events": ("events.", {}),
+                   "critic_observation": ("critic_observation.", {})}
 
     def _state_tensors(self):
         named = {"starts": self._starts}
@@ -692,6 +778,8 @@ class Ppo:
                            "progress_remaining": self.progress_remaining, "policy_seed": int(self.policy.seed)},
               "trainer": tr.host_state(),
               "sizes": {"n_envs": self.n_envs, "n_steps": self.n_steps}}
+        if self.critic_normalizer is not None:  # (a run without a privileged critic writes the names it always did)
+            sd["critic_normalizer"] = self.critic_normalizer.state_dict()
         torch.save(sd, path)
 
     @classmethod
@@ -712,6 +800,10 @@ class Ppo:
         tr.generator.set_state(sd["generator"])
         if model.normalizer is not None:
             model.normalizer.load_state_dict(sd["normalizer"])
+        if model.critic_normalizer is not None:
+            if sd.get("critic_normalizer") is None:
+                raise ValueError("the file has no critic_normalizer: it was saved from a run without critic_observation")
+            model.critic_normalizer.load_state_dict(sd["critic_normalizer"])
         c = sd["counters"]
         model.num_timesteps, model.iterations, model.total_timesteps = c["num_timesteps"], c["iterations"], c["total_timesteps"]
         model.progress_remaining = c["progress_remaining"]

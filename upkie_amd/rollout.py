@@ -41,15 +41,18 @@ def compute_gae(
 
 
 class RolloutBuffer:
-    """``buffer_size`` steps of ``n_envs`` envs, on the device."""
+    """``buffer_size`` steps of ``n_envs`` envs, on the device. ``critic_obs_shape``: also `critic_observations`
+    ``[T, N, Dc]``, the rows an asymmetric policy's critic read (None: no such tensor)."""
 
-    def __init__(self, buffer_size: int, n_envs: int, obs_shape, action_shape, device="cuda:0", gamma: float = 0.99, gae_lambda: float = 0.95):
+    def __init__(self, buffer_size: int, n_envs: int, obs_shape, action_shape, device="cuda:0", gamma: float = 0.99, gae_lambda: float = 0.95,
+                 critic_obs_shape=None):
         self.buffer_size, self.n_envs = int(buffer_size), int(n_envs)
         self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
         self.device = torch.device(device)
         T, N = self.buffer_size, self.n_envs
         f32 = dict(dtype=torch.float32, device=self.device)
         self.observations = torch.zeros((T, N) + tuple(obs_shape), **f32)
+        self.critic_observations = None if critic_obs_shape is None else torch.zeros((T, N) + tuple(critic_obs_shape), **f32)
         self.actions = torch.zeros((T, N) + tuple(action_shape), **f32)
         self.rewards = torch.zeros((T, N), **f32)
         self.values = torch.zeros((T, N), **f32)
