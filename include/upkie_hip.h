@@ -207,7 +207,8 @@ enum UpkieStructId {
   UPKIE_STRUCT_MLP_SHAPE = 9,
   UPKIE_STRUCT_PPO_CONFIG = 10,
   UPKIE_STRUCT_EPISODE_EVENTS = 11,
-  UPKIE_STRUCT_COUNT = 12
+  UPKIE_STRUCT_TASK_TARGETS = 12,
+  UPKIE_STRUCT_COUNT = 13
 };
 int64_t upkie_hip_struct_bytes(int which);
 
@@ -513,6 +514,98 @@ int upkie_sim_episode_events_step(UpkieSim* sim, const UpkieEpisodeEvents* param
 int upkie_sim_episode_events_reset(UpkieSim* sim, const UpkieEpisodeEvents* params, const uint8_t* mask, uint32_t* calls,
                                    int32_t* remaining, uint32_t* pushes, uint32_t* episodes, float* force,
                                    float* body_inertials, float* link_scale, void* stream);
+
+/* ---- Task targets (goals in the observation, a curriculum) ----------------
+ * The goal an env is asked to reach -- a ground and a yaw velocity, say --
+ * drawn per env on the device, held a random number of env steps, drawn again
+ * when the hold or the episode ends, and appended to the observation row the
+ * policy, the reward terms and the critic read: legged_gym's "commands" and
+ * "command curriculum" (csrc/task_targets.hpp), ONE launch per env step, so
+ * that it can live inside a captured rollout. ("Command" is the shaped action
+ * here, so the goal is the TARGET.) D = obs_dim words of observation,
+ * G = num_targets words of target, 1 <= G <= UPKIE_TASK_TARGETS_MAX,
+ * D + G <= 256; N = the handle's num_envs. Device buffers:
+ *   calls uint32 [N]: draws so far;  remaining int32 [N]: steps the current
+ *   target is still held, the coming one included;  target float [G][N];
+ *   limits float [G][2]: (low, high) of every word, read at every draw -- a
+ *   device block, not a launch argument: whoever rewrites it (a device copy,
+ *   the curriculum below) is followed by a captured step at its next replay;
+ *   observation, final_observation float [N][D + G].
+ * upkie_sim_task_targets_step, per env n, in this order:
+ *   1. r = Philox4x32-10, counter (global env id lo, hi, calls[n],
+ *      STREAM_TARGETS << 24 | 0) with STREAM_TARGETS = 7, key = the handle's
+ *      seed; calls[n] += 1. Every env, every call: an env's draws depend
+ *      neither on the batch, nor on the sharding, nor on other envs.
+ *   2. final_observation[n], for EVERY env: final_obs[n] where
+ *      terminated[n] | truncated[n] (bytes; either may be NULL: 0; next_obs[n]
+ *      when final_obs is NULL) and next_obs[n] elsewhere, followed by the OLD
+ *      target[:][n]: the step's outcome under the target the policy was given.
+ *   3. an ended episode: remaining[n] = 0; otherwise if remaining[n] > 0:
+ *      remaining[n] -= 1.
+ *   4. if remaining[n] == 0, a new target, "the draw" of (n, c = the calls[n]
+ *      that step 1 read, r):
+ *      remaining[n] = resample_steps_min + (r[3] >> 8) % (resample_steps_max -
+ *      resample_steps_min + 1); if (r[0] >> 8) < llround(stand_prob * 2^24)
+ *      every word is +0; otherwise word g is fma(limits[g][1] - limits[g][0],
+ *      u, limits[g][0]) in float32 with u = (w >> 8) / 2^24 and w word g % 4 of
+ *      the Philox block of counter (id lo, hi, c, STREAM_TARGETS << 24 |
+ *      1 + g / 4); a word with |x| < deadband[g] becomes +0.
+ *   5. observation[n] = next_obs[n] followed by the current target[:][n].
+ * upkie_sim_task_targets_reset, for the envs with mask[n] != 0 (all when mask
+ * is NULL): the draw of (n, c = 0, r of counter word 2 = 0), calls[n] = 1 (the
+ * draw was the env's call 0: no step draws from its blocks again), then
+ * observation[n] = obs[n] followed by the target. final_observation and the
+ * other envs' words are not written.
+ * upkie_sim_task_targets_curriculum (one launch per training iteration,
+ * outside the rollout): score double [N] and finished int32 [N] are an
+ * episode score per env and the count of episodes it has finished (the reward
+ * terms' term_last[k] and finished); seen int32 [N], zero at first. Over the
+ * envs with finished[n] != seen[n]: S = sum of score[n], M = their count,
+ * seen[n] = finished[n]. If M > 0 and S > threshold * M (fp64, no division),
+ * for every g: limits[g][0] = max(limits[g][0] - step[g], limit[g][0]) and
+ * limits[g][1] = min(limits[g][1] + step[g], limit[g][1]) in float32;
+ * otherwise limits is not written. step [G] and limit [G][2] are HOST arrays.
+ * The sum is taken in a fixed order (per block of 2048 envs: thread t of 256
+ * adds envs t, t + 256, ... in that order, then a halving tree; the blocks'
+ * partials in block order), in fp64, without float atomics: the same bits
+ * every call. workspace: upkie_sim_task_targets_workspace_bytes bytes (a
+ * function of num_envs alone; negative: refused), zero before the first call.
+ * Refused with UPKIE_ERR_INVALID_ARGUMENT before anything else, with or
+ * without a device: num_targets outside 1..UPKIE_TASK_TARGETS_MAX, obs_dim < 1
+ * or obs_dim + num_targets > 256, stand_prob outside [0, 1], resample steps
+ * outside 1 <= min <= max <= 65535, a deadband that is negative or not finite,
+ * a curriculum step that is negative or not finite, a curriculum limit that
+ * is not finite with low <= high, a threshold that is NaN, a NULL handle,
+ * state buffer, limits or next_obs. (The ranges themselves are device words:
+ * upkie_amd.targets checks them, finite with low <= high, before it writes
+ * them.) No allocation, no host synchronisation, no host argument that
+ * changes between calls: a step can be captured in a hipGraph; the handle's
+ * seed and env_id_offset are read when the launch is recorded. */
+#define UPKIE_TASK_TARGETS_MAX 8
+
+typedef struct UpkieTaskTargets {
+  double stand_prob; /* per draw: every word +0 */
+  double deadband[UPKIE_TASK_TARGETS_MAX];
+  int32_t obs_dim;     /* D */
+  int32_t num_targets; /* G */
+  int32_t resample_steps_min; /* env steps a target is held */
+  int32_t resample_steps_max;
+} UpkieTaskTargets;
+
+int upkie_sim_task_targets_step(UpkieSim* sim, const UpkieTaskTargets* params, const float* next_obs, const float* final_obs,
+                                const uint8_t* terminated, const uint8_t* truncated, const float* limits, uint32_t* calls,
+                                int32_t* remaining, float* target, float* observation, float* final_observation,
+                                void* stream);
+
+int upkie_sim_task_targets_reset(UpkieSim* sim, const UpkieTaskTargets* params, const float* obs, const uint8_t* mask,
+                                 const float* limits, uint32_t* calls, int32_t* remaining, float* target,
+                                 float* observation, void* stream);
+
+int64_t upkie_sim_task_targets_workspace_bytes(int32_t num_envs);
+
+int upkie_sim_task_targets_curriculum(UpkieSim* sim, int32_t num_targets, double threshold, const float* step,
+                                      const float* limit, const double* score, const int32_t* finished, int32_t* seen,
+                                      float* limits, void* workspace, void* stream);
 
 /* Diagnostic: the projected Gauss-Seidel sweeps the step kernels run when the
  * direct contact solution leaves its friction cone (what Bullet's

@@ -333,6 +333,22 @@ class UpkieEpisodeEvents(C.Structure):
     ]
 
 
+TASK_TARGETS_MAX = 8  # UPKIE_TASK_TARGETS_MAX
+
+
+class UpkieTaskTargets(C.Structure):
+    """The settings of `upkie_sim_task_targets_step` (include/upkie_hip.h, "Task targets")."""
+
+    _fields_ = [
+        ("stand_prob", C.c_double),
+        ("deadband", C.c_double * TASK_TARGETS_MAX),
+        ("obs_dim", C.c_int32),
+        ("num_targets", C.c_int32),
+        ("resample_steps_min", C.c_int32),
+        ("resample_steps_max", C.c_int32),
+    ]
+
+
 # enum UpkieStructId -> the mirror of that struct here (`upkie_hip_struct_bytes`: lib.load() compares sizes)
 STRUCT_IDS = {
     0: UpkieModel,
@@ -347,10 +363,12 @@ STRUCT_IDS = {
     9: UpkieMlpShape,
     10: UpkiePpoConfig,
     11: UpkieEpisodeEvents,
+    12: UpkieTaskTargets,
 }
 # structs that only newer, optional entry points read: a build without that entry point (an older library loaded through
 # UPKIE_HIP_LIBRARY for an A/B run) answers -1 for them, and lib.load() still accepts it
-OPTIONAL_STRUCTS = {9: "upkie_mlp_actor_critic", 10: "upkie_ppo_minibatch_update", 11: "upkie_sim_episode_events_step"}
+OPTIONAL_STRUCTS = {9: "upkie_mlp_actor_critic", 10: "upkie_ppo_minibatch_update", 11: "upkie_sim_episode_events_step",
+                    12: "upkie_sim_task_targets_step"}
 MAX_GRAPH_CAPTURES = 8  # UPKIE_MAX_GRAPH_CAPTURES
 
 # the PPO control block's fp64 words (enum UPKIE_PPO_CTRL_*)

@@ -27,8 +27,12 @@ __host__ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1,
 // Stream tags, the top byte of counter word 3: two draws can share a Philox block only under one tag, so every user of the
 // rounds takes its tag from this one list. 0-3 are the simulator's (reset states, torque noise, per-episode inertias,
 // pushes), under the sim's seed; the MLP policy's samples and the agent pipeline's noise count (env, call, 0) under their own;
-// 6 is the episode events' schedule (env, call), under the sim's seed too (episode_events.hpp, which also redraws 2 per episode).
-enum { STREAM_RESET = 0, STREAM_NOISE = 1, STREAM_INERTIA = 2, STREAM_PUSH = 3, STREAM_POLICY = 4, STREAM_PIPELINE = 5, STREAM_EVENTS = 6 };
+// 6 is the episode events' schedule (env, call), under the sim's seed too (episode_events.hpp, which also redraws 2 per episode);
+// 7 the task targets' (env, call), under the sim's seed: block 0 the schedule, blocks 1 and 2 the values (task_targets.hpp).
+enum {
+  STREAM_RESET = 0, STREAM_NOISE = 1, STREAM_INERTIA = 2, STREAM_PUSH = 3, STREAM_POLICY = 4, STREAM_PIPELINE = 5, STREAM_EVENTS = 6,
+  STREAM_TARGETS = 7
+};
 
 template <class ConfigT>
 __device__ __forceinline__ void philox_uniform4(const ConfigT& C, unsigned env_local, unsigned episode, unsigned stream,

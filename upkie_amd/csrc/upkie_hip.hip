@@ -18,6 +18,7 @@
 #include "step_dispatch.hpp"
 #include "host_setup.hpp"
 #include "episode_events.hpp"
+#include "task_targets.hpp"
 #include "abi_host.hpp"
 
 namespace upkie {
@@ -332,6 +333,7 @@ extern "C" int64_t upkie_hip_struct_bytes(int which) {
     case UPKIE_STRUCT_MLP_SHAPE: return (int64_t)sizeof(UpkieMlpShape);
     case UPKIE_STRUCT_PPO_CONFIG: return (int64_t)sizeof(UpkiePpoConfig);
     case UPKIE_STRUCT_EPISODE_EVENTS: return (int64_t)sizeof(UpkieEpisodeEvents);
+    case UPKIE_STRUCT_TASK_TARGETS: return (int64_t)sizeof(UpkieTaskTargets);
     default: return -1;
   }
 }
@@ -534,6 +536,84 @@ extern "C" int upkie_sim_episode_events_reset(UpkieSim* sim, const UpkieEpisodeE
                      sim->links, P, mask, (unsigned*)calls, (int*)remaining, (unsigned*)pushes, (unsigned*)episodes, force, body_inertials,
                      link_scale);
   return check_hip(sim, hipGetLastError(), "episode_events_reset_kernel");
+}
+
+// Task targets (include/upkie_hip.h): the settings checked and converted; every refusal comes before any device use.
+static int targets_params(UpkieSim* sim, const UpkieTaskTargets* p, const void* obs, const void* limits, const void* calls,
+                          const void* remaining, const void* target, const void* observation, TargetsParams* out) {
+  if (!p) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  if (!(p->num_targets >= 1 && p->num_targets <= UPKIE_TASK_TARGETS_MAX))
+    return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "num_targets must be in 1-" + std::to_string(UPKIE_TASK_TARGETS_MAX));
+  if (!(p->obs_dim >= 1 && p->obs_dim + p->num_targets <= 256))
+    return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "obs_dim must be positive with obs_dim + num_targets <= 256");
+  if (!(p->stand_prob >= 0.0 && p->stand_prob <= 1.0)) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "stand_prob must be in [0, 1]");
+  if (!(p->resample_steps_min >= 1 && p->resample_steps_min <= p->resample_steps_max && p->resample_steps_max <= 65535))
+    return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "resample_steps must hold 1 <= min <= max <= 65535");
+  for (int g = 0; g < p->num_targets; ++g)
+    if (!(std::isfinite(p->deadband[g]) && p->deadband[g] >= 0.0)) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "deadband must be finite and non-negative");
+  if (!sim || !obs || !limits || !calls || !remaining || !target || !observation) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  out->obs_dim = p->obs_dim;
+  out->count = p->num_targets;
+  out->threshold = (unsigned)std::llround(p->stand_prob * 16777216.0);
+  out->steps_min = p->resample_steps_min;
+  out->steps_span = (unsigned)(p->resample_steps_max - p->resample_steps_min + 1);
+  for (int g = 0; g < UPKIE_TASK_TARGETS_MAX; ++g) out->deadband[g] = g < p->num_targets ? (float)p->deadband[g] : 0.f;
+  return UPKIE_OK;
+}
+static dim3 targets_grid_for(int B) { return dim3((unsigned)((B + TARGETS_ENVS - 1) / TARGETS_ENVS)); }
+
+extern "C" int upkie_sim_task_targets_step(UpkieSim* sim, const UpkieTaskTargets* params, const float* next_obs, const float* final_obs,
+                                           const uint8_t* terminated, const uint8_t* truncated, const float* limits, uint32_t* calls,
+                                           int32_t* remaining, float* target, float* observation, float* final_observation, void* stream) {
+  TargetsParams P;
+  const int status = targets_params(sim, params, next_obs, limits, calls, remaining, target, observation, &P);
+  if (status != UPKIE_OK) return status;
+  if (!final_observation) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  hipLaunchKernelGGL(task_targets_kernel, targets_grid_for(sim->config.num_envs), dim3(TARGETS_THREADS), 0, (hipStream_t)stream, sim->config, P,
+                     next_obs, final_obs, terminated, truncated, limits, (unsigned*)calls, (int*)remaining, target, observation,
+                     final_observation);
+  return check_hip(sim, hipGetLastError(), "task_targets_kernel");
+}
+
+extern "C" int upkie_sim_task_targets_reset(UpkieSim* sim, const UpkieTaskTargets* params, const float* obs, const uint8_t* mask,
+                                            const float* limits, uint32_t* calls, int32_t* remaining, float* target, float* observation,
+                                            void* stream) {
+  TargetsParams P;
+  const int status = targets_params(sim, params, obs, limits, calls, remaining, target, observation, &P);
+  if (status != UPKIE_OK) return status;
+  hipLaunchKernelGGL(task_targets_reset_kernel, targets_grid_for(sim->config.num_envs), dim3(TARGETS_THREADS), 0, (hipStream_t)stream, sim->config,
+                     P, obs, mask, limits, (unsigned*)calls, (int*)remaining, target, observation);
+  return check_hip(sim, hipGetLastError(), "task_targets_reset_kernel");
+}
+
+extern "C" int64_t upkie_sim_task_targets_workspace_bytes(int32_t num_envs) {
+  if (num_envs < 1) return fail(UPKIE_ERR_INVALID_ARGUMENT, "num_envs must be positive");
+  return curriculum_workspace_bytes(num_envs);
+}
+
+extern "C" int upkie_sim_task_targets_curriculum(UpkieSim* sim, int32_t num_targets, double threshold, const float* step, const float* limit,
+                                                 const double* score, const int32_t* finished, int32_t* seen, float* limits, void* workspace,
+                                                 void* stream) {
+  if (!(num_targets >= 1 && num_targets <= UPKIE_TASK_TARGETS_MAX))
+    return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "num_targets must be in 1-" + std::to_string(UPKIE_TASK_TARGETS_MAX));
+  if (std::isnan(threshold)) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "threshold must be a number");
+  if (!step || !limit) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  CurriculumParams P{};
+  P.count = num_targets;
+  P.threshold = threshold;
+  for (int g = 0; g < num_targets; ++g) {
+    if (!(std::isfinite(step[g]) && step[g] >= 0.f)) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "a curriculum step must be finite and non-negative");
+    if (!(std::isfinite(limit[2 * g]) && std::isfinite(limit[2 * g + 1]) && limit[2 * g] <= limit[2 * g + 1]))
+      return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "a curriculum limit must be finite with low <= high");
+    P.step[g] = step[g];
+    P.limit[g][0] = limit[2 * g];
+    P.limit[g][1] = limit[2 * g + 1];
+  }
+  if (!sim || !score || !finished || !seen || !limits || !workspace) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  const int N = sim->config.num_envs;
+  hipLaunchKernelGGL(task_targets_curriculum_kernel, dim3((unsigned)curriculum_blocks(N)), dim3(CURRICULUM_THREADS), 0, (hipStream_t)stream, N, P,
+                     score, finished, seen, limits, (double*)((char*)workspace + 8), (unsigned*)workspace);
+  return check_hip(sim, hipGetLastError(), "task_targets_curriculum_kernel");
 }
 
 // What the choice of a step kernel (step_dispatch.hpp) reads from the handle, for an entry point that launches `mode`.

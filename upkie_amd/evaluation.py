@@ -125,13 +125,13 @@ class PolicyEvaluator:
     arguments and the order of a step."""
 
     def __init__(self, policy, env, capacity: int, deterministic: bool = True, pipeline=None, reward=None, reward_fn: Optional[Callable] = None,
-                 chunk: int = 32, graph: bool = True, events=None):
+                 chunk: int = 32, graph: bool = True, events=None, targets=None):
         mode = getattr(env, "autoreset_mode", None)
         if mode != "same_step":
             raise ValueError(f"evaluation needs an env with autoreset_mode='same_step' (SB3's VecEnv semantics, and the terminal observation "
                              f"the reward terms read), this one has {mode!r}")
-        self._agent = AgentStep(env, policy, pipeline, reward, reward_fn, noun="evaluation", events=events)  # (checks the sizes)
-        self.events = events
+        self._agent = AgentStep(env, policy, pipeline, reward, reward_fn, noun="evaluation", events=events, targets=targets)  # (checks the sizes)
+        self.events, self.targets = events, targets
         if int(chunk) < 1:
             raise ValueError("chunk must be positive")
         self.policy, self.env, self.pipeline, self.reward, self.reward_fn = policy, env, pipeline, reward, reward_fn
@@ -203,7 +203,7 @@ class PolicyEvaluator:
 
 def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool = True, pipeline=None, reward=None,
                     reward_fn: Optional[Callable] = None, seed: Optional[int] = None, max_steps: Optional[int] = None, chunk: int = 32,
-                    graph: bool = True, return_episode_rewards: bool = False, events=None):
+                    graph: bool = True, return_episode_rewards: bool = False, events=None, targets=None):
     """SB3's ``evaluate_policy`` on the device: run ``policy`` (an `upkie_amd.policies.MlpActorCritic`) in ``env`` until
     ``n_eval_episodes`` episodes have ended, env ``i`` giving ``(n_eval_episodes + i) // num_envs`` of them, and return
     ``(mean_reward, std_reward)``, or ``(episode_rewards, episode_lengths)`` with ``return_episode_rewards``.
@@ -216,7 +216,9 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
     which `RunningNormalizer.attach` keeps live: the evaluation env needs no normaliser and is always in sync with
     training (SB3's ``sync_envs_normalization``). ``pipeline`` and ``reward`` are the evaluation's own instances (sized
     for ``env``), reset when it begins; so is ``events`` (a `upkie_amd.events.EpisodeEvents` built on ``env``: the
-    evaluation under random pushes and per-episode inertias), stepped after the reward.
+    evaluation under random pushes and per-episode inertias), stepped after the reward, and ``targets`` (a
+    `upkie_amd.targets.TaskTargets` built on ``env``, with the ranges to evaluate at: a goal-conditioned policy reads its
+    rows), stepped right after the env and reset with it.
 
     ``env`` is reset (``reset(seed=seed)``) first. The loop runs ``chunk`` steps per graph replay (``graph=False``:
     eagerly) and reads `EpisodeTally.remaining` once per chunk; the steps after the last record change nothing, every
@@ -228,7 +230,7 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
     With ``deterministic=False`` the action is sampled with ``policy.act``: that needs ``env.num_envs`` to be the
     policy's batch size and ADVANCES the policy's per-env noise counters (the warm-up step included), so a training
     run that shares the policy does not continue as it would have."""
-    runner = PolicyEvaluator(policy, env, int(n_eval_episodes), deterministic, pipeline, reward, reward_fn, chunk, graph, events)
+    runner = PolicyEvaluator(policy, env, int(n_eval_episodes), deterministic, pipeline, reward, reward_fn, chunk, graph, events, targets)
     result = runner.run(n_eval_episodes, seed, max_steps)
     if return_episode_rewards:
         return result["episode_rewards"], result["episode_lengths"]
@@ -249,16 +251,17 @@ class EvalCallback:
     The tally and the captured loop are built by the first evaluation and reused. Evaluation reads the policy's packed
     weights and writes nothing the training run reads (`MlpActorCritic.mean_action`, its own env, tally, ``pipeline``
     and ``reward`` instances, and ``events``, a `upkie_amd.events.EpisodeEvents` built on ``eval_env``, to evaluate
-    under pushes and per-episode inertias): a run with this callback trains bit for bit as one without."""
+    under pushes and per-episode inertias, and ``targets``, a `upkie_amd.targets.TaskTargets` built on ``eval_env``): a run with this callback trains bit for bit as one without."""
 
     def __init__(self, eval_env, n_eval_episodes: int = 5, eval_freq: int = 10000, best_model_save_path=None, pipeline=None, reward=None,
                  seed: int = 0, reward_fn: Optional[Callable] = None, max_steps: Optional[int] = None, chunk: int = 32, graph: bool = True,
-                 events=None):
+                 events=None, targets=None):
         self.eval_env, self.n_eval_episodes, self.eval_freq = eval_env, int(n_eval_episodes), int(eval_freq)
         if self.n_eval_episodes < 1 or self.eval_freq < 1:
             raise ValueError("n_eval_episodes and eval_freq must be positive")
         self.best_model_save_path, self.pipeline, self.reward, self.reward_fn = best_model_save_path, pipeline, reward, reward_fn
         self.events = events  # (the evaluation env's own `EpisodeEvents`)
+        self.targets = targets  # (the evaluation env's own `TaskTargets`, at the ranges to evaluate at)
         self.seed, self.max_steps, self.chunk, self.graph = seed, max_steps, int(chunk), bool(graph)
         self.best_mean_reward, self.last_mean_reward = -math.inf, None
         self.evaluations = {"timesteps": [], "results": [], "ep_lengths": []}
@@ -269,7 +272,7 @@ class EvalCallback:
         """One evaluation of ``model.policy`` (`EpisodeTally.result`'s dict)."""
         if self._runner is None or self._runner.policy is not model.policy:
             self._runner = PolicyEvaluator(model.policy, self.eval_env, self.n_eval_episodes, True, self.pipeline, self.reward, self.reward_fn,
-                                           self.chunk, self.graph, self.events)
+                                           self.chunk, self.graph, self.events, self.targets)
         return self._runner.run(self.n_eval_episodes, self.seed, self.max_steps)
 
     def __call__(self, model, record) -> None:

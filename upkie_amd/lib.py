@@ -53,6 +53,7 @@ SOURCES = [
     os.path.join(_CSRC, "reward_terms.hpp"),
     os.path.join(_CSRC, "episode_events.hpp"),
     os.path.join(_CSRC, "privileged_obs.hpp"),
+    os.path.join(_CSRC, "task_targets.hpp"),
     os.path.join(_CSRC, "wave_io.hpp"),
     os.path.join(_HERE, "..", "include", "upkie_hip.h"),
 ]
@@ -99,6 +100,11 @@ def _abi_table():
         # the episode events (random pushes, per-episode inertias)
         ("upkie_sim_episode_events_step", status, [vp, P(abi.UpkieEpisodeEvents)] + [vp] * 10, "upkie_sim_episode_events_step"),
         ("upkie_sim_episode_events_reset", status, [vp, P(abi.UpkieEpisodeEvents)] + [vp] * 9, "upkie_sim_episode_events_step"),
+        # the task targets (goals in the observation) and their curriculum
+        ("upkie_sim_task_targets_step", status, [vp, P(abi.UpkieTaskTargets)] + [vp] * 11, "upkie_sim_task_targets_step"),
+        ("upkie_sim_task_targets_reset", status, [vp, P(abi.UpkieTaskTargets)] + [vp] * 8, "upkie_sim_task_targets_step"),
+        ("upkie_sim_task_targets_workspace_bytes", C.c_int64, [i32], "upkie_sim_task_targets_step"),
+        ("upkie_sim_task_targets_curriculum", status, [vp, i32, f64, P(C.c_float), P(C.c_float)] + [vp] * 6, "upkie_sim_task_targets_step"),
         ("upkie_sim_reset", status, [vp, vp, vp, vp, vp], None),
         ("upkie_sim_step_pendulum", status, step, None),
         ("upkie_sim_step_gyropod", status, step, None),

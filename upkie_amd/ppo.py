@@ -561,16 +561,34 @@ class Ppo:
     `RunningNormalizer` (``critic_normalizer``, ``norm_reward=False``, attached with ``tower="critic"``; its return
     statistics are unused) into ``buffer.critic_observations``; the time-limit bootstrap reads the row's
     ``final_observation`` and ``last_values`` the current row. `save` / `load` carry ``critic_observation.*`` and the
-    critic's normaliser. Evaluation never runs the critic and takes such a policy unchanged."""
+    critic's normaliser. Evaluation never runs the critic and takes such a policy unchanged.
+
+    ``targets`` (a `upkie_amd.targets.TaskTargets` built on ``env``) trains a goal-conditioned policy: one more launch per
+    step right after ``env.step`` (`AgentStep`) appends the env's target to the raw observation, so ``policy`` (or
+    ``pipeline``) reads D + G words, ``reward`` is built with ``obs_dim = D + G`` (a tracking term taps ``obs(D + g)``)
+    and scores the step under the target the policy was given, and a ``critic_observation`` is built with
+    ``obs_dim=D + G``. Without a pipeline the normaliser has D + G columns. With a `TargetCurriculum` one launch after
+    every rollout widens the ranges from the named reward term's episode sums (it must be one of ``reward``'s; with a
+    ``process_group`` it is refused); a record carries ``rollout/target_<name>_low`` and ``_high``. `save` / `load`
+    carry ``targets.*``, the ranges included. ``targets=None``: every launch and every bit as without."""
 
     def __init__(self, env, policy, n_steps: int = 128, gamma: float = 0.99, gae_lambda: float = 0.95, n_epochs: int = 10, batch_size: int = 64,
                  learning_rate: Schedule = 3e-4, clip_range: Schedule = 0.2, clip_range_vf: Optional[Schedule] = None,
                  normalize_advantage: bool = True, ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5,
                  target_kl: Optional[float] = None, normalize: bool = True, bootstrap_time_limits: bool = True, stats_window_size: int = 100,
                  reward_fn: Optional[Callable] = None, graph: bool = True, seed: int = 0, process_group=None, pipeline=None, reward=None,
-                 events=None, critic_observation=None):
+                 events=None, critic_observation=None, targets=None):
         if int(n_steps) < 1:
             raise ValueError("n_steps must be positive")
+        curriculum = getattr(targets, "curriculum", None)
+        if curriculum is not None and process_group is not None:
+            raise ValueError("a TargetCurriculum with a process_group is not supported: every rank would widen its own ranges from its own "
+                             "envs' scores and the ranks' ranges would part (targets without a curriculum shard: their draws are keyed by "
+                             "global env ids)")
+        if curriculum is not None and (reward is None or curriculum.term not in reward.names):
+            raise ValueError(f"the curriculum reads the reward term {curriculum.term!r}, the reward has "
+                             f"{list(reward.names) if reward is not None else 'no terms (give reward=, a RewardTerms)'}")
+        self._curriculum_term = reward.names.index(curriculum.term) if curriculum is not None else None
         D = int(getattr(getattr(policy, "shape", None), "obs_dim", 0))
         Dc = int(getattr(policy, "critic_obs_dim", D))
         if getattr(policy, "asymmetric", False) and critic_observation is None:
@@ -584,8 +602,8 @@ class Ppo:
         if critic_observation is not None and int(critic_observation.num_envs) != int(env.num_envs):
             raise ValueError(f"critic_observation serves {int(critic_observation.num_envs)} envs, the env has {int(env.num_envs)}")
         self.critic_observation = critic_observation
-        self._agent = AgentStep(env, policy, pipeline, reward, reward_fn, noun="rollout", events=events)  # (checks the sizes)
-        self.reward, self.pipeline, self.events = reward, pipeline, events
+        self._agent = AgentStep(env, policy, pipeline, reward, reward_fn, noun="rollout", events=events, targets=targets)  # (checks the sizes)
+        self.reward, self.pipeline, self.events, self.targets = reward, pipeline, events, targets
         self.env, self.policy = env, policy
         self.n_envs = int(env.num_envs)
         self.n_steps, self.gamma, self.gae_lambda = int(n_steps), float(gamma), float(gae_lambda)
@@ -613,9 +631,9 @@ class Ppo:
         D, A = int(pol.shape.obs_dim), int(pol.shape.act_dim)
         if self.normalize:
             kw = {} if self.process_group is None else {"process_group": self.process_group}
-            if self.pipeline is None:
+            if self.pipeline is None and self.targets is None:
                 self.normalizer = RunningNormalizer.for_env(env, gamma=self.gamma, **kw)
-            else:  # (SB3: VecNormalize over VecFrameStack, so its columns are the stack's, not the env's)
+            else:  # (SB3: VecNormalize over VecFrameStack, so its columns are the stack's, not the env's; with targets: D + G)
                 self.normalizer = RunningNormalizer(N, D, gamma=self.gamma, device=dev, **kw)
             self.normalizer.attach(pol)
             if self.critic_observation is not None:  # (the privileged rows' own statistics; the reward is the first one's)
@@ -732,6 +750,8 @@ class Ppo:
             self.total_timesteps = int(total_timesteps) + self.num_timesteps
         while self.num_timesteps < self.total_timesteps:
             self.collect_rollouts()
+            if self._curriculum_term is not None:  # (one launch: the ranges of the next rollout's draws)
+                self.targets.curriculum_step(self.reward.term_last[self._curriculum_term], self.reward.finished)
             self.iterations += 1
             self.progress_remaining = 1.0 - float(self.num_timesteps) / float(self.total_timesteps)
             self.trainer.set_progress(self.progress_remaining)
@@ -743,6 +763,8 @@ class Ppo:
                                "time/total_timesteps": self.num_timesteps, "time/iterations": self.iterations})
                 if self.reward is not None:
                     record.update({f"rollout/ep_rew_{name}_mean": mean for name, mean in self.reward.term_means().items()})
+                if self.targets is not None:
+                    record.update({f"rollout/{name}": value for name, value in self.targets.log().items()})
                 self.records.append(record)
             if callback is not None and callback(self, record) is False:
                 break
@@ -757,7 +779,7 @@ class Ppo:
     # where a stage's `state_tensors` go under "tensors" in the file: stage -> (prefix, the names that differ from the stage's own)
     _FILE_NAMES = {"policy": ("", {}), "trainer": ("", {}), "episodes": ("", {"counters": "ep_counters", "means": "ep_means"}),
                    "pipeline": ("pipeline.", {}), "reward": ("reward.", {}), "events": ("events.", {}),
-                   "critic_observation": ("critic_observation.", {})}
+                   "critic_observation": ("critic_observation.", {}), "targets": ("targets.", {})}
 
     def _state_tensors(self):
         named = {"starts": self._starts}
