@@ -1440,6 +1440,75 @@ int upkie_ppo_minibatch_gradient_asym(const UpkieMlpShape* shape, const UpkiePpo
 int upkie_ppo_explained_variance(int32_t total, const float* returns, const float* values, int32_t phase,
                                  const double* slots, int32_t world, double* slot, double* out, void* stream);
 
+/* ---- Policy distillation ------------------------------------------------
+ * One minibatch of a supervised (behaviour-cloning) update of the ACTOR
+ * tower of the MLP actor-critic of `shape`, on the device (csrc/distill.hpp),
+ * in place on the packed weight buffer. B = the minibatch's samples, s =
+ * perm[minibatch_start + j], j < minibatch_size, of `total` rows (obs
+ * [total][obs_dim], labels [total][act_dim]: what a teacher would have done
+ * on the sample); x = the observation normalised as upkie_mlp_actor_critic
+ * does, unless obs_normalized; A = act_dim.
+ *   mu   = the actor tower on x (the Gaussian's mean, NOT clamped to the
+ *          action bounds)
+ *   loss = 1 / (B A) sum_j sum_a (mu_a(x_j) - label_ja)^2
+ * which is torch.nn.functional.mse_loss(mu, label). g = d loss / d params,
+ * the gradient torch autograd gives: the head's dZ = 2 (mu - label) / (B A),
+ * then the layers of the actor as in the PPO update (its forward, backward
+ * and weight-gradient device functions, unchanged). The parameters are the
+ * ACTOR's weights and biases (head included) alone: the partial gradients,
+ * their fold, the norm and Adam range over exactly the actor's packed words,
+ * every one of which every block writes (the layout's padding words too, as
+ * zeros: the partials need no zeroed workspace; the zeroing is for the
+ * fold's counter), so log_std, every critic word and
+ * the fixed words before log_std (observation statistics, action bounds) are
+ * neither read-modified nor written, and their words of adam_m and adam_v
+ * stay what they were (0 under a fresh optimiser state). Then
+ * clip_grad_norm_ and torch.optim.Adam as in the PPO update:
+ *   coef = min(1, max_grad_norm / (||g||_2 + 1e-6)),  g = coef g
+ *   t += 1;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2
+ *   p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + adam_eps)
+ * with lr = adam_scalars[0] and t = adam_scalars[1], fp64 words in DEVICE
+ * memory (the first two words of a PPO control block serve): a captured
+ * update follows a learning-rate schedule without a re-capture.
+ * stats[UPKIE_DISTILL_STATS] = loss, ||g||_2 before the clip, coef. Three
+ * launches (gradient partials per block; their fold in block order, whose
+ * last block forms ||g||, coef, the statistics and t in a fixed order; Adam),
+ * no float atomics: the same bits every call; no allocation, no host
+ * synchronisation, every argument constant across iterations. Every shape
+ * the PPO update takes is taken, asymmetric ones included (critic_obs_dim > 0
+ * changes nothing here: the critic's rows are not read); a shape without a
+ * critic is refused as there. The workspace (upkie_distill_workspace_bytes,
+ * <= 64 MiB) is zeroed once before the first call. Argument and shape errors
+ * return UPKIE_ERR_INVALID_ARGUMENT before any device use, the reason in
+ * upkie_sim_last_error(NULL); no CPU fallback. */
+enum { UPKIE_DISTILL_STATS = 3 };
+
+int64_t upkie_distill_workspace_bytes(const UpkieMlpShape* shape, int32_t max_minibatch);
+
+int upkie_distill_minibatch_update(const UpkieMlpShape* shape, int32_t total, int32_t minibatch_start,
+                                   int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm, const float* obs,
+                                   const float* labels, float* packed, float* adam_m, float* adam_v, double* adam_scalars,
+                                   double max_grad_norm, double adam_beta1, double adam_beta2, double adam_eps,
+                                   int32_t obs_normalized, void* workspace, float* stats, void* stream);
+
+/* The DAgger mix of a distillation rollout step, one launch, on the sim
+ * handle (its seed and global env ids). Per env n < num_envs:
+ *   r = Philox4x32-10(counter (global env id lo, hi, calls[n], 8 << 24), key
+ *       = the handle's seed);  calls[n] += 1        (stream tag 8: the mix's)
+ *   teacher = (r[0] >> 8) < threshold[0]
+ *   applied[n][a] = clamp(teacher ? label[n][a] : student_action[n][a],
+ *                         low[a], high[a]),  a < act_dim (1-64)
+ *   drove[n] = teacher (a byte, 0 / 1)
+ * threshold: ONE uint32 word in device memory, llround(beta 2^24) for a
+ * probability beta that the teacher drives (0: never, 2^24: always), so that
+ * a beta schedule moves under a captured rollout. Selection and clamp only:
+ * exact. Keyed by the global env id: N envs are the same bits however they
+ * are sharded. label, student_action, applied: [num_envs][act_dim]; low,
+ * high: [act_dim]; calls: [num_envs], zeroed by the caller at a reset. */
+int upkie_sim_distill_mix(UpkieSim* sim, int32_t act_dim, const uint32_t* threshold, const float* label,
+                          const float* student_action, const float* low, const float* high, uint32_t* calls,
+                          float* applied, uint8_t* drove, void* stream);
+
 /* ---- Time-limit bootstrap (SB3 collect_rollouts) ----------------------
  * For every env n < num_envs with truncated[n] && !terminated[n] (bytes;
  * terminated may be NULL: none terminated), in place:

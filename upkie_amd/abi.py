@@ -382,6 +382,11 @@ PPO_CTRL_N_UPDATES = 6
 PPO_CTRL_MINIBATCHES_RUN = 7
 PPO_CTRL_WORDS = 8
 
+# policy distillation (upkie_distill_minibatch_update, upkie_sim_distill_mix)
+DISTILL_STATS = 3  # UPKIE_DISTILL_STATS: loss, ||g|| before the clip, the clip coefficient
+DISTILL_STAT_NAMES = ("loss", "grad_norm", "clip_coef")
+STREAM_DISTILL = 8  # the mix's Philox stream tag (csrc/random.hpp)
+
 # observer memory words (enum UpkieObserverStateWord)
 O_WHEEL = 0
 O_UPPER_LEG_TORQUE = 10

@@ -330,8 +330,10 @@ __device__ __forceinline__ float ppo_uniform(float x) {  // (a value every lane 
 
 // One tower of one chunk: forward, loss, backward, dW. ACTOR: the policy loss through the Gaussian head (and log_std);
 // otherwise the value loss through the critic's dot head. `st` collects the loss sums of the lane's sample (lanes of
-// group 0 only).
-template <int WT, int ACT, bool ACTOR>
+// group 0 only). BC (distill.hpp; ACTOR only): the behaviour-cloning head instead of the surrogate -- the labels are read
+// where the actions are, dZ = 2 (mean - label) / (count A), st[0] collects every lane's own (mean - label)^2, and
+// log_std gets no stage rows and no partial words. BC = false compiles to what it did before the parameter.
+template <int WT, int ACT, bool ACTOR, bool BC = false>
 __device__ __forceinline__ void ppo_tower(const PpoDev& P, const PpoClip& K, float* stage, int sample, bool valid, float* part, bool first,
                                           double (&st)[PPO_STATS], int wave, int lane) {
   const int q = lane >> 4, r = lane & 15, tid = wave * 64 + lane;
@@ -368,51 +370,71 @@ __device__ __forceinline__ void ppo_tower(const PpoDev& P, const PpoClip& K, flo
       if (T.head_dot) m1 = mlp_dot<WT>(packed, T.head, h, lane);
       else mlp_dense<WT, ACT, false, false>(packed, T.head, in_dim, h, head, lane);
       if (T.head_dot) head[0][0] = m1;
-      constexpr float HALF_LOG_2PI = 0.91893853320467274f;
-      float lp = 0.f, d[4][4] = {}, sig2[4][4] = {};
+      if constexpr (BC) {
+        const float inv_ba = 1.f / ((float)P.count * (float)P.net.act_dim);
 #pragma unroll
-      for (int o = 0; o < (WT < 4 ? WT : 4); ++o) {
-        const int a0 = 16 * o + 4 * q;
-        if (o < P.net.act_tiles && a0 < P.net.act_dim) {
-          const mlp_f4 log_std = mlp_load4(packed + P.net.log_std_off + a0);
+        for (int o = 0; o < (WT < 4 ? WT : 4); ++o) {
+          if (o < P.net.act_tiles) {
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int a = a0 + i;
-            if (a < P.net.act_dim) {
-              const float sigma = expf(log_std[i]);
-              const float dd = P.actions[(size_t)sample * P.net.act_dim + a] - head[o][i];
-              d[o][i] = dd, sig2[o][i] = sigma * sigma;
-              lp += -(dd * dd) / (2.f * sigma * sigma) - log_std[i] - HALF_LOG_2PI;
+            for (int i = 0; i < 4; ++i) {
+              const int a = 16 * o + 4 * q + i;
+              float dz = 0.f;
+              if (valid && a < P.net.act_dim) {
+                const float e = head[o][i] - P.actions[(size_t)sample * P.net.act_dim + a];  // (the label)
+                st[0] += (double)e * (double)e;
+                dz = 2.f * e * inv_ba;
+              }
+              cur[o][i] = dz;
             }
           }
         }
-      }
-      lp += __shfl_xor(lp, 16);
-      lp += __shfl_xor(lp, 32);
-      // clipped surrogate: d loss / d log_prob (torch.minimum splits a tie half / half; clamp passes at its bounds)
-      const double* as = P.adv_stats;
-      const float adv = (float)(((double)P.advantages[sample] - as[0]) / as[1]);
-      const float log_ratio = lp - P.old_log_prob[sample];
-      const float ratio = expf(log_ratio);
-      const float a1 = adv * ratio, a2 = adv * fminf(fmaxf(ratio, K.lo), K.hi);
-      const float w1 = a1 < a2 ? 1.f : a1 == a2 ? 0.5f : 0.f, w2 = 1.f - w1;
-      const float pass = ratio >= K.lo && ratio <= K.hi ? 1.f : 0.f;
-      const float g_lp = valid ? -inv_b * (w1 * adv + w2 * adv * pass) * ratio : 0.f;
-      if (valid && q == 0) {
-        st[0] += (double)fminf(a1, a2);
-        st[2] += (double)((ratio - 1.f) - log_ratio);
-        st[3] += fabsf(ratio - 1.f) > K.range ? 1.0 : 0.0;
-      }
-      // head dZ = d loss / d mean, and the per-sample log_std terms, into the stage
+      } else {
+        constexpr float HALF_LOG_2PI = 0.91893853320467274f;
+        float lp = 0.f, d[4][4] = {}, sig2[4][4] = {};
 #pragma unroll
-      for (int o = 0; o < (WT < 4 ? WT : 4); ++o) {
-        if (o < P.net.act_tiles) {
+        for (int o = 0; o < (WT < 4 ? WT : 4); ++o) {
+          const int a0 = 16 * o + 4 * q;
+          if (o < P.net.act_tiles && a0 < P.net.act_dim) {
+            const mlp_f4 log_std = mlp_load4(packed + P.net.log_std_off + a0);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const bool on = 16 * o + 4 * q + i < P.net.act_dim;
-            const float dmu = on ? g_lp * d[o][i] / sig2[o][i] : 0.f;
-            cur[o][i] = dmu;
-            my[S.ls_off + (16 * o + 4 * q + i) * 16 + r] = on ? g_lp * (d[o][i] * d[o][i] / sig2[o][i] - 1.f) : 0.f;
+            for (int i = 0; i < 4; ++i) {
+              const int a = a0 + i;
+              if (a < P.net.act_dim) {
+                const float sigma = expf(log_std[i]);
+                const float dd = P.actions[(size_t)sample * P.net.act_dim + a] - head[o][i];
+                d[o][i] = dd, sig2[o][i] = sigma * sigma;
+                lp += -(dd * dd) / (2.f * sigma * sigma) - log_std[i] - HALF_LOG_2PI;
+              }
+            }
+          }
+        }
+        lp += __shfl_xor(lp, 16);
+        lp += __shfl_xor(lp, 32);
+        // clipped surrogate: d loss / d log_prob (torch.minimum splits a tie half / half; clamp passes at its bounds)
+        const double* as = P.adv_stats;
+        const float adv = (float)(((double)P.advantages[sample] - as[0]) / as[1]);
+        const float log_ratio = lp - P.old_log_prob[sample];
+        const float ratio = expf(log_ratio);
+        const float a1 = adv * ratio, a2 = adv * fminf(fmaxf(ratio, K.lo), K.hi);
+        const float w1 = a1 < a2 ? 1.f : a1 == a2 ? 0.5f : 0.f, w2 = 1.f - w1;
+        const float pass = ratio >= K.lo && ratio <= K.hi ? 1.f : 0.f;
+        const float g_lp = valid ? -inv_b * (w1 * adv + w2 * adv * pass) * ratio : 0.f;
+        if (valid && q == 0) {
+          st[0] += (double)fminf(a1, a2);
+          st[2] += (double)((ratio - 1.f) - log_ratio);
+          st[3] += fabsf(ratio - 1.f) > K.range ? 1.0 : 0.0;
+        }
+        // head dZ = d loss / d mean, and the per-sample log_std terms, into the stage
+#pragma unroll
+        for (int o = 0; o < (WT < 4 ? WT : 4); ++o) {
+          if (o < P.net.act_tiles) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const bool on = 16 * o + 4 * q + i < P.net.act_dim;
+              const float dmu = on ? g_lp * d[o][i] / sig2[o][i] : 0.f;
+              cur[o][i] = dmu;
+              my[S.ls_off + (16 * o + 4 * q + i) * 16 + r] = on ? g_lp * (d[o][i] * d[o][i] / sig2[o][i] - 1.f) : 0.f;
+            }
           }
         }
       }
@@ -476,7 +498,7 @@ __device__ __forceinline__ void ppo_tower(const PpoDev& P, const PpoClip& K, flo
   }
   __syncthreads();
   ppo_dw_mfma(P, stage, T.hidden[0], true, 0, S.h_off[0], part, first, wave, lane);
-  if constexpr (ACTOR) ppo_row_sums(P, stage, S.ls_off, 16 * P.net.act_tiles, P.net.log_std_off - P.train_off, part, first, tid);
+  if constexpr (ACTOR && !BC) ppo_row_sums(P, stage, S.ls_off, 16 * P.net.act_tiles, P.net.log_std_off - P.train_off, part, first, tid);
 }
 
 // The x rows of the wave's tile from `src` [total][dim]: element k of the sample, normalised as act() does (statistics at
@@ -502,7 +524,9 @@ __device__ __forceinline__ void ppo_stage_x(const PpoDev& P, float* my, const fl
   }
 }
 
-template <int W, int ACT>
+// BC (distill.hpp): the actor tower alone under the behaviour-cloning head; the partials then span the actor's words
+// (train_off = the actor's first weight word), so no log_std word and no critic word is written or folded.
+template <int W, int ACT, bool BC = false>
 __global__ __launch_bounds__(256) void ppo_grad_kernel(const PpoDev P) {
   extern __shared__ float stage[];
   __shared__ double red[4][PPO_STATS];
@@ -526,7 +550,8 @@ __global__ __launch_bounds__(256) void ppo_grad_kernel(const PpoDev P) {
     const int sample = P.perm[(int64_t)P.mb_start + (valid ? j : 0)];
     __syncthreads();  // (the previous chunk's critic is done reading x)
     ppo_stage_x<WT>(P, my, P.obs, P.net.obs_dim, P.net.mean_off, P.net.std_off, sample, q, r);
-    ppo_tower<WT, ACT, true>(P, K, stage, sample, valid, part, first, st, wave, lane);
+    ppo_tower<WT, ACT, true, BC>(P, K, stage, sample, valid, part, first, st, wave, lane);
+    if constexpr (BC) continue;
     if (P.asym) {
       __syncthreads();  // (every wave is done reading the actor's x: its first-layer dW reads every wave's rows)
       ppo_stage_x<WT>(P, my, P.critic_obs, P.net.critic_obs_dim, P.net.critic_mean_off, P.net.critic_std_off, sample, q, r);

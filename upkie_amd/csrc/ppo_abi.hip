@@ -1,6 +1,8 @@
 // ppo_abi.hip -- the PPO update of include/upkie_hip.h (one rank, data-parallel and controlled forms): host code around
-// the kernels of ppo.hpp. Handle-free like trainer_abi.hip, and a unit of its own because its ten gradient-kernel
-// instantiations take as long to compile as everything else outside the step kernels.
+// the kernels of ppo.hpp, and the distillation update (distill.hpp), whose launches are ppo.hpp's kernels under another head
+// and so live in the unit that defines them. Handle-free like trainer_abi.hip, and a unit of its own because its gradient-
+// kernel instantiations (ten of PPO, ten of the behaviour-cloning head) take as long to compile as everything else outside
+// the step kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,6 +11,7 @@
 #include <cstdint>
 #include <string>
 
+#include "distill.hpp"
 #include "mlp_instances.hpp"
 #include "ppo.hpp"
 
@@ -346,5 +349,76 @@ extern "C" int upkie_ppo_advantage_finish(int32_t total, int32_t batch_size, int
   const int M = (int)((total + (int64_t)batch_size - 1) / batch_size);
   hipLaunchKernelGGL(upkie::ppo_adv_finish_kernel, dim3((unsigned)((M + upkie::PPO_THREADS - 1) / upkie::PPO_THREADS)), dim3(upkie::PPO_THREADS), 0,
                      (hipStream_t)stream, total, batch_size, M, normalize ? 1 : 0, slots, world, adv_stats);
+  return launch_status();
+}
+
+// ---- the distillation update (include/upkie_hip.h; distill.hpp)
+static int check_distill_shape(const UpkieMlpShape* shape, upkie::PpoPlan* plan) {
+  if (!shape) return fail(UPKIE_ERR_INVALID_ARGUMENT, "null shape");
+  if (upkie::mlp_layout(*shape, nullptr) < 0) return (int)upkie_mlp_packed_words(shape);  // (sets the message)
+  if (!upkie::distill_plan(*shape, plan))
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "distillation needs a student with a critic (critic_layers > 0), as PPO does");
+  return UPKIE_OK;
+}
+
+extern "C" int64_t upkie_distill_workspace_bytes(const UpkieMlpShape* shape, int32_t max_minibatch) {
+  upkie::PpoPlan plan;
+  if (check_distill_shape(shape, &plan)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (max_minibatch < 1) return fail(UPKIE_ERR_INVALID_ARGUMENT, "max_minibatch must be positive");
+  return upkie::ppo_workspace_bytes(plan, upkie::ppo_grid(plan, max_minibatch));
+}
+
+extern "C" int upkie_distill_minibatch_update(const UpkieMlpShape* shape, int32_t total, int32_t minibatch_start, int32_t minibatch_size,
+                                              int32_t max_minibatch, const int32_t* perm, const float* obs, const float* labels, float* packed,
+                                              float* adam_m, float* adam_v, double* adam_scalars, double max_grad_norm, double adam_beta1,
+                                              double adam_beta2, double adam_eps, int32_t obs_normalized, void* workspace, float* stats,
+                                              void* stream) {
+  upkie::PpoPlan plan;
+  if (check_distill_shape(shape, &plan)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!(max_grad_norm > 0.0) || !(adam_eps > 0.0) || !(adam_beta1 >= 0.0 && adam_beta1 < 1.0) || !(adam_beta2 >= 0.0 && adam_beta2 < 1.0))
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "max_grad_norm and adam_eps must be positive, adam betas in [0, 1)");
+  if (total < 1 || minibatch_size < 1 || max_minibatch < 1 || minibatch_start < 0 || minibatch_size > max_minibatch ||
+      (int64_t)minibatch_start + minibatch_size > total)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT,
+                "minibatch out of range: 0 <= minibatch_start, 1 <= minibatch_size <= max_minibatch, start + size <= total");
+  if ((int64_t)total * (shape->obs_dim > shape->act_dim ? shape->obs_dim : shape->act_dim) > INT_MAX)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "total * obs_dim (or act_dim) must stay below 2^31");
+  if (!perm || !obs || !labels || !packed || !adam_m || !adam_v || !adam_scalars || !workspace || !stats)
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  if ((uintptr_t)adam_scalars % 8 != 0) return fail(UPKIE_ERR_INVALID_ARGUMENT, "adam_scalars must be 8-byte aligned");
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  upkie::PpoDev P{};
+  upkie::mlp_layout(*shape, &P.net);
+  P.stage[0] = plan.stage[0], P.stage[1] = plan.stage[1];
+  P.train_off = plan.train_off, P.train_words = plan.train_words;  // (the actor's span: distill.hpp)
+  P.nw = plan.nw, P.tile_floats = plan.tile_floats, P.fold_blocks = plan.fold_blocks;
+  P.part_stride = plan.train_words, P.stat_stride = upkie::PPO_STATS;
+  P.mb_start = minibatch_start, P.mb_size = minibatch_size, P.count = minibatch_size;
+  P.grid = upkie::ppo_grid(plan, minibatch_size);
+  P.obs_normalized = obs_normalized ? 1 : 0;
+  P.max_grad_norm = (float)max_grad_norm, P.beta1 = (float)adam_beta1, P.beta2 = (float)adam_beta2, P.adam_eps = (float)adam_eps;
+  P.perm = perm, P.obs = obs, P.actions = labels;  // (the behaviour-cloning head reads the labels where PPO's reads the actions)
+  P.packed = packed, P.m = adam_m, P.v = adam_v, P.scalars = adam_scalars, P.ctrl = nullptr, P.stats = stats;
+  const int ws_grid = upkie::ppo_grid(plan, max_minibatch);  // (the workspace's layout)
+  char* ws = (char*)workspace;
+  P.ticket = (unsigned*)ws;
+  P.header = (float*)ws;
+  P.partials = (float*)(ws + upkie::PPO_HEADER_BYTES);
+  P.stat_partials = (double*)(ws + upkie::ppo_stat_partials_at(plan, ws_grid));
+  P.grad = (float*)(ws + upkie::ppo_grad_at(plan, ws_grid));
+  P.sq_partials = (double*)(ws + upkie::ppo_sq_at(plan, ws_grid));
+  const hipStream_t s = (hipStream_t)stream;
+  const int status = for_mlp_instance(*shape, [&](auto w, auto act) {
+    auto kernel = upkie::ppo_grad_kernel<w(), act(), true>;
+    if (plan.lds_bytes > upkie::PPO_LDS_BUDGET) {  // (as ppo_abi.hip raises it: once per instantiation, to what any valid shape can need)
+      static const hipError_t raised = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, upkie::PPO_LDS_MAX);
+      if (raised != hipSuccess) return launch_status(raised);
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)P.grid), dim3(64 * P.nw), (size_t)plan.lds_bytes, s, P);
+    return launch_status();
+  });
+  if (status != UPKIE_OK) return status;
+  hipLaunchKernelGGL(upkie::distill_fold_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
+  hipLaunchKernelGGL(upkie::ppo_adam_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
   return launch_status();
 }

@@ -28,10 +28,11 @@ __host__ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1,
 // rounds takes its tag from this one list. 0-3 are the simulator's (reset states, torque noise, per-episode inertias,
 // pushes), under the sim's seed; the MLP policy's samples and the agent pipeline's noise count (env, call, 0) under their own;
 // 6 is the episode events' schedule (env, call), under the sim's seed too (episode_events.hpp, which also redraws 2 per episode);
-// 7 the task targets' (env, call), under the sim's seed: block 0 the schedule, blocks 1 and 2 the values (task_targets.hpp).
+// 7 the task targets' (env, call), under the sim's seed: block 0 the schedule, blocks 1 and 2 the values (task_targets.hpp);
+// 8 the distillation mix's (env, call), under the sim's seed: who drives the env this step (distill_mix.hpp).
 enum {
   STREAM_RESET = 0, STREAM_NOISE = 1, STREAM_INERTIA = 2, STREAM_PUSH = 3, STREAM_POLICY = 4, STREAM_PIPELINE = 5, STREAM_EVENTS = 6,
-  STREAM_TARGETS = 7
+  STREAM_TARGETS = 7, STREAM_DISTILL = 8
 };
 
 template <class ConfigT>

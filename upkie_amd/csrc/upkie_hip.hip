@@ -19,6 +19,7 @@
 #include "host_setup.hpp"
 #include "episode_events.hpp"
 #include "task_targets.hpp"
+#include "distill_mix.hpp"
 #include "abi_host.hpp"
 
 namespace upkie {
@@ -614,6 +615,17 @@ extern "C" int upkie_sim_task_targets_curriculum(UpkieSim* sim, int32_t num_targ
   hipLaunchKernelGGL(task_targets_curriculum_kernel, dim3((unsigned)curriculum_blocks(N)), dim3(CURRICULUM_THREADS), 0, (hipStream_t)stream, N, P,
                      score, finished, seen, limits, (double*)((char*)workspace + 8), (unsigned*)workspace);
   return check_hip(sim, hipGetLastError(), "task_targets_curriculum_kernel");
+}
+
+// The distillation mix (include/upkie_hip.h): every refusal comes before any device use.
+extern "C" int upkie_sim_distill_mix(UpkieSim* sim, int32_t act_dim, const uint32_t* threshold, const float* label, const float* student_action,
+                                     const float* low, const float* high, uint32_t* calls, float* applied, uint8_t* drove, void* stream) {
+  if (!(act_dim >= 1 && act_dim <= 64)) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "act_dim must be in 1-64");
+  if (!sim || !threshold || !label || !student_action || !low || !high || !calls || !applied || !drove)
+    return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  hipLaunchKernelGGL(distill_mix_kernel, grid_for(sim->config.num_envs), dim3(block_lanes()), 0, (hipStream_t)stream, sim->config, (int)act_dim,
+                     (const unsigned*)threshold, label, student_action, low, high, (unsigned*)calls, applied, drove);
+  return check_hip(sim, hipGetLastError(), "distill_mix_kernel");
 }
 
 // What the choice of a step kernel (step_dispatch.hpp) reads from the handle, for an entry point that launches `mode`.

@@ -1,0 +1,547 @@
+"""Policy distillation on the device: fit a student `MlpActorCritic`'s actor to a teacher's actions, supervised.
+
+`DistillTrainer` is the update: ``n_epochs`` epochs of minibatches of a behaviour-cloning loss -- torch's ``mse_loss`` of
+the student's unclamped Gaussian mean against the teacher's label -- its gradient through the actor tower,
+``clip_grad_norm_`` and Adam, three HIP launches per minibatch (csrc/distill.hpp: the PPO gradient kernel under another
+head) on the packed weight buffer the rollout kernel reads. `Distillation` is the driver, shaped like `upkie_amd.ppo.Ppo`:
+it rolls the STUDENT out (behind its `AgentPipeline`, under `EpisodeEvents` and `TaskTargets`), labels every visited
+state with the teacher, lets the teacher drive an env with probability ``beta`` (the DAgger mix, one launch per step:
+``upkie_sim_distill_mix``) and updates the student on the rollout. include/upkie_hip.h states the arithmetic.
+
+Not here: a negative-log-likelihood loss (it would train ``log_std``), students without a
+critic, distillation across ranks, recurrent students, per-sample weights, a replay of older iterations' data (DAgger's
+aggregated dataset), and the mix fused into the policy launch."""
+
+import ctypes as C
+import math
+from typing import Callable, Optional
+
+import torch
+
+from . import abi, lib
+from .agent_step import AgentStep
+from .exceptions import UpkieRuntimeError
+from .launch import check, device_tensor, launcher, ptr
+from .ppo import PackedTrainerState, Schedule, _at
+
+STAT_NAMES = abi.DISTILL_STAT_NAMES
+
+
+def beta_threshold(beta: float) -> int:
+    """The mix's device word for a probability ``beta`` that the teacher drives: ``llround(beta * 2**24)`` (0: never,
+    2**24: always)."""
+    beta = float(beta)
+    if not 0.0 <= beta <= 1.0:
+        raise ValueError(f"beta must be in [0, 1], got {beta}")
+    return int(math.floor(beta * 16777216.0 + 0.5))
+
+
+class DistillTrainer(PackedTrainerState):
+    """``train(observations, labels)`` runs ``n_epochs`` epochs of minibatches of ``batch_size`` samples over ``total``
+    rows (``observations`` ``[..., D]``, ``labels`` ``[..., A]``, contiguous float32 device tensors with the same leading
+    sizes): per epoch one ``randperm`` (a device ``torch.Generator`` seeded with ``seed``), per minibatch the gradient of
+    ``mse_loss(student mean, label)`` through the ACTOR tower, ``clip_grad_norm_`` and Adam (betas 0.9 / 0.999,
+    ``adam_eps`` 1e-5 as `PpoTrainer`'s). ``log_std``, the critic and the fixed words get no gradient: the launches range
+    over the actor's packed words alone, so those words, and their ``m`` and ``v``, are never written. It returns the
+    device tensor ``[n_epochs, n_minibatches, 3]`` of `STAT_NAMES` (loss, gradient norm before the clip, clip
+    coefficient).
+
+    As `PpoTrainer`: ``train`` is ``prepare`` (outside any capture: sizes the buffers, draws the permutations) then
+    ``update`` (capturable, allocation-free, bit-for-bit deterministic, its arguments constant across iterations). The
+    learning rate and Adam's step count are device words (`scalars`): `set_lr` moves a captured update's rate without a
+    re-capture. A trainer serves ONE pair of tensors. ``obs_normalized``: the rows are already normalised (a rollout's
+    ``norm_obs``); otherwise the launch normalises them with the packed statistics as ``act()`` does, which a student
+    with a live `RunningNormalizer` refuses. An asymmetric student is taken as it is: its critic's rows are not needed.
+    A student without a critic and a ``process_group`` are refused."""
+
+    def __init__(self, student, lr: float = 1e-3, n_epochs: int = 5, batch_size: int = 256, max_grad_norm: float = 1.0,
+                 obs_normalized: bool = False, seed: int = 0, process_group=None, adam_eps: float = 1e-5):
+        from .policies import MlpActorCritic
+
+        if not isinstance(student, MlpActorCritic):
+            raise TypeError("DistillTrainer trains an MlpActorCritic")
+        if int(student.shape.critic_layers) < 1:
+            raise ValueError("distillation needs a student with a critic: the policy has none (students without a critic are not supported)")
+        if process_group is not None:
+            raise ValueError("distillation with a process_group is not supported: the update is one rank's (distillation across ranks is out "
+                             "of scope)")
+        if int(n_epochs) < 1 or int(batch_size) < 1:
+            raise ValueError("n_epochs and batch_size must be positive")
+        if not float(max_grad_norm) > 0.0 or not (float(lr) >= 0.0 and math.isfinite(float(lr))):
+            raise ValueError("max_grad_norm must be positive, lr finite and not negative")
+        self.policy = student
+        self.device = student.device
+        self.n_epochs, self.batch_size, self.max_grad_norm = int(n_epochs), int(batch_size), float(max_grad_norm)
+        self.obs_normalized = bool(obs_normalized)
+        self.betas, self.eps = (0.9, 0.999), float(adam_eps)
+        self._lib = lib.load()
+        lib.require(self._lib, "upkie_distill_minibatch_update")
+        self._launcher = launcher(self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        words = student.packed.numel()
+        self.m = torch.zeros(words, **f32)
+        self.v = torch.zeros(words, **f32)
+        self.scalars = torch.zeros(2, dtype=torch.float64, device=self.device)  # lr, t: where a PPO control block has them
+        self.scalars[0] = float(lr)
+        self._lr = float(lr)
+        self.generator = torch.Generator(device=self.device)
+        self.generator.manual_seed(int(seed))
+        self._sizes = [t.numel() for t in student.sources()]
+        self._flat = torch.zeros(sum(self._sizes) + 1, **f32)
+        self._total = self._data = None
+
+    def _check(self, observations, labels) -> int:
+        D, A = int(self.policy.shape.obs_dim), int(self.policy.shape.act_dim)
+        for name, t in (("observations", observations), ("labels", labels)):
+            if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype is not torch.float32 or not t.is_contiguous() or t.dim() < 2:
+                raise ValueError(f"{name} must be a contiguous float32 [..., words] tensor on {self.device}")
+        if observations.shape[-1] != D:
+            raise ValueError(f"observations hold {observations.shape[-1]} words per sample, the student reads {D}")
+        if labels.shape[-1] != A or tuple(labels.shape[:-1]) != tuple(observations.shape[:-1]):
+            raise ValueError(f"labels must be {list(observations.shape[:-1]) + [A]} (one row of the student's {A} actions per observation), "
+                             f"got {list(labels.shape)}")
+        if not self.obs_normalized and getattr(self.policy, "_normalizer", None) is not None:
+            raise UpkieRuntimeError("the student reads a live RunningNormalizer: its statistics moved during the rollout, so train on the "
+                                    "normalised observations the rollout stored (norm_obs) with obs_normalized=True")
+        return observations.numel() // D
+
+    def _allocate(self, total: int) -> None:
+        if self._total == total:
+            return
+        if self._total is not None:
+            raise ValueError(f"this trainer serves datasets of {self._total} samples (its buffers are sized by the first prepare()); build "
+                             f"another for {total}")
+        mb = min(self.batch_size, total)
+        self.n_minibatches = (total + mb - 1) // mb
+        nbytes = int(self._lib.upkie_distill_workspace_bytes(C.byref(self.policy.shape), mb))
+        check(nbytes)
+        self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self.perm = torch.empty((self.n_epochs, total), dtype=torch.int32, device=self.device)
+        self.stats = torch.zeros((self.n_epochs, self.n_minibatches, abi.DISTILL_STATS), dtype=torch.float32, device=self.device)
+        self._mb, self._total = mb, total
+
+    def prepare(self, observations: torch.Tensor, labels: torch.Tensor) -> None:
+        """Outside any capture: size the buffers (first call), bind the two tensors and draw this iteration's
+        permutations (`shuffle`)."""
+        self._allocate(self._check(observations, labels))
+        addresses = (observations.data_ptr(), labels.data_ptr())
+        if self._data is None:
+            self._data = addresses
+        elif addresses != self._data:
+            raise ValueError("this trainer serves one pair of tensors (a captured update reads them): build another trainer")
+        self.shuffle()
+
+    def shuffle(self) -> None:
+        """One ``randperm`` per epoch into the persistent index buffer (outside any capture)."""
+        if self._total is None:
+            raise UpkieRuntimeError("call prepare(observations, labels) first (it sizes the buffers)")
+        for e in range(self.n_epochs):
+            self.perm[e].copy_(torch.randperm(self._total, generator=self.generator, device=self.device))
+
+    def update(self, observations: torch.Tensor, labels: torch.Tensor, sync: bool = True) -> torch.Tensor:
+        """Every epoch and minibatch on the current permutations (no randperm, no allocation, no host synchronisation:
+        capturable), then `sync_modules` when ``sync``."""
+        total = self._check(observations, labels)
+        if self._data is None:
+            raise UpkieRuntimeError("call prepare(observations, labels) first: it sizes the buffers and draws the permutations")
+        if (observations.data_ptr(), labels.data_ptr()) != self._data or total != self._total:
+            raise ValueError("this trainer serves one pair of tensors (a captured update reads them): build another trainer")
+        fn, launch, mb, shape = self._lib.upkie_distill_minibatch_update, self._launcher, self._mb, C.byref(self.policy.shape)
+        tail = (ptr(self.policy.packed), ptr(self.m), ptr(self.v), ptr(self.scalars), self.max_grad_norm, self.betas[0], self.betas[1], self.eps,
+                int(self.obs_normalized), ptr(self.workspace))
+        with torch.cuda.device(self.device):
+            for e in range(self.n_epochs):
+                for j in range(self.n_minibatches):
+                    start = j * mb
+                    launch(fn, shape, total, start, min(mb, total - start), mb, ptr(self.perm[e]), ptr(observations), ptr(labels), *tail,
+                           ptr(self.stats[e, j]))
+        if sync:
+            self.sync_modules()
+        return self.stats
+
+    def train(self, observations: torch.Tensor, labels: torch.Tensor, sync: bool = True) -> torch.Tensor:
+        """`prepare` then `update`. Returns ``[n_epochs, n_minibatches, 3]`` (`STAT_NAMES`), on the device."""
+        self.prepare(observations, labels)
+        return self.update(observations, labels, sync)
+
+    def set_lr(self, lr: float) -> None:
+        """Write the learning rate (a device word: a captured update reads the new value)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise UpkieRuntimeError("set the learning rate outside a graph capture (a captured write would replay its old value)")
+        self.scalars[0].fill_(float(lr))
+        self._lr = float(lr)
+
+    def log(self) -> dict:
+        """The record of the last update with ONE device-to-host copy: `STAT_NAMES` averaged over its minibatches,
+        ``learning_rate`` and ``n_updates`` (Adam's step count)."""
+        if self._total is None:
+            raise UpkieRuntimeError("call train(observations, labels) first")
+        host = torch.cat([self.stats.reshape(-1).double(), self.scalars]).cpu().numpy()  # the one copy
+        rows = host[:-2].reshape(-1, abi.DISTILL_STATS)
+        record = {name: float(rows[:, k].mean()) for k, name in enumerate(STAT_NAMES)}
+        record.update(learning_rate=float(host[-2]), n_updates=int(host[-1]))
+        return record
+
+    # ---- state
+    def state_tensors(self) -> dict:
+        """Adam's moments and the (lr, t) words (what `Distillation.save` carries)."""
+        return {"m": self.m, "v": self.v, "scalars": self.scalars}
+
+    def state_dict(self) -> dict:
+        """Adam's state: ``m`` and ``v`` as lists in ``policy.sources()`` order of the trainable tensors (log_std, then
+        weight and bias per layer of the actor and of the critic; zero outside the actor), the step count ``t`` and
+        ``lr``."""
+        lr, t = self.scalars.cpu().tolist()
+        return {"m": self._unpack(self.m), "v": self._unpack(self.v), "t": int(t), "lr": float(lr)}
+
+    def load_state_dict(self, sd: dict) -> None:
+        self._pack(sd["m"], self.m)
+        self._pack(sd["v"], self.v)
+        self.scalars.copy_(torch.tensor([float(sd["lr"]), float(sd["t"])], dtype=torch.float64))
+        self._lr = float(sd["lr"])
+
+
+class DaggerMix:
+    """The DAgger mix of a rollout step on the envs of a simulation handle (``sim``: a `upkie_amd.sim.BatchedSim`, e.g.
+    ``env.sim``), one launch (``upkie_sim_distill_mix``): per env one Philox block keyed (global env id, ``calls[n]``, a
+    stream tag of its own) under the sim's seed, then ``calls[n] += 1``; the teacher drives the env when the block's first
+    word, shifted right by 8, is below `threshold`; ``applied[n]`` is the driver's row (the ``label`` or the
+    ``student_action``) clamped to ``[action_low, action_high]``, ``drove[n]`` a byte. Selection and clamp only, so exact;
+    keyed by global env ids, so independent of the batch and of the sharding.
+
+    `threshold` is ONE device word, ``llround(beta * 2**24)``: `set_beta` rewrites it with a device copy and a captured
+    rollout follows it at its next replay. All state is allocated at construction; `step` allocates nothing."""
+
+    def __init__(self, sim, act_dim: int, action_low, action_high, beta: float = 0.0):
+        self.sim, self.num_envs, self.act_dim = sim, int(sim.num_envs), int(act_dim)
+        self.device = torch.device(sim.device)
+        if self.device.type != "cuda":
+            raise UpkieRuntimeError("DaggerMix runs on the HIP device only (there is no CPU fallback)")
+        self._lib = lib.load()
+        lib.require(self._lib, "upkie_sim_distill_mix")
+        N, A, dev = self.num_envs, self.act_dim, self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.low = torch.as_tensor(action_low, dtype=torch.float32).reshape(-1).to(dev).contiguous()
+        self.high = torch.as_tensor(action_high, dtype=torch.float32).reshape(-1).to(dev).contiguous()
+        if self.low.numel() != A or self.high.numel() != A:
+            raise ValueError(f"action_low and action_high need {A} values each")
+        self.calls = torch.zeros(N, dtype=torch.int32, device=dev)  # (uint32 words)
+        self.threshold = torch.zeros(1, dtype=torch.int32, device=dev)  # (one uint32 word, <= 2^24)
+        self.applied = torch.zeros((N, A), **f32)
+        self.drove = torch.zeros(N, dtype=torch.uint8, device=dev)
+        self.beta = 0.0
+        self.set_beta(beta)
+
+    def set_beta(self, beta: float) -> None:
+        """Write the probability that the teacher drives. Outside a graph capture (a captured write would replay its old
+        value)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise UpkieRuntimeError("set beta outside a graph capture (a captured write would replay its old value)")
+        self.threshold.fill_(beta_threshold(beta))
+        self.beta = float(beta)
+
+    def step(self, label: torch.Tensor, student_action: torch.Tensor, drove: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``label`` and ``student_action`` [N, A] float32; ``drove`` [N] uint8 to write instead of `drove`. Returns
+        `applied`."""
+        N, A, dev = self.num_envs, self.act_dim, self.device
+        label = device_tensor(label, "label", dev, (N, A))
+        student_action = device_tensor(student_action, "student_action", dev, (N, A))
+        drove = self.drove if drove is None else device_tensor(drove, "drove", dev, (N,), (torch.uint8,))
+        self.sim._launch(self._lib.upkie_sim_distill_mix, A, ptr(self.threshold), ptr(label), ptr(student_action), ptr(self.low), ptr(self.high),
+                         ptr(self.calls), ptr(self.applied), ptr(drove))
+        return self.applied
+
+    def reset(self) -> None:
+        """The draws start over (every env's call 0)."""
+        self.calls.zero_()
+
+    def state_tensors(self) -> dict:
+        """The counters and the threshold word (what `Distillation.save` carries under ``mix.``)."""
+        return {"calls": self.calls, "threshold": self.threshold}
+
+
+class LinearTeacher:
+    """A `upkie_amd.policies.LinearPolicy` as a teacher: ``teacher(obs, out)`` writes its action into ``out``."""
+
+    def __init__(self, policy):
+        self.policy, self.obs_dim, self.act_dim = policy, int(policy.obs_dim), int(policy.act_dim)
+
+    def __call__(self, obs: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        out.copy_(self.policy(obs))
+        return out
+
+
+class Distillation:
+    """``Distillation(env, student, teacher).learn(total_timesteps)``: rsl_rl's ``Distillation`` on the device.
+
+    ``teacher``: an `MlpActorCritic` (its own frozen packed statistics normalise its input; the label is its unclamped
+    Gaussian mean, by a launch that touches no call counter), a `LinearPolicy` (wrapped in a `LinearTeacher`), or any
+    callable ``teacher(obs, out)`` that writes ``[N, A]`` float32 on the device (give it ``obs_dim`` to have the width
+    checked). ``teacher_observation``: ``"raw"`` -- the teacher reads `AgentStep.raw_observation`, the env's D words (D + G
+    with ``targets``) -- or a `upkie_amd.privileged.PrivilegedObservation`, stepped where `Ppo` steps its critic's.
+
+    One rollout step: the student's observation (`AgentStep.observation`) and the teacher's row at the same instant;
+    ``student.act_actor`` (the normalised observation straight into ``observations[t]``; the sampled action, or the mean
+    with ``student_deterministic``; no critic); the teacher's label into ``labels[t]``; the mix launch (the env action and
+    ``drove[t]``: the teacher drives an env with probability ``beta``, a device word); `AgentStep.apply`; the privileged
+    row's step; ``episodes.step``; `AgentStep.observe`; ``normalizer.step`` (live statistics attached to the student, as
+    in `Ppo`). No bootstrap, no values, no GAE. With ``graph=True`` an iteration is two graph replays: ``n_steps`` rollout
+    steps through `GraphedLoop` (ONE real warm-up step first, not counted), then the update.
+
+    `learn` follows `Ppo.learn`: after each rollout ``progress_remaining`` sets the learning rate and ``beta`` through
+    their device words (floats or callables of ``progress_remaining``); every ``log_interval`` iterations a record
+    (``distill/loss``, ``distill/grad_norm``, ``distill/clip_coef``, ``distill/learning_rate``, ``distill/beta``,
+    ``distill/teacher_drove_frac``, ``rollout/ep_rew_mean``, ``rollout/ep_len_mean``, ``time/*``; one device-to-host copy)
+    is appended to ``records`` and handed to ``callback(model, record)``; `upkie_amd.evaluation.EvalCallback` works
+    unchanged (it reads ``model.policy``, the student). `save` / `load` resume bit for bit. ``Ppo(env, student, ...)`` on
+    a distilled student just works: the packed weights are the policy, and with ``normalize`` on both sides the `Ppo` run
+    goes on under the student's live normaliser (same env size, same ``gamma``: the discount of the normaliser's reward
+    statistics, all that ``gamma`` is here)."""
+
+    def __init__(self, env, student, teacher, teacher_observation="raw", n_steps: int = 24, n_epochs: int = 5, batch_size: int = 256,
+                 learning_rate: Schedule = 1e-3, max_grad_norm: float = 1.0, beta: Schedule = 0.0, student_deterministic: bool = False,
+                 normalize: bool = True, pipeline=None, reward=None, reward_fn: Optional[Callable] = None, events=None, targets=None,
+                 stats_window_size: int = 100, graph: bool = True, seed: int = 0, process_group=None, gamma: float = 0.99):
+        from .policies import LinearPolicy, MlpActorCritic
+
+        if int(n_steps) < 1:
+            raise ValueError("n_steps must be positive")
+        if process_group is not None:
+            raise ValueError("distillation with a process_group is not supported (distillation across ranks is out of scope)")
+        if isinstance(teacher, LinearPolicy):
+            teacher = LinearTeacher(teacher)
+        if not isinstance(teacher, MlpActorCritic) and not callable(teacher):
+            raise TypeError("teacher must be an MlpActorCritic, a LinearPolicy or a callable teacher(obs, out)")
+        self._agent = AgentStep(env, student, pipeline, reward, reward_fn, noun="distillation", events=events, targets=targets)
+        D, A = int(student.shape.obs_dim), int(student.shape.act_dim)
+        raw = int(pipeline.obs_dim) if pipeline is not None else D  # (what AgentStep.raw_observation holds per env)
+        privileged = None if isinstance(teacher_observation, str) else teacher_observation
+        if privileged is None and teacher_observation != "raw":
+            raise ValueError(f"teacher_observation must be 'raw' or a PrivilegedObservation, got {teacher_observation!r}")
+        if privileged is not None and int(privileged.num_envs) != int(env.num_envs):
+            raise ValueError(f"teacher_observation serves {int(privileged.num_envs)} envs, the env has {int(env.num_envs)}")
+        width = int(privileged.dim) if privileged is not None else raw
+        reads = int(teacher.shape.obs_dim) if isinstance(teacher, MlpActorCritic) else getattr(teacher, "obs_dim", None)
+        if reads is not None and int(reads) != width:
+            raise ValueError(f"teacher_observation has {width} words, the teacher's obs_dim is {int(reads)}")
+        acts = int(teacher.shape.act_dim) if isinstance(teacher, MlpActorCritic) else getattr(teacher, "act_dim", None)
+        if acts is not None and int(acts) != A:
+            raise ValueError(f"the teacher gives {int(acts)} actions, the student's act_dim is {A}")
+        self.env, self.policy, self.student, self.teacher, self.teacher_observation = env, student, student, teacher, privileged
+        self.pipeline, self.reward, self.reward_fn, self.events, self.targets = pipeline, reward, reward_fn, events, targets
+        self.n_envs, self.n_steps, self.seed = int(env.num_envs), int(n_steps), int(seed)
+        self.normalize, self.window, self.graph = bool(normalize), int(stats_window_size), bool(graph)
+        self.student_deterministic, self.gamma = bool(student_deterministic), float(gamma)
+        self._schedules = {"lr": learning_rate, "beta": beta}
+        self._beta = _at(beta, 1.0)
+        beta_threshold(self._beta)  # (refuses a value out of range now)
+        self.mix = None
+        self._trainer_args = dict(lr=_at(learning_rate, 1.0), n_epochs=n_epochs, batch_size=batch_size, max_grad_norm=max_grad_norm,
+                                  obs_normalized=self.normalize, seed=seed)
+        self.num_timesteps, self.iterations, self.total_timesteps, self.progress_remaining = 0, 0, 0, 1.0
+        self.records = []
+        self.trainer = self.normalizer = self.episodes = self.observations = None
+        self._loop = self._update_graph = None
+
+    # ---- the objects, built by the first learn() (or by load())
+    def _setup(self) -> None:
+        if self.observations is not None:
+            return
+        from .episodes import EpisodeStatistics
+        from .normalize import RunningNormalizer
+
+        env, pol, N, T = self.env, self.student, self.n_envs, self.n_steps
+        dev = self.device = torch.device(env.device)
+        D, A = int(pol.shape.obs_dim), int(pol.shape.act_dim)
+        self.mix = DaggerMix(env.sim, A, pol.action_low, pol.action_high, self._beta)
+        if self.normalize:
+            if self.pipeline is None and self.targets is None:
+                self.normalizer = RunningNormalizer.for_env(env, gamma=self.gamma)
+            else:
+                self.normalizer = RunningNormalizer(N, D, gamma=self.gamma, device=dev)
+            self.normalizer.attach(pol)
+        self.episodes = EpisodeStatistics(N, window=self.window, device=dev)
+        self.trainer = DistillTrainer(pol, **self._trainer_args)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.observations = torch.zeros((T, N, D), **f32)
+        self.labels = torch.zeros((T, N, A), **f32)
+        self.drove = torch.zeros((T, N), dtype=torch.uint8, device=dev)
+        self._action = torch.zeros((N, A), **f32)  # the student's raw action (the sample, or the mean)
+        self._norm_reward = torch.zeros(N, **f32)  # (the normaliser's outputs: nothing here reads them)
+        self._starts = torch.ones(N, dtype=torch.uint8, device=dev)
+        self._agent.reset(seed=self.seed)
+        if self.teacher_observation is not None:
+            self.teacher_observation.reset(self._agent.raw_observation)
+        if self.normalizer is not None:
+            self.normalizer.reset(self._agent.observation)
+        self._slot = self.n_steps - 1 if self.graph else 0  # (the capture's warm-up step takes the last slot)
+        if self.graph:
+            from .graphs import GraphedLoop
+
+            self._loop = GraphedLoop(self._rollout_step, unroll=T, warmup=1, device=dev)
+
+    def _label(self, rows: torch.Tensor, out: torch.Tensor) -> None:
+        from .policies import MlpActorCritic
+
+        if isinstance(self.teacher, MlpActorCritic):
+            self.teacher.mean(rows, out)
+        else:
+            self.teacher(rows, out)
+
+    def _rollout_step(self) -> None:
+        """One step of every env into slot ``_slot`` (the class docstring's order)."""
+        t, pol, agent, priv = self._slot, self.student, self._agent, self.teacher_observation
+        obs = agent.observation
+        rows = agent.raw_observation if priv is None else priv.observation
+        out = {"action": self._action}
+        if self.normalizer is not None:
+            out["norm_obs"] = self.observations[t]
+        else:
+            self.observations[t].copy_(obs)
+        pol.act_actor(obs, deterministic=self.student_deterministic, out=out)
+        self._label(rows, self.labels[t])
+        applied = self.mix.step(self.labels[t], self._action, self.drove[t])
+        raw_next, reward, terminated, truncated, final_obs, _ = agent.apply(applied)
+        if priv is not None:
+            priv.step(raw_next, terminated, truncated, final_obs=final_obs)
+        self.episodes.step(reward, terminated, truncated)
+        next_obs, _ = agent.observe()
+        if self.normalizer is not None:
+            self.normalizer.step(next_obs, reward, terminated, truncated, out={"reward": self._norm_reward, "episode_starts": self._starts})
+        self._slot = (t + 1) % self.n_steps
+
+    def collect_rollouts(self) -> None:
+        """``n_steps`` steps of every env into ``observations``, ``labels`` and ``drove``."""
+        if self._loop is not None:
+            self._loop.replay()
+        else:
+            for _ in range(self.n_steps):
+                self._rollout_step()
+        self.num_timesteps += self.n_steps * self.n_envs
+
+    def train(self) -> None:
+        """The update on the collected rollout: `DistillTrainer.prepare`, then `update` (a graph replay when ``graph``)."""
+        tr, obs, labels = self.trainer, self.observations, self.labels
+        tr.prepare(obs, labels)
+        if not self.graph:
+            tr.update(obs, labels)
+            return
+        if self._update_graph is None:
+            kept = (self.student.packed, tr.m, tr.v, tr.scalars, tr.stats)
+            state = [x.clone() for x in kept]
+            tr.update(obs, labels)  # (warm-up off the capture, undone below: the first replay is the first update)
+            torch.cuda.synchronize(self.device)
+            self._update_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._update_graph):
+                tr.update(obs, labels)
+            for dst, src in zip(kept, state):
+                dst.copy_(src)
+        self._update_graph.replay()
+
+    def set_progress(self, progress_remaining: float) -> None:
+        """Evaluate the callables among ``learning_rate`` and ``beta`` at ``progress_remaining`` and write their device
+        words (outside any capture); constants stay what they are."""
+        self.progress_remaining = float(progress_remaining)
+        if callable(self._schedules["lr"]):
+            self.trainer.set_lr(_at(self._schedules["lr"], self.progress_remaining))
+        if callable(self._schedules["beta"]):
+            self.set_beta(_at(self._schedules["beta"], self.progress_remaining))
+
+    def set_beta(self, beta: float) -> None:
+        """Write the probability that the teacher drives (a device word: a captured rollout reads the new value)."""
+        beta_threshold(beta)
+        self._beta = float(beta)
+        if self.mix is not None:
+            self.mix.set_beta(beta)
+
+    def log(self) -> dict:
+        """The ``distill/*`` record of the last iteration, one device-to-host copy."""
+        tr = self.trainer
+        drove = self.drove.double().mean().reshape(1)
+        host = torch.cat([tr.stats.reshape(-1).double(), tr.scalars, self.mix.threshold.double(), drove]).cpu().numpy()  # the one copy
+        rows = host[:-4].reshape(-1, abi.DISTILL_STATS)
+        record = {f"distill/{name}": float(rows[:, k].mean()) for k, name in enumerate(STAT_NAMES)}
+        record.update({"distill/learning_rate": float(host[-4]), "distill/n_updates": int(host[-3]), "distill/beta": float(host[-2]) / 16777216.0,
+                       "distill/teacher_drove_frac": float(host[-1])})
+        return record
+
+    def learn(self, total_timesteps: int, callback: Optional[Callable] = None, log_interval: int = 1, reset_num_timesteps: bool = True):
+        """Distil for ``total_timesteps`` env steps (whole iterations of ``n_steps * n_envs``). With
+        ``reset_num_timesteps=False`` it continues: ``total_timesteps`` more. Returns self."""
+        self._setup()
+        if reset_num_timesteps:
+            self.num_timesteps, self.iterations = 0, 0
+            self.total_timesteps = int(total_timesteps)
+        else:
+            self.total_timesteps = int(total_timesteps) + self.num_timesteps
+        while self.num_timesteps < self.total_timesteps:
+            self.collect_rollouts()
+            self.iterations += 1
+            beta_ran = self._beta  # (what this rollout ran under: the record's distill/beta)
+            self.set_progress(1.0 - float(self.num_timesteps) / float(self.total_timesteps))  # (this update's lr, the next rollout's beta)
+            self.train()
+            record = None
+            if log_interval and self.iterations % int(log_interval) == 0:
+                record = self.log()
+                record.update({"distill/beta": beta_ran, "rollout/ep_rew_mean": self.episodes.ep_rew_mean(),
+                               "rollout/ep_len_mean": self.episodes.ep_len_mean(), "time/total_timesteps": self.num_timesteps,
+                               "time/iterations": self.iterations})
+                self.records.append(record)
+            if callback is not None and callback(self, record) is False:
+                break
+        return self
+
+    # ---- saving and loading
+    def _env_tensors(self):
+        named = dict(self.env.state_tensors())
+        named.setdefault("observation", self._agent.raw_observation)
+        return {k: v for k, v in named.items() if isinstance(v, torch.Tensor)}
+
+    _STAGES = {"policy": "", "trainer": "", "episodes": "episodes.", "pipeline": "pipeline.", "reward": "reward.", "events": "events.",
+               "teacher_observation": "teacher_observation.", "targets": "targets.", "mix": "mix."}
+
+    def _state_tensors(self):
+        named = {}
+        named.update({f"env.{k}": v for k, v in self._env_tensors().items()})
+        for stage, prefix in self._STAGES.items():
+            if getattr(self, stage) is not None:
+                named.update({prefix + k: v for k, v in getattr(self, stage).state_tensors().items()})
+        return {k: v for k, v in named.items() if v is not None}
+
+    def save(self, path) -> None:
+        """``torch.save`` of the training state (tensors and numbers only): the weights, Adam's state, the device words,
+        the mix counters, the normaliser, the episode statistics, every stage's state and the env."""
+        self._setup()
+        torch.cuda.synchronize(self.device)
+        sd = {"tensors": {k: v.cpu() for k, v in self._state_tensors().items()}, "generator": self.trainer.generator.get_state().cpu(),
+              "normalizer": self.normalizer.state_dict() if self.normalizer is not None else None,
+              "counters": {"num_timesteps": self.num_timesteps, "iterations": self.iterations, "total_timesteps": self.total_timesteps,
+                           "progress_remaining": self.progress_remaining, "policy_seed": int(self.student.seed), "beta": self._beta,
+                           "lr": self.trainer._lr},
+              "sizes": {"n_envs": self.n_envs, "n_steps": self.n_steps}}
+        torch.save(sd, path)
+
+    @classmethod
+    def load(cls, path, env, student, teacher, **kwargs):
+        """A `Distillation` on fresh ``env`` and ``student`` objects (same sizes, same keyword arguments as the saved one;
+        the teacher and the schedules are code: give them again) that continues the saved run:
+        ``learn(more, reset_num_timesteps=False)``."""
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        model = cls(env, student, teacher, **kwargs)
+        if sd["sizes"] != {"n_envs": model.n_envs, "n_steps": model.n_steps}:
+            raise ValueError(f"the file holds a run of {sd['sizes']}, this one is {model.n_envs} envs x {model.n_steps} steps")
+        model._setup()
+        student.reseed(sd["counters"]["policy_seed"])
+        student._buffers(model.n_envs)  # (the noise counters exist before they are restored)
+        for name, dst in model._state_tensors().items():
+            if name not in sd["tensors"]:
+                raise ValueError(f"the file has no {name}: it was saved from another kind of env, student or stage")
+            dst.copy_(sd["tensors"][name])
+        model.trainer.generator.set_state(sd["generator"])
+        if model.normalizer is not None:
+            model.normalizer.load_state_dict(sd["normalizer"])
+        c = sd["counters"]
+        model.num_timesteps, model.iterations, model.total_timesteps = c["num_timesteps"], c["iterations"], c["total_timesteps"]
+        model.progress_remaining, model._beta, model.trainer._lr = c["progress_remaining"], c["beta"], c["lr"]
+        model.trainer.sync_modules()
+        return model

@@ -45,6 +45,8 @@ SOURCES = [
     os.path.join(_CSRC, "policy_mlp.hpp"),
     os.path.join(_CSRC, "vecnorm.hpp"),
     os.path.join(_CSRC, "ppo.hpp"),
+    os.path.join(_CSRC, "distill.hpp"),
+    os.path.join(_CSRC, "distill_mix.hpp"),
     os.path.join(_CSRC, "time_limits.hpp"),
     os.path.join(_CSRC, "episode_append.hpp"),
     os.path.join(_CSRC, "episodes.hpp"),
@@ -73,6 +75,7 @@ def _abi_table():
     pipeline = [i32] * 5 + [f64, f64, vp, C.c_uint64]  # (the settings every pipeline launch begins with)
     controlled = "upkie_ppo_minibatch_update_controlled"
     asym = "upkie_mlp_actor_critic_asym"
+    distill = "upkie_distill_minibatch_update"
     return (
         ("upkie_hip_device_count", status, None, None),
         ("upkie_hip_struct_bytes", C.c_int64, [C.c_int], "upkie_hip_struct_bytes"),  # (see _check_struct_sizes)
@@ -185,6 +188,10 @@ def _abi_table():
         ("upkie_ppo_minibatch_update_asym", status, [shape_p, cfg_p] + [i32] * 4 + [vp] * 17, asym),
         ("upkie_ppo_minibatch_gradient_asym", status, [shape_p, cfg_p] + [i32] * 5 + [vp] * 14, asym),
         ("upkie_privileged_observation", status, [i32] * 4 + [vp] * 10 + [i32, vp, vp, vp], asym),
+        # policy distillation: the behaviour-cloning update and the DAgger mix
+        ("upkie_distill_workspace_bytes", C.c_int64, [shape_p, i32], distill),
+        ("upkie_distill_minibatch_update", status, [shape_p] + [i32] * 4 + [vp] * 7 + [f64] * 4 + [i32, vp, vp, vp], distill),
+        ("upkie_sim_distill_mix", status, [vp, i32] + [vp] * 9, distill),
     )
 
 

@@ -538,6 +538,34 @@ class MlpActorCritic:
                        None, None, None, out.data_ptr(), None, None)
         return out
 
+    def mean(self, obs: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """The Gaussian's mean, NOT clamped to the action bounds, of a batch of any size into the caller's ``out``
+        ``[N, act_dim]``, which is returned: a teacher's label (`upkie_amd.distill`). Like `mean_action` the launch is
+        handed no call counters and writes nothing but ``out``."""
+        obs = self._obs(obs)
+        out = self._check_out("mean", out, obs.shape[0])
+        if self.asymmetric:
+            self._launcher(self._lib.upkie_mlp_actor_critic_asym, obs.shape[0], C.byref(self.shape), self.packed.data_ptr(), obs.data_ptr(), None,
+                           None, self.seed, 1, None, None, out.data_ptr(), None, None, None, None)
+            return out
+        self._launcher(self._lib.upkie_mlp_actor_critic, obs.shape[0], C.byref(self.shape), self.packed.data_ptr(), obs.data_ptr(), None, self.seed, 1,
+                       None, out.data_ptr(), None, None, None, None)
+        return out
+
+    def act_actor(self, obs: torch.Tensor, deterministic: bool = False, out: Optional[dict] = None):
+        """`act` without the critic (no value output, so its wave returns at once, and an asymmetric policy needs no
+        ``critic_obs``): returns ``(env_action, action, log_prob)``. The noise counters advance as in `act`."""
+        obs = self._obs(obs)
+        n = obs.shape[0]
+        outs = dict(self._buffers(n))
+        del outs["n"], outs["value"]
+        for name, t in (out or {}).items():
+            if name == "value":
+                raise ValueError("act_actor does not run the critic: no value output")
+            outs[name] = self._check_out(name, t, n)
+        self._launch(obs, deterministic, outs, None)
+        return outs["env_action"], outs["action"], outs["log_prob"]
+
     def value(self, obs: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The critic alone (e.g. the bootstrap values of the observations after a rollout's last step). An asymmetric
         policy takes the critic's rows ``[N, Dc]``."""

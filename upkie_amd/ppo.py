@@ -34,7 +34,46 @@ def trainable_offset(shape) -> int:
     return 2 * ((int(shape.obs_dim) + 3) // 4 * 4) + 2 * at + 2 * ((int(getattr(shape, "critic_obs_dim", 0)) + 3) // 4 * 4)
 
 
-class PpoTrainer:
+class PackedTrainerState:
+    """What the trainers of an `MlpActorCritic`'s packed buffer share (`PpoTrainer`, `upkie_amd.distill.DistillTrainer`):
+    the write-back of the trained words into the tensors the policy was built from, and the conversion between the packed
+    layout of Adam's moments and lists in ``policy.sources()`` order. A subclass sets ``policy``, ``device``, ``_sizes``
+    (the element counts of ``policy.sources()``) and ``_flat`` (``sum(_sizes) + 1`` float32 words on the device)."""
+
+    def sync_modules(self) -> None:
+        """Write the packed weights back into the tensors the policy was built from (the modules' parameters, or the
+        tensors of `from_sb3_state_dict`): one scatter on the device, then a copy per tensor. The fixed sources
+        (observation statistics, action bounds) are not written."""
+        pol = self.policy
+        self._flat.index_copy_(0, pol._index, pol.packed)  # (padding words, all mapped to the last slot, are zero)
+        params = pol._params
+        trainable = [params[-1]] + params[:-1]  # sources() order after the fixed tensors
+        nf = getattr(pol, "n_fixed", 4)
+        start = sum(self._sizes[:nf])
+        with torch.no_grad():
+            for t, n in zip(trainable, self._sizes[nf:]):
+                t.detach().view(-1).copy_(self._flat[start:start + n])
+                start += n
+
+    def _unpack(self, packed: torch.Tensor):
+        flat = torch.zeros(sum(self._sizes) + 1, dtype=torch.float32, device=self.device)
+        flat.index_copy_(0, self.policy._index, packed)
+        return [t.clone() for t in torch.split(flat[:-1], self._sizes)[getattr(self.policy, "n_fixed", 4):]]
+
+    def _pack(self, tensors, into: torch.Tensor) -> None:
+        nf = getattr(self.policy, "n_fixed", 4)
+        if len(tensors) != len(self._sizes) - nf:
+            raise ValueError(f"need {len(self._sizes) - nf} tensors (log_std, then weight and bias per layer)")
+        flat = [torch.zeros(n, dtype=torch.float32, device=self.device) for n in self._sizes[:nf]]
+        for t, n in zip(tensors, self._sizes[nf:]):
+            t = torch.as_tensor(t, dtype=torch.float32).to(self.device).reshape(-1)
+            if t.numel() != n:
+                raise ValueError(f"a tensor of {t.numel()} values where {n} belong")
+            flat.append(t)
+        torch.index_select(torch.cat(flat + [torch.zeros(1, dtype=torch.float32, device=self.device)]), 0, self.policy._index, out=into)
+
+
+class PpoTrainer(PackedTrainerState):
     """``train(buffer)`` runs ``n_epochs`` epochs of minibatches of ``batch_size`` samples over a full `RolloutBuffer`
     (after ``compute_returns_and_advantage``): per epoch one ``randperm`` of the ``T N`` samples (a ``torch.Generator``
     on the device seeded with ``seed``), one launch for the advantage statistics of its minibatches, then per minibatch
@@ -463,21 +502,6 @@ class PpoTrainer:
             return int(ctrl[abi.PPO_CTRL_N_UPDATES])
         return int(ctrl[abi.PPO_CTRL_T]) // self.n_minibatches if self._total is not None else 0
 
-    def sync_modules(self) -> None:
-        """Write the packed weights back into the tensors the policy was built from (the modules' parameters, or the
-        tensors of `from_sb3_state_dict`): one scatter on the device, then a copy per tensor. The fixed sources
-        (observation statistics, action bounds) are not written."""
-        pol = self.policy
-        self._flat.index_copy_(0, pol._index, pol.packed)  # (padding words, all mapped to the last slot, are zero)
-        params = pol._params
-        trainable = [params[-1]] + params[:-1]  # sources() order after the fixed tensors
-        nf = getattr(pol, "n_fixed", 4)
-        start = sum(self._sizes[:nf])
-        with torch.no_grad():
-            for t, n in zip(trainable, self._sizes[nf:]):
-                t.detach().view(-1).copy_(self._flat[start:start + n])
-                start += n
-
     # ---- state
     def state_tensors(self) -> dict:
         """Adam's moments and the control block (what `Ppo.save` carries)."""
@@ -491,23 +515,6 @@ class PpoTrainer:
         """`host_state` of a saved run, and where its schedules stood (the control block itself is a tensor)."""
         self._clip_range, self._clip_range_vf, self._target_kl, self._lr = (state[k] for k in ("clip_range", "clip_range_vf", "target_kl", "lr"))
         self.progress_remaining = progress_remaining
-
-    def _unpack(self, packed: torch.Tensor):
-        flat = torch.zeros(sum(self._sizes) + 1, dtype=torch.float32, device=self.device)
-        flat.index_copy_(0, self.policy._index, packed)
-        return [t.clone() for t in torch.split(flat[:-1], self._sizes)[getattr(self.policy, "n_fixed", 4):]]
-
-    def _pack(self, tensors, into: torch.Tensor) -> None:
-        nf = getattr(self.policy, "n_fixed", 4)
-        if len(tensors) != len(self._sizes) - nf:
-            raise ValueError(f"need {len(self._sizes) - nf} tensors (log_std, then weight and bias per layer)")
-        flat = [torch.zeros(n, dtype=torch.float32, device=self.device) for n in self._sizes[:nf]]
-        for t, n in zip(tensors, self._sizes[nf:]):
-            t = torch.as_tensor(t, dtype=torch.float32).to(self.device).reshape(-1)
-            if t.numel() != n:
-                raise ValueError(f"a tensor of {t.numel()} values where {n} belong")
-            flat.append(t)
-        torch.index_select(torch.cat(flat + [torch.zeros(1, dtype=torch.float32, device=self.device)]), 0, self.policy._index, out=into)
 
     def state_dict(self) -> dict:
         """Adam's state: ``m`` and ``v`` as lists in ``policy.sources()`` order of the trainable tensors (log_std, then
@@ -570,7 +577,13 @@ class Ppo:
     ``obs_dim=D + G``. Without a pipeline the normaliser has D + G columns. With a `TargetCurriculum` one launch after
     every rollout widens the ranges from the named reward term's episode sums (it must be one of ``reward``'s; with a
     ``process_group`` it is refused); a record carries ``rollout/target_<name>_low`` and ``_high``. `save` / `load`
-    carry ``targets.*``, the ranges included. ``targets=None``: every launch and every bit as without."""
+    carry ``targets.*``, the ranges included. ``targets=None``: every launch and every bit as without.
+
+    A ``policy`` that arrives with a live `RunningNormalizer` and has been called (a student of
+    `upkie_amd.distill.Distillation`) keeps that normaliser: with ``normalize`` the run goes on under the statistics the
+    policy was fitted under, on an env of the same size and with the same ``gamma`` (another size or ``gamma`` is refused).
+    The hand-over is for symmetric training: with ``critic_observation=`` it is refused, because the critic's rows would need
+    a second normaliser and a policy that has been called cannot be attached to one."""
 
     def __init__(self, env, policy, n_steps: int = 128, gamma: float = 0.99, gae_lambda: float = 0.95, n_epochs: int = 10, batch_size: int = 64,
                  learning_rate: Schedule = 3e-4, clip_range: Schedule = 0.2, clip_range_vf: Optional[Schedule] = None,
@@ -631,11 +644,24 @@ class Ppo:
         D, A = int(pol.shape.obs_dim), int(pol.shape.act_dim)
         if self.normalize:
             kw = {} if self.process_group is None else {"process_group": self.process_group}
-            if self.pipeline is None and self.targets is None:
+            live = getattr(pol, "_normalizer", None)
+            if live is not None and pol._out and self.process_group is None:
+                # a policy handed over with its statistics (`upkie_amd.distill.Distillation` trained it under them; a policy
+                # that has been called cannot be attached to new ones): training goes on under the same normaliser
+                if self.critic_observation is not None:
+                    raise ValueError("a policy that arrives with a live normaliser is taken over for symmetric training only: its critic's "
+                                     "rows would need a second normaliser, and a policy that has been called cannot be attached to one "
+                                     "(build a fresh policy from the trained modules for critic_observation=)")
+                if int(live.num_envs) != N or float(live.gamma) != self.gamma:
+                    raise ValueError(f"the policy's normaliser serves {int(live.num_envs)} envs at gamma {float(live.gamma)}, this run has {N} at "
+                                     f"{self.gamma}: hand the policy over on an env of the same size, with the same gamma")
+                self.normalizer = live
+            elif self.pipeline is None and self.targets is None:
                 self.normalizer = RunningNormalizer.for_env(env, gamma=self.gamma, **kw)
             else:  # (SB3: VecNormalize over VecFrameStack, so its columns are the stack's, not the env's; with targets: D + G)
                 self.normalizer = RunningNormalizer(N, D, gamma=self.gamma, device=dev, **kw)
-            self.normalizer.attach(pol)
+            if self.normalizer is not live:
+                self.normalizer.attach(pol)
             if self.critic_observation is not None:  # (the privileged rows' own statistics; the reward is the first one's)
                 self.critic_normalizer = RunningNormalizer(N, int(pol.critic_obs_dim), gamma=self.gamma, norm_reward=False, device=dev, **kw)
                 self.critic_normalizer.attach(pol, tower="critic")
