@@ -146,19 +146,25 @@ def plan(shape):
 
 # ---------------------------------------------------------------- the privileged row (csrc/privileged_obs.hpp)
 MUTATIONS = ("new_tail_in_terminal_row", "force_before_events_step", "final_obs_ignored")
+# two more, which only a masked reset or an `include` out of the default order can show
+LAYOUT_MUTATIONS = MUTATIONS + ("mask_ignored_on_reset", "default_order_starts")
+SEGMENTS = ("observation", "command", "push_force", "link_scale")
 
 
 class PrivilegedTwin:
     """The privileged stage in numpy. ``include``: the segments in order, each of "observation" (D words of next_obs),
     "command" (A words), "push_force" (3 words of force[:, n]) and "link_scale" (link_scale[links, n]). `step` is one
-    call after ``events.step``; where the episode ended the terminal row is final_obs followed by the OLD row's other
-    words. ``mutation``: one of `MUTATIONS`, a one-line break of that rule."""
+    call after ``events.step``; where the episode ended the terminal row is final_obs (next_obs where there is none) with
+    the OLD row's other words around it; without end flags no episode ended. `reset` writes the rows of the envs with
+    ``mask`` set (None: all) and leaves the terminal rows alone. ``mutation``: one of `LAYOUT_MUTATIONS`, a one-line
+    break of these rules ("default_order_starts": the segments land where the default order would put them)."""
 
     def __init__(self, num_envs, obs_dim, act_dim, links, include=("observation", "command", "push_force", "link_scale"), mutation=None):
-        assert mutation is None or mutation in MUTATIONS
+        assert mutation is None or mutation in LAYOUT_MUTATIONS
         self.N, self.D, self.A, self.links, self.include, self.mutation = num_envs, obs_dim, act_dim, list(links), tuple(include), mutation
         counts = {"observation": obs_dim, "command": act_dim, "push_force": 3, "link_scale": len(self.links)}
-        self.counts = [counts[k] for k in self.include]
+        self.order = tuple(k for k in SEGMENTS if k in self.include) if mutation == "default_order_starts" else self.include
+        self.counts = [counts[k] for k in self.order]
         self.dim = sum(self.counts)
         self.observation = np.zeros((num_envs, self.dim), dtype=np.float32)
         self.final_observation = np.zeros((num_envs, self.dim), dtype=np.float32)
@@ -167,23 +173,29 @@ class PrivilegedTwin:
     def _row(self, obs, command, force, link_scale):
         parts = {"observation": lambda: obs[:, : self.D], "command": lambda: command[:, : self.A], "push_force": lambda: force[:3].T,
                  "link_scale": lambda: link_scale[self.links].T}
-        return np.concatenate([np.asarray(parts[k](), dtype=np.float32).reshape(self.N, -1) for k in self.include], axis=1)
+        return np.concatenate([np.asarray(parts[k](), dtype=np.float32).reshape(self.N, -1) for k in self.order], axis=1)
 
     def _obs_columns(self):
         cols = np.zeros(self.dim, dtype=bool)
-        if "observation" in self.include:
-            k = self.include.index("observation")
+        if "observation" in self.order:
+            k = self.order.index("observation")
             start = sum(self.counts[:k])
             cols[start:start + self.D] = True
         return cols
 
-    def reset(self, obs, command, force, link_scale):
-        self.observation = self._row(obs, command, force, link_scale)
+    def reset(self, obs, command, force, link_scale, mask=None):
+        new = self._row(obs, command, force, link_scale)
+        take = np.ones(self.N, dtype=bool) if mask is None or self.mutation == "mask_ignored_on_reset" else np.asarray(mask) != 0
+        self.observation = np.where(take[:, None], new, self.observation)
         self._force_before = np.array(force[:3], dtype=np.float32)
         return self.observation
 
-    def step(self, next_obs, final_obs, command, force, link_scale, terminated, truncated):
-        """``force`` / ``link_scale``: the events' buffers AFTER ``events.step`` of this env step."""
+    def step(self, next_obs, final_obs, command, force, link_scale, terminated=None, truncated=None):
+        """``force`` / ``link_scale``: the events' buffers AFTER ``events.step`` of this env step. ``final_obs`` None:
+        ``next_obs`` stands in; an end flag None: all zero."""
+        final_obs = next_obs if final_obs is None else final_obs
+        terminated = np.zeros(self.N, dtype=np.uint8) if terminated is None else terminated
+        truncated = np.zeros(self.N, dtype=np.uint8) if truncated is None else truncated
         used = self._force_before if self.mutation == "force_before_events_step" else force
         self._force_before = np.array(force[:3], dtype=np.float32)
         new = self._row(next_obs, command, used, link_scale)

@@ -1,6 +1,8 @@
 """The shapes the asymmetric actor-critic (a critic observation of its own) is tested at, and the builders the CPU and GPU
 tests share: tests/test_asymmetric_critic.py shows on the host that these inputs tell the feature from its likely bugs,
-tests/test_asymmetric_critic_gpu.py runs them on the device. Style and helpers of tests/mlp_shapes.py."""
+tests/test_asymmetric_critic_gpu.py runs them on the device, tests/ppo_distributed_worker.py two of the rows under a
+process group. Style and helpers of tests/mlp_shapes.py. Below the rows: the layouts, sizes and call lists the privileged
+stage is run at."""
 
 from collections import namedtuple
 
@@ -27,7 +29,19 @@ ROWS = [
     Row(100, 4, [16], 1, 129, [64], "relu", "W256 set by Dc alone; nine input tiles; tiny actor in a wide unroll"),
     Row(333, 6, [64, 64], 2, 6, [64, 64], "relu", "Dc = D but different tensors"),
     Row(1001, 5, [40, 24], 3, 12, [40, 24], "tanh", "N and widths off the tile sizes"),
+    # the rows below take the symmetric matrix's geometries (tests/mlp_shapes.py) through the critic's own pointer, width,
+    # statistics and restage; tests/test_asymmetric_critic.py asserts what they cover
+    Row(1, 3, [16], 2, 9, [16], "relu", "W16 relu; N = 1", seed=2),
+    Row(1001, 5, [32], 3, 17, [20, 32], "tanh", "W32 tanh; the critic's second input tile holds one word"),
+    Row(1000, 16, [128, 128], 2, 24, [128, 128], "relu", "W128 relu; three-wave blocks", seed=1),
+    Row(500, 8, [128, 128, 128], 1, 100, [128, 128, 128], "tanh", "W128 tanh; two-wave blocks; the critic's stage is the larger"),
+    Row(1000, 30, [256, 256, 128], 36, 48, [256, 256, 128], "tanh",
+        "W256 tanh; one-wave blocks above the grid cap: restage, the next chunk's actor stage, partials added to; Dc a multiple of 16"),
+    Row(100, 256, [256] * 4, 64, 256, [256] * 4, "relu", "the widest: raised dynamic-LDS limit, one-wave blocks, both inputs 16 full tiles", seed=4),
+    Row(333, 255, [64], 6, 7, [64], "tanh", "the actor takes 16 input tiles, the critic one: the most stale rows under the critic's stage"),
+    Row(64, 4, [16], 1, 32, [256, 16], "tanh", "Dc = 32 exactly; W256 set by a critic hidden layer alone; three-wave blocks"),
 ]
+DEGENERATE = (4, 5, 8, 10)  # rows run with Dc = D on the same rows and statistics: 8 has three-wave blocks, 10 is above the grid cap
 
 
 def row_id(row):
@@ -136,22 +150,61 @@ def row_rollout(row, shape, sources, seed=0, obs_normalized=False):
 
 
 # ---------------------------------------------------------------- the privileged stage's inputs
-PRIVILEGED_SIZES = (1, 65, 1000)
-PRIVILEGED_CALLS = 40
-PRIVILEGED_D, PRIVILEGED_A, PRIVILEGED_LINKS, PRIVILEGED_MAX_LINKS = 4, 2, (1, 2, 5, 12), 24
+SEGMENTS = AR.SEGMENTS
+PRIVILEGED_MAX_LINKS = 24
+_ALL_LINKS = tuple(range(PRIVILEGED_MAX_LINKS))
+_BLOCK_EDGES = (1, 63, 64, 65, 129, 1000)  # around the 64 envs of a block: one short of it, exactly it, one more, two blocks and one env
+
+# name, `include`, D, A, the links the model randomises, the batch sizes, the calls after the first reset, the seed of the
+# call list. The first is the layout of the Ppo tests; the others are the layouts the kernel serves besides.
+Layout = namedtuple("Layout", "name include D A links sizes calls seed", defaults=(0,))
+PRIVILEGED_LAYOUTS = [
+    Layout("default", SEGMENTS, 4, 2, (1, 2, 5, 12), (1, 65, 1000), 40),
+    Layout("reversed", SEGMENTS[::-1], 4, 2, (1, 2, 5, 12), _BLOCK_EDGES, 12),  # the observation last
+    Layout("observation-256", ("observation",), 256, 2, (), (1, 65, 1000), 12),  # a 256-word row, no staged column
+    Layout("force-alone", ("push_force",), 4, 2, (), (1, 65, 1000), 12),  # no observation segment: a terminal row is the old row
+    Layout("27-columns", SEGMENTS, 4, 2, _ALL_LINKS, _BLOCK_EDGES, 12),  # seven passes of the staging loop
+    Layout("256-words", ("command", "link_scale", "observation", "push_force"), 200, 29, _ALL_LINKS, (1, 65, 1000), 12),  # 29 + 24 + 200 + 3
+]
+DEFAULT_LAYOUT = PRIVILEGED_LAYOUTS[0]
+NEW_LAYOUTS = PRIVILEGED_LAYOUTS[1:]
+PRIVILEGED_SIZES, PRIVILEGED_CALLS = DEFAULT_LAYOUT.sizes, DEFAULT_LAYOUT.calls
+PRIVILEGED_D, PRIVILEGED_A, PRIVILEGED_LINKS = DEFAULT_LAYOUT.D, DEFAULT_LAYOUT.A, DEFAULT_LAYOUT.links
+# what the calls of a new layout are, in order: a step as Ppo issues it, a step with no final_obs (next_obs stands in), a step
+# with no end flags (nothing ended), and resets mid-run under a mixed mask, an all-zero mask and no mask
+SCRIPT = ("step", "step", "step_no_final", "reset_mixed", "step", "step_no_flags", "reset_zero", "step", "reset_all", "step", "step_no_final", "step")
 
 
-def privileged_calls(num_envs, seed=0, calls=PRIVILEGED_CALLS):
+def layout_dim(layout):
+    counts = {"observation": layout.D, "command": layout.A, "push_force": 3, "link_scale": len(layout.links)}
+    return sum(counts[k] for k in layout.include)
+
+
+def layout_cases(layouts=None):
+    """[(layout, num_envs)] of the layouts (default: the new ones) at their sizes, and the ids."""
+    cases = [(lay, n) for lay in (NEW_LAYOUTS if layouts is None else layouts) for n in lay.sizes]
+    return cases, [f"{lay.name}-{n}" for lay, n in cases]
+
+
+def end_rate(num_envs):
+    """Ends per env and step of a new layout's call list: enough for every size above 1 to see both kinds of end."""
+    return min(0.5, max(0.08, 4.0 / num_envs))
+
+
+def privileged_calls(num_envs, seed=0, calls=PRIVILEGED_CALLS, layout=DEFAULT_LAYOUT, rate=0.05, script=None):
     """The inputs of `calls` calls of the privileged stage after a reset (element 0): per call next_obs and a final_obs that
     differs from it [N, D], the command [N, A], the force [3, N] and link scales [24, N] as the events would have left them
-    (rewritten between calls; zero force and fresh scales where the episode ended) and end flags at about 5 % per step."""
+    (rewritten between calls; zero force and fresh scales where the episode ended) and end flags at about `rate` per step.
+    With a ``script`` (one of `SCRIPT`'s words per call) a call also carries its "op" and, for a reset, its "mask"; only
+    a step that passes end flags ends an episode."""
     rng = np.random.default_rng(100 * seed + num_envs)
-    N, D, A = num_envs, PRIVILEGED_D, PRIVILEGED_A
+    N, D, A = num_envs, layout.D, layout.A
     f = lambda *shape: rng.normal(size=shape).astype(np.float32)  # noqa: E731
     scale = (1.0 + 0.2 * rng.uniform(-1, 1, size=(PRIVILEGED_MAX_LINKS, N))).astype(np.float32)
     out = []
     for k in range(calls + 1):
-        ended = rng.uniform(size=N) < (0.05 if k else 0.0)
+        op = script[k - 1] if script is not None and k else "step"
+        ended = rng.uniform(size=N) < (rate if k and op in ("step", "step_no_final") else 0.0)
         terminated = ended & (rng.uniform(size=N) < 0.5)
         truncated = ended & ~terminated
         force = (f(3, N) * (rng.uniform(size=N) < 0.5)).astype(np.float32)
@@ -160,16 +213,32 @@ def privileged_calls(num_envs, seed=0, calls=PRIVILEGED_CALLS):
         scale[:, ended] = (1.0 + 0.2 * rng.uniform(-1, 1, size=(PRIVILEGED_MAX_LINKS, int(ended.sum())))).astype(np.float32)
         out.append({"next_obs": f(N, D), "final_obs": f(N, D), "command": f(N, A), "force": force, "link_scale": scale,
                     "terminated": terminated.astype(np.uint8), "truncated": truncated.astype(np.uint8)})
+        if script is not None:
+            mixed = (rng.uniform(size=N) < 0.5).astype(np.uint8)
+            out[-1].update(op=op, mask={"reset_mixed": mixed, "reset_zero": np.zeros(N, dtype=np.uint8)}.get(op))
     return out
 
 
-def run_privileged_twin(num_envs, calls, mutation=None):
+def layout_calls(layout, num_envs):
+    """The call list of a (layout, size) of `PRIVILEGED_LAYOUTS`: the default's 40 plain steps, or `SCRIPT`."""
+    if layout is DEFAULT_LAYOUT:
+        return privileged_calls(num_envs)
+    assert layout.calls == len(SCRIPT)
+    return privileged_calls(num_envs, seed=layout.seed, calls=layout.calls, layout=layout, rate=end_rate(num_envs), script=SCRIPT)
+
+
+def run_privileged_twin(num_envs, calls, mutation=None, layout=DEFAULT_LAYOUT):
     """(observation, final_observation) after each call of `privileged_calls`' list on the twin."""
-    twin = AR.PrivilegedTwin(num_envs, PRIVILEGED_D, PRIVILEGED_A, PRIVILEGED_LINKS, mutation=mutation)
+    twin = AR.PrivilegedTwin(num_envs, layout.D, layout.A, layout.links, include=layout.include, mutation=mutation)
     first = calls[0]
     twin.reset(first["next_obs"], first["command"], first["force"], first["link_scale"])
     rows = [(twin.observation.copy(), None)]
     for c in calls[1:]:
-        twin.step(c["next_obs"], c["final_obs"], c["command"], c["force"], c["link_scale"], c["terminated"], c["truncated"])
+        op = c.get("op", "step")
+        if op.startswith("reset"):
+            twin.reset(c["next_obs"], c["command"], c["force"], c["link_scale"], mask=c["mask"])
+        else:
+            flags = (None, None) if op == "step_no_flags" else (c["terminated"], c["truncated"])
+            twin.step(c["next_obs"], None if op == "step_no_final" else c["final_obs"], c["command"], c["force"], c["link_scale"], *flags)
         rows.append((twin.observation.copy(), twin.final_observation.copy()))
     return rows

@@ -5,6 +5,8 @@ data-parallel PpoTrainer and RunningNormalizer.
     against the fused path without one, bit for bit.
   world2 (--nproc-per-node 2, gloo, both ranks on cuda:0): two ranks with different data against one learner /
     normaliser on the union.
+  Both also run an asymmetric policy (a row of tests/asymmetric_shapes.py, critic rows of its own in the buffer) and,
+  world1, a normaliser attached to its critic block.
 
 Every rank writes its findings as JSON to `<out>.<rank>`."""
 
@@ -20,6 +22,8 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
+from tests import asymmetric_reference as AR  # noqa: E402
+from tests import asymmetric_shapes as AS  # noqa: E402
 from tests import ppo_reference as R  # noqa: E402
 from tests.test_ppo_gpu import CASES, T, _tower  # noqa: E402
 from upkie_amd.distributed import init_distributed  # noqa: E402
@@ -57,6 +61,29 @@ def _setup(case, wseed, dseed, first=False):
     buf.observations.copy_(torch.randn(T, N, D, device=DEV, generator=gen))
     for t in range(T):
         pol.act(buf.observations[t], out={"action": buf.actions[t], "value": buf.values[t], "log_prob": buf.log_probs[t]})
+    _fill(buf, N, dseed, first)
+    return pol, buf
+
+
+def _setup_asymmetric(row, dseed, first=False):
+    """`_setup` for a row of tests/asymmetric_shapes.py: an asymmetric policy (`AS.policy`: the row's weights on every
+    rank, the noise under `dseed`), a buffer whose critic rows are drawn apart from the observations, data under `dseed`."""
+    N, D, A, Dc = row.N, row.obs_dim, row.act_dim, row.critic_obs_dim
+    pol, _, _, _ = AS.policy(row, log_std=nn.Parameter(torch.full((A,), -0.5, device=DEV)))
+    pol.reseed(dseed)
+    buf = RolloutBuffer(T, N, obs_shape=(D,), action_shape=(A,), device=DEV, critic_obs_shape=(Dc,))
+    gen = torch.Generator(DEV).manual_seed(dseed + 7)
+    buf.observations.copy_(torch.randn(T, N, D, device=DEV, generator=gen))
+    buf.critic_observations.copy_(torch.randn(T, N, Dc, device=DEV, generator=gen))
+    for t in range(T):
+        pol.act(buf.observations[t], out={"action": buf.actions[t], "value": buf.values[t], "log_prob": buf.log_probs[t]},
+                critic_obs=buf.critic_observations[t])
+    _fill(buf, N, dseed, first)
+    return pol, buf
+
+
+def _fill(buf, N, dseed, first):
+    """Old log-probs that make ratios clip (unless `first`), advantages, returns and old values around the policy's."""
     rng = np.random.default_rng(dseed)
     if not first:
         delta = rng.normal(0.0, 0.25, size=(T, N))
@@ -68,7 +95,6 @@ def _setup(case, wseed, dseed, first=False):
     buf.returns = (buf.values + torch.as_tensor(rng.normal(0.0, 1.0, size=(T, N)), dtype=torch.float32, device=DEV)).contiguous()
     buf.values.add_(torch.as_tensor(rng.normal(0.0, 0.2, size=(T, N)), dtype=torch.float32, device=DEV))
     buf.pos, buf.full = T, True
-    return pol, buf
 
 
 def _state(pol, tr):
@@ -89,26 +115,37 @@ def _gather(t: torch.Tensor, group):
 
 
 # ---------------------------------------------------------------- world 1: split path == fused path, bit for bit
+def _split_against_fused(pol, buf, group, total):
+    """[packed, m, v, scalars, stats equal; training moved the weights] of the split path with the group against the fused
+    path without one, from the same state."""
+    kw = dict(n_epochs=2, batch_size=(total + 2) // 3, seed=1, ent_coef=0.003)
+    fused = PpoTrainer(pol, **kw)
+    fused.prepare(buf)
+    s0 = _state(pol, fused)
+    fused.update(buf, sync=False)
+    want = _state(pol, fused) + [fused.stats.clone()]
+    _restore(pol, fused, s0)
+    split = PpoTrainer(pol, process_group=group, **kw)
+    split.prepare(buf)
+    assert torch.equal(split.perm, fused.perm)
+    split.update(buf, sync=False)
+    got = _state(pol, split) + [split.stats.clone()]
+    torch.cuda.synchronize()
+    return [bool(torch.equal(a, b)) for a, b in zip(got, want)] + [not torch.equal(want[0], s0[0])]
+
+
 def world1(group):
     out = {}
     for case in CASES:
         pol, buf = _setup(case, 0, 3)
-        kw = dict(n_epochs=2, batch_size=(T * case[0] + 2) // 3, seed=1, ent_coef=0.003)
-        fused = PpoTrainer(pol, **kw)
-        fused.prepare(buf)
-        s0 = _state(pol, fused)
-        fused.update(buf, sync=False)
-        want = _state(pol, fused) + [fused.stats.clone()]
-        _restore(pol, fused, s0)
-        split = PpoTrainer(pol, process_group=group, **kw)
-        split.prepare(buf)
-        assert torch.equal(split.perm, fused.perm)
-        split.update(buf, sync=False)
-        got = _state(pol, split) + [split.stats.clone()]
-        torch.cuda.synchronize()
-        out[f"ppo {case}"] = [bool(torch.equal(a, b)) for a, b in zip(got, want)] + [not torch.equal(want[0], s0[0])]
+        out[f"ppo {case}"] = _split_against_fused(pol, buf, group, T * case[0])
+    row = AS.ROWS[5]
+    pol, buf = _setup_asymmetric(row, 3)
+    assert pol.asymmetric and buf.critic_observations is not None
+    out[f"ppo asymmetric {AS.row_id(row)}"] = _split_against_fused(pol, buf, group, T * row.N)
     for norm_reward, outputs in ((True, ("norm_obs", "episode_starts")), (False, ("episode_starts",))):
         out[f"vecnorm norm_reward={norm_reward}"] = _normalizer_world1(group, norm_reward, outputs)
+    out["vecnorm critic tower"] = _critic_normalizer_world1(group)
     return out
 
 
@@ -137,6 +174,36 @@ def _normalizer_world1(group, norm_reward, outputs):
         runs.append(seq)
     torch.cuda.synchronize()
     return all(torch.equal(a, b) for sa, sb in zip(*runs) for a, b in zip(sa, sb))
+
+
+def _critic_normalizer_world1(group):
+    """A normaliser of the critic's rows, attached to an asymmetric policy's critic block: the same bits with the group as
+    without, the policy's packed words included, and the actor's block is left alone."""
+    row = AS.ROWS[5]
+    N, D, Dc = row.N, row.obs_dim, row.critic_obs_dim
+    runs = []
+    for g in (None, group):
+        pol, _, _, _ = AS.policy(row)  # (attached before its first call)
+        norm = RunningNormalizer(N, Dc, norm_reward=False, clip_obs=3.0, device=DEV, process_group=g)
+        norm.attach(pol, tower="critic")
+        gen = torch.Generator(DEV).manual_seed(5)
+        rows = torch.randn(N, Dc, device=DEV, generator=gen) * 2 + 0.5
+        norm.reset(rows)
+        seq = []
+        for _ in range(20):
+            rows = torch.randn(N, Dc, device=DEV, generator=gen) * 2 + 0.5
+            reward = torch.randn(N, device=DEV, generator=gen)
+            term = torch.rand(N, device=DEV, generator=gen) < 0.05
+            nobs = torch.empty(N, Dc, device=DEV)
+            norm.step(rows, reward, term, out={"norm_obs": nobs})
+            value = pol.value(rows, out=torch.empty(N, device=DEV))
+            seq.append([norm.obs_stats.clone(), norm.obs_mean_f32.clone(), norm.obs_std_f32.clone(), pol.packed.clone(), nobs, value.clone()])
+        at = pol.critic_stats_offset()
+        moved = float(pol.packed[at:at + Dc].abs().sum()) > 0.0 and bool(torch.equal(pol.packed[at:at + Dc], norm.obs_mean_f32))
+        untouched = bool(torch.equal(pol.packed[:D], torch.zeros(D, device=DEV)))
+        runs.append((seq, moved and untouched))
+    torch.cuda.synchronize()
+    return all(ok for _, ok in runs) and all(torch.equal(a, b) for sa, sb in zip(runs[0][0], runs[1][0]) for a, b in zip(sa, sb))
 
 
 # ---------------------------------------------------------------- world 2: two gloo ranks == one learner on the union
@@ -221,6 +288,7 @@ def world2(group, rank):
         out["union_stats_ok"] = bool(ok.all())
         out["union_stats_worst"] = float(np.max(np.abs(s[..., cols] - su[..., cols]) / (2e-5 + 2e-3 * np.abs(su[..., cols]))))
     out["fp64_twin"] = _world2_twin(group, rank)
+    out["asymmetric"] = _world2_asymmetric(group, rank)
     out["normalizer"] = _world2_normalizer(group, rank)
     return out
 
@@ -239,10 +307,16 @@ def _world2_twin(group, rank):
     x, act = cat(buf.observations), cat(buf.actions)
     v, lp, adv, ret = (cat(t)[:, 0] for t in (buf.values, buf.log_probs, buf.advantages, buf.returns))
     ref_stats, grads, ratio = R.minibatch(pol.shape, src0, x.reshape(-1, D), act.reshape(-1, A), v, lp, adv, ret)
-    params0 = R.trainable(pol.shape, src0)
+    return _against_twin_update(pol, stats, ref_stats, grads, ratio, R.trainable(pol.shape, src0), 4, lr)
+
+
+def _against_twin_update(pol, stats, ref_stats, grads, ratio, params0, first_trainable, lr):
+    """One clipped Adam step of the twin's gradient from zero moments against the policy's sources after the update
+    (`first_trainable`: where log_std sits among them), and the statistics row: tests/test_ppo_gpu.py's bound."""
     zeros = [0 * g for g in grads]
     params, m, _, _ = R.adam_step(params0, grads, zeros, zeros, 0, 0.5, lr)
-    after = [_np(p) for p in pol.sources()[4:]]
+    after = [_np(p) for p in pol.sources()[first_trainable:]]
+    assert len(after) == len(params0) == len(grads)
     coef = min(1.0, 0.5 / (ref_stats[6] + 1e-6))
     worst = 0.0
     for p1, p0, pr, g in zip(after, params0, params, grads):
@@ -253,6 +327,29 @@ def _world2_twin(group, rank):
     s = stats.double().cpu().numpy()[0, 0]
     stats_ok = bool(np.allclose(s[[0, 1, 2, 3, 6]], ref_stats[[0, 1, 2, 3, 6]], rtol=1e-4, atol=1e-6))
     return {"worst_over_bound": worst, "stats_ok": stats_ok, "ratio_one": bool(np.all(np.abs(ratio - 1.0) < 1e-4))}
+
+
+def _world2_asymmetric(group, rank):
+    """An asymmetric policy on two ranks, each with its own observations and critic rows: the same bits on both after the
+    update, and the first full-batch update against the composed fp64 twin on the union (`_world2_twin`'s bound)."""
+    row = AS.ROWS[4]
+    N, D, A, Dc = row.N, row.obs_dim, row.act_dim, row.critic_obs_dim
+    lr = 1e-3
+    pol, buf = _setup_asymmetric(row, 60 + rank, first=True)
+    tr = PpoTrainer(pol, lr=lr, n_epochs=1, batch_size=T * N, seed=5, process_group=group)
+    src0 = [_np(s) for s in pol.sources()]
+    start_equal = bool(torch.equal(*_gather(pol.packed, group)))
+    stats = tr.train(buf).clone()
+    torch.cuda.synchronize()
+    bit_equal = [bool(torch.equal(*_gather(t, group))) for t in _state(pol, tr) + [stats]]
+    moved = not np.array_equal(_np(pol.sources()[AR.N_FIXED + 1]), src0[AR.N_FIXED + 1])
+    data_apart = not torch.equal(*_gather(buf.critic_observations, group))
+    cat = lambda t: np.concatenate([x.double().numpy().reshape(T * N, -1) for x in _gather(t, group)])  # noqa: E731
+    x, xc, act = cat(buf.observations), cat(buf.critic_observations), cat(buf.actions)
+    v, lp, adv, ret = (cat(t)[:, 0] for t in (buf.values, buf.log_probs, buf.advantages, buf.returns))
+    ref_stats, grads, ratio = AR.minibatch(pol.shape, src0, x.reshape(-1, D), xc.reshape(-1, Dc), act.reshape(-1, A), v, lp, adv, ret)
+    twin = _against_twin_update(pol, stats, ref_stats, grads, ratio, AR.trainable(pol.shape, src0), AR.N_FIXED, lr)
+    return dict(twin, ranks_bit_equal=bit_equal, start_equal=start_equal, moved=moved, data_apart=data_apart)
 
 
 def _ulps(a: torch.Tensor, b: torch.Tensor) -> float:

@@ -1,7 +1,8 @@
 """The asymmetric actor-critic without a device: the packed layout and the gradient launch's plan against their twins,
-symmetric shapes pinned to what they were, `pack_index` round trips, every refusal, and that the inputs of
-tests/test_asymmetric_critic_gpu.py tell the feature from its likely bugs (the critic fed the actor's observation; the
-privileged stage's three one-line mistakes)."""
+symmetric shapes pinned to what they were, `pack_index` round trips, every refusal, that the matrix of
+tests/asymmetric_shapes.py reaches every instantiation, block geometry, grid regime and input-tile edge (and needs each of
+its later rows for that), and that the inputs of tests/test_asymmetric_critic_gpu.py tell the feature from its likely
+bugs (the critic fed the actor's observation; the privileged stage's one-line mistakes, at every layout of its table)."""
 
 import ctypes as C
 import types
@@ -93,6 +94,65 @@ def test_pack_index_round_trip(index, row):
         unit, k = 16 * o + (lane & 15), 16 * t + 4 * s + (lane >> 4)
         want = Wc[unit, k] if unit < Wc.shape[0] and k < Dc else 0.0
         assert packed[w_off + ((o * in_t + t) * 64 + lane) * 4 + s] == want, (o, t, lane, s)
+
+
+# ---------------------------------------------------------------- what the matrix covers
+NEW_ROWS = range(6, len(AS.ROWS))
+
+
+def _geometry(row):
+    """What decides the code a row runs: the plan twin's launch geometry of its T N minibatch and the layout twin's tiles."""
+    shape = AS.shape_of(row)
+    lay, plan = AR.layout(shape), AR.plan(shape)
+    cls = lambda *ws: next(c for c in (16, 32, 64, 128, 256) if max(ws) <= c)  # noqa: E731
+    rest = cls(row.obs_dim, row.act_dim, row.critic_obs_dim, *row.actor)
+    return {"W": lay["W"], "nw": plan["nw"], "chunks": PR.chunks(plan, AS.T * row.N), "grid_cap": plan["grid_cap"], "lds_bytes": plan["lds_bytes"],
+            "actor_tiles": lay["actor"][0][3], "critic_tiles": lay["critic"][0][3], "W_by_critic_layers_alone": cls(*row.critic) > rest}
+
+
+def _uncovered(rows):
+    """The claims of the matrix that `rows` leave open (none, for the whole table)."""
+    geo = [_geometry(r) for r in rows]
+    both = list(zip(rows, geo))
+    tiles = {g["critic_tiles"] for g in geo}
+    claims = {
+        "the ten (W, activation) instantiations": {(g["W"], r.activation) for r, g in both} == {(w, a) for w in (16, 32, 64, 128, 256) for a in ("tanh", "relu")},
+        "gradient blocks of 1, 2, 3 and 4 waves": {g["nw"] for g in geo} == {1, 2, 3, 4},
+        "a row above the grid cap: a block restages, then stages the next chunk's actor rows and adds to its partial": any(g["chunks"] > g["grid_cap"] for g in geo),
+        "a row below the grid cap": any(g["chunks"] < g["grid_cap"] for g in geo),
+        "a stage above the default dynamic-LDS limit": any(g["lds_bytes"] > PR.LDS_BUDGET for g in geo),
+        "critic input tiles of 1, 2, more than 8, and 16": {1, 2, 16} <= tiles and any(8 < t < 16 for t in tiles),
+        "a Dc that is a multiple of 16 and one that is no multiple of 4": any(r.critic_obs_dim % 16 == 0 for r in rows) and any(r.critic_obs_dim % 4 for r in rows),
+        "more actor input tiles than critic's, and the reverse": any(g["actor_tiles"] > g["critic_tiles"] for g in geo) and any(g["actor_tiles"] < g["critic_tiles"] for g in geo),
+        "sixteen actor input tiles over one critic tile, the largest stale overlap": any(g["actor_tiles"] == 16 and g["critic_tiles"] == 1 for g in geo),
+        "a width class set by a critic hidden layer alone": any(g["W_by_critic_layers_alone"] for g in geo),
+        "N = 1, and a T N that is no multiple of 16": any(r.N == 1 for r in rows) and any((AS.T * r.N) % 16 for r in rows),
+    }
+    return [name for name, held in claims.items() if not held]
+
+
+def test_the_matrix_covers_every_geometry_and_no_new_row_is_spare():
+    """The table reaches every instantiation, block geometry, grid regime and input-tile edge of the kernels the critic's
+    own row goes through -- and each row appended for that is needed: without it some claim is open."""
+    assert _uncovered(AS.ROWS) == []
+    assert len({AS.row_id(r) for r in AS.ROWS}) == len(AS.ROWS) and max(r.N for r in AS.ROWS) <= 1001
+    for index in NEW_ROWS:
+        rest = [r for k, r in enumerate(AS.ROWS) if k != index]
+        assert _uncovered(rest), f"row {index} ({AS.row_id(AS.ROWS[index])}) adds nothing the others do not cover"
+    widest = _geometry(AS.ROWS[11])
+    assert widest["lds_bytes"] == 90112 and widest["nw"] == 1 and widest["actor_tiles"] == widest["critic_tiles"] == 16 and AS.T * AS.ROWS[11].N == 200
+
+
+def test_the_degenerate_rows_reach_a_short_block_and_the_grid_cap():
+    """The bit-for-bit test runs its rows with Dc = D: also then one of them has fewer than four waves per block, and one
+    has more chunks than blocks (its full update is where the asymmetric Adam and fold are compared)."""
+    assert AS.DEGENERATE[:2] == (4, 5)
+    geo = [_geometry(AS.ROWS[i]._replace(critic_obs_dim=AS.ROWS[i].obs_dim)) for i in AS.DEGENERATE]
+    assert any(g["nw"] < 4 for g in geo) and any(g["chunks"] > g["grid_cap"] for g in geo), geo
+    # the update's minibatches are N + 7 samples and the rest: the row above the cap stays above it in both
+    row = AS.ROWS[10]
+    plan = AR.plan(AS.shape_of(row._replace(critic_obs_dim=row.obs_dim)))
+    assert all(PR.chunks(plan, n) > plan["grid_cap"] for n in (row.N + 7, AS.T * row.N - (row.N + 7)))
 
 
 # ---------------------------------------------------------------- refusals
@@ -240,9 +300,7 @@ def test_each_one_line_mistake_of_the_privileged_stage_shows(num_envs):
     D, A = AS.PRIVILEGED_D, AS.PRIVILEGED_A
     assert good[1][0].shape == (num_envs, D + A + 3 + len(AS.PRIVILEGED_LINKS))
     for mutation in AR.MUTATIONS:
-        bad = AS.run_privileged_twin(num_envs, calls, mutation)
-        differs = any(not np.array_equal(g[0], b[0]) or not np.array_equal(g[1], b[1]) for g, b in zip(good[1:], bad[1:]))
-        assert differs, mutation
+        assert _shows(AS.DEFAULT_LAYOUT, num_envs, calls, good, mutation), mutation
     # and the rule itself: where the episode ended the terminal row is final_obs, then the previous row's tail
     for k in range(1, len(calls)):
         c, (row, final), (before, _) = calls[k], good[k], good[k - 1]
@@ -250,3 +308,95 @@ def test_each_one_line_mistake_of_the_privileged_stage_shows(num_envs):
         assert np.array_equal(final[done, :D], c["final_obs"][done]) and np.array_equal(final[done, D:], before[done, D:])
         assert np.array_equal(final[~done], row[~done]) and np.array_equal(row[:, :D], c["next_obs"])
         assert np.array_equal(row[:, D + A: D + A + 3], c["force"].T) and np.array_equal(row[:, D + A + 3:], c["link_scale"][list(AS.PRIVILEGED_LINKS)].T)
+
+
+def _shows(layout, num_envs, calls, good, mutation):
+    bad = AS.run_privileged_twin(num_envs, calls, mutation, layout)
+    return any(not np.array_equal(g[0], b[0]) or not np.array_equal(g[1], b[1]) for g, b in zip(good[1:], bad[1:]))
+
+
+def _applies(layout, mutation):
+    """Whether a layout has the segment a mutation breaks."""
+    include = layout.include
+    return {"new_tail_in_terminal_row": include != ("observation",), "force_before_events_step": "push_force" in include,
+            "final_obs_ignored": "observation" in include, "mask_ignored_on_reset": True,
+            "default_order_starts": include != tuple(k for k in AS.SEGMENTS if k in include)}[mutation]
+
+
+def test_the_layout_table_holds_what_the_kernel_serves():
+    by_name = {lay.name: lay for lay in AS.PRIVILEGED_LAYOUTS}
+    assert len(by_name) == len(AS.PRIVILEGED_LAYOUTS) and AS.PRIVILEGED_LAYOUTS[0] is AS.DEFAULT_LAYOUT
+    assert (AS.DEFAULT_LAYOUT.include, AS.DEFAULT_LAYOUT.sizes, AS.DEFAULT_LAYOUT.calls) == (AS.SEGMENTS, (1, 65, 1000), 40)
+    assert by_name["reversed"].include == ("link_scale", "push_force", "command", "observation")
+    assert by_name["observation-256"].include == ("observation",) and AS.layout_dim(by_name["observation-256"]) == 256
+    assert by_name["force-alone"].include == ("push_force",)
+    staged = lambda lay: sum({"push_force": 3, "link_scale": len(lay.links)}.get(k, 0) for k in lay.include)  # noqa: E731
+    assert staged(by_name["27-columns"]) == 27 and staged(AS.DEFAULT_LAYOUT) == 7 and staged(by_name["observation-256"]) == 0
+    assert -(-27 * 64 // 256) == 7 and -(-7 * 64 // 256) == 2, "passes of the 256-thread staging loop over 64 envs per column"
+    full = by_name["256-words"]
+    assert AS.layout_dim(full) == 256 and set(full.include) == set(AS.SEGMENTS)
+    for name in ("reversed", "27-columns"):
+        assert by_name[name].sizes == (1, 63, 64, 65, 129, 1000)
+    assert all(lay.sizes == (1, 65, 1000) for lay in AS.PRIVILEGED_LAYOUTS if lay.name not in ("reversed", "27-columns"))
+    assert all(AS.layout_dim(lay) <= 256 and lay.A <= 64 and max(lay.links, default=0) < AS.PRIVILEGED_MAX_LINKS for lay in AS.PRIVILEGED_LAYOUTS)
+    for op in ("step", "step_no_final", "step_no_flags", "reset_mixed", "reset_zero", "reset_all"):
+        assert op in AS.SCRIPT
+    # every mutation has a new layout to show on, and the order mutation more than one
+    for mutation in AR.LAYOUT_MUTATIONS:
+        assert sum(_applies(lay, mutation) for lay in AS.NEW_LAYOUTS) >= 2, mutation
+
+
+LAYOUT_CASES, LAYOUT_IDS = AS.layout_cases()
+
+
+@pytest.mark.parametrize("layout,num_envs", LAYOUT_CASES, ids=LAYOUT_IDS)
+def test_each_one_line_mistake_shows_on_every_layout(layout, num_envs):
+    """On the inputs the GPU test feeds the kernel at a new layout and size: episodes of both kinds end, every mutation
+    whose segment the layout has changes some output of some call, and the twin keeps the rules call by call."""
+    N, D = num_envs, layout.D
+    calls = AS.layout_calls(layout, N)
+    assert len(calls) == 1 + layout.calls and [c["op"] for c in calls[1:]] == list(AS.SCRIPT)
+    terminated, truncated = (sum(int(c[k].sum()) for c in calls) for k in ("terminated", "truncated"))
+    assert terminated + truncated >= 1 and (N == 1 or (terminated >= 1 and truncated >= 1)), (terminated, truncated)
+    ended_without_final = sum(int((c["terminated"] | c["truncated"]).sum()) for c in calls[1:] if c["op"] == "step_no_final")
+    assert N == 1 or ended_without_final >= 1, "an episode ends in a step that has no final_obs"
+    good = AS.run_privileged_twin(N, calls, layout=layout)
+    assert good[1][0].shape == (N, AS.layout_dim(layout))
+    for mutation in AR.LAYOUT_MUTATIONS:
+        if _applies(layout, mutation):
+            assert _shows(layout, N, calls, good, mutation), mutation
+
+    # the rules, stated over the row's columns without the twin's own row builder
+    counts = {"observation": D, "command": layout.A, "push_force": 3, "link_scale": len(layout.links)}
+    at, cols = 0, {}
+    for name in layout.include:
+        cols[name] = slice(at, at + counts[name])
+        at += counts[name]
+    obs_cols = np.zeros(at, dtype=bool)
+    if "observation" in cols:
+        obs_cols[cols["observation"]] = True
+
+    def new_row(c):
+        parts = {"observation": c["next_obs"], "command": c["command"], "push_force": c["force"].T, "link_scale": c["link_scale"][list(layout.links)].T}
+        return np.concatenate([parts[name] for name in layout.include], axis=1)
+
+    assert np.array_equal(good[0][0], new_row(calls[0]))
+    final_before = np.zeros((N, at), dtype=np.float32)
+    for k in range(1, len(calls)):
+        c, (row, final), (before, _) = calls[k], good[k], good[k - 1]
+        op = c["op"]
+        if op.startswith("reset"):
+            take = np.ones(N, dtype=bool) if c["mask"] is None else c["mask"] != 0
+            assert (op == "reset_mixed") <= (N == 1 or 0 < take.sum() < N) and (op != "reset_zero" or not take.any())
+            assert np.array_equal(row[take], new_row(c)[take]) and np.array_equal(row[~take], before[~take]), (k, op)
+            assert np.array_equal(final, final_before), "a reset leaves the terminal rows alone"
+        else:
+            done = ((c["terminated"] | c["truncated"]) != 0) & (op != "step_no_flags")
+            last = c["next_obs"] if op == "step_no_final" else c["final_obs"]
+            assert np.array_equal(row, new_row(c)), (k, op)
+            assert np.array_equal(final[~done], row[~done])
+            assert np.array_equal(final[done][:, ~obs_cols], before[done][:, ~obs_cols])
+            if "observation" in cols:
+                assert np.array_equal(final[done][:, obs_cols], last[done])
+            assert op != "step_no_flags" or np.array_equal(final, row)
+        final_before = final

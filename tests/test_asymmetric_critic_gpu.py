@@ -1,7 +1,9 @@
 """The asymmetric actor-critic on the MI355X: the policy launch, the time-limit bootstrap and the PPO gradient launch with
 a critic observation of its own against the composed fp64 twins (tests/asymmetric_reference.py) on every row of
 tests/asymmetric_shapes.py; the degenerate case (Dc = D, the same rows and statistics) bit for bit against the symmetric
-policy, a full update included; the privileged stage against its twin call by call, eager and replayed from a graph;
+policy, a full update included; the privileged stage against its twin call by call, eager and replayed from a graph,
+at the default layout and at every other layout of the table (orders, subsets, 256-word rows, 27 staged columns, masked
+resets, steps without final_obs or end flags);
 and `Ppo(critic_observation=...)` graphed against eager, saved and resumed, with the buffer's rows against the twin.
 tests/test_asymmetric_critic.py shows on the host that these inputs tell the feature from its likely bugs.
 
@@ -19,6 +21,7 @@ import torch.nn as nn
 from tests import asymmetric_reference as AR
 from tests import asymmetric_shapes as AS
 from tests import mlp_shapes as S
+from tests import ppo_reference as PR
 from upkie_amd.ppo import PpoTrainer, trainable_offset
 from upkie_amd.rollout import RolloutBuffer
 
@@ -113,7 +116,7 @@ def _twins_of_one_network(row):
     return out
 
 
-@pytest.mark.parametrize("index", [4, 5], ids=[AS.row_id(AS.ROWS[4]), AS.row_id(AS.ROWS[5])])
+@pytest.mark.parametrize("index", AS.DEGENERATE, ids=[AS.row_id(AS.ROWS[i]) for i in AS.DEGENERATE])
 def test_the_degenerate_case_is_the_symmetric_policy_bit_for_bit(index):
     row = AS.ROWS[index]
     N, D, A = row.N, row.obs_dim, row.act_dim
@@ -218,7 +221,7 @@ def test_gradient_against_the_twin(index, row, short, obs_normalized):
     the composed fp64 twin (read from Adam's m after one step), the statistics row, and the same bits from the same state."""
     N, D, A, Dc = row.N, row.obs_dim, row.act_dim, row.critic_obs_dim
     total = T * N
-    size = total - 7 if short else total
+    size = total - min(7, total - 1) if short else total  # (the N = 1 row has two samples: its short minibatch is one of them)
     log_std = nn.Parameter(torch.full((A,), -0.5, device=DEV))
     pol, _, _, _ = AS.policy(row, normalize=True, log_std=log_std)
     src0 = S.sources_of(pol)
@@ -240,8 +243,8 @@ def test_gradient_against_the_twin(index, row, short, obs_normalized):
     errors = [_rel(_np(mm).reshape(g.shape) / float(BETA1_F32), g) for mm, g in zip(m, ref_grads)]
     worst = int(np.argmax(errors))
     plan = AR.plan(pol.shape)
-    _report("gradient", row, size=size, obs_normalized=obs_normalized, W=AR.layout(pol.shape)["W"], nw=plan["nw"], worst_tensor=worst,
-            grad=float(errors[worst]), critic_first_layer=float(errors[1 + 2 * (len(row.actor) + 1)]), bound_grad=BOUND["grad"])
+    _report("gradient", row, size=size, obs_normalized=obs_normalized, W=AR.layout(pol.shape)["W"], nw=plan["nw"], chunks=PR.chunks(plan, size),
+            grid_cap=plan["grid_cap"], worst_tensor=worst, grad=float(errors[worst]), critic_first_layer=float(errors[1 + 2 * (len(row.actor) + 1)]), bound_grad=BOUND["grad"])
     for k, e in enumerate(errors):
         assert e <= BOUND["grad"], (k, e)
     s = stats.double().cpu().numpy()
@@ -286,17 +289,17 @@ def test_the_trainer_names_both_sizes_on_every_mismatch():
 
 
 # ---------------------------------------------------------------- 5. the privileged stage
-def _stage(num_envs):
+def _stage(num_envs, layout=AS.DEFAULT_LAYOUT):
     from upkie_amd.privileged import PrivilegedObservation
 
-    N, D, A = num_envs, AS.PRIVILEGED_D, AS.PRIVILEGED_A
+    N, D, A = num_envs, layout.D, layout.A
     dev = torch.device(DEV)
-    randomized = [1 if k in AS.PRIVILEGED_LINKS else 0 for k in range(AS.PRIVILEGED_MAX_LINKS)]
+    randomized = [1 if k in layout.links else 0 for k in range(AS.PRIVILEGED_MAX_LINKS)]
     env = types.SimpleNamespace(num_envs=N, device=dev, model=types.SimpleNamespace(num_links=AS.PRIVILEGED_MAX_LINKS, link_randomized=randomized))
     events = types.SimpleNamespace(num_envs=N, force=torch.zeros(1, 3, N, device=dev), link_scale=torch.ones(AS.PRIVILEGED_MAX_LINKS, N, device=dev))
     pipeline = types.SimpleNamespace(num_envs=N, obs_dim=D, act_dim=A, command=torch.zeros(N, A, device=dev))
-    stage = PrivilegedObservation(env, events=events, pipeline=pipeline)
-    assert stage.dim == D + A + 3 + len(AS.PRIVILEGED_LINKS) and stage.links.tolist() == list(AS.PRIVILEGED_LINKS)
+    stage = PrivilegedObservation(env, events=events, pipeline=pipeline, include=layout.include)
+    assert stage.dim == AS.layout_dim(layout) and ("link_scale" not in layout.include or stage.links.tolist() == list(layout.links))
     inputs = {"next_obs": torch.zeros(N, D, device=dev), "final_obs": torch.zeros(N, D, device=dev),
               "terminated": torch.zeros(N, dtype=torch.uint8, device=dev), "truncated": torch.zeros(N, dtype=torch.uint8, device=dev)}
     return stage, events, pipeline, inputs
@@ -339,6 +342,57 @@ def test_the_privileged_stage_is_its_twin_after_every_call(num_envs):
         assert final is None or np.array_equal(view(final), view(want_final)), k
     for k, ((row, final), (g_row, g_final)) in enumerate(zip(results[False], results[True])):
         assert np.array_equal(view(row), view(g_row)) and (final is None or np.array_equal(view(final), view(g_final))), k
+
+
+LAYOUT_CASES, LAYOUT_IDS = AS.layout_cases()
+GRAPHED_LAYOUT = ("27-columns", 129)  # replayed from graphs as well: seven staging passes, a last block of one env
+
+
+@pytest.mark.parametrize("layout,num_envs", LAYOUT_CASES, ids=LAYOUT_IDS)
+def test_the_privileged_stage_at_its_layouts(layout, num_envs):
+    """Every layout of tests/asymmetric_shapes.py besides the default, at its sizes, through `SCRIPT`: steps with and
+    without final_obs and end flags, resets under a mixed mask, a zero mask and none. Both buffers are the twin's bits after
+    every call (a masked reset's other rows and every terminal row keep theirs); one case also replays each kind of call
+    from a graph of its own."""
+    N = num_envs
+    calls = AS.layout_calls(layout, N)
+    want = AS.run_privileged_twin(N, calls, layout=layout)
+    view = lambda a: np.ascontiguousarray(a).view(np.uint32)  # noqa: E731
+    results = {}
+    for graphed in (False, True) if (layout.name, N) == GRAPHED_LAYOUT else (False,):
+        stage, events, pipeline, inputs = _stage(N, layout)
+        mask = torch.zeros(N, dtype=torch.uint8, device=DEV)
+        _feed(calls[0], events, pipeline, inputs)
+        stage.reset(inputs["next_obs"])
+        flags = (inputs["terminated"], inputs["truncated"])
+        ops = {"step": lambda: stage.step(inputs["next_obs"], *flags, final_obs=inputs["final_obs"]),
+               "step_no_final": lambda: stage.step(inputs["next_obs"], *flags),
+               "step_no_flags": lambda: stage.step(inputs["next_obs"], final_obs=inputs["final_obs"]),
+               "reset_mixed": lambda: stage.reset(inputs["next_obs"], mask),
+               "reset_zero": lambda: stage.reset(inputs["next_obs"], mask),
+               "reset_all": lambda: stage.reset(inputs["next_obs"])}
+        if graphed:
+            torch.cuda.synchronize()
+            for op in list(ops):
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    ops[op]()
+                ops[op] = graph.replay
+        got = [(stage.observation.cpu().numpy().copy(), None)]
+        for call in calls[1:]:
+            _feed(call, events, pipeline, inputs)
+            if call["mask"] is not None:
+                mask.copy_(torch.from_numpy(call["mask"]))
+            ops[call["op"]]()
+            torch.cuda.synchronize()
+            got.append((stage.observation.cpu().numpy().copy(), stage.final_observation.cpu().numpy().copy()))
+        results[graphed] = got
+    assert np.array_equal(view(results[False][0][0]), view(want[0][0])), "the first rows"
+    for graphed, got in results.items():
+        for k, ((row, final), (want_row, want_final)) in enumerate(zip(got[1:], want[1:]), start=1):
+            where = (k, calls[k]["op"], "graphed" if graphed else "eager")
+            assert np.array_equal(view(row), view(want_row)), where
+            assert np.array_equal(view(final), view(want_final)), where
 
 
 # ---------------------------------------------------------------- 6. Ppo with a privileged critic

@@ -1,6 +1,7 @@
 """Data-parallel PpoTrainer and RunningNormalizer on the MI355X (tests/ppo_distributed_worker.py under
 `torch.distributed.run`): a one-rank RCCL group gives the same bits as no group; two gloo ranks sharing cuda:0 train
-as one learner on the union of their samples and keep the same bits on both ranks; the sharded example runs."""
+as one learner on the union of their samples and keep the same bits on both ranks, with a symmetric policy and with an
+asymmetric one (critic rows of its own, a normaliser on the critic's block); the sharded example runs."""
 
 import json
 import os
@@ -47,7 +48,7 @@ def world2(tmp_path_factory):
 
 def test_one_rank_rccl_group_trainer_is_bit_identical_to_no_group(world1):
     cases = {k: v for k, v in world1.items() if k.startswith("ppo")}
-    assert len(cases) == 5
+    assert len(cases) == 6 and sum("asymmetric" in k for k in cases) == 1
     for case, flags in cases.items():
         # packed, m, v, scalars, stats equal; and training moved the weights
         assert flags == [True] * 6, (case, flags)
@@ -55,6 +56,24 @@ def test_one_rank_rccl_group_trainer_is_bit_identical_to_no_group(world1):
 
 def test_one_rank_rccl_group_normalizer_is_bit_identical_to_no_group(world1):
     assert world1["vecnorm norm_reward=True"] and world1["vecnorm norm_reward=False"], world1
+
+
+def test_one_rank_rccl_group_critic_normalizer_is_bit_identical_to_no_group(world1):
+    """`attach(pol, tower="critic")` with the group: statistics, mirrors, the policy's packed words, the normalised rows
+    and the values the critic then gives."""
+    assert world1["vecnorm critic tower"] is True, world1
+
+
+def test_two_gloo_ranks_asymmetric_update_same_bits_and_the_fp64_twin_on_the_union(world2):
+    """An asymmetric policy, each rank with critic rows of its own: packed, m, v, scalars and stats are the same bits on
+    both ranks, and the first full-batch update is the composed twin's on the union of the samples."""
+    for rank, res in enumerate(world2):
+        a = res["asymmetric"]
+        print(f"\nasymmetric world2 rank={rank} worst_over_bound={a['worst_over_bound']:.3e}")
+        assert a["start_equal"] and a["data_apart"] and a["moved"], a
+        assert a["ranks_bit_equal"] == [True] * 5, (rank, a["ranks_bit_equal"])
+        assert a["ratio_one"] and a["stats_ok"], a
+        assert a["worst_over_bound"] <= 1.0, a
 
 
 def test_two_gloo_ranks_hold_the_same_bits_and_differ_from_a_lone_rank(world2):
