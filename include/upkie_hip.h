@@ -850,7 +850,8 @@ int upkie_mpc_reset(UpkieMpc* mpc, float* workspace, float* commanded_velocity,
  * accumulation, the constant part of the product (Minv q) computed once per step
  * from fp64 host products (csrc/mpc.hpp: first input within 5e-4 m/s2 of the fp64
  * oracle's at N = 16 .. 64). A solve whose iterates leave fp16's range (a finite but
- * absurd target or state, e.g. a target velocity of 1e30: |64 rho (2 z - w)| > 65504)
+ * absurd target or state: |64 rho (2 z - w)| > 65504), or whose constant part Minv q
+ * exceeds 1e5 in any element (e.g. a target velocity of 1e30),
  * is discarded as a whole: zero warm start, first_input 0, the commanded velocity
  * decays as for a fallen robot; nothing non-finite is ever stored (non-finite TARGETS
  * are replaced by 0 up front, see "Non-finite commands and states").

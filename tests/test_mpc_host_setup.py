@@ -24,7 +24,10 @@ def logical(t, g, r):  # horizon index of element (row tile t, lane group g, reg
     return 16 * t + 4 * r + g
 
 
-@pytest.mark.parametrize("N, rho", [(16, 1e-3), (17, 1e-3), (32, 1e-3), (50, 1e-3), (64, 1e-3), (50, 1e-6), (16, 1e-1)])
+@pytest.mark.parametrize("N, rho", [(16, 1e-3), (17, 1e-3), (32, 1e-3), (50, 1e-3), (64, 1e-3), (50, 1e-6), (16, 1e-1),
+                                    # the horizons of tests/mpc_shapes.py below 16 and beside a tile's edge
+                                    (1, 1e-3), (2, 1e-3), (3, 1e-3), (5, 1e-3), (15, 1e-3), (31, 1e-3), (33, 1e-3), (47, 1e-3), (48, 1e-3),
+                                    (49, 1e-3), (51, 1e-3), (63, 1e-3), (7, 1e-6), (9, 1e-1)])
 def test_host_setup_layouts_hold_the_checkers_matrix(harness, N, rho):  # noqa: F811
     cfg = abi.default_mpc_config(1, N)
     cfg.admm_rho = rho

@@ -536,8 +536,19 @@ __device__ __forceinline__ void mpc_tile_h(const MpcDev& P, float* __restrict__ 
   // r is carried TIMES P.scale and Minv divided by it on the host (a power of two: nothing rounds; 32 with the default weights,
   // chosen so that the largest entry of Minv / scale lies in [8, 16) whatever rho and the cost weights are): fp16's normal
   // range, 6e-5 .. 65504, then holds both terms of |r| from 4e-3 to 2e3; u_q is clamped once, so that a state far outside anything the balancer is for
-  // (|w| follows |u_q|) gives a wrong but finite plan.
+  // (|w| follows |u_q|) iterates on finite numbers (its plan is discarded, below).
   constexpr float kLargest = 1.0e5f;
+  // A u_q that the clamp cuts belongs to a solve that is discarded at the end like one that left fp16's range: cut to 1e5 the
+  // iterates stay INSIDE that range (a target of 1e30 at rho = 1e-3: |scale r| reaches 4.4e4 of fp16's 65504, the duals 1e6), so
+  // the check of the iterates alone let such a solve through and its duals stayed in the warm start. The four lanes of a column
+  // hold different elements and must decide alike: two exchanges, once per solve, collected behind the loop.
+  int absurd = 0;
+#pragma unroll
+  for (int t = 0; t < T; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) absurd |= !(fabsf(uq[t][r]) <= kLargest);
+  absurd |= __shfl_xor(absurd, 16);
+  absurd |= __shfl_xor(absurd, 32);
   const float rho = P.rho * P.scale, bound = P.bound;
   floatx2 rbp[T][2], nauq[T][2], zp[T][2], carry[T][2];
   floatx4 yv[T];
@@ -580,7 +591,10 @@ __device__ __forceinline__ void mpc_tile_h(const MpcDev& P, float* __restrict__ 
     else
       asm volatile("s_nop 1" : "+v"(bh[0]), "+v"(bl[0]));
 #pragma unroll
-    for (int t = 0; t < T; ++t) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %3" : "=&v"(acc[t]) : "v"(ah[t][0]), "v"(bh[0]), "v"(yv[t]));
+    // (the accumulator starts from 0, not from y: a dual of 1e3 -- a robot that lies on the ground -- as C operand made each of the
+    // 3 KJ accumulations round at y's size, the product's terms are a hundredth of it; y joins once, on the vector unit, below:
+    // tests/test_mpc_matrix_gpu.py, the duals' worst distance from the fp64 twin at N = 48 from 5.4e-3 to 3.5e-3)
+    for (int t = 0; t < T; ++t) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc[t]) : "v"(ah[t][0]), "v"(bh[0]));
     if (KJ > 1) {
 #pragma unroll
       for (int t = 0; t < T; ++t) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc[t]) : "v"(ah[t][KJ - 1]), "v"(bh[KJ - 1]));
@@ -611,7 +625,8 @@ __device__ __forceinline__ void mpc_tile_h(const MpcDev& P, float* __restrict__ 
       floatx2 yn[2];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        const floatx2 plain = h == 0 ? floatx2{acc[t][0], acc[t][1]} : floatx2{acc[t][2], acc[t][3]};  // Minv r + y
+        const floatx2 plain = (h == 0 ? floatx2{acc[t][0], acc[t][1]} : floatx2{acc[t][2], acc[t][3]}) +
+                              (h == 0 ? floatx2{yv[t][0], yv[t][1]} : floatx2{yv[t][2], yv[t][3]});  // Minv r + y
         const floatx2 w = __builtin_elementwise_fma(alpha2, plain, carry[t][h]);
         carry[t][h] = __builtin_elementwise_fma(beta2, w, nauq[t][h]);
         const floatx2 zi = floatx2{__builtin_amdgcn_fmed3f(w.x, -bound, bound), __builtin_amdgcn_fmed3f(w.y, -bound, bound)};
@@ -625,7 +640,7 @@ __device__ __forceinline__ void mpc_tile_h(const MpcDev& P, float* __restrict__ 
   // A solve that left fp16's range (a finite but absurd target or state: |64 r| > 65504 turns into an infinity in the split and
   // into NaNs in every row of the next product) is discarded as a whole: zero warm start, the commanded velocity decays as for
   // a fallen robot. Every lane of the column sees it in its own elements (the matrix is dense), so each decides alone.
-  bool sound = true;
+  bool sound = !absurd;
 #pragma unroll
   for (int t = 0; t < T; ++t)
 #pragma unroll
