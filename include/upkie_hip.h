@@ -515,6 +515,77 @@ int upkie_sim_episode_events_reset(UpkieSim* sim, const UpkieEpisodeEvents* para
                                    int32_t* remaining, uint32_t* pushes, uint32_t* episodes, float* force,
                                    float* body_inertials, float* link_scale, void* stream);
 
+/* ---- Push curriculum (per-env difficulty levels, live push settings) ------
+ * The episode events with two additions, in the launch the stage already has:
+ * the push settings are a device block read at every call, not launch
+ * arguments, so whoever rewrites the block (a device copy) is followed by a
+ * captured step at its next replay; and every env carries a difficulty level
+ * that rises when its episode survives to the time limit under pushes, falls
+ * when the robot falls, and scales the norm range of that env's pushes
+ * (legged_gym's terrain levels, applied to pushes). A level depends on its own
+ * env's history alone: no reduction, no host decision, nothing to exchange
+ * between the ranks of a sharded run. upkie_sim_episode_events_step / _reset
+ * above are not changed by any of this.
+ * State beyond the four counters, N words each:
+ *   level uint32: the env's difficulty level;  episode_pushes uint32: push
+ *   starts in the current episode;  difficulty float: the fraction the coming
+ *   step's pushes are scaled by, written for every env at every call.
+ * settings: UPKIE_EVENTS_SETTINGS_WORDS 32-bit device words, in this order:
+ *   threshold uint32 (llround(push_prob * 2^24)), norm_min, norm_max float,
+ *   steps_min, steps_span uint32 (steps_span = steps_max - steps_min + 1; 0 is
+ *   read as 1), levels = L uint32 (0..UPKIE_EVENTS_LEVELS_MAX), up, down
+ *   uint32 (0..L), min_pushes uint32.
+ * inertia_variation stays a host argument: it decides which buffers exist.
+ * upkie_sim_episode_events_step_levels, per env n, with l = min(level[n], L)
+ * (a level read above L is taken as L):
+ *   1. as step 1 above: the same stream, counter and key. A level never
+ *      changes which random words an env draws.
+ *   2. if the episode ended, before anything else of step 2: if terminated[n]
+ *      (it wins when both flags are set): l -= min(l, down); otherwise (the
+ *      episode was truncated) if episode_pushes[n] >= min_pushes:
+ *      l = min(l + up, L). Then episode_pushes[n] = 0, then step 2 above.
+ *   3. as above.
+ *   4. as above, with the block's threshold, steps_min and steps_span, and at
+ *      a push start: hi = norm_max when l >= L (which includes L = 0),
+ *      otherwise hi = fma(norm_max - norm_min, (float)l / (float)L, norm_min)
+ *      in float32; the norm is fma(hi - norm_min, u0, norm_min): with
+ *      hi = norm_max the expression of step 4 above, to the bit;
+ *      episode_pushes[n] += 1. A push that starts on the call that ended an
+ *      episode uses the new level.
+ *   5. as above. Then level[n] = l, and difficulty[n] = 1 when l >= L, else
+ *      (float)l / (float)L (IEEE division).
+ * upkie_sim_episode_events_reset_levels: the reset above, then, for the same
+ * envs, level[n] = start_level, episode_pushes[n] = 0 and difficulty[n] that
+ * of start_level.
+ * upkie_sim_episode_events_level_counts: counts uint32
+ * [UPKIE_EVENTS_LEVELS_MAX + 1], zeroed by the call (a memset node in front of
+ * the launch), then counts[l] = the number of envs with level[n] == l (a level
+ * above UPKIE_EVENTS_LEVELS_MAX counts at UPKIE_EVENTS_LEVELS_MAX). Integer
+ * sums only: the order of the additions cannot change a bit. Any N.
+ * Refused with UPKIE_ERR_INVALID_ARGUMENT before anything else, with or
+ * without a device: a NULL handle, state buffer or settings, start_level above
+ * UPKIE_EVENTS_LEVELS_MAX, inertia_variation outside [0, 1), body_inertials /
+ * link_scale not given exactly when inertia_variation > 0. (The block's words
+ * are device words: upkie_amd.events checks them before it writes them.) No
+ * allocation, no host synchronisation, no host argument that changes between
+ * calls: a step can be captured in a hipGraph. */
+#define UPKIE_EVENTS_SETTINGS_WORDS 9
+#define UPKIE_EVENTS_LEVELS_MAX 255
+
+int upkie_sim_episode_events_step_levels(UpkieSim* sim, double inertia_variation, const uint32_t* settings,
+                                         const uint8_t* terminated, const uint8_t* truncated, uint32_t* calls,
+                                         int32_t* remaining, uint32_t* pushes, uint32_t* episodes, uint32_t* level,
+                                         uint32_t* episode_pushes, float* difficulty, float* force, float* body_inertials,
+                                         float* link_scale, void* stream);
+
+int upkie_sim_episode_events_reset_levels(UpkieSim* sim, double inertia_variation, const uint32_t* settings,
+                                          uint32_t start_level, const uint8_t* mask, uint32_t* calls, int32_t* remaining,
+                                          uint32_t* pushes, uint32_t* episodes, uint32_t* level, uint32_t* episode_pushes,
+                                          float* difficulty, float* force, float* body_inertials, float* link_scale,
+                                          void* stream);
+
+int upkie_sim_episode_events_level_counts(UpkieSim* sim, const uint32_t* level, uint32_t* counts, void* stream);
+
 /* ---- Task targets (goals in the observation, a curriculum) ----------------
  * The goal an env is asked to reach -- a ground and a yaw velocity, say --
  * drawn per env on the device, held a random number of env steps, drawn again

@@ -333,6 +333,11 @@ class UpkieEpisodeEvents(C.Structure):
     ]
 
 
+# the device block of `upkie_sim_episode_events_step_levels` (include/upkie_hip.h, "Push curriculum"): its words, in order
+EVENTS_SETTINGS = ("threshold", "norm_min", "norm_max", "steps_min", "steps_span", "levels", "up", "down", "min_pushes")
+EVENTS_SETTINGS_WORDS = 9  # UPKIE_EVENTS_SETTINGS_WORDS
+EVENTS_LEVELS_MAX = 255  # UPKIE_EVENTS_LEVELS_MAX
+
 TASK_TARGETS_MAX = 8  # UPKIE_TASK_TARGETS_MAX
 
 

@@ -521,9 +521,9 @@ extern "C" int upkie_sim_episode_events_step(UpkieSim* sim, const UpkieEpisodeEv
   EventsParams P;
   const int status = events_params(sim, params, calls, remaining, pushes, episodes, force, body_inertials, link_scale, &P);
   if (status != UPKIE_OK) return status;
-  hipLaunchKernelGGL(episode_events_kernel, grid_for(sim->config.num_envs), dim3(block_lanes()), 0, (hipStream_t)stream, sim->config, sim->links,
-                     P, terminated, truncated, (unsigned*)calls, (int*)remaining, (unsigned*)pushes, (unsigned*)episodes, force, body_inertials,
-                     link_scale);
+  hipLaunchKernelGGL(episode_events_kernel<false>, grid_for(sim->config.num_envs), dim3(block_lanes()), 0, (hipStream_t)stream, sim->config,
+                     sim->links, P, EventsLevels<false>{}, terminated, truncated, (unsigned*)calls, (int*)remaining, (unsigned*)pushes,
+                     (unsigned*)episodes, force, body_inertials, link_scale);
   return check_hip(sim, hipGetLastError(), "episode_events_kernel");
 }
 
@@ -533,10 +533,70 @@ extern "C" int upkie_sim_episode_events_reset(UpkieSim* sim, const UpkieEpisodeE
   EventsParams P;
   const int status = events_params(sim, params, calls, remaining, pushes, episodes, force, body_inertials, link_scale, &P);
   if (status != UPKIE_OK) return status;
-  hipLaunchKernelGGL(episode_events_reset_kernel, grid_for(sim->config.num_envs), dim3(block_lanes()), 0, (hipStream_t)stream, sim->config,
-                     sim->links, P, mask, (unsigned*)calls, (int*)remaining, (unsigned*)pushes, (unsigned*)episodes, force, body_inertials,
-                     link_scale);
+  hipLaunchKernelGGL(episode_events_reset_kernel<false>, grid_for(sim->config.num_envs), dim3(block_lanes()), 0, (hipStream_t)stream,
+                     sim->config, sim->links, P, EventsLevels<false>{}, 0u, mask, (unsigned*)calls, (int*)remaining, (unsigned*)pushes,
+                     (unsigned*)episodes, force, body_inertials, link_scale);
   return check_hip(sim, hipGetLastError(), "episode_events_reset_kernel");
+}
+
+// Push curriculum (include/upkie_hip.h): the push settings are the device block's; the host checks what it is handed.
+static int events_levels_params(UpkieSim* sim, double inertia_variation, const void* settings, const void* calls, const void* remaining,
+                                const void* pushes, const void* episodes, const void* level, const void* episode_pushes,
+                                const void* difficulty, const void* force, const void* body_inertials, const void* link_scale,
+                                EventsParams* out) {
+  if (!(inertia_variation >= 0.0 && inertia_variation < 1.0)) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "inertia_variation must be in [0, 1)");
+  const bool inertia = inertia_variation > 0.0;
+  if (inertia != (body_inertials != nullptr) || inertia != (link_scale != nullptr))
+    return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "body_inertials and link_scale are given exactly when inertia_variation > 0");
+  if (!sim || !settings || !calls || !remaining || !pushes || !episodes || !level || !episode_pushes || !difficulty || !force)
+    return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  *out = EventsParams{};  // (the kernel reads the push settings from the block)
+  out->variation = (float)inertia_variation;
+  return UPKIE_OK;
+}
+
+extern "C" int upkie_sim_episode_events_step_levels(UpkieSim* sim, double inertia_variation, const uint32_t* settings,
+                                                    const uint8_t* terminated, const uint8_t* truncated, uint32_t* calls, int32_t* remaining,
+                                                    uint32_t* pushes, uint32_t* episodes, uint32_t* level, uint32_t* episode_pushes,
+                                                    float* difficulty, float* force, float* body_inertials, float* link_scale, void* stream) {
+  EventsParams P;
+  const int status = events_levels_params(sim, inertia_variation, settings, calls, remaining, pushes, episodes, level, episode_pushes, difficulty,
+                                          force, body_inertials, link_scale, &P);
+  if (status != UPKIE_OK) return status;
+  const EventsLevels<true> S{(const unsigned*)settings, (unsigned*)level, (unsigned*)episode_pushes, difficulty};
+  hipLaunchKernelGGL(episode_events_kernel<true>, grid_for(sim->config.num_envs), dim3(block_lanes()), 0, (hipStream_t)stream, sim->config,
+                     sim->links, P, S, terminated, truncated, (unsigned*)calls, (int*)remaining, (unsigned*)pushes, (unsigned*)episodes, force,
+                     body_inertials, link_scale);
+  return check_hip(sim, hipGetLastError(), "episode_events_kernel<levels>");
+}
+
+extern "C" int upkie_sim_episode_events_reset_levels(UpkieSim* sim, double inertia_variation, const uint32_t* settings, uint32_t start_level,
+                                                     const uint8_t* mask, uint32_t* calls, int32_t* remaining, uint32_t* pushes,
+                                                     uint32_t* episodes, uint32_t* level, uint32_t* episode_pushes, float* difficulty,
+                                                     float* force, float* body_inertials, float* link_scale, void* stream) {
+  if (start_level > UPKIE_EVENTS_LEVELS_MAX)
+    return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "start_level must be at most " + std::to_string(UPKIE_EVENTS_LEVELS_MAX));
+  EventsParams P;
+  const int status = events_levels_params(sim, inertia_variation, settings, calls, remaining, pushes, episodes, level, episode_pushes, difficulty,
+                                          force, body_inertials, link_scale, &P);
+  if (status != UPKIE_OK) return status;
+  const EventsLevels<true> S{(const unsigned*)settings, (unsigned*)level, (unsigned*)episode_pushes, difficulty};
+  hipLaunchKernelGGL(episode_events_reset_kernel<true>, grid_for(sim->config.num_envs), dim3(block_lanes()), 0, (hipStream_t)stream,
+                     sim->config, sim->links, P, S, (unsigned)start_level, mask, (unsigned*)calls, (int*)remaining, (unsigned*)pushes,
+                     (unsigned*)episodes, force, body_inertials, link_scale);
+  return check_hip(sim, hipGetLastError(), "episode_events_reset_kernel<levels>");
+}
+
+extern "C" int upkie_sim_episode_events_level_counts(UpkieSim* sim, const uint32_t* level, uint32_t* counts, void* stream) {
+  if (!sim || !level || !counts) return fail(sim, UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  const int B = sim->config.num_envs;
+  const int status = check_hip(sim, hipMemsetAsync(counts, 0, sizeof(uint32_t) * (UPKIE_EVENTS_LEVELS_MAX + 1), (hipStream_t)stream),
+                               "episode_events_level_counts (zeroing)");
+  if (status != UPKIE_OK) return status;
+  const int blocks = std::min((B + EVENTS_COUNT_LANES - 1) / EVENTS_COUNT_LANES, EVENTS_COUNT_BLOCKS);
+  hipLaunchKernelGGL(episode_events_level_counts_kernel, dim3((unsigned)blocks), dim3(EVENTS_COUNT_LANES), 0, (hipStream_t)stream, B,
+                     (const unsigned*)level, (unsigned*)counts);
+  return check_hip(sim, hipGetLastError(), "episode_events_level_counts_kernel");
 }
 
 // Task targets (include/upkie_hip.h): the settings checked and converted; every refusal comes before any device use.

@@ -76,6 +76,7 @@ def _abi_table():
     controlled = "upkie_ppo_minibatch_update_controlled"
     asym = "upkie_mlp_actor_critic_asym"
     distill = "upkie_distill_minibatch_update"
+    levels = "upkie_sim_episode_events_step_levels"
     return (
         ("upkie_hip_device_count", status, None, None),
         ("upkie_hip_struct_bytes", C.c_int64, [C.c_int], "upkie_hip_struct_bytes"),  # (see _check_struct_sizes)
@@ -103,6 +104,10 @@ def _abi_table():
         # the episode events (random pushes, per-episode inertias)
         ("upkie_sim_episode_events_step", status, [vp, P(abi.UpkieEpisodeEvents)] + [vp] * 10, "upkie_sim_episode_events_step"),
         ("upkie_sim_episode_events_reset", status, [vp, P(abi.UpkieEpisodeEvents)] + [vp] * 9, "upkie_sim_episode_events_step"),
+        # the push curriculum: the events with per-env levels and their settings in a device block
+        ("upkie_sim_episode_events_step_levels", status, [vp, f64] + [vp] * 14, levels),
+        ("upkie_sim_episode_events_reset_levels", status, [vp, f64, vp, C.c_uint32] + [vp] * 12, levels),
+        ("upkie_sim_episode_events_level_counts", status, [vp, vp, vp, vp], levels),
         # the task targets (goals in the observation) and their curriculum
         ("upkie_sim_task_targets_step", status, [vp, P(abi.UpkieTaskTargets)] + [vp] * 11, "upkie_sim_task_targets_step"),
         ("upkie_sim_task_targets_reset", status, [vp, P(abi.UpkieTaskTargets)] + [vp] * 8, "upkie_sim_task_targets_step"),

@@ -560,7 +560,11 @@ class Ppo:
     resumed in fresh objects continues bit for bit. Schedules, ``reward_fn``, ``reward`` and ``events`` are code: give them to `load` again.
 
     ``events`` (a `upkie_amd.events.EpisodeEvents` built on ``env``) perturbs the rollout: random pushes and per-episode
-    inertias, one more launch per step, after the reward (`AgentStep`).
+    inertias, one more launch per step, after the reward (`AgentStep`). Built with a ``curriculum`` (`PushLevels`) every
+    env carries a push difficulty level, decided in that same launch from the env's own episodes: nothing to reduce, so
+    it runs under a ``process_group`` as it is; a record then carries ``rollout/push_level_mean`` and
+    ``rollout/push_level_top_frac``, and with ``live`` ``rollout/push_prob`` and ``rollout/push_norm_high`` (read once
+    per record, outside the rollout). A callback's ``events.set_push(...)`` is followed by the captured rollout.
 
     ``critic_observation`` (a `upkie_amd.privileged.PrivilegedObservation` built on ``env``, ``events`` and ``pipeline``)
     trains an asymmetric ``policy``: the critic reads the privileged row, the actor what the robot will see. One more
@@ -791,6 +795,8 @@ class Ppo:
                     record.update({f"rollout/ep_rew_{name}_mean": mean for name, mean in self.reward.term_means().items()})
                 if self.targets is not None:
                     record.update({f"rollout/{name}": value for name, value in self.targets.log().items()})
+                if hasattr(self.events, "log"):  # (a push curriculum's levels, live push settings; a plain stage adds nothing)
+                    record.update({f"rollout/{name}": value for name, value in self.events.log().items()})
                 self.records.append(record)
             if callback is not None and callback(self, record) is False:
                 break
