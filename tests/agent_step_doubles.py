@@ -1,7 +1,8 @@
 """Recording doubles for the stages around an agent step (the policy, the pipeline, the normaliser, the episode
 statistics, the reward, the evaluation tally) and a recorder around the CPU oracle env: what tests/test_ppo_rollout_step.py
 and tests/test_agent_step.py drive `Ppo` and `PolicyEvaluator` with. Every double logs its calls, in order and with the
-argument OBJECTS, in one `Calls`."""
+argument OBJECTS, in one `Calls`. And host stand-ins for the stages a driver saves (`stage`, `saved_parts`): what the
+file-layout tests of `Ppo` (tests/test_ppo_learn.py) and `Distillation` (tests/test_distill.py) save and load."""
 
 import types
 
@@ -147,3 +148,44 @@ class Tally:
 
     def step(self, reward, terminated, truncated):
         self.calls.add("tally", reward=reward, terminated=terminated, truncated=truncated)
+
+
+# ---------------------------------------------------------------- host stand-ins for what a driver's file holds
+def stage(cls, **attributes):
+    obj = cls.__new__(cls)  # (no device: the stage's own class around host tensors)
+    vars(obj).update(attributes)
+    return obj
+
+
+def filler(numbers, scale):
+    """``f(*shape, dtype=)``: a host tensor filled with the next of ``numbers`` times ``scale``, so that every tensor of
+    a set of stand-ins holds its own number and two sets (two scales) differ everywhere."""
+    fill = iter(numbers)
+    return lambda *shape, dtype=torch.float32: torch.full(shape, next(fill) * scale, dtype=dtype)
+
+
+def saved_parts(scale, pipeline, reward, stages=()):
+    """A stand-in env (2 envs, no persistent observation buffer: the driver supplies its own), an `MlpActorCritic` around
+    host tensors, and the keyword arguments of the stages asked for; ``stages`` names further ones (``events``,
+    ``targets``, ...) that only hold tensors."""
+    from tests.mlp_shapes import dims
+    from upkie_amd.policies import MlpActorCritic, mlp_shape
+
+    f = filler(range(100, 200), scale)
+    sim = types.SimpleNamespace(state=f(3, 2), reward=f(2), terminated=f(2, dtype=torch.uint8), truncated=f(2, dtype=torch.uint8))
+    env = types.SimpleNamespace(num_envs=2, sim=sim, _final_obs=f(2, 4), scale=scale)
+    env.state_tensors = lambda: dict(vars(sim), final_obs=env._final_obs)
+    shape = mlp_shape(dims(4, [8], 1), dims(4, [8], 1), "tanh", False, 3.0)
+    policy = stage(MlpActorCritic, shape=shape, packed=f(6), calls=f(2, dtype=torch.int32), seed=7 * scale, _out={"n": 2})
+    kwargs = {}
+    if pipeline:
+        tensors = {"prev_command": f(2, 1), "observation": f(2, 4), "calls": f(2, dtype=torch.int32)}
+        kwargs["pipeline"] = types.SimpleNamespace(num_envs=2, obs_dim=3, act_dim=1, stack=1, frame_dim=4, stacked_dim=4, state_tensors=lambda: tensors)
+    if reward:
+        terms = {"prev_action": f(1, 2), "term_sum": f(2, 2, dtype=torch.float64), "term_last": f(2, 2, dtype=torch.float64),
+                 "finished": f(2, dtype=torch.int32)}
+        kwargs["reward"] = types.SimpleNamespace(num_envs=2, obs_dim=3 if pipeline else 4, act_dim=1, state_tensors=lambda: terms)
+    for name in stages:
+        held = {"calls": f(2, dtype=torch.int32), "observation": f(2, 4)}
+        kwargs[name] = types.SimpleNamespace(num_envs=2, dim=3 if pipeline else 4, obs_dim=4, num_targets=0, state_tensors=lambda held=held: held)
+    return env, policy, kwargs

@@ -173,3 +173,46 @@ def row_rollout(row, shape, sources, seed=0):
     return {"observations": f32(obs, row.obs_dim), "actions": f32(actions, A), "log_probs": f32(log_prob + delta),
             "advantages": f32(rng.normal(0.3, 1.0, size=T * N)), "returns": f32(value + rng.normal(0.0, 1.0, size=T * N)),
             "values": f32(value + rng.normal(0.0, 0.2, size=T * N))}
+
+
+# ---------------------------------------------------------------- a trainer's case: policy, full buffer, state
+def trainer_case(case, seed=0, first=False, normalize=False):
+    """Policy (built from modules), a full rollout buffer of T x N samples whose actions, values and log-probs come from
+    the policy, perturbed old log-probs (none within 1e-3 of a clip bound unless `first`: every ratio is then 1)."""
+    from upkie_amd.rollout import RolloutBuffer
+
+    N, D, widths, A, act = case
+    torch.manual_seed(seed)
+    actor, critic = tower(D, widths, A, act).to(DEV), tower(D, widths, 1, act).to(DEV)
+    log_std = nn.Parameter(torch.full((A,), -0.5, device=DEV))
+    kw = {}
+    if normalize:
+        g = torch.Generator().manual_seed(seed + 1)
+        kw = dict(obs_mean=0.3 * torch.randn(D, generator=g), obs_var=torch.rand(D, generator=g) * 3 + 0.2, clip_obs=3.0)
+    pol = MlpActorCritic.from_modules(actor, critic, log_std, torch.full((A,), -1.0), torch.full((A,), 1.0), seed=seed, **kw)
+    buf = RolloutBuffer(T, N, obs_shape=(D,), action_shape=(A,), device=DEV)
+    gen = torch.Generator(DEV).manual_seed(seed + 7)
+    buf.observations.copy_(torch.randn(T, N, D, device=DEV, generator=gen))
+    for t in range(T):
+        pol.act(buf.observations[t], out={"action": buf.actions[t], "value": buf.values[t], "log_prob": buf.log_probs[t]})
+    rng = np.random.default_rng(seed)
+    if not first:
+        delta = rng.normal(0.0, 0.25, size=(T, N))
+        for bound in (1.2, 0.8):  # ratio = exp(-delta): keep it >= 1e-3 away from the clip bounds
+            near = np.abs(np.exp(-delta) - bound) < 1e-3
+            delta[near] += 0.01
+        buf.log_probs.add_(torch.as_tensor(delta, dtype=torch.float32, device=DEV))
+    buf.advantages = torch.as_tensor(rng.normal(0.3, 1.0, size=(T, N)), dtype=torch.float32, device=DEV)
+    buf.returns = (buf.values + torch.as_tensor(rng.normal(0.0, 1.0, size=(T, N)), dtype=torch.float32, device=DEV)).contiguous()
+    buf.values.add_(torch.as_tensor(rng.normal(0.0, 0.2, size=(T, N)), dtype=torch.float32, device=DEV))
+    buf.pos, buf.full = T, True
+    return pol, actor, critic, log_std, buf
+
+
+def trainer_state(pol, tr):
+    return [pol.packed.clone(), tr.m.clone(), tr.v.clone(), tr.scalars.clone()]
+
+
+def restore_trainer(pol, tr, st):
+    for dst, src in zip((pol.packed, tr.m, tr.v, tr.scalars), st):
+        dst.copy_(src)

@@ -52,7 +52,7 @@ def _policy(case, wseed, seed):
 
 
 def _setup(case, wseed, dseed, first=False):
-    """tests/test_ppo_gpu.py's _setup with separate seeds for the weights (`wseed`, the same on every rank) and for the
+    """tests/mlp_shapes.py's `trainer_case` with separate seeds for the weights (`wseed`, the same on every rank) and for the
     data and the policy's noise (`dseed`, one per rank)."""
     N, D, widths, A, act = case
     pol = _policy(case, wseed, dseed)

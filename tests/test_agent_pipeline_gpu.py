@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from tests import agent_pipeline_reference as P
 from tests.agent_pipeline_shapes import _dev, _np
+from tests.training_rig import pendulum, tower
 from upkie_amd.pipeline import AgentPipeline
 from upkie_amd.ppo import Ppo
 
@@ -134,29 +135,21 @@ def test_arithmetic_one_step_at_a_time_from_the_devices_own_state(noise):
 
 
 # ---------------------------------------------------------------- with an env and a policy
-def _tower(d_in, d_out):
-    return nn.Sequential(nn.Linear(d_in, 64), nn.Tanh(), nn.Linear(64, 64), nn.Tanh(), nn.Linear(64, d_out))
-
-
 def _reward(next_obs, info):
     return torch.abs(next_obs[:, 1]).mul_(-0.25).sub_(torch.abs(next_obs[:, 0])).add_(1.0)
 
 
 def _make(B, K=8, noise=True, shaped=True, limit=40):
-    import upkie_amd.envs as envs
     from upkie_amd.policies import MlpActorCritic
-    from upkie_amd.utils.robot_state import RobotState
-    from upkie_amd.utils.robot_state_randomization import RobotStateRandomization
 
     torch.manual_seed(0)
-    init = RobotState(randomization=RobotStateRandomization(pitch=0.1))
-    env = envs.make("Upkie-HIP-Pendulum-Vec", num_envs=B, frequency=200.0, init_state=init, autoreset_mode="same_step", max_episode_steps=limit)
+    env = pendulum(B, limit, pitch=0.1)
     dev = env.device
     pipe = AgentPipeline(B, 4, [-1.0], [1.0], 1.0 / 200.0, stack=K, integrate_action=shaped, action_lag=0.05 if shaped else None,
                          action_noise=[0.02] if noise else None, observation_noise=[0.002, 0.002, 0.01, 0.01] if noise else None, seed=3,
                          device=dev)
     D = pipe.stacked_dim
-    actor, critic = _tower(D, 1).to(dev), _tower(D, 1).to(dev)
+    actor, critic = tower(D, 1, 64).to(dev), tower(D, 1, 64).to(dev)
     log_std = nn.Parameter(torch.zeros(1, device=dev))
     bound = 2.0 if shaped else 1.0
     policy = MlpActorCritic.from_modules(actor, critic, log_std, action_low=[-bound], action_high=[bound], seed=0)

@@ -22,6 +22,7 @@ from tests import asymmetric_reference as AR
 from tests import asymmetric_shapes as AS
 from tests import mlp_shapes as S
 from tests import ppo_reference as PR
+from tests.training_rig import np64, pendulum, pitch_reward, rel, same, snapshot, tower
 from upkie_amd.ppo import PpoTrainer, trainable_offset
 from upkie_amd.rollout import RolloutBuffer
 
@@ -35,14 +36,6 @@ BOUND = AS.BOUNDS
 
 def _report(family, row, **figures):
     print(f"\nasymmetric {family} {AS.row_id(row)} " + " ".join(f"{k}={v:.3e}" if isinstance(v, float) else f"{k}={v}" for k, v in figures.items()))
-
-
-def _np(t):
-    return t.detach().double().cpu().numpy()
-
-
-def _rel(a, b):
-    return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30)
 
 
 def _bits(t):
@@ -66,12 +59,12 @@ def test_policy_against_the_twin(index, row, normalize):
     env_action, action, value, log_prob = pol.act(obs, deterministic=True, out={"mean": mean, "norm_obs": norm, "norm_critic_obs": cnorm},
                                                   critic_obs=cobs)
     torch.cuda.synchronize()
-    x64, m64, xc64, v64 = AR.forward(pol.shape, S.sources_of(pol), _np(obs), _np(cobs))
-    err = {"mean": np.abs(_np(mean) - m64).max(), "value": np.abs(_np(value) - v64).max(), "norm_obs": np.abs(_np(norm) - x64).max(),
-           "norm_critic_obs": np.abs(_np(cnorm) - xc64).max()}
+    x64, m64, xc64, v64 = AR.forward(pol.shape, S.sources_of(pol), np64(obs), np64(cobs))
+    err = {"mean": np.abs(np64(mean) - m64).max(), "value": np.abs(np64(value) - v64).max(), "norm_obs": np.abs(np64(norm) - x64).max(),
+           "norm_critic_obs": np.abs(np64(cnorm) - xc64).max()}
     from tests import mlp_reference as R
 
-    err["log_prob"] = np.abs(_np(log_prob) - R.log_prob(m64, m64, _np(log_std))).max()
+    err["log_prob"] = np.abs(np64(log_prob) - R.log_prob(m64, m64, np64(log_std))).max()
     _report("policy", row, normalize=normalize, **{k: float(v) for k, v in err.items()})
     assert err["norm_obs"] <= BOUND["norm_obs"] and err["norm_critic_obs"] <= BOUND["norm_obs"]
     assert err["mean"] <= BOUND["mean"]
@@ -185,8 +178,8 @@ def test_bootstrap_is_the_value_of_the_final_critic_row(index, row):
     want = torch.where(boot, reward0 + torch.tensor(0.97, dtype=torch.float32, device=DEV) * value, reward0)
     assert torch.equal(_bits(reward), _bits(want)), "reward + fl(gamma * value(final critic row)) where truncated, untouched elsewhere"
     assert int(boot.sum()) >= 1 and (int((~boot).sum()) >= 1 or N == 1)
-    _, _, _, v64 = AR.forward(pol.shape, S.sources_of(pol), np.zeros((N, row.obs_dim)), _np(final))
-    assert np.abs(_np(value) - v64).max() <= BOUND["value"]
+    _, _, _, v64 = AR.forward(pol.shape, S.sources_of(pol), np.zeros((N, row.obs_dim)), np64(final))
+    assert np.abs(np64(value) - v64).max() <= BOUND["value"]
 
 
 # ---------------------------------------------------------------- 4. PPO gradient launch
@@ -240,7 +233,7 @@ def test_gradient_against_the_twin(index, row, short, obs_normalized):
         assert not (np.abs(ratio - edge) < 1e-4).any(), "no sample's ratio within 1e-4 of a clip bound"
     m = tr.state_dict()["m"]
     assert len(m) == len(ref_grads)
-    errors = [_rel(_np(mm).reshape(g.shape) / float(BETA1_F32), g) for mm, g in zip(m, ref_grads)]
+    errors = [rel(np64(mm).reshape(g.shape) / float(BETA1_F32), g) for mm, g in zip(m, ref_grads)]
     worst = int(np.argmax(errors))
     plan = AR.plan(pol.shape)
     _report("gradient", row, size=size, obs_normalized=obs_normalized, W=AR.layout(pol.shape)["W"], nw=plan["nw"], chunks=PR.chunks(plan, size),
@@ -400,20 +393,6 @@ B, STEPS = 64, 8
 EVENTS = dict(push_prob=0.1, push_norm=(5.0, 20.0), push_steps=(1, 3), inertia_variation=0.2)
 
 
-def _tower(d_in, d_out):
-    return nn.Sequential(nn.Linear(d_in, 16), nn.Tanh(), nn.Linear(16, 16), nn.Tanh(), nn.Linear(16, d_out))
-
-
-def _reward(obs, info):
-    return torch.abs(obs[:, 0]).neg_().add_(1.0)
-
-
-def _pendulum(num_envs, limit, seed=0):
-    from tests.test_episode_events_gpu import _pendulum as make
-
-    return make(num_envs, limit, seed=seed)
-
-
 def _make(privileged=True, **kw):
     from upkie_amd.events import EpisodeEvents
     from upkie_amd.pipeline import AgentPipeline
@@ -422,38 +401,17 @@ def _make(privileged=True, **kw):
     from upkie_amd.privileged import PrivilegedObservation
 
     torch.manual_seed(0)
-    env = _pendulum(B, 5)
+    env = pendulum(B, 5, seed=0)
     dev = env.device
     events = EpisodeEvents(env, **EVENTS)
     pipeline = AgentPipeline(B, 4, [-1.0], [1.0], dt=1.0 / 200.0, stack=2, observation_noise=[0.01] * 4, action_lag=0.05, seed=5, device=dev)
     rows = PrivilegedObservation(env, events=events, pipeline=pipeline) if privileged else None
-    actor = _tower(pipeline.stacked_dim, 1).to(dev)
-    critic = _tower(rows.dim if privileged else pipeline.stacked_dim, 1).to(dev)
+    actor = tower(pipeline.stacked_dim, 1).to(dev)
+    critic = tower(rows.dim if privileged else pipeline.stacked_dim, 1).to(dev)
     policy = MlpActorCritic.from_modules(actor, critic, nn.Parameter(torch.zeros(1, device=dev)), action_low=[-1.0], action_high=[1.0], seed=0)
-    args = dict(n_steps=STEPS, n_epochs=2, batch_size=B * STEPS // 2, seed=0, reward_fn=_reward)
+    args = dict(n_steps=STEPS, n_epochs=2, batch_size=B * STEPS // 2, seed=0, reward_fn=pitch_reward)
     model = Ppo(env, policy, events=events, pipeline=pipeline, critic_observation=rows, **args, **kw)
     return env, policy, model, args
-
-
-def _snapshot(model):
-    torch.cuda.synchronize()
-    state = {k: v.clone() for k, v in model._state_tensors().items()}
-    for name in ("normalizer", "critic_normalizer"):
-        norm = getattr(model, name)
-        if norm is not None:
-            state[name] = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in norm.state_dict().items()}
-    state["buffer.critic_observations"] = model.buffer.critic_observations.clone()
-    return state, [dict(r) for r in model.records]
-
-
-def _same(a, b):
-    if isinstance(a, torch.Tensor):
-        return torch.equal(a, b)
-    if isinstance(a, dict):
-        return a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
-    if isinstance(a, (list, tuple)):
-        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
-    return a == b or (a != a and b != b)
 
 
 def test_ppo_with_a_privileged_critic_graphed_eager_and_resumed(tmp_path):
@@ -463,19 +421,19 @@ def test_ppo_with_a_privileged_critic_graphed_eager_and_resumed(tmp_path):
     assert policy.asymmetric and policy.critic_obs_dim == model.critic_observation.dim == 4 + 1 + 3 + len(model.critic_observation.links)
     with env:
         model.learn(2 * B * STEPS)
-        graphed = _snapshot(model)
+        graphed = snapshot(model, ("buffer.critic_observations",))
     env, policy, model, _ = _make(graph=False)
     with env:
         model._setup()
         model._slot = model.n_steps - 1  # (a graphed Ppo runs one real rollout step into the last slot before it captures)
         model._rollout_step()
         model.learn(2 * B * STEPS)
-        eager = _snapshot(model)
+        eager = snapshot(model, ("buffer.critic_observations",))
     keys = ("critic_observation.observation", "critic_observation.final_observation", "critic_normalizer", "packed", "m", "v", "events.force")
     assert all(k in graphed[0] for k in keys)
     for k in graphed[0]:
-        assert _same(graphed[0][k], eager[0][k]), k
-    assert _same(graphed[1], eager[1]) and len(graphed[1]) == 2
+        assert same(graphed[0][k], eager[0][k]), k
+    assert same(graphed[1], eager[1]) and len(graphed[1]) == 2
     assert float(graphed[0]["critic_normalizer"]["obs_count"]) > 2 * STEPS * B and graphed[0]["events.pushes"].sum() > 0
 
     path = str(tmp_path / "ppo.pt")
@@ -488,10 +446,10 @@ def test_ppo_with_a_privileged_critic_graphed_eager_and_resumed(tmp_path):
     with env:
         resumed = Ppo.load(path, env, policy, events=fresh.events, pipeline=fresh.pipeline, critic_observation=fresh.critic_observation, **args)
         resumed.learn(B * STEPS, reset_num_timesteps=False)
-        end = _snapshot(resumed)
+        end = snapshot(resumed, ("buffer.critic_observations",))
     for k in graphed[0]:
-        assert _same(graphed[0][k], end[0][k]), k
-    assert _same(graphed[1][1:], end[1])
+        assert same(graphed[0][k], end[0][k]), k
+    assert same(graphed[1][1:], end[1])
 
 
 def test_the_buffers_rows_are_the_twins_and_evaluation_ignores_the_critic():
@@ -534,16 +492,16 @@ def test_the_buffers_rows_are_the_twins_and_evaluation_ignores_the_critic():
         assert ended > 0 and np.abs(got[:, :, rows.segment("push_force")]).sum() > 0 and np.ptp(got[:, :, rows.segment("link_scale")]) > 0
 
         actor = model.policy._modules[0]
-        symmetric = MlpActorCritic.from_modules(actor, _tower(pipeline.stacked_dim, 1).to(env.device), model.policy._modules[2], action_low=[-1.0],
+        symmetric = MlpActorCritic.from_modules(actor, tower(pipeline.stacked_dim, 1).to(env.device), model.policy._modules[2], action_low=[-1.0],
                                                 action_high=[1.0], seed=0)
         results = []
         for pol in (policy, symmetric):
-            with _pendulum(32, 6, seed=9) as eval_env:
+            with pendulum(32, 6, seed=9) as eval_env:
                 from upkie_amd.pipeline import AgentPipeline
 
                 eval_pipe = AgentPipeline(32, 4, [-1.0], [1.0], dt=1.0 / 200.0, stack=2, observation_noise=[0.01] * 4, action_lag=0.05, seed=5,
                                           device=eval_env.device)
-                results.append(evaluate_policy(pol, eval_env, n_eval_episodes=48, reward_fn=_reward, seed=9, pipeline=eval_pipe, chunk=4,
+                results.append(evaluate_policy(pol, eval_env, n_eval_episodes=48, reward_fn=pitch_reward, seed=9, pipeline=eval_pipe, chunk=4,
                                                return_episode_rewards=True))
         assert results[0] == results[1] and len(results[0][0]) == 48
 

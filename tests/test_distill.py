@@ -180,7 +180,7 @@ def test_the_trainer_refuses_by_name():
 
 
 # ---------------------------------------------------------------- the driver on doubles
-from tests.agent_step_doubles import A, D, N, T, Calls, Env, Episodes, Normalizer, Pipeline, Policy  # noqa: E402
+from tests.agent_step_doubles import A, D, N, T, Calls, Env, Episodes, Normalizer, Pipeline, Policy, filler, saved_parts, stage  # noqa: E402
 
 
 class _Student(Policy):
@@ -385,6 +385,93 @@ def test_the_twins_launch_geometry_is_the_librarys():
         above += PR.chunks(plan, S.T * row.N) > plan["grid_cap"]
         waves.add(plan["nw"])
     assert above >= 1 and waves == {1, 2, 3, 4}
+
+
+# ---------------------------------------------------------------- Distillation.save / Distillation.load: what the file holds
+def _saved_distillation():
+    from upkie_amd.distill import DaggerMix, Distillation, DistillTrainer
+    from upkie_amd.episodes import EpisodeStatistics
+
+    class Saved(Distillation):
+        """`Distillation` whose stages are host stand-ins (as tests/test_ppo_learn.py's `_SavedPpo`)."""
+
+        def _setup(self):
+            if self.observations is not None:
+                return
+            scale = self.env.scale
+            f = filler(range(1, 100), scale)
+            self.observations, self.device, self.normalizer = object(), torch.device("cpu"), None
+            self.trainer = stage(DistillTrainer, m=f(6), v=f(6), scalars=f(2, dtype=torch.float64), generator=torch.Generator(), _lr=1e-3 * scale,
+                                 sync_modules=lambda: None)
+            self.trainer.generator.manual_seed(5 * scale)
+            self.episodes = stage(EpisodeStatistics, ep_return=f(2, dtype=torch.float64), ep_length=f(2, dtype=torch.int32),
+                                  ring_return=f(3, dtype=torch.float64), ring_length=f(3, dtype=torch.int32), counters=f(3, dtype=torch.int64),
+                                  means=f(2, dtype=torch.float64))
+            self.mix = stage(DaggerMix, calls=f(2, dtype=torch.int32), threshold=f(1, dtype=torch.int32))
+            self._starts, self._agent.raw_observation = f(2, dtype=torch.uint8), f(2, 4)
+
+    return Saved
+
+
+class _RawTeacher:
+    act_dim = A
+
+    def __call__(self, obs, out):
+        out.zero_()
+
+
+DISTILL_TENSORS = (["packed", "calls", "m", "v", "scalars", "mix.calls", "mix.threshold"]
+                   + ["episodes." + k for k in ("ep_return", "ep_length", "ring_return", "ring_length", "counters", "means")]
+                   + ["env." + k for k in ("state", "reward", "terminated", "truncated", "final_obs", "observation")])
+EXTRA_STAGES = ("events", "targets", "teacher_observation")
+
+
+@pytest.mark.parametrize("pipeline,reward,stages", [(False, False, ()), (True, False, ()), (False, True, ()), (False, True, EXTRA_STAGES)],
+                         ids=("plain", "pipeline", "reward", "every-stage"))
+def test_save_writes_these_names_and_load_puts_them_back(tmp_path, monkeypatch, pipeline, reward, stages):
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda device=None: None)
+    Saved, path = _saved_distillation(), str(tmp_path / "distill.pt")
+    env, student, kwargs = saved_parts(1, pipeline, reward, stages)
+    model = Saved(env, student, _RawTeacher(), n_steps=4, beta=0.25, **kwargs)
+    model._setup()
+    model.num_timesteps, model.iterations, model.total_timesteps, model.progress_remaining = 24, 3, 80, 0.7
+    model.save(path)
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    assert sorted(sd) == ["counters", "generator", "normalizer", "sizes", "tensors"]
+    names = DISTILL_TENSORS + [f"{s}.{k}" for s in kwargs for k in kwargs[s].state_tensors()]
+    assert sorted(sd["tensors"]) == sorted(names) and "starts" not in sd["tensors"]
+    for s, given in (("pipeline", pipeline), ("reward", reward), ("events", stages), ("targets", stages), ("teacher_observation", stages)):
+        assert any(k.startswith(s + ".") for k in sd["tensors"]) == bool(given), s
+    assert sd["counters"] == {"num_timesteps": 24, "iterations": 3, "total_timesteps": 80, "progress_remaining": 0.7, "policy_seed": 7, "beta": 0.25,
+                              "lr": 1e-3}
+    assert sd["sizes"] == {"n_envs": 2, "n_steps": 4} and sd["normalizer"] is None
+    # every name holds the tensor of the stage that owns it
+    tr, ep = model.trainer, model.episodes
+    owners = {"packed": student.packed, "calls": student.calls, "m": tr.m, "v": tr.v, "scalars": tr.scalars, "mix.calls": model.mix.calls,
+              "mix.threshold": model.mix.threshold, "env.state": env.sim.state, "env.reward": env.sim.reward, "env.terminated": env.sim.terminated,
+              "env.truncated": env.sim.truncated, "env.observation": model._agent.raw_observation, "env.final_obs": env._final_obs}
+    owners.update({f"episodes.{k}": v for k, v in ep.state_tensors().items()})
+    owners.update({f"{s}.{k}": v for s in kwargs for k, v in kwargs[s].state_tensors().items()})
+    assert owners.keys() == sd["tensors"].keys() and all(torch.equal(sd["tensors"][k], v) and sd["tensors"][k].dtype == v.dtype for k, v in owners.items())
+    # into fresh objects holding other numbers
+    env2, student2, kwargs2 = saved_parts(2, pipeline, reward, stages)
+    loaded = Saved.load(path, env2, student2, _RawTeacher(), n_steps=4, beta=0.5, **kwargs2)
+    assert all(torch.equal(sd["tensors"][k], v) for k, v in loaded._state_tensors().items()) and loaded._state_tensors().keys() == owners.keys()
+    assert torch.equal(student2.packed, student.packed) and torch.equal(loaded.episodes.counters, ep.counters) and student2.seed == 7
+    assert torch.equal(loaded.mix.threshold, model.mix.threshold) and torch.equal(loaded.trainer.scalars, tr.scalars)
+    assert torch.equal(loaded.trainer.generator.get_state(), tr.generator.get_state())
+    assert (loaded.num_timesteps, loaded.iterations, loaded.total_timesteps, loaded.progress_remaining) == (24, 3, 80, 0.7)
+    assert (loaded._beta, loaded.trainer._lr) == (0.25, 1e-3)
+    if not reward:  # a file without a stage's tensors does not load into a run with that stage: refused by name
+        env3, student3, kwargs3 = saved_parts(2, pipeline, True)
+        with pytest.raises(ValueError, match="the file has no reward.prev_action"):
+            Saved.load(path, env3, student3, _RawTeacher(), n_steps=4, **kwargs3)
+    if not stages and not pipeline:
+        env3, student3, kwargs3 = saved_parts(2, pipeline, reward, ("events",))
+        with pytest.raises(ValueError, match="the file has no events.calls"):
+            Saved.load(path, env3, student3, _RawTeacher(), n_steps=4, **kwargs3)
+    with pytest.raises(ValueError, match=r"the file holds a run of \{'n_envs': 2, 'n_steps': 4\}, this one is 2 envs x 5 steps"):
+        Saved.load(path, env2, student2, _RawTeacher(), n_steps=5, **kwargs2)
 
 
 # ---------------------------------------------------------------- the mix twin

@@ -19,6 +19,7 @@ from tests import asymmetric_shapes as AS
 from tests import distill_reference as R
 from tests import mlp_shapes as S
 from tests import ppo_reference as PR
+from tests.training_rig import bits, np64, pendulum, rel, same, snapshot, tower, warm_up_as_the_capture_does
 from upkie_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -27,14 +28,6 @@ DEV = S.DEV
 T = S.T
 BETA1_F32 = np.float32(1.0) - np.float32(0.9)
 GRAD_BOUND = S.DEFAULT_BOUNDS["grad"]
-
-
-def _np(t):
-    return t.detach().double().cpu().numpy()
-
-
-def _rel(a, b):
-    return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30)
 
 
 def _param(index, row):
@@ -97,7 +90,7 @@ def test_gradient_against_the_fp64_twin(index, row):
     # torch fp32 on the device, before the update writes the trained weights back into the modules: the row's own distance to the twin
     x = torch.as_tensor(R.normalized(shape, src0, obs), dtype=torch.float32, device=DEV)
     params = [p for m in actor if isinstance(m, nn.Linear) for p in (m.weight, m.bias)]
-    torch_grads = [_np(g) for g in torch.autograd.grad(nn.functional.mse_loss(actor(x), d_labels.reshape(total, A)), params)]
+    torch_grads = [np64(g) for g in torch.autograd.grad(nn.functional.mse_loss(actor(x), d_labels.reshape(total, A)), params)]
     tr = _trainer(pol, n_epochs=1, batch_size=total, max_grad_norm=1e9, seed=3)
     tr.prepare(d_obs, d_labels)
     packed0 = pol.packed.clone()
@@ -108,8 +101,8 @@ def test_gradient_against_the_fp64_twin(index, row):
     loss, grads, norm = R.minibatch(shape, src0, obs.astype(np.float64)[idx], labels.astype(np.float64)[idx])
     sl = R.actor_slice(shape)
     m = tr.state_dict()["m"]
-    errors = [_rel(_np(mm).reshape(g.shape) / float(BETA1_F32), g) for mm, g in zip(m[sl], grads[sl])]
-    torch_errors = [_rel(tg.reshape(g.shape), g) for tg, g in zip(torch_grads, grads[sl])]
+    errors = [rel(np64(mm).reshape(g.shape) / float(BETA1_F32), g) for mm, g in zip(m[sl], grads[sl])]
+    torch_errors = [rel(tg.reshape(g.shape), g) for tg, g in zip(torch_grads, grads[sl])]
     s = stats.double().cpu().numpy()[0, 0]
     plan = R.actor_plan(S.shape_of(row))  # (the launch's own geometry: the grid cap follows the actor's span)
     print(f"\ndistill gradient {S.row_id(row)} nw={plan['nw']} grad={max(errors):.3e} torch_grad={max(torch_errors):.3e} bound_grad={GRAD_BOUND:.0e} "
@@ -168,14 +161,14 @@ def _check_full_update(pol, shape, src0, obs, labels):
         assert max_grad_norm == 1.0 or np.all(ref_stats[:, :, 2] < 1.0), "the clip bites at every minibatch"
         for p0, grads, coef in trace:
             parted = [d + R.step_bound(p, g, coef, lr) for d, p, g in zip(parted, p0, grads)]
-        got = [_np(p) for p in pol.sources()[pol.n_fixed:]]
+        got = [np64(p) for p in pol.sources()[pol.n_fixed:]]
         for k, (p1, pr, bound) in enumerate(zip(got, R.trainable(shape, src), parted)):
             err = np.abs(p1.reshape(pr.shape) - pr)
             worst = max(worst, float(np.max(err / bound)))
             assert np.all(err <= bound), (k, max_grad_norm, worst)
         for got_s, want in ((sd["m"], m), (sd["v"], v)):
             for a, b in zip(got_s[sl], want[sl]):
-                assert _rel(_np(a).reshape(b.shape), b) <= 1e-4
+                assert rel(np64(a).reshape(b.shape), b) <= 1e-4
         _unchanged_words(pol, tr, packed0)
     assert any(np.any(a != b) for a, b in zip(R.trainable(shape, src)[sl], params_start[sl])), "the update moved the actor"
     return worst
@@ -277,10 +270,6 @@ def _mix(num_envs, act_dim, offset, beta=0.0):
     return sim, DaggerMix(sim, act_dim, low, high, beta)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 @pytest.mark.parametrize("num_envs,act_dim", R.mix_cases())
 def test_the_mix_is_the_twin_after_every_call(num_envs, act_dim):
     sim, mix = _mix(num_envs, act_dim, R.MIX_OFFSET)
@@ -296,7 +285,7 @@ def test_the_mix_is_the_twin_after_every_call(num_envs, act_dim):
             want, drove = twin.step(label, student)
             torch.cuda.synchronize()
             assert np.array_equal(mix.drove.cpu().numpy(), drove), (beta, c)
-            assert np.array_equal(_bits(applied.cpu().numpy()), _bits(want)), (beta, c)
+            assert np.array_equal(bits(applied.cpu().numpy()), bits(want)), (beta, c)
             assert np.array_equal(mix.calls.cpu().numpy().view(np.uint32), twin.calls), (beta, c)
             teacher_rows += int(drove.sum())
         assert teacher_rows == {0.0: 0, 1.0: R.MIX_CALLS * num_envs}.get(beta, teacher_rows)
@@ -343,27 +332,14 @@ def test_two_shards_of_32_are_one_batch_of_64_and_a_captured_loop_follows_beta()
 
 # ---------------------------------------------------------------- the driver
 B, STEPS, SEED = 64, 8, 5
-
-
-def _tower(d_in, d_out, width=32):
-    return nn.Sequential(nn.Linear(d_in, width), nn.Tanh(), nn.Linear(width, width), nn.Tanh(), nn.Linear(width, d_out))
-
-
-def _pendulum(num_envs=B, limit=6, seed=0):
-    import upkie_amd.envs as envs
-    from upkie_amd.utils.robot_state import RobotState
-    from upkie_amd.utils.robot_state_randomization import RobotStateRandomization
-
-    init = RobotState(randomization=RobotStateRandomization(pitch=0.3))
-    return envs.make("Upkie-HIP-Pendulum-Vec", num_envs=num_envs, frequency=200.0, init_state=init, autoreset_mode="same_step",
-                     max_episode_steps=limit, seed=seed)
+STORED = ("observations", "labels", "drove")  # (what a rollout stores: part of every snapshot)
 
 
 def _actor_critic(d_in, seed, dev, low=-1.0, high=1.0, **kw):
     from upkie_amd.policies import MlpActorCritic
 
     torch.manual_seed(seed)
-    return MlpActorCritic.from_modules(_tower(d_in, 1).to(dev), _tower(d_in, 1).to(dev), nn.Parameter(torch.zeros(1, device=dev)),
+    return MlpActorCritic.from_modules(tower(d_in, 1, 32).to(dev), tower(d_in, 1, 32).to(dev), nn.Parameter(torch.zeros(1, device=dev)),
                                        action_low=[low], action_high=[high], seed=seed, **kw)
 
 
@@ -372,7 +348,7 @@ def _make(staged=False, teacher_kind="mlp", **kw):
     own, and (``staged``) a student behind a pipeline with targets and events."""
     from upkie_amd.distill import Distillation
 
-    env = _pendulum()
+    env = pendulum(B, 6, seed=0)
     dev = env.device
     args = dict(n_steps=STEPS, n_epochs=2, batch_size=B * STEPS // 2, seed=SEED, beta=0.5)
     raw = 4
@@ -404,31 +380,6 @@ def _make(staged=False, teacher_kind="mlp", **kw):
     return env, student, teacher, Distillation(env, student, teacher, **args)
 
 
-def _warm_up_as_the_capture_does(model):
-    model._setup()
-    model._slot = model.n_steps - 1
-    model._rollout_step()
-
-
-def _snapshot(model):
-    torch.cuda.synchronize()
-    state = {k: v.clone() for k, v in model._state_tensors().items()}
-    if model.normalizer is not None:
-        state["normalizer"] = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in model.normalizer.state_dict().items()}
-    state.update(observations=model.observations.clone(), labels=model.labels.clone(), drove=model.drove.clone())
-    return state, [dict(r) for r in model.records]
-
-
-def _same(a, b):
-    if isinstance(a, torch.Tensor):
-        return torch.equal(a, b)
-    if isinstance(a, dict):
-        return a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
-    if isinstance(a, (list, tuple)):
-        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
-    return a == b or (a != a and b != b)
-
-
 ITERATIONS = 3
 RECORD_KEYS = ("distill/loss", "distill/grad_norm", "distill/beta", "distill/teacher_drove_frac", "rollout/ep_rew_mean", "rollout/ep_len_mean",
                "time/total_timesteps", "time/iterations")
@@ -440,16 +391,16 @@ def test_graphed_equals_eager_bit_for_bit(staged):
     env, student, teacher, model = _make(staged, graph=True, **schedule)
     with env:
         model.learn(ITERATIONS * B * STEPS)
-        graphed = _snapshot(model)
+        graphed = snapshot(model, STORED)
     env, student, teacher, model = _make(staged, graph=False, **schedule)
     with env:
-        _warm_up_as_the_capture_does(model)
+        warm_up_as_the_capture_does(model)
         model.learn(ITERATIONS * B * STEPS)
-        eager = _snapshot(model)
+        eager = snapshot(model, STORED)
     assert all(k in graphed[0] for k in ("packed", "m", "v", "scalars", "mix.calls", "mix.threshold", "calls"))
     for k in graphed[0]:
-        assert _same(graphed[0][k], eager[0][k]), k
-    assert _same(graphed[1], eager[1]) and len(graphed[1]) == ITERATIONS
+        assert same(graphed[0][k], eager[0][k]), k
+    assert same(graphed[1], eager[1]) and len(graphed[1]) == ITERATIONS
     for i, record in enumerate(graphed[1]):
         assert all(k in record for k in RECORD_KEYS), sorted(record)
         assert 0.0 < record["distill/teacher_drove_frac"] < 1.0 and record["distill/loss"] > 0.0
@@ -469,9 +420,9 @@ def test_a_linear_and_a_privileged_teacher_survive_capture(teacher_kind, staged)
         env, student, teacher, model = _make(staged, teacher_kind, graph=graph)
         with env:
             if not graph:
-                _warm_up_as_the_capture_does(model)
+                warm_up_as_the_capture_does(model)
             model.learn(2 * B * STEPS)
-            results.append(_snapshot(model))
+            results.append(snapshot(model, STORED))
             torch.cuda.synchronize()
             if teacher_kind == "linear":
                 assert type(model.teacher).__name__ == "LinearTeacher" and model.teacher_observation is None
@@ -485,8 +436,8 @@ def test_a_linear_and_a_privileged_teacher_survive_capture(teacher_kind, staged)
                 assert want.shape == model.labels[0].shape and float(model.labels.abs().sum()) > 0.0
                 assert "teacher_observation.observation" in results[-1][0]
     for k in results[0][0]:
-        assert _same(results[0][0][k], results[1][0][k]), k
-    assert _same(results[0][1], results[1][1]) and len(results[0][1]) == 2
+        assert same(results[0][0][k], results[1][0][k]), k
+    assert same(results[0][1], results[1][1]) and len(results[0][1]) == 2
 
 
 def test_a_run_saved_after_two_iterations_resumes_bit_for_bit(tmp_path):
@@ -496,7 +447,7 @@ def test_a_run_saved_after_two_iterations_resumes_bit_for_bit(tmp_path):
     env, student, teacher, model = _make(True, graph=True)
     with env:
         model.learn(ITERATIONS * B * STEPS)
-        whole = _snapshot(model)
+        whole = snapshot(model, STORED)
     env, student, teacher, model = _make(True, graph=True)
     with env:
         model.learn(ITERATIONS * B * STEPS, callback=lambda m, rec: m.iterations < 2)
@@ -507,10 +458,10 @@ def test_a_run_saved_after_two_iterations_resumes_bit_for_bit(tmp_path):
         resumed = Distillation.load(path, env, student, teacher, n_steps=STEPS, n_epochs=2, batch_size=B * STEPS // 2, seed=SEED, beta=0.5,
                                     targets=fresh.targets, pipeline=fresh.pipeline, events=fresh.events)
         resumed.learn(B * STEPS, reset_num_timesteps=False)
-        end = _snapshot(resumed)
+        end = snapshot(resumed, STORED)
     for k in whole[0]:
-        assert _same(whole[0][k], end[0][k]), k
-    assert _same(whole[1][2:], end[1])
+        assert same(whole[0][k], end[0][k]), k
+    assert same(whole[1][2:], end[1])
 
 
 @pytest.mark.parametrize("staged", (False, True), ids=("plain", "pipeline-targets-events"))
@@ -539,11 +490,11 @@ def test_the_buffer_holds_what_the_twins_give_on_the_recorded_observations(stage
             row = rows[t]
             assert torch.equal(model.observations[t], row["seen"]), t
             assert row["raw"].shape[1] == (5 if staged else 4) and row["seen"].shape[1] == (12 if staged else 4)
-            want = R.mean_of(teacher.shape, src, _np(row["raw"]))
-            assert np.abs(_np(model.labels[t]) - want).max() <= S.DEFAULT_BOUNDS["mean"], t
+            want = R.mean_of(teacher.shape, src, np64(row["raw"]))
+            assert np.abs(np64(model.labels[t]) - want).max() <= S.DEFAULT_BOUNDS["mean"], t
             applied, drove = twin.step(model.labels[t].cpu().numpy(), row["action"].cpu().numpy())
             assert np.array_equal(model.drove[t].cpu().numpy(), drove), t
-            assert np.array_equal(_bits(row["applied"].cpu().numpy()), _bits(applied)), t
+            assert np.array_equal(bits(row["applied"].cpu().numpy()), bits(applied)), t
         assert 0 < int(model.drove.sum()) < B * STEPS
 
 
@@ -551,7 +502,7 @@ def test_ppo_takes_a_distilled_student_over_with_its_normaliser():
     from upkie_amd.ppo import Ppo
 
     env, student, teacher, model = _make(False, graph=True)
-    with env, _pendulum(32) as smaller:
+    with env, pendulum(32, 6, seed=0) as smaller:
         model.learn(2 * B * STEPS)
         statistics = model.normalizer.obs_mean.clone()
         with pytest.raises(ValueError, match=f"the policy's normaliser serves {B} envs at gamma 0.99, this run has 32 at 0.99"):
@@ -573,18 +524,18 @@ def test_an_eval_callback_leaves_the_run_alone():
 
     def learn(with_callback):
         env, student, teacher, model = _make(False, graph=True)
-        with env, _pendulum(32, 6, seed=9) as eval_env:
+        with env, pendulum(32, 6, seed=9) as eval_env:
             callback = EvalCallback(eval_env, n_eval_episodes=48, eval_freq=STEPS, seed=9, chunk=4) if with_callback else None
             model.learn(2 * B * STEPS, callback=callback)
             if with_callback:
                 assert len(callback.evaluations["timesteps"]) == 2 and all("eval/mean_reward" in r for r in model.records)
-            return _snapshot(model)
+            return snapshot(model, STORED)
 
     plain, evald = learn(False), learn(True)
     for k in plain[0]:
-        assert _same(plain[0][k], evald[0][k]), k
+        assert same(plain[0][k], evald[0][k]), k
     strip = lambda records: [{k: v for k, v in r.items() if not k.startswith("eval/")} for r in records]  # noqa: E731
-    assert _same(strip(plain[1]), strip(evald[1]))
+    assert same(strip(plain[1]), strip(evald[1]))
 
 
 @pytest.mark.parametrize("beta", (0.0, 1.0))

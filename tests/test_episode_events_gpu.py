@@ -6,7 +6,6 @@ the example."""
 import os
 import subprocess
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -14,6 +13,8 @@ import torch
 import torch.nn as nn
 
 from tests import episode_events_reference as R
+from tests.training_rig import (bits, check_event_records, events_stage, pendulum, pitch_reward, read_state, same, snapshot, tower,
+                                warm_up_as_the_capture_does)
 from upkie_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -29,29 +30,7 @@ def model():
 
 
 def _stage(model, num_envs, offset, seed=R.GPU_SEED, **settings):
-    """A simulation handle that is never stepped, and the stage on it."""
-    from upkie_amd.events import EpisodeEvents
-    from upkie_amd.sim import BatchedSim
-
-    cfg = abi.default_sim_config(num_envs, seed=seed)
-    cfg.env_id_offset = offset
-    sim = BatchedSim(cfg, model.struct)
-    env = types.SimpleNamespace(sim=sim, model=model, num_envs=num_envs, device=sim.device)
-    return sim, EpisodeEvents(env, **(settings or R.GPU_SETTINGS))
-
-
-def _read(events):
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy().copy() for k, v in events.state_tensors().items()}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _check_records(got, want, envs):
-    np.testing.assert_allclose(got["link_scale"][:, envs], want["link_scale"][:, envs], atol=1e-6, rtol=0.0)
-    np.testing.assert_allclose(got["body_inertials"][:, envs].astype(np.float64), want["body_inertials"][:, envs], rtol=3e-5, atol=1e-9)
+    return events_stage(model, num_envs, offset, seed, **(settings or R.GPU_SETTINGS))
 
 
 @pytest.mark.parametrize("num_envs,offset", R.GPU_SIZES)
@@ -63,29 +42,29 @@ def test_the_kernel_is_the_twin_after_every_call(model, num_envs, offset):
     term, trunc = R.gpu_flags(num_envs, offset)
     d_term, d_trunc = torch.from_numpy(term).to(sim.device), torch.from_numpy(trunc).to(sim.device)
     every = np.arange(num_envs)
-    prev = _read(events)
-    _check_records(prev, twin.snapshot(), every)  # construction: episode 0
+    prev = read_state(events)
+    check_event_records(prev, twin.snapshot(), every)  # construction: episode 0
     worst_force, worst_record, starts = 0.0, 0.0, 0
     for t in range(R.GPU_CALLS):
         events.step(d_term[t], d_trunc[t])
         happened = twin.step(term[t], trunc[t])
-        got, want = _read(events), twin.snapshot()
+        got, want = read_state(events), twin.snapshot()
         for name in ("calls", "remaining", "pushes", "episodes"):
-            assert np.array_equal(_bits(got[name]), _bits(want[name].astype(np.uint32) if name != "remaining" else want[name])), (name, t)
+            assert np.array_equal(bits(got[name]), bits(want[name].astype(np.uint32) if name != "remaining" else want[name])), (name, t)
         force, before = got["force"][0], prev["force"][0]
-        assert np.all(_bits(force[:, happened["zero"]]) == 0), "a free step without a start: +0.0 in every word"
-        assert np.array_equal(_bits(force[:, happened["hold"]]), _bits(before[:, happened["hold"]])), "a held force is not written"
+        assert np.all(bits(force[:, happened["zero"]]) == 0), "a free step without a start: +0.0 in every word"
+        assert np.array_equal(bits(force[:, happened["hold"]]), bits(before[:, happened["hold"]])), "a held force is not written"
         s = happened["start"]
         if s.any():
             worst_force = max(worst_force, float(np.abs(force[:, s].astype(np.float64) - want["force"][:, s]).max()))
             starts += int(s.sum())
         done = happened["redrawn"]
         if done.any():
-            _check_records(got, want, np.flatnonzero(done))
+            check_event_records(got, want, np.flatnonzero(done))
             ref = want["body_inertials"][:, done]
             worst_record = max(worst_record, float((np.abs(got["body_inertials"][:, done] - ref) / (3e-5 * np.abs(ref) + 1e-9)).max()))
         for name in ("body_inertials", "link_scale"):
-            assert np.array_equal(_bits(got[name][:, ~done]), _bits(prev[name][:, ~done])), f"{name} of envs that did not end is not written"
+            assert np.array_equal(bits(got[name][:, ~done]), bits(prev[name][:, ~done])), f"{name} of envs that did not end is not written"
         prev = got
     print(f"N = {num_envs}, offset {offset}: {starts} starts, worst |force - twin| {worst_force:.3g} N (bound {2e-6 * MAX_NORM:.3g}), "
           f"worst record error / bound {worst_record:.3g}")
@@ -104,27 +83,27 @@ def test_reset_gives_randomize_inertias_and_a_mask_restarts_only_its_envs(model)
     want = {"body_inertials": other.randomize_inertias(0.3).cpu().numpy().astype(np.float64), "link_scale": other.link_scale.cpu().numpy()}
     term, trunc = R.gpu_flags(N, offset)
     d_term, d_trunc = torch.from_numpy(term).to(sim.device), torch.from_numpy(trunc).to(sim.device)
-    _check_records(_read(events), want, np.arange(N))
+    check_event_records(read_state(events), want, np.arange(N))
     for t in range(12):
         events.step(d_term[t], d_trunc[t])
-    moved = _read(events)
+    moved = read_state(events)
     assert moved["episodes"].max() >= 1 and moved["pushes"].max() >= 1 and np.all(moved["calls"] == 12)
     mask = np.zeros(N, dtype=np.uint8)
     mask[::3] = 1
     events.reset(torch.from_numpy(mask).to(sim.device))
-    got, m = _read(events), mask.astype(bool)
+    got, m = read_state(events), mask.astype(bool)
     for name in ("calls", "remaining", "pushes", "episodes"):
         assert np.all(got[name][m] == 0) and np.array_equal(got[name][~m], moved[name][~m]), name
-    assert np.all(_bits(got["force"][0][:, m]) == 0)
+    assert np.all(bits(got["force"][0][:, m]) == 0)
     for name in ("force", "body_inertials", "link_scale"):
-        assert np.array_equal(_bits(got[name][..., ~m]), _bits(moved[name][..., ~m])), name
-    _check_records(got, want, np.flatnonzero(m))
+        assert np.array_equal(bits(got[name][..., ~m]), bits(moved[name][..., ~m])), name
+    check_event_records(got, want, np.flatnonzero(m))
     events.reset()
-    got = _read(events)
+    got = read_state(events)
     assert all(not got[name].any() for name in ("calls", "remaining", "pushes", "episodes", "force"))
-    _check_records(got, want, np.arange(N))
+    check_event_records(got, want, np.arange(N))
     # the same bits as the handle's own draw: one arithmetic, one key
-    assert np.array_equal(_bits(got["body_inertials"]), _bits(other.body_inertials.cpu().numpy()))
+    assert np.array_equal(bits(got["body_inertials"]), bits(other.body_inertials.cpu().numpy()))
     sim.close()
     other.close()
 
@@ -139,7 +118,7 @@ def test_one_handle_of_64_is_two_of_32_bit_for_bit(model):
         trace = []
         for t in range(R.GPU_CALLS):
             events.step(d_term[t], d_trunc[t])
-            trace.append(_read(events))
+            trace.append(read_state(events))
         sim.close()
         return trace
 
@@ -147,27 +126,16 @@ def test_one_handle_of_64_is_two_of_32_bit_for_bit(model):
     for lo in (0, 32):
         for a, b in zip(whole, run(32, lo, lo)):
             for name in a:
-                assert np.array_equal(_bits(a[name][..., lo:lo + 32]), _bits(b[name])), name
+                assert np.array_equal(bits(a[name][..., lo:lo + 32]), bits(b[name])), name
 
 
 # ---------------------------------------------------------------- the step kernels read what the stage wrote
-def _pendulum(num_envs, limit, seed=3, pitch=0.3, model=None):
-    import upkie_amd.envs as envs
-    from upkie_amd.utils.robot_state import RobotState
-    from upkie_amd.utils.robot_state_randomization import RobotStateRandomization
-
-    init = RobotState(randomization=RobotStateRandomization(pitch=pitch))
-    extra = {} if model is None else {"model": model}
-    return envs.make("Upkie-HIP-Pendulum-Vec", num_envs=num_envs, frequency=200.0, init_state=init, autoreset_mode="same_step",
-                     max_episode_steps=limit, seed=seed, **extra)
-
-
 def test_the_sim_steps_under_the_force_and_the_records_the_stage_wrote(model):
     from upkie_amd.events import EpisodeEvents
 
     N = 65
     rng = np.random.default_rng(8)
-    with _pendulum(N, 7, model=model) as a, _pendulum(N, 7, model=model) as b, _pendulum(N, 7, model=model) as plain:
+    with pendulum(N, 7, seed=3, model=model) as a, pendulum(N, 7, seed=3, model=model) as b, pendulum(N, 7, seed=3, model=model) as plain:
         events = EpisodeEvents(a, push_prob=0.5, push_norm=(5.0, 20.0), push_steps=(1, 3), inertia_variation=0.3)
         body, point, _ = model.link_attachment("torso")
         assert body == 0
@@ -206,51 +174,19 @@ B, T = 64, 8
 SETTINGS = dict(push_prob=0.1, push_norm=(5.0, 20.0), push_steps=(1, 3), inertia_variation=0.2)
 
 
-def _tower(d_in, d_out):
-    return nn.Sequential(nn.Linear(d_in, 16), nn.Tanh(), nn.Linear(16, 16), nn.Tanh(), nn.Linear(16, d_out))
-
-
-def _reward(obs, info):
-    return torch.abs(obs[:, 0]).neg_().add_(1.0)
-
-
 def _make(with_events=True, **kw):
     from upkie_amd.events import EpisodeEvents
     from upkie_amd.policies import MlpActorCritic
     from upkie_amd.ppo import Ppo
 
     torch.manual_seed(0)
-    env = _pendulum(B, 5, seed=0)
+    env = pendulum(B, 5, seed=0)
     dev = env.device
-    policy = MlpActorCritic.from_modules(_tower(4, 1).to(dev), _tower(4, 1).to(dev), nn.Parameter(torch.zeros(1, device=dev)), action_low=[-1.0],
+    policy = MlpActorCritic.from_modules(tower(4, 1).to(dev), tower(4, 1).to(dev), nn.Parameter(torch.zeros(1, device=dev)), action_low=[-1.0],
                                          action_high=[1.0], seed=0)
     events = EpisodeEvents(env, **SETTINGS) if with_events else None
-    model = Ppo(env, policy, n_steps=T, n_epochs=2, batch_size=B * T // 2, seed=0, reward_fn=_reward, events=events, **kw)
+    model = Ppo(env, policy, n_steps=T, n_epochs=2, batch_size=B * T // 2, seed=0, reward_fn=pitch_reward, events=events, **kw)
     return env, policy, model
-
-
-def _warm_up_as_the_capture_does(model):
-    """A graphed `Ppo` runs one real rollout step into the last slot before it captures; the same by hand."""
-    model._setup()
-    model._slot = model.n_steps - 1
-    model._rollout_step()
-
-
-def _snapshot(model):
-    torch.cuda.synchronize()
-    state = {k: v.clone() for k, v in model._state_tensors().items()}
-    state["normalizer"] = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in model.normalizer.state_dict().items()}
-    return state, [dict(r) for r in model.records]
-
-
-def _same(a, b):
-    if isinstance(a, torch.Tensor):
-        return torch.equal(a, b)
-    if isinstance(a, dict):
-        return a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
-    if isinstance(a, (list, tuple)):
-        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
-    return a == b or (a != a and b != b)
 
 
 EVENT_KEYS = ("events.calls", "events.remaining", "events.pushes", "events.episodes", "events.force", "events.body_inertials", "events.link_scale")
@@ -260,22 +196,22 @@ def test_ppo_with_events_graphed_equals_not_graphed():
     env, policy, model = _make(graph=True)
     with env:
         model.learn(2 * B * T)
-        graphed = _snapshot(model)
+        graphed = snapshot(model)
     env, policy, model = _make(graph=False)
     with env:
-        _warm_up_as_the_capture_does(model)
+        warm_up_as_the_capture_does(model)
         model.learn(2 * B * T)
-        eager = _snapshot(model)
+        eager = snapshot(model)
     assert all(k in graphed[0] for k in EVENT_KEYS + ("packed", "m", "v"))
     for k in graphed[0]:
-        assert _same(graphed[0][k], eager[0][k]), k
-    assert _same(graphed[1], eager[1]) and len(graphed[1]) == 2 and all("train/loss" in r for r in graphed[1])
+        assert same(graphed[0][k], eager[0][k]), k
+    assert same(graphed[1], eager[1]) and len(graphed[1]) == 2 and all("train/loss" in r for r in graphed[1])
     assert int(graphed[0]["events.calls"][0]) == 2 * T + 1 and graphed[0]["events.pushes"].sum() > 0 and graphed[0]["events.episodes"].sum() > 0
     # and the events change the run: without them it ends elsewhere
     env, policy, model = _make(with_events=False, graph=True)
     with env:
         model.learn(2 * B * T)
-        plain = _snapshot(model)
+        plain = snapshot(model)
     assert not any(k.startswith("events.") for k in plain[0]) and not torch.equal(plain[0]["packed"], graphed[0]["packed"])
 
 
@@ -287,7 +223,7 @@ def test_ppo_with_events_resumes_bit_for_bit(tmp_path):
     env, policy, model = _make(graph=True)
     with env:
         model.learn(2 * B * T)
-        whole = _snapshot(model)
+        whole = snapshot(model)
     env, policy, model = _make(graph=True)
     with env:
         model.learn(2 * B * T, callback=lambda m, rec: m.iterations < 1)
@@ -295,12 +231,12 @@ def test_ppo_with_events_resumes_bit_for_bit(tmp_path):
         model.save(path)
     env, policy, fresh = _make(graph=True)
     with env:
-        resumed = Ppo.load(path, env, policy, n_steps=T, n_epochs=2, batch_size=B * T // 2, seed=0, reward_fn=_reward, events=fresh.events)
+        resumed = Ppo.load(path, env, policy, n_steps=T, n_epochs=2, batch_size=B * T // 2, seed=0, reward_fn=pitch_reward, events=fresh.events)
         resumed.learn(B * T, reset_num_timesteps=False)
-        end = _snapshot(resumed)
+        end = snapshot(resumed)
     for k in whole[0]:
-        assert _same(whole[0][k], end[0][k]), k
-    assert _same(whole[1][1:], end[1])
+        assert same(whole[0][k], end[0][k]), k
+    assert same(whole[1][1:], end[1])
     # a file written without events loads as before, and not into a run with events
     env, policy, model = _make(with_events=False, graph=False)
     with env:
@@ -308,9 +244,9 @@ def test_ppo_with_events_resumes_bit_for_bit(tmp_path):
         model.save(path)
     env, policy, model = _make(with_events=False, graph=False)
     with env:
-        assert Ppo.load(path, env, policy, n_steps=T, n_epochs=2, batch_size=B * T // 2, seed=0, graph=False, reward_fn=_reward).iterations == 1
+        assert Ppo.load(path, env, policy, n_steps=T, n_epochs=2, batch_size=B * T // 2, seed=0, graph=False, reward_fn=pitch_reward).iterations == 1
         with pytest.raises(ValueError, match="events.calls"):
-            Ppo.load(path, env, policy, n_steps=T, n_epochs=2, batch_size=B * T // 2, seed=0, graph=False, reward_fn=_reward,
+            Ppo.load(path, env, policy, n_steps=T, n_epochs=2, batch_size=B * T // 2, seed=0, graph=False, reward_fn=pitch_reward,
                      events=EpisodeEvents(env, **SETTINGS))
 
 
@@ -320,34 +256,34 @@ def test_an_eval_callback_with_events_of_its_own_leaves_training_alone():
 
     def learn(with_callback):
         env, policy, model = _make(graph=True)
-        with env, _pendulum(32, 6, seed=9) as eval_env:
+        with env, pendulum(32, 6, seed=9) as eval_env:
             callback, eval_events = None, None
             if with_callback:
                 eval_events = EpisodeEvents(eval_env, push_prob=0.5, push_norm=(5.0, 20.0), push_steps=(1, 2))
-                callback = EvalCallback(eval_env, n_eval_episodes=48, eval_freq=T, reward_fn=_reward, seed=9, events=eval_events, chunk=4)
+                callback = EvalCallback(eval_env, n_eval_episodes=48, eval_freq=T, reward_fn=pitch_reward, seed=9, events=eval_events, chunk=4)
             model.learn(2 * B * T, callback=callback)
-            result = _snapshot(model)
+            result = snapshot(model)
             if with_callback:
                 assert int(eval_events.pushes.sum()) > 0, "the evaluation env is pushed"
                 assert len(callback.evaluations["timesteps"]) == 2 and all("eval/mean_reward" in r for r in model.records)
                 # graphed and eager evaluations under events give the same episodes
-                runs = [evaluate_policy(policy, eval_env, n_eval_episodes=48, reward_fn=_reward, seed=9, events=eval_events, chunk=4, graph=g,
+                runs = [evaluate_policy(policy, eval_env, n_eval_episodes=48, reward_fn=pitch_reward, seed=9, events=eval_events, chunk=4, graph=g,
                                         return_episode_rewards=True) for g in (True, False)]
                 assert runs[0] == runs[1]
             return result
 
     plain, evald = learn(False), learn(True)
     for k in plain[0]:
-        assert _same(plain[0][k], evald[0][k]), k
+        assert same(plain[0][k], evald[0][k]), k
     strip = lambda records: [{k: v for k, v in r.items() if not k.startswith("eval/")} for r in records]  # noqa: E731
-    assert _same(strip(plain[1]), strip(evald[1]))
+    assert same(strip(plain[1]), strip(evald[1]))
 
 
 def test_construction_refuses_forces_already_there_and_host_flags(model):
     from upkie_amd.events import EpisodeEvents
     from upkie_amd.exceptions import UpkieRuntimeError
 
-    with _pendulum(4, 5) as env:
+    with pendulum(4, 5, seed=3) as env:
         env.set_external_forces("torso", torch.tensor([1.0, 0.0, 0.0]))
         with pytest.raises(ValueError, match="already carries external forces"):
             EpisodeEvents(env, push_prob=0.5)

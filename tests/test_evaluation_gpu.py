@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from tests import evaluation_reference as R
+from tests.training_rig import pendulum, pitch_reward, same, tower
 from upkie_amd import evaluation
 from upkie_amd.evaluation import EpisodeTally, EvalCallback, evaluate_policy
 from upkie_amd.exceptions import UpkieRuntimeError
@@ -37,7 +38,7 @@ def _state(tally):
             "ep_length": tally.ep_length.cpu().numpy(), "summary": tally.summary.cpu().numpy()}
 
 
-def _same(a, b):
+def _same_state(a, b):
     return a.keys() == b.keys() and all(np.array_equal(np.asarray(a[k]), np.asarray(b[k])) for k in a)
 
 
@@ -114,13 +115,13 @@ def test_reset_starts_clean():
     fresh = EpisodeTally(row.N, row.E, device=DEV)
     fresh.reset(E2)
     used.reset(E2)
-    assert _same(_state(used), _state(fresh)) and used.remaining() == E2
+    assert _same_state(_state(used), _state(fresh)) and used.remaining() == E2
     twin = R.EvaluateTwin(row.N, E2)
     for t in range(R.EVAL_STEPS):
         for tally in (used, fresh):
             tally.step(rewards[t], term[t], trunc[t])
         twin.step(script.rewards[t], script.terminated[t], script.truncated[t])
-        assert _same(_state(used), _state(fresh)), t
+        assert _same_state(_state(used), _state(fresh)), t
         _compare(used, twin, f"step {t} after the reset")
     assert twin.filled == E2 and used.result() == fresh.result()
 
@@ -152,17 +153,13 @@ def test_the_tally_under_graph_replay_gives_the_eager_bits():
         tally.reset(row.E)
         loop.replay()
         torch.cuda.synchronize()
-        assert _same(_state(tally), want), f"replay {replay}"
+        assert _same_state(_state(tally), want), f"replay {replay}"
     loop.replay()  # a full list: twelve more steps change nothing
     torch.cuda.synchronize()
-    assert _same(_state(tally), want)
+    assert _same_state(_state(tally), want)
 
 
 # ---------------------------------------------------------------- evaluate_policy on a real env
-def _tower(d_in, d_out, width=16):
-    return nn.Sequential(nn.Linear(d_in, width), nn.Tanh(), nn.Linear(width, width), nn.Tanh(), nn.Linear(width, d_out))
-
-
 def _env(num_envs=64, mode="same_step", limit=20, **kw):
     import upkie_amd.envs as envs
     from upkie_amd.utils.robot_state import RobotState
@@ -178,12 +175,8 @@ def _policy(obs_dim=4, low=-1.0, high=1.0, seed=0):
     from upkie_amd.policies import MlpActorCritic
 
     torch.manual_seed(3)
-    actor, critic = _tower(obs_dim, 1).to(DEV), _tower(obs_dim, 1).to(DEV)
+    actor, critic = tower(obs_dim, 1).to(DEV), tower(obs_dim, 1).to(DEV)
     return MlpActorCritic.from_modules(actor, critic, nn.Parameter(torch.zeros(1, device=DEV)), action_low=[low], action_high=[high], seed=seed)
-
-
-def _reward(next_obs, info):
-    return torch.abs(next_obs[:, 0]).neg_().add_(1.0)
 
 
 class _Recorded:
@@ -210,7 +203,7 @@ class _Recorded:
 def _run(E=100, **kw):
     """One whole evaluation in fresh objects: `EpisodeTally.result`'s dict."""
     with _env() as env:
-        runner = evaluation.PolicyEvaluator(_policy(), env, E, reward_fn=_reward, chunk=kw.pop("chunk", 32), graph=kw.pop("graph", True))
+        runner = evaluation.PolicyEvaluator(_policy(), env, E, reward_fn=pitch_reward, chunk=kw.pop("chunk", 32), graph=kw.pop("graph", True))
         return runner.run(E, seed=kw.pop("seed", 5), **kw)
 
 
@@ -239,8 +232,8 @@ def test_evaluate_policy_on_a_real_env_is_the_twin_graphed_and_eager(monkeypatch
     # the public function: SB3's two return forms
     with _env() as env:
         policy = _policy()
-        assert evaluate_policy(policy, env, n_eval_episodes=E, reward_fn=_reward, seed=5) == (mean_r, math.sqrt(var_r))
-        assert evaluate_policy(policy, env, n_eval_episodes=E, reward_fn=_reward, seed=5, return_episode_rewards=True) == (rewards, lengths)
+        assert evaluate_policy(policy, env, n_eval_episodes=E, reward_fn=pitch_reward, seed=5) == (mean_r, math.sqrt(var_r))
+        assert evaluate_policy(policy, env, n_eval_episodes=E, reward_fn=pitch_reward, seed=5, return_episode_rewards=True) == (rewards, lengths)
         own = evaluate_policy(policy, env, n_eval_episodes=E, seed=5, return_episode_rewards=True)  # the env's own reward: the reference's constant 0
         assert own == ([0.0] * E, lengths)
 
@@ -306,11 +299,11 @@ def test_a_sampled_evaluation_runs_at_the_policys_batch_size_and_advances_its_co
     E = 100
     with _env() as env:
         policy = _policy()
-        sampled = evaluate_policy(policy, env, n_eval_episodes=E, deterministic=False, reward_fn=_reward, seed=5, graph=False, return_episode_rewards=True)
+        sampled = evaluate_policy(policy, env, n_eval_episodes=E, deterministic=False, reward_fn=pitch_reward, seed=5, graph=False, return_episode_rewards=True)
         calls = policy.calls.clone()
         assert len(sampled[0]) == E and max(sampled[1]) <= 20
         assert int(calls.min()) >= max(sampled[1]) and int(calls.min()) == int(calls.max()), "one draw per env per step taken"
-        mean = evaluate_policy(policy, env, n_eval_episodes=E, reward_fn=_reward, seed=5, graph=False, return_episode_rewards=True)
+        mean = evaluate_policy(policy, env, n_eval_episodes=E, reward_fn=pitch_reward, seed=5, graph=False, return_episode_rewards=True)
         assert torch.equal(policy.calls, calls), "the deterministic evaluation draws nothing"
         assert mean[0] != sampled[0], "the noise is in the actions"
     with _env(num_envs=32) as env:
@@ -320,11 +313,16 @@ def test_a_sampled_evaluation_runs_at_the_policys_batch_size_and_advances_its_co
 
 # ---------------------------------------------------------------- training is untouched
 def _learn(tmp_path, with_callback):
-    from tests.test_ppo_learn_gpu import _driver
+    from upkie_amd.policies import MlpActorCritic
     from upkie_amd.ppo import Ppo
 
-    B, n_steps = 256, 32  # the smallest case of tests/test_ppo_learn_gpu.py
-    env, policy, kw = _driver(B, n_steps)
+    B, n_steps = 256, 32  # the smallest case of tests/test_ppo_learn_gpu.py: its env, its policy, its arguments
+    torch.manual_seed(0)
+    env = pendulum(B, 40, pitch=0.1)
+    dev = env.device
+    policy = MlpActorCritic.from_modules(tower(4, 1, 64).to(dev), tower(4, 1, 64).to(dev), nn.Parameter(torch.zeros(1, device=dev)), action_low=[-1.0],
+                                         action_high=[1.0], seed=0)
+    kw = dict(n_steps=n_steps, n_epochs=3, batch_size=B * n_steps // 4, reward_fn=pitch_reward, seed=0)
     with env, _env(num_envs=96, limit=40) as eval_env:
         # iterations end at vec-env steps 32, 64, 96: evaluations behind the second and the third
         callback = EvalCallback(eval_env, n_eval_episodes=150, eval_freq=40, best_model_save_path=str(tmp_path / "best.pt"), seed=9) if with_callback else None
@@ -341,13 +339,6 @@ def test_a_run_with_an_eval_callback_trains_bit_for_bit_as_one_without(tmp_path)
     evald, evald_norm, evald_records, callback = _learn(tmp_path, True)
     for a, b in zip(evald, plain):
         assert torch.equal(a, b)
-
-    def same(a, b):
-        if isinstance(a, torch.Tensor):
-            return torch.equal(a, b)
-        if isinstance(a, dict):
-            return a.keys() == b.keys() and all(same(a[k], b[k]) for k in a)
-        return a == b or (a != a and b != b)
 
     assert same(evald_norm, plain_norm), "the normaliser's statistics"
     assert len(evald_records) == len(plain_records) == 3

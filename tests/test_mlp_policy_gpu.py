@@ -16,6 +16,7 @@ from tests.mlp_shapes import CASES, DEV
 from tests.mlp_shapes import policy as _policy
 from tests.mlp_shapes import sources_of as _src
 from tests.mlp_shapes import tower as _tower
+from tests.training_rig import reset_pendulum
 from upkie_amd.graphs import GraphedLoop
 from upkie_amd.policies import MlpActorCritic, MlpPolicy
 from upkie_amd.rollout import RolloutBuffer
@@ -172,17 +173,6 @@ def test_buffer_outputs_and_no_allocation():
         assert torch.equal(buf.observations[t], obs)
 
 
-def _pendulum(n, seed=0):
-    import upkie_amd.envs as envs
-    from upkie_amd.utils.robot_state import RobotState
-    from upkie_amd.utils.robot_state_randomization import RobotStateRandomization
-
-    env = envs.make("Upkie-HIP-Pendulum-Vec", num_envs=n, frequency=200.0, init_state=RobotState(randomization=RobotStateRandomization(pitch=0.1)),
-                    autoreset_mode="same_step", max_episode_steps=400)
-    env.reset(seed=seed)
-    return env
-
-
 def test_graph_replay_is_bit_equal_to_the_eager_loop():
     """{policy -> env.step -> buffer slot} x 50, recorded as one hipGraph (GraphedLoop, unroll=50) and replayed, against
     the same 50 steps run eagerly from the same state and seed."""
@@ -190,7 +180,7 @@ def test_graph_replay_is_bit_equal_to_the_eager_loop():
     results = []
     for graphed in (False, True):
         pol, _, _, _ = _policy(4, [64, 64], 1, "tanh", seed=9, low=-0.9, high=0.9)
-        with _pendulum(N) as env:
+        with reset_pendulum(N) as env:
             obs = env.observation
             buf = RolloutBuffer(T, N, obs_shape=(4,), action_shape=(1,), device=env.device)
             env_action = torch.empty(N, 1, device=env.device)
@@ -228,7 +218,7 @@ def test_closed_loop_against_torch_modules_per_step():
     actor = _tower(4, [64, 64], 1, "tanh").to(DEV)
     policy = MlpPolicy.from_modules(actor, torch.tensor([-1.0]), torch.tensor([1.0]))
     worst = 0.0
-    with _pendulum(N, seed=1) as env, torch.no_grad():
+    with reset_pendulum(N, seed=1) as env, torch.no_grad():
         obs = env.observation
         for _ in range(T):
             action = policy(obs)

@@ -13,7 +13,10 @@ import torch.nn as nn
 
 from tests import ppo_reference as R
 from tests.mlp_shapes import CASES, IDS, WIDEST, T
+from tests.mlp_shapes import restore_trainer as _restore
 from tests.mlp_shapes import tower as _tower
+from tests.mlp_shapes import trainer_case as _setup
+from tests.mlp_shapes import trainer_state as _state
 from upkie_amd.exceptions import UpkieRuntimeError
 from upkie_amd.normalize import RunningNormalizer
 from upkie_amd.policies import MlpActorCritic
@@ -24,37 +27,6 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 BETA1_F32 = np.float32(1.0) - np.float32(0.9)
-
-
-def _setup(case, seed=0, first=False, normalize=False):
-    """Policy (built from modules), a full rollout buffer of T x N samples whose actions, values and log-probs come from
-    the policy, perturbed old log-probs (none within 1e-3 of a clip bound unless `first`: every ratio is then 1)."""
-    N, D, widths, A, act = case
-    torch.manual_seed(seed)
-    actor, critic = _tower(D, widths, A, act).to(DEV), _tower(D, widths, 1, act).to(DEV)
-    log_std = nn.Parameter(torch.full((A,), -0.5, device=DEV))
-    kw = {}
-    if normalize:
-        g = torch.Generator().manual_seed(seed + 1)
-        kw = dict(obs_mean=0.3 * torch.randn(D, generator=g), obs_var=torch.rand(D, generator=g) * 3 + 0.2, clip_obs=3.0)
-    pol = MlpActorCritic.from_modules(actor, critic, log_std, torch.full((A,), -1.0), torch.full((A,), 1.0), seed=seed, **kw)
-    buf = RolloutBuffer(T, N, obs_shape=(D,), action_shape=(A,), device=DEV)
-    gen = torch.Generator(DEV).manual_seed(seed + 7)
-    buf.observations.copy_(torch.randn(T, N, D, device=DEV, generator=gen))
-    for t in range(T):
-        pol.act(buf.observations[t], out={"action": buf.actions[t], "value": buf.values[t], "log_prob": buf.log_probs[t]})
-    rng = np.random.default_rng(seed)
-    if not first:
-        delta = rng.normal(0.0, 0.25, size=(T, N))
-        for bound in (1.2, 0.8):  # ratio = exp(-delta): keep it >= 1e-3 away from the clip bounds
-            near = np.abs(np.exp(-delta) - bound) < 1e-3
-            delta[near] += 0.01
-        buf.log_probs.add_(torch.as_tensor(delta, dtype=torch.float32, device=DEV))
-    buf.advantages = torch.as_tensor(rng.normal(0.3, 1.0, size=(T, N)), dtype=torch.float32, device=DEV)
-    buf.returns = (buf.values + torch.as_tensor(rng.normal(0.0, 1.0, size=(T, N)), dtype=torch.float32, device=DEV)).contiguous()
-    buf.values.add_(torch.as_tensor(rng.normal(0.0, 0.2, size=(T, N)), dtype=torch.float32, device=DEV))
-    buf.pos, buf.full = T, True
-    return pol, actor, critic, log_std, buf
 
 
 def _np(t):
@@ -179,15 +151,6 @@ def test_one_epoch_of_four_minibatches_against_torch_fp32(case):
         assert np.all(np.abs(da - db) <= 4 * 4 * lr + 1e-6)
     s = stats.double().cpu().numpy()[0]
     np.testing.assert_allclose(s[:, [0, 1, 3, 6]], ref_stats, rtol=2e-3, atol=2e-5)
-
-
-def _state(pol, tr):
-    return [pol.packed.clone(), tr.m.clone(), tr.v.clone(), tr.scalars.clone()]
-
-
-def _restore(pol, tr, st):
-    for dst, src in zip((pol.packed, tr.m, tr.v, tr.scalars), st):
-        dst.copy_(src)
 
 
 @pytest.mark.parametrize("case", [CASES[0], CASES[2], CASES[4]], ids=[IDS[0], IDS[2], IDS[4]])

@@ -5,7 +5,6 @@ against a fake trainer."""
 
 import ctypes as C
 import math
-import types
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ import torch
 from tests import mlp_reference as MR
 from tests import ppo_learn_reference as L
 from tests import ppo_reference as R
+from tests.agent_step_doubles import filler, saved_parts, stage
 from tests.test_ppo import _modules, _shape, _sources
 from upkie_amd import abi, lib
 from upkie_amd.exceptions import UpkieRuntimeError
@@ -275,12 +275,6 @@ def test_learn_follows_sb3s_bookkeeping():
 
 
 # ---------------------------------------------------------------- Ppo.save / Ppo.load: what the file holds
-def _stage(cls, **attributes):
-    obj = cls.__new__(cls)  # (no device: the stage's own class around host tensors)
-    vars(obj).update(attributes)
-    return obj
-
-
 class _SavedPpo(Ppo):
     """`Ppo` whose stages are host stand-ins: every tensor a stage owns is filled with its own number (times the
     stand-in env's ``scale``, so that two sets of objects differ everywhere)."""
@@ -290,35 +284,17 @@ class _SavedPpo(Ppo):
             return
         from upkie_amd.episodes import EpisodeStatistics
 
-        fill, scale = iter(range(1, 100)), self.env.scale
-        f = lambda *shape, dtype=torch.float32: torch.full(shape, next(fill) * scale, dtype=dtype)  # noqa: E731
+        scale = self.env.scale
+        f = filler(range(1, 100), scale)
         self.buffer, self.device, self.normalizer = object(), torch.device("cpu"), None
-        self.trainer = _stage(PpoTrainer, m=f(6), v=f(6), control=f(abi.PPO_CTRL_WORDS, dtype=torch.float64), generator=torch.Generator(),
+        self.trainer = stage(PpoTrainer, m=f(6), v=f(6), control=f(abi.PPO_CTRL_WORDS, dtype=torch.float64), generator=torch.Generator(),
                               _clip_range=0.2 * scale, _clip_range_vf=None, _target_kl=0.03 * scale, _lr=1e-3 * scale,
                               progress_remaining=1.0, sync_modules=lambda: None)
         self.trainer.generator.manual_seed(5 * scale)
-        self.episodes = _stage(EpisodeStatistics, ep_return=f(2, dtype=torch.float64), ep_length=f(2, dtype=torch.int32),
+        self.episodes = stage(EpisodeStatistics, ep_return=f(2, dtype=torch.float64), ep_length=f(2, dtype=torch.int32),
                                ring_return=f(3, dtype=torch.float64), ring_length=f(3, dtype=torch.int32), counters=f(3, dtype=torch.int64),
                                means=f(2, dtype=torch.float64))
         self._starts, self._obs = f(2, dtype=torch.uint8), f(2, 4)
-
-
-def _saved_parts(scale, pipeline, reward):
-    fill = iter(range(100, 200))
-    f = lambda *shape, dtype=torch.float32: torch.full(shape, next(fill) * scale, dtype=dtype)  # noqa: E731
-    sim = types.SimpleNamespace(state=f(3, 2), reward=f(2), terminated=f(2, dtype=torch.uint8), truncated=f(2, dtype=torch.uint8))
-    env = types.SimpleNamespace(num_envs=2, sim=sim, _final_obs=f(2, 4), scale=scale)
-    env.state_tensors = lambda: dict(vars(sim), final_obs=env._final_obs)  # (no persistent observation buffer: `Ppo` supplies its own)
-    policy = _stage(MlpActorCritic, shape=_shape(4, [8], 1), packed=f(6), calls=f(2, dtype=torch.int32), seed=7 * scale)
-    kwargs = {}
-    if pipeline:
-        tensors = {"prev_command": f(2, 1), "observation": f(2, 4), "calls": f(2, dtype=torch.int32)}
-        kwargs["pipeline"] = types.SimpleNamespace(num_envs=2, obs_dim=3, act_dim=1, stack=1, frame_dim=4, stacked_dim=4, state_tensors=lambda: tensors)
-    if reward:
-        terms = {"prev_action": f(1, 2), "term_sum": f(2, 2, dtype=torch.float64), "term_last": f(2, 2, dtype=torch.float64),
-                 "finished": f(2, dtype=torch.int32)}
-        kwargs["reward"] = types.SimpleNamespace(num_envs=2, obs_dim=3 if pipeline else 4, act_dim=1, state_tensors=lambda: terms)
-    return env, policy, kwargs
 
 
 STAGE_TENSORS = ["calls", "control", "env.final_obs", "env.observation", "env.reward", "env.state", "env.terminated", "env.truncated", "ep_counters",
@@ -332,7 +308,7 @@ REWARD_TENSORS = ["reward.finished", "reward.prev_action", "reward.term_last", "
 def test_save_writes_these_names_and_load_puts_them_back(tmp_path, monkeypatch, pipeline, reward, names):
     monkeypatch.setattr(torch.cuda, "synchronize", lambda device=None: None)
     path = str(tmp_path / "ppo.pt")
-    env, policy, kwargs = _saved_parts(1, pipeline, reward)
+    env, policy, kwargs = saved_parts(1, pipeline, reward)
     model = _SavedPpo(env, policy, n_steps=4, **kwargs)
     model._setup()
     model.num_timesteps, model.iterations, model.total_timesteps, model.progress_remaining = 24, 3, 80, 0.7
@@ -353,7 +329,7 @@ def test_save_writes_these_names_and_load_puts_them_back(tmp_path, monkeypatch, 
     owners.update({f"reward.{k}": v for k, v in (kwargs["reward"].state_tensors() if reward else {}).items()})
     assert owners.keys() == sd["tensors"].keys() and all(torch.equal(sd["tensors"][k], v) and sd["tensors"][k].dtype == v.dtype for k, v in owners.items())
     # into fresh objects holding other numbers
-    env2, policy2, kwargs2 = _saved_parts(2, pipeline, reward)
+    env2, policy2, kwargs2 = saved_parts(2, pipeline, reward)
     loaded = _SavedPpo.load(path, env2, policy2, n_steps=4, **kwargs2)
     assert all(torch.equal(sd["tensors"][k], v) for k, v in loaded._state_tensors().items()) and loaded._state_tensors().keys() == owners.keys()
     assert torch.equal(policy2.packed, policy.packed) and torch.equal(loaded.episodes.counters, ep.counters) and policy2.seed == 7
@@ -362,6 +338,6 @@ def test_save_writes_these_names_and_load_puts_them_back(tmp_path, monkeypatch, 
     assert torch.equal(tr2.generator.get_state(), tr.generator.get_state())
     assert (loaded.num_timesteps, loaded.iterations, loaded.total_timesteps, loaded.progress_remaining) == (24, 3, 80, 0.7)
     if not reward:  # a file without the reward's tensors does not load into a Ppo with one
-        env3, policy3, kwargs3 = _saved_parts(2, pipeline, True)
+        env3, policy3, kwargs3 = saved_parts(2, pipeline, True)
         with pytest.raises(ValueError, match="the file has no reward.prev_action"):
             _SavedPpo.load(path, env3, policy3, n_steps=4, **kwargs3)

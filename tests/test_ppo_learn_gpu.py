@@ -15,7 +15,11 @@ import torch
 import torch.nn as nn
 
 from tests import ppo_learn_reference as L
-from tests.test_ppo_gpu import CASES, DEV, T, _np, _restore, _setup, _state
+from tests.mlp_shapes import CASES, T
+from tests.mlp_shapes import restore_trainer as _restore
+from tests.mlp_shapes import trainer_case as _setup
+from tests.mlp_shapes import trainer_state as _state
+from tests.training_rig import np64, pendulum, pitch_reward, tower
 from upkie_amd.ppo import STAT_NAMES, Ppo, PpoTrainer
 
 pytestmark = pytest.mark.gpu
@@ -26,8 +30,8 @@ MB = TOTAL // 4
 
 
 def _data(buf, case):
-    flat = lambda t: _np(t).reshape(-1)  # noqa: E731
-    return dict(obs=_np(buf.observations).reshape(-1, case[1]), actions=_np(buf.actions).reshape(-1, case[3]), old_values=flat(buf.values),
+    flat = lambda t: np64(t).reshape(-1)  # noqa: E731
+    return dict(obs=np64(buf.observations).reshape(-1, case[1]), actions=np64(buf.actions).reshape(-1, case[3]), old_values=flat(buf.values),
                 old_log_prob=flat(buf.log_probs), advantages=flat(buf.advantages), returns=flat(buf.returns))
 
 
@@ -41,7 +45,7 @@ def test_early_stop_lands_where_sb3s_does():
     tr = PpoTrainer(pol, lr=lr, n_epochs=4, batch_size=MB, seed=5, controlled=True)
     tr.prepare(buf)
     perms = [tr.perm[e].long().cpu().numpy() for e in range(4)]
-    src0 = [_np(s) for s in pol.sources()]
+    src0 = [np64(s) for s in pol.sources()]
     data = _data(buf, CASE)
     free = L.train(pol.shape, src0, data, perms, MB, lr=lr)
     kls = free["rows"][:, 4]
@@ -171,7 +175,7 @@ def test_explained_variance_against_numpy_fp64():
     tr.prepare(buf)
     a = tr.explained_variance().clone()
     b = tr.explained_variance().clone()
-    want = L.explained_variance(_np(buf.values), _np(buf.returns))
+    want = L.explained_variance(np64(buf.values), np64(buf.returns))
     print("explained variance:", float(a), "numpy fp64:", want, "difference:", abs(float(a) - want))
     assert abs(float(a) - want) <= 1e-6
     assert a.view(torch.int64).item() == b.view(torch.int64).item(), "the same bits on two calls"
@@ -183,8 +187,8 @@ def test_explained_variance_against_numpy_fp64():
     tr3 = PpoTrainer(pol3, n_epochs=1, batch_size=500)
     tr3.train(buf3)
     rec = tr3.log()
-    assert abs(rec["explained_variance"] - L.explained_variance(_np(buf3.values), _np(buf3.returns))) <= 1e-6
-    assert rec["std"] == pytest.approx(float(np.exp(_np(pol3.sources()[4])).mean()), rel=1e-6)
+    assert abs(rec["explained_variance"] - L.explained_variance(np64(buf3.values), np64(buf3.returns))) <= 1e-6
+    assert rec["std"] == pytest.approx(float(np.exp(np64(pol3.sources()[4])).mean()), rel=1e-6)
 
 
 def test_two_gloo_ranks_stop_at_the_same_minibatch(tmp_path):
@@ -208,25 +212,13 @@ def test_two_gloo_ranks_stop_at_the_same_minibatch(tmp_path):
 
 
 # ---------------------------------------------------------------- the driver
-def _tower(d_in, d_out):
-    return nn.Sequential(nn.Linear(d_in, 64), nn.Tanh(), nn.Linear(64, 64), nn.Tanh(), nn.Linear(64, d_out))
-
-
-def _reward(next_obs, info):
-    return torch.abs(next_obs[:, 0]).neg_().add_(1.0)  # the example's stand-in reward
-
-
 def _make(B):
-    import upkie_amd.envs as envs
     from upkie_amd.policies import MlpActorCritic
-    from upkie_amd.utils.robot_state import RobotState
-    from upkie_amd.utils.robot_state_randomization import RobotStateRandomization
 
     torch.manual_seed(0)
-    init = RobotState(randomization=RobotStateRandomization(pitch=0.1))
-    env = envs.make("Upkie-HIP-Pendulum-Vec", num_envs=B, frequency=200.0, init_state=init, autoreset_mode="same_step", max_episode_steps=40)
+    env = pendulum(B, 40, pitch=0.1)
     dev = env.device
-    actor, critic = _tower(4, 1).to(dev), _tower(4, 1).to(dev)
+    actor, critic = tower(4, 1, 64).to(dev), tower(4, 1, 64).to(dev)
     log_std = nn.Parameter(torch.zeros(1, device=dev))
     policy = MlpActorCritic.from_modules(actor, critic, log_std, action_low=[-1.0], action_high=[1.0], seed=0)
     return env, policy
@@ -281,7 +273,7 @@ def _hand_written_loop(B, n_steps, iterations):
 
 def _driver(B, n_steps, **kw):
     env, policy = _make(B)
-    return env, policy, dict(n_steps=n_steps, n_epochs=3, batch_size=B * n_steps // 4, reward_fn=_reward, seed=0, **kw)
+    return env, policy, dict(n_steps=n_steps, n_epochs=3, batch_size=B * n_steps // 4, reward_fn=pitch_reward, seed=0, **kw)
 
 
 def test_learn_equals_the_hand_written_loop_and_resumes_bit_for_bit(tmp_path):

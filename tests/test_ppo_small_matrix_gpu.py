@@ -31,7 +31,7 @@ def _dev(a):
     return torch.tensor(np.ascontiguousarray(a), device=DEV)
 
 
-def _same(a, b):
+def _same_bytes(a, b):
     return torch.equal(a.reshape(-1).contiguous().view(torch.uint8), b.reshape(-1).contiguous().view(torch.uint8))
 
 
@@ -72,7 +72,7 @@ def test_advantage_statistics_at_every_size(row, api):
             launch(lb.upkie_ppo_advantage_finish, row.total, row.batch, normalize, ptr(slots), world, ptr(out))
             check(out, world, normalize, f"0a 0b world {world}" if normalize else f"0a 0b world {world} unnormalised")
             if world == 1:
-                assert _same(out, fused[normalize]), "one shard gives the fused form's bits"
+                assert _same_bytes(out, fused[normalize]), "one shard gives the fused form's bits"
     plan = S.adv_plan(row)
     print(f"matrix advantage {row.total}/{row.batch} (M {M}, last {plan['last']}, {plan['sweeps']} sweeps): (0, 1) exact where it belongs; worst error / "
           "bound: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items() if "unnormalised" not in k))
@@ -88,7 +88,7 @@ def test_explained_variance_at_every_size(row, api):
     outs = torch.full((2, 2), -7.0, dtype=F64, device=DEV)
     for i in range(2):
         launch(lb.upkie_ppo_explained_variance, row.n, ptr(ret), ptr(val), -1, None, 1, None, ptr(outs[i]))
-    assert _same(outs[0], outs[1]) and float(outs[0, 1]) == -7.0, "two calls give the same bits; the word behind out is untouched"
+    assert _same_bytes(outs[0], outs[1]) and float(outs[0, 1]) == -7.0, "two calls give the same bits; the word behind out is untouched"
     worst = {"phase -1": S.ev_ratio(float(outs[0, 0]), row, 1)}
     for world in S.SHARD_WORLDS:
         slots = torch.full((world, 4), float("nan"), dtype=F64, device=DEV)
@@ -100,7 +100,7 @@ def test_explained_variance_at_every_size(row, api):
         assert not torch.isnan(slots).any() and float(out[1]) == -7.0
         worst[f"world {world}"] = S.ev_ratio(float(out[0]), row, world)
         if world == 1:
-            assert _same(out[0], outs[0, 0]), "one shard gives the bits of phase -1"
+            assert _same_bytes(out[0], outs[0, 0]), "one shard gives the bits of phase -1"
     want, _ = S.ev_twin(row)
     print(f"matrix explained variance {row.n} {row.kind}: {float(outs[0, 0])!r} (twin {want!r}); worst error / bound: "
           + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
@@ -218,7 +218,7 @@ def test_three_applies_replayed_from_a_graph(api):
     torch.cuda.synchronize()
     state.check_workspace()
     for a, b in zip(eager, state.bits()):
-        assert _same(a, b)
+        assert _same_bytes(a, b)
     assert int(state.control[1]) == S.FOLD_APPLIES
 
 
@@ -272,7 +272,7 @@ def test_controlled_form_stops_skips_and_counts(api):
     assert torch.isnan(state.stats[3, :7]).all() and float(state.stats[3, 7]) == 0.0, "a NaN row, and the word behind it untouched"
     state.stats[3].copy_(frozen[4][3])
     for a, b in zip(frozen, state.bits()):
-        assert _same(a, b), "an apply after the stop changes nothing: weights, m, v, the control block, the workspace's gradient"
+        assert _same_bytes(a, b), "an apply after the stop changes nothing: weights, m, v, the control block, the workspace's gradient"
     state.check_workspace()
     launch(lb.upkie_ppo_update_begin, ptr(state.control))
     assert control() == {"T": 2, "STOPPED": 0, "N_UPDATES": 1, "MINIBATCHES_RUN": 0, "LR": S.LR, "TARGET_KL": target_kl}

@@ -12,14 +12,14 @@ import pytest
 import torch
 
 from tests import push_curriculum_reference as P
-from tests import test_episode_events_gpu as E  # (its helpers: the never-stepped handle, the pendulum env, the small Ppo)
+from tests.training_rig import (bits, check_event_records, events_stage, pendulum, pitch_reward, read_state, same, snapshot, tower,
+                                warm_up_as_the_capture_does)
 from upkie_amd import abi
 
 pytestmark = pytest.mark.gpu
-ROOT = E.ROOT
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAX_NORM = P.GPU_SETTINGS["push_norm"][1]
 INTEGERS = ("calls", "remaining", "pushes", "episodes", "level", "episode_pushes")
-_bits, _read = E._bits, E._read
 
 
 @pytest.fixture(scope="module")
@@ -34,7 +34,7 @@ def _stage(model, num_envs, offset, levels=P.GPU_LEVELS, settings=P.GPU_SETTINGS
 
     if levels is not None:
         kw["curriculum"] = PushLevels(**levels)
-    return E._stage(model, num_envs, offset, **dict(settings, **kw))
+    return events_stage(model, num_envs, offset, P.GPU_SEED, **dict(settings, **kw))
 
 
 def _flags(num_envs, offset, device):
@@ -44,8 +44,8 @@ def _flags(num_envs, offset, device):
 
 def _integers_equal(got, want, where):
     for name in INTEGERS:
-        assert np.array_equal(_bits(got[name]), _bits(want[name].astype(np.uint32) if name != "remaining" else want[name])), (name, where)
-    assert np.array_equal(_bits(got["difficulty"]), _bits(want["difficulty"])), ("difficulty", where)
+        assert np.array_equal(bits(got[name]), bits(want[name].astype(np.uint32) if name != "remaining" else want[name])), (name, where)
+    assert np.array_equal(bits(got["difficulty"]), bits(want["difficulty"])), ("difficulty", where)
 
 
 @pytest.mark.parametrize("num_envs,offset", P.GPU_SIZES)
@@ -55,30 +55,30 @@ def test_the_levelled_kernel_is_the_twin_after_every_call(model, num_envs, offse
     assert sim.ext_force.data_ptr() == events.force.data_ptr() and sim.body_inertials.data_ptr() == events.body_inertials.data_ptr()
     term, trunc, d_term, d_trunc = _flags(num_envs, offset, sim.device)
     every = np.arange(num_envs)
-    prev = _read(events)
+    prev = read_state(events)
     assert set(prev) == set(INTEGERS) | {"force", "body_inertials", "link_scale", "settings", "difficulty"}
-    E._check_records(prev, twin.snapshot(), every)  # construction: episode 0
+    check_event_records(prev, twin.snapshot(), every)  # construction: episode 0
     _integers_equal(prev, twin.snapshot(), "construction")
     worst_force, starts = 0.0, 0
     for t in range(P.GPU_CALLS):
         events.step(d_term[t], d_trunc[t])
         happened = twin.step(term[t], trunc[t])
-        got, want = _read(events), twin.snapshot()
+        got, want = read_state(events), twin.snapshot()
         _integers_equal(got, want, t)
-        assert np.array_equal(_bits(got["difficulty"]), _bits(P.difficulty_of(got["level"].astype(np.int64), P.GPU_LEVELS["levels"])))
+        assert np.array_equal(bits(got["difficulty"]), bits(P.difficulty_of(got["level"].astype(np.int64), P.GPU_LEVELS["levels"])))
         force, before = got["force"][0], prev["force"][0]
-        assert np.all(_bits(force[:, happened["zero"]]) == 0), "a free step without a start: +0.0 in every word"
-        assert np.array_equal(_bits(force[:, happened["hold"]]), _bits(before[:, happened["hold"]])), "a held force is not written"
+        assert np.all(bits(force[:, happened["zero"]]) == 0), "a free step without a start: +0.0 in every word"
+        assert np.array_equal(bits(force[:, happened["hold"]]), bits(before[:, happened["hold"]])), "a held force is not written"
         s = happened["start"]
         if s.any():
             worst_force = max(worst_force, float(np.abs(force[:, s].astype(np.float64) - want["force"][:, s]).max()))
             starts += int(s.sum())
         done = happened["redrawn"]
         if done.any():
-            E._check_records(got, want, np.flatnonzero(done))
+            check_event_records(got, want, np.flatnonzero(done))
         for name in ("body_inertials", "link_scale"):
-            assert np.array_equal(_bits(got[name][:, ~done]), _bits(prev[name][:, ~done])), f"{name} of envs that did not end is not written"
-        assert np.array_equal(_bits(got["settings"]), _bits(prev["settings"])), "the block is read, never written"
+            assert np.array_equal(bits(got[name][:, ~done]), bits(prev[name][:, ~done])), f"{name} of envs that did not end is not written"
+        assert np.array_equal(bits(got["settings"]), bits(prev["settings"])), "the block is read, never written"
         prev = got
     print(f"N = {num_envs}, offset {offset}: {starts} starts, worst |force - twin| {worst_force:.3g} N (bound {2.5e-6 * MAX_NORM:.3g})")
     assert worst_force < 2.5e-6 * MAX_NORM
@@ -94,10 +94,10 @@ def test_with_one_level_the_new_entry_point_leaves_the_bits_of_the_old_one(model
     for t in range(P.GPU_CALLS):
         old.step(d_term[t], d_trunc[t])
         new.step(d_term[t], d_trunc[t])
-        a, b = _read(old), _read(new)
+        a, b = read_state(old), read_state(new)
         assert set(b) - set(a) == {"settings", "level", "episode_pushes", "difficulty"}
         for name in a:
-            assert np.array_equal(_bits(a[name]), _bits(b[name])), (name, t)
+            assert np.array_equal(bits(a[name]), bits(b[name])), (name, t)
         assert not b["level"].any() and np.all(b["difficulty"] == 1.0)
     assert a["pushes"].sum() > 0 or num_envs == 1
     sim_a.close()
@@ -114,7 +114,7 @@ def test_one_levelled_handle_of_64_is_two_of_32_bit_for_bit(model):
         trace = []
         for t in range(P.GPU_CALLS):
             events.step(d_term[t], d_trunc[t])
-            trace.append(_read(events))
+            trace.append(read_state(events))
         sim.close()
         return trace
 
@@ -124,35 +124,35 @@ def test_one_levelled_handle_of_64_is_two_of_32_bit_for_bit(model):
         for a, b in zip(whole, run(32, lo, lo)):
             for name in a:
                 sl = a[name] if name == "settings" else a[name][..., lo:lo + 32]
-                assert np.array_equal(_bits(sl), _bits(b[name])), name
+                assert np.array_equal(bits(sl), bits(b[name])), name
 
 
 def test_a_masked_reset_restarts_only_its_envs_at_the_start_level(model):
     N, offset = 65, 1000
     sim, events = _stage(model, N, offset, levels=dict(P.GPU_LEVELS, start=1))
     term, trunc, d_term, d_trunc = _flags(N, offset, sim.device)
-    first = _read(events)
+    first = read_state(events)
     assert np.all(first["level"] == 1) and np.all(first["difficulty"] == np.float32(1) / np.float32(3))
     for t in range(12):
         events.step(d_term[t], d_trunc[t])
-    moved = _read(events)
+    moved = read_state(events)
     assert len(set(moved["level"].tolist())) >= 3 and moved["episode_pushes"].max() >= 1 and np.all(moved["calls"] == 12)
     mask = np.zeros(N, dtype=np.uint8)
     mask[::3] = 1
     events.reset(torch.from_numpy(mask).to(sim.device))
-    got, m = _read(events), mask.astype(bool)
+    got, m = read_state(events), mask.astype(bool)
     for name in ("calls", "remaining", "pushes", "episodes", "episode_pushes"):
         assert np.all(got[name][m] == 0), name
-    assert np.all(got["level"][m] == 1) and np.all(got["difficulty"][m] == np.float32(1) / np.float32(3)) and np.all(_bits(got["force"][0][:, m]) == 0)
+    assert np.all(got["level"][m] == 1) and np.all(got["difficulty"][m] == np.float32(1) / np.float32(3)) and np.all(bits(got["force"][0][:, m]) == 0)
     for name in got:
         if name != "settings":
-            assert np.array_equal(_bits(got[name][..., ~m]), _bits(moved[name][..., ~m])), name
+            assert np.array_equal(bits(got[name][..., ~m]), bits(moved[name][..., ~m])), name
     for name in ("body_inertials", "link_scale"):  # (the masked envs: the records of episode 0 again)
-        assert np.array_equal(_bits(got[name][:, m]), _bits(first[name][:, m])), name
+        assert np.array_equal(bits(got[name][:, m]), bits(first[name][:, m])), name
     events.reset()
-    again = _read(events)
+    again = read_state(events)
     for name in first:
-        assert np.array_equal(_bits(again[name]), _bits(first[name])), name
+        assert np.array_equal(bits(again[name]), bits(first[name])), name
     sim.close()
 
 
@@ -190,7 +190,7 @@ def test_a_captured_loop_follows_set_push_and_set_levels(model):
         graph.replay()
         for t in range(rows.start, rows.stop):
             twin.step(term[t], trunc[t])
-        got, want = _read(events), twin.snapshot()
+        got, want = read_state(events), twin.snapshot()
         _integers_equal(got, want, replay)
         worst = max(worst, float(np.abs(got["force"][0].astype(np.float64) - want["force"]).max()))
     print(f"worst |force - twin| over the replays {worst:.3g} N (bound {2.5e-6 * 30.0:.3g})")
@@ -205,7 +205,7 @@ def test_a_captured_loop_follows_set_push_and_set_levels(model):
         events.set_levels(torch.full((N,), 4, dtype=torch.int32))
     with pytest.raises(ValueError, match="integer tensor"):
         events.set_levels(torch.zeros(N + 1, dtype=torch.int32))
-    assert np.array_equal(_bits(_read(events)["settings"]), _bits(got["settings"])), "a refused change writes nothing"
+    assert np.array_equal(bits(read_state(events)["settings"]), bits(got["settings"])), "a refused change writes nothing"
     sim.close()
 
 
@@ -235,7 +235,8 @@ def test_level_counts_is_numpys_bincount(model, num_envs):
 
 
 # ---------------------------------------------------------------- Ppo
-B, T = E.B, E.T
+B, T = 64, 8
+EVENT_KEYS = ("events.calls", "events.remaining", "events.pushes", "events.episodes", "events.force", "events.body_inertials", "events.link_scale")
 SETTINGS = dict(push_prob=0.3, push_norm=(5.0, 20.0), push_steps=(1, 3), inertia_variation=0.2)
 LEVELS = dict(levels=3, start=1, up=1, down=2, min_pushes=1)
 LEVEL_KEYS = ("events.settings", "events.level", "events.episode_pushes", "events.difficulty")
@@ -247,12 +248,12 @@ def _make(**kw):
     from upkie_amd.ppo import Ppo
 
     torch.manual_seed(0)
-    env = E._pendulum(B, 5, seed=0)
+    env = pendulum(B, 5, seed=0)
     dev = env.device
-    policy = MlpActorCritic.from_modules(E._tower(4, 1).to(dev), E._tower(4, 1).to(dev), torch.nn.Parameter(torch.zeros(1, device=dev)),
+    policy = MlpActorCritic.from_modules(tower(4, 1).to(dev), tower(4, 1).to(dev), torch.nn.Parameter(torch.zeros(1, device=dev)),
                                          action_low=[-1.0], action_high=[1.0], seed=0)
     events = EpisodeEvents(env, curriculum=PushLevels(**LEVELS), live=True, **SETTINGS)
-    model = Ppo(env, policy, n_steps=T, n_epochs=2, batch_size=B * T // 2, seed=0, reward_fn=E._reward, events=events, **kw)
+    model = Ppo(env, policy, n_steps=T, n_epochs=2, batch_size=B * T // 2, seed=0, reward_fn=pitch_reward, events=events, **kw)
     return env, policy, model
 
 
@@ -265,16 +266,16 @@ def test_ppo_with_levelled_events_graphed_equals_not_graphed_and_records_the_lev
     env, policy, model = _make(graph=True)
     with env:
         model.learn(3 * B * T, callback=_harder_after_the_first)
-        graphed = E._snapshot(model)
+        graphed = snapshot(model)
     env, policy, model = _make(graph=False)
     with env:
-        E._warm_up_as_the_capture_does(model)
+        warm_up_as_the_capture_does(model)
         model.learn(3 * B * T, callback=_harder_after_the_first)
-        eager = E._snapshot(model)
-    assert all(k in graphed[0] for k in E.EVENT_KEYS + LEVEL_KEYS + ("packed", "m", "v"))
+        eager = snapshot(model)
+    assert all(k in graphed[0] for k in EVENT_KEYS + LEVEL_KEYS + ("packed", "m", "v"))
     for k in graphed[0]:
-        assert E._same(graphed[0][k], eager[0][k]), k
-    assert E._same(graphed[1], eager[1]) and len(graphed[1]) == 3
+        assert same(graphed[0][k], eager[0][k]), k
+    assert same(graphed[1], eager[1]) and len(graphed[1]) == 3
     level = graphed[0]["events.level"].cpu().numpy()
     first, last = graphed[1][0], graphed[1][-1]
     assert level.max() == 3 and first["rollout/push_level_mean"] < last["rollout/push_level_mean"], "the levels moved inside the captured rollout"
@@ -292,7 +293,7 @@ def test_ppo_with_levelled_events_resumes_bit_for_bit(tmp_path):
     env, policy, model = _make(graph=True)
     with env:
         model.learn(2 * B * T, callback=_harder_after_the_first)
-        whole = E._snapshot(model)
+        whole = snapshot(model)
     env, policy, model = _make(graph=True)
     with env:
         model.learn(2 * B * T, callback=lambda m, rec: (_harder_after_the_first(m, rec), m.iterations < 1)[1])
@@ -302,15 +303,15 @@ def test_ppo_with_levelled_events_resumes_bit_for_bit(tmp_path):
     assert all(k in saved for k in LEVEL_KEYS) and saved["events.level"].dtype == torch.int32
     env, policy, fresh = _make(graph=True)
     with env:
-        resumed = Ppo.load(path, env, policy, n_steps=T, n_epochs=2, batch_size=B * T // 2, seed=0, reward_fn=E._reward, events=fresh.events)
+        resumed = Ppo.load(path, env, policy, n_steps=T, n_epochs=2, batch_size=B * T // 2, seed=0, reward_fn=pitch_reward, events=fresh.events)
         assert torch.equal(fresh.events.settings.cpu(), saved["events.settings"]), "the loaded block is the harder one"
         resumed.learn(B * T, reset_num_timesteps=False)
-        end = E._snapshot(resumed)
+        end = snapshot(resumed)
         fresh.events.set_push(steps=(1, 3))  # (merges with the block as loaded, not with the constructor's settings)
         assert fresh.events.push_norm == (5.0, 25.0) and round(fresh.events.push_prob * 2 ** 24) == round(0.6 * 2 ** 24)
     for k in whole[0]:
-        assert E._same(whole[0][k], end[0][k]), k
-    assert E._same(whole[1][1:], end[1])
+        assert same(whole[0][k], end[0][k]), k
+    assert same(whole[1][1:], end[1])
 
 
 def test_an_eval_callback_at_the_top_level_leaves_training_alone():
@@ -319,13 +320,13 @@ def test_an_eval_callback_at_the_top_level_leaves_training_alone():
 
     def learn(with_callback):
         env, policy, model = _make(graph=True)
-        with env, E._pendulum(32, 6, seed=9) as eval_env:
+        with env, pendulum(32, 6, seed=9) as eval_env:
             callback = None
             if with_callback:
                 top = EpisodeEvents(eval_env, push_prob=0.5, push_norm=(5.0, 20.0), push_steps=(1, 2), curriculum=PushLevels(3, start=3, up=0, down=0))
-                callback = EvalCallback(eval_env, n_eval_episodes=48, eval_freq=T, reward_fn=E._reward, seed=9, events=top, chunk=4)
+                callback = EvalCallback(eval_env, n_eval_episodes=48, eval_freq=T, reward_fn=pitch_reward, seed=9, events=top, chunk=4)
             model.learn(2 * B * T, callback=callback)
-            result = E._snapshot(model)
+            result = snapshot(model)
             if with_callback:
                 assert int(top.pushes.sum()) > 0 and bool((top.level == 3).all()) and bool((top.difficulty == 1.0).all())
                 assert len(callback.evaluations["timesteps"]) == 2 and all("eval/mean_reward" in r for r in model.records)
@@ -333,9 +334,9 @@ def test_an_eval_callback_at_the_top_level_leaves_training_alone():
 
     plain, evald = learn(False), learn(True)
     for k in plain[0]:
-        assert E._same(plain[0][k], evald[0][k]), k
+        assert same(plain[0][k], evald[0][k]), k
     strip = lambda records: [{k: v for k, v in r.items() if not k.startswith("eval/")} for r in records]  # noqa: E731
-    assert E._same(strip(plain[1]), strip(evald[1]))
+    assert same(strip(plain[1]), strip(evald[1]))
 
 
 def test_the_push_curriculum_example_runs():

@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from tests import reward_terms_cases as CASES
 from tests.reward_terms_reference import MUTATIONS, Twin, float32_reward
+from tests.training_rig import same, snapshot, tower, warm_up_as_the_capture_does
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -221,10 +222,6 @@ def test_graph_replay_and_two_eager_runs_give_the_same_bits():
 
 
 # ---------------------------------------------------------------- Ppo(reward=...)
-def _tower(d_in, d_out):
-    return nn.Sequential(nn.Linear(d_in, 16), nn.Tanh(), nn.Linear(16, d_out))
-
-
 TERMS = lambda: CASES.terms_for(4, 1, 5)  # noqa: E731
 B, T = 64, 8
 
@@ -262,7 +259,7 @@ def _make(pipeline, record=False, max_episode_steps=5, **kw):
     pipe = AgentPipeline(B, 4, [-1.0], [1.0], dt=1.0 / 200.0, stack=2, integrate_action=True, action_noise=[0.02], action_lag=0.05,
                          observation_noise=[0.002, 0.002, 0.01, 0.01], seed=0, device=dev) if pipeline else None
     D = pipe.stacked_dim if pipeline else 4
-    policy = MlpActorCritic.from_modules(_tower(D, 1).to(dev), _tower(D, 1).to(dev), nn.Parameter(torch.zeros(1, device=dev)), action_low=[-1.0],
+    policy = MlpActorCritic.from_modules(tower(D, 1, hidden=1).to(dev), tower(D, 1, hidden=1).to(dev), nn.Parameter(torch.zeros(1, device=dev)), action_low=[-1.0],
                                          action_high=[1.0], seed=0)
     if "reward" not in kw and "reward_fn" not in kw:
         kw["reward"] = RewardTerms(B, 4, 1, 1.0 / 200.0, TERMS(), clip=CASES.CLIP, device=dev)
@@ -273,39 +270,21 @@ def _make(pipeline, record=False, max_episode_steps=5, **kw):
     return env, policy, model
 
 
-def _warm_up_as_the_capture_does(model):
-    """A graphed `Ppo` runs one real rollout step into the last slot before it captures; the same by hand."""
-    model._setup()
-    model._slot = model.n_steps - 1
-    model._rollout_step()
-
-
-def _snapshot(model, policy):
-    torch.cuda.synchronize()
-    state = {k: v.clone() for k, v in model._state_tensors().items()}
-    state["buffer.rewards"] = model.buffer.rewards.clone()
-    return state, [dict(r) for r in model.records]
-
-
-def _equal_records(a, b):
-    return len(a) == len(b) and all(x.keys() == y.keys() and all(x[k] == y[k] or (x[k] != x[k] and y[k] != y[k]) for k in x) for x, y in zip(a, b))
-
-
 @pytest.mark.parametrize("pipeline", (False, True))
 def test_ppo_graphed_equals_not_graphed_and_logs_every_term(pipeline):
     env, policy, model = _make(pipeline, graph=True)
     with env:
         model.learn(B * T)
-        graphed = _snapshot(model, policy)
+        graphed = snapshot(model, ("buffer.rewards",))
     env, policy, model = _make(pipeline, graph=False)
     with env:
-        _warm_up_as_the_capture_does(model)
+        warm_up_as_the_capture_does(model)
         model.learn(B * T)
-        eager = _snapshot(model, policy)
+        eager = snapshot(model, ("buffer.rewards",))
     assert graphed[0].keys() == eager[0].keys() and all(k in graphed[0] for k in ("reward.prev_action", "reward.term_sum", "reward.term_last", "reward.finished"))
     for k in graphed[0]:
-        assert torch.equal(graphed[0][k], eager[0][k]), k
-    assert _equal_records(graphed[1], eager[1])
+        assert same(graphed[0][k], eager[0][k]), k
+    assert same(graphed[1], eager[1])
     record = graphed[1][-1]
     assert graphed[0]["reward.finished"].sum() > 0
     for name, _ in TERMS():
@@ -345,7 +324,7 @@ def test_ppo_save_load_resumes_bit_for_bit(tmp_path):
     env, policy, model = _make(True, graph=True)
     with env:
         model.learn(3 * B * T)
-        whole = _snapshot(model, policy)
+        whole = snapshot(model, ("buffer.rewards",))
     env, policy, model = _make(True, graph=True)
     with env:
         model.learn(3 * B * T, callback=lambda m, rec: m.iterations < 2)
@@ -357,10 +336,10 @@ def test_ppo_save_load_resumes_bit_for_bit(tmp_path):
     with env:
         resumed = Ppo.load(path, env, policy, n_steps=T, n_epochs=2, batch_size=B * T // 2, seed=0, pipeline=fresh.pipeline, reward=fresh.reward)
         resumed.learn(B * T, reset_num_timesteps=False)
-        end = _snapshot(resumed, policy)
+        end = snapshot(resumed, ("buffer.rewards",))
     for k in whole[0]:
-        assert torch.equal(whole[0][k], end[0][k]), k
-    assert _equal_records(whole[1][2:], end[1])
+        assert same(whole[0][k], end[0][k]), k
+    assert same(whole[1][2:], end[1])
     # a file saved without a reward loads into a Ppo without one, and not into one with
     env, policy, model = _make(False, graph=False, reward_fn=lambda obs, info: torch.abs(obs[:, 0]).neg_().add_(1.0))
     with env:
@@ -392,7 +371,7 @@ def test_ppo_refuses_both_rewards_and_wrong_sizes_and_is_unchanged_without():
     with env:
         assert model.reward is None and model.reward_fn is None
         model.learn(B * T)
-        learned = _snapshot(model, policy)
+        learned = snapshot(model, ("buffer.rewards",))
         assert not any(k.startswith("reward.") for k in learned[0]) and not any("ep_rew_t" in k for k in learned[1][-1])
     env, policy, model = _make(False, graph=False, reward_fn=None)
     with env:

@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from tests import task_targets_reference as R
+from tests.training_rig import bits, read_state, same, snapshot, tower, warm_up_as_the_capture_does
 from upkie_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -35,22 +36,13 @@ def _stage(num_envs, offset, D, G=None, seed=R.GPU_SEED, **settings):
     return sim, TaskTargets(env, obs_dim=D, names=names, **settings)
 
 
-def _read(targets):
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy().copy() for k, v in targets.state_tensors().items()}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _check_targets(got, want, limits, where):
     """Drawn values within one float32 ulp of max(|low|, |high|) of the twin (the device's one fma rounding is half of
     one; the fp64 twin's own error is negligible beside it); every +0.0 of the twin is +0.0, bit for bit. Returns the worst
     error in ulps."""
     worst = 0.0
     zero = want == 0.0
-    assert np.all(_bits(got.astype(np.float32))[zero] == 0), f"{where}: a zero target is +0.0 in every bit"
+    assert np.all(bits(got.astype(np.float32))[zero] == 0), f"{where}: a zero target is +0.0 in every bit"
     for g in range(got.shape[0]):
         ulp = float(np.spacing(np.float32(np.abs(limits[g]).max())))
         err = np.abs(got[g].astype(np.float64) - want[g]).max() / ulp
@@ -71,34 +63,34 @@ def test_the_kernel_is_the_twin_after_every_call(num_envs, offset, D, G):
     d_term, d_trunc, d_nxt, d_fin = (torch.from_numpy(a).to(dev) for a in (term, trunc, nxt, fin))
     targets.reset(torch.from_numpy(obs0).to(dev))
     twin.reset(obs0)
-    prev = _read(targets)
+    prev = read_state(targets)
     assert np.all(prev["calls"] == 1) and np.array_equal(prev["remaining"], twin.remaining) and not prev["final_observation"].any()
     worst = _check_targets(prev["target"], twin.target, limits, "reset")
-    assert np.array_equal(_bits(prev["observation"][:, :D]), _bits(obs0)) and np.array_equal(_bits(prev["observation"][:, D:]), _bits(prev["target"].T))
+    assert np.array_equal(bits(prev["observation"][:, :D]), bits(obs0)) and np.array_equal(bits(prev["observation"][:, D:]), bits(prev["target"].T))
     draws = 0
     for t in range(R.GPU_CALLS):
         targets.step(d_nxt[t], d_term[t], d_trunc[t], final_obs=d_fin[t])
         happened = twin.step(nxt[t], term[t], trunc[t], fin[t])
-        got = _read(targets)
+        got = read_state(targets)
         assert np.array_equal(got["calls"].view(np.uint32), twin.calls), t
         assert np.array_equal(got["remaining"], twin.remaining), t
         worst = max(worst, _check_targets(got["target"], twin.target, limits, f"call {t}"))
         held = happened["held"]
-        assert np.array_equal(_bits(got["target"][:, held]), _bits(prev["target"][:, held])), "a held target is not written"
+        assert np.array_equal(bits(got["target"][:, held]), bits(prev["target"][:, held])), "a held target is not written"
         draws += int(happened["drawn"].sum())
         # the D observation words of both rows: copies, bit for bit
         done = happened["done"]
-        assert np.array_equal(_bits(got["observation"][:, :D]), _bits(nxt[t])), t
-        assert np.array_equal(_bits(got["final_observation"][:, :D]), _bits(np.where(done[:, None], fin[t], nxt[t]))), t
+        assert np.array_equal(bits(got["observation"][:, :D]), bits(nxt[t])), t
+        assert np.array_equal(bits(got["final_observation"][:, :D]), bits(np.where(done[:, None], fin[t], nxt[t]))), t
         # the G target words of both rows: the device's own target after and before the call, bit for bit
-        assert np.array_equal(_bits(got["observation"][:, D:]), _bits(got["target"].T)), t
-        assert np.array_equal(_bits(got["final_observation"][:, D:]), _bits(prev["target"].T)), t
+        assert np.array_equal(bits(got["observation"][:, D:]), bits(got["target"].T)), t
+        assert np.array_equal(bits(got["final_observation"][:, D:]), bits(prev["target"].T)), t
         prev = got
     print(f"N = {num_envs}, offset {offset}, (D, G) = ({D}, {G}): {draws} draws, worst |target - twin| {worst:.3g} ulp of the range's end (bound 1)")
     # without a final_obs the terminal row's observation words are next_obs everywhere
     targets.step(d_nxt[0], d_term[0], d_trunc[0])
-    got = _read(targets)
-    assert np.array_equal(_bits(got["final_observation"][:, :D]), _bits(nxt[0])) and np.array_equal(_bits(got["final_observation"][:, D:]), _bits(prev["target"].T))
+    got = read_state(targets)
+    assert np.array_equal(bits(got["final_observation"][:, :D]), bits(nxt[0])) and np.array_equal(bits(got["final_observation"][:, D:]), bits(prev["target"].T))
     sim.close()
 
 
@@ -109,23 +101,23 @@ def test_reset_with_a_mask_restarts_only_its_envs():
     obs0, nxt, fin = R.gpu_observations(N, D)
     dev = sim.device
     targets.reset(torch.from_numpy(obs0).to(dev))
-    first = _read(targets)
+    first = read_state(targets)
     for t in range(12):
         targets.step(torch.from_numpy(nxt[t]).to(dev), torch.from_numpy(term[t]).to(dev), torch.from_numpy(trunc[t]).to(dev), final_obs=torch.from_numpy(fin[t]).to(dev))
-    moved = _read(targets)
+    moved = read_state(targets)
     assert np.all(moved["calls"] == 13) and not np.array_equal(moved["target"], first["target"])
     mask = np.zeros(N, dtype=np.uint8)
     mask[::3] = 1
     targets.reset(torch.from_numpy(fin[0]).to(dev), torch.from_numpy(mask).to(dev))
-    got, m = _read(targets), mask.astype(bool)
+    got, m = read_state(targets), mask.astype(bool)
     # the masked envs are back at their first draw, on the new observation; the others and every final row are untouched
     assert np.all(got["calls"][m] == 1) and np.array_equal(got["remaining"][m], first["remaining"][m])
-    assert np.array_equal(_bits(got["target"][:, m]), _bits(first["target"][:, m]))
-    assert np.array_equal(_bits(got["observation"][m, :D]), _bits(fin[0][m])) and np.array_equal(_bits(got["observation"][m, D:]), _bits(first["target"][:, m].T))
+    assert np.array_equal(bits(got["target"][:, m]), bits(first["target"][:, m]))
+    assert np.array_equal(bits(got["observation"][m, :D]), bits(fin[0][m])) and np.array_equal(bits(got["observation"][m, D:]), bits(first["target"][:, m].T))
     for name in ("calls", "remaining"):
         assert np.array_equal(got[name][~m], moved[name][~m]), name
-    assert np.array_equal(_bits(got["target"][:, ~m]), _bits(moved["target"][:, ~m])) and np.array_equal(_bits(got["observation"][~m]), _bits(moved["observation"][~m]))
-    assert np.array_equal(_bits(got["final_observation"]), _bits(moved["final_observation"]))
+    assert np.array_equal(bits(got["target"][:, ~m]), bits(moved["target"][:, ~m])) and np.array_equal(bits(got["observation"][~m]), bits(moved["observation"][~m]))
+    assert np.array_equal(bits(got["final_observation"]), bits(moved["final_observation"]))
     sim.close()
 
 
@@ -139,10 +131,10 @@ def test_one_handle_of_64_is_two_of_32_bit_for_bit():
         part = slice(lo, lo + num_envs)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(sim.device)  # noqa: E731
         targets.reset(up(obs0[part]))
-        trace = [_read(targets)]
+        trace = [read_state(targets)]
         for t in range(R.GPU_CALLS):
             targets.step(up(nxt[t][part]), up(term[t][part]), up(trunc[t][part]), final_obs=up(fin[t][part]))
-            trace.append(_read(targets))
+            trace.append(read_state(targets))
         sim.close()
         return trace
 
@@ -153,7 +145,7 @@ def test_one_handle_of_64_is_two_of_32_bit_for_bit():
                 if name == "limits":
                     continue
                 mine = a[name][:, lo:lo + 32] if name == "target" else a[name][lo:lo + 32]
-                assert np.array_equal(_bits(mine), _bits(b[name])), name
+                assert np.array_equal(bits(mine), bits(b[name])), name
 
 
 def test_a_captured_loop_follows_set_ranges_and_equals_eager():
@@ -173,17 +165,17 @@ def test_a_captured_loop_follows_set_ranges_and_equals_eager():
             body()  # (the capture's warm-up step)
             loop = types.SimpleNamespace(replay=lambda: [body() for _ in range(4)])
         loop.replay()
-        before = _read(targets)
+        before = read_state(targets)
         targets.set_ranges([(2.0, 3.0), (-7.0, -6.0)])
         loop.replay()  # (no re-capture)
-        after = _read(targets)
+        after = read_state(targets)
         sim.close()
         return before, after
 
     (g_before, g_after), (e_before, e_after) = run(True), run(False)
     for a, b in ((g_before, e_before), (g_after, e_after)):
         for name in a:
-            assert np.array_equal(_bits(a[name]), _bits(b[name])), name
+            assert np.array_equal(bits(a[name]), bits(b[name])), name
     assert np.all(g_before["calls"] == 6) and np.all(g_after["calls"] == 10)
     assert np.all(np.abs(g_before["target"][0]) <= 0.5) and np.all(np.abs(g_before["target"][1]) <= 0.25)
     # holds are 1-2 steps and four steps went by: every env has drawn from the new ranges
@@ -204,8 +196,8 @@ def test_the_curriculum_launch_is_its_twin(num_envs):
     for k in range(6):
         targets.curriculum_step(torch.from_numpy(score[k]).cuda(), torch.from_numpy(finished[k]).cuda())
         moved.append(R.curriculum_step(limits, seen, score[k], finished[k], S["threshold"], S["step"], S["limit"]))
-        got = _read(targets)
-        assert np.array_equal(_bits(got["limits"]), _bits(limits)), (k, got["limits"], limits)
+        got = read_state(targets)
+        assert np.array_equal(bits(got["limits"]), bits(limits)), (k, got["limits"], limits)
         assert np.array_equal(got["seen"], seen), k
     assert moved == [True, False, True, True, False, False]
     assert not targets._workspace[:8].any(), "the ticket is back to zero for the next launch"
@@ -225,10 +217,6 @@ def _gyropod(num_envs, limit, seed=3):
     init = RobotState(randomization=RobotStateRandomization(pitch=0.3))
     return envs.make("Upkie-HIP-Gyropod-Vec", num_envs=num_envs, frequency=200.0, init_state=init, autoreset_mode="same_step",
                      max_episode_steps=limit, seed=seed)
-
-
-def _tower(d_in, d_out):
-    return nn.Sequential(nn.Linear(d_in, 16), nn.Tanh(), nn.Linear(16, 16), nn.Tanh(), nn.Linear(16, d_out))
 
 
 def _terms():
@@ -255,38 +243,13 @@ def _make(with_targets=True, curriculum=True, **kw):
     env = _gyropod(B, 5, seed=0)
     dev = env.device
     width = D + G if with_targets else D
-    policy = MlpActorCritic.from_modules(_tower(width, 2).to(dev), _tower(width, 1).to(dev), nn.Parameter(torch.zeros(2, device=dev)),
+    policy = MlpActorCritic.from_modules(tower(width, 2).to(dev), tower(width, 1).to(dev), nn.Parameter(torch.zeros(2, device=dev)),
                                          action_low=[-1.0, -1.0], action_high=[1.0, 1.0], seed=0)
     targets = _targets(env, curriculum) if with_targets else None
     reward = RewardTerms(B, D + G, 2, dt=DT, terms=_terms(), device=dev) if with_targets else None
     args = dict(n_steps=T, n_epochs=2, batch_size=B * T // 2, seed=0, reward=reward, targets=targets)
     args.update(kw)
     return env, policy, Ppo(env, policy, **args)
-
-
-def _warm_up_as_the_capture_does(model):
-    """A graphed `Ppo` runs one real rollout step into the last slot before it captures; the same by hand."""
-    model._setup()
-    model._slot = model.n_steps - 1
-    model._rollout_step()
-
-
-def _snapshot(model):
-    torch.cuda.synchronize()
-    state = {k: v.clone() for k, v in model._state_tensors().items()}
-    if model.normalizer is not None:
-        state["normalizer"] = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in model.normalizer.state_dict().items()}
-    return state, [dict(r) for r in model.records]
-
-
-def _same(a, b):
-    if isinstance(a, torch.Tensor):
-        return torch.equal(a, b)
-    if isinstance(a, dict):
-        return a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
-    if isinstance(a, (list, tuple)):
-        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
-    return a == b or (a != a and b != b)
 
 
 TARGET_KEYS = ("targets.calls", "targets.remaining", "targets.target", "targets.limits", "targets.observation", "targets.final_observation",
@@ -298,16 +261,16 @@ def test_ppo_with_targets_graphed_equals_not_graphed():
     env, policy, model = _make(graph=True)
     with env:
         model.learn(ITERATIONS * B * T)
-        graphed = _snapshot(model)
+        graphed = snapshot(model)
     env, policy, model = _make(graph=False)
     with env:
-        _warm_up_as_the_capture_does(model)
+        warm_up_as_the_capture_does(model)
         model.learn(ITERATIONS * B * T)
-        eager = _snapshot(model)
+        eager = snapshot(model)
     assert all(k in graphed[0] for k in TARGET_KEYS + ("packed", "m", "v", "reward.term_last"))
     for k in graphed[0]:
-        assert _same(graphed[0][k], eager[0][k]), k
-    assert _same(graphed[1], eager[1]) and len(graphed[1]) == ITERATIONS
+        assert same(graphed[0][k], eager[0][k]), k
+    assert same(graphed[1], eager[1]) and len(graphed[1]) == ITERATIONS
     for record in graphed[1]:
         assert "train/loss" in record and "rollout/ep_rew_track_mean" in record
         for name in ("ground_velocity", "yaw_velocity"):
@@ -322,7 +285,7 @@ def test_ppo_with_targets_graphed_equals_not_graphed():
     env, policy, model = _make(curriculum=False, graph=True)
     with env:
         model.learn(ITERATIONS * B * T)
-        fixed = _snapshot(model)
+        fixed = snapshot(model)
     assert "targets.seen" not in fixed[0] and not torch.equal(fixed[0]["packed"], graphed[0]["packed"])
     assert fixed[0]["targets.limits"].cpu().tolist() == [[-0.5, 0.5], [-0.25, 0.25]]
 
@@ -334,7 +297,7 @@ def test_ppo_with_targets_resumes_bit_for_bit(tmp_path):
     env, policy, model = _make(graph=True)
     with env:
         model.learn(ITERATIONS * B * T)
-        whole = _snapshot(model)
+        whole = snapshot(model)
     env, policy, model = _make(graph=True)
     with env:
         model.learn(ITERATIONS * B * T, callback=lambda m, rec: m.iterations < 2)
@@ -344,10 +307,10 @@ def test_ppo_with_targets_resumes_bit_for_bit(tmp_path):
     with env:
         resumed = Ppo.load(path, env, policy, n_steps=T, n_epochs=2, batch_size=B * T // 2, seed=0, reward=fresh.reward, targets=fresh.targets)
         resumed.learn(B * T, reset_num_timesteps=False)
-        end = _snapshot(resumed)
+        end = snapshot(resumed)
     for k in whole[0]:
-        assert _same(whole[0][k], end[0][k]), k
-    assert _same(whole[1][2:], end[1])
+        assert same(whole[0][k], end[0][k]), k
+    assert same(whole[1][2:], end[1])
     # a file written without targets does not load into a run with them
     env, policy, model = _make(with_targets=False, graph=False)
     with env:
@@ -413,7 +376,7 @@ def test_an_eval_callback_with_targets_of_its_own_leaves_training_alone():
                 eval_reward = RewardTerms(32, D + G, 2, dt=DT, terms=_terms(), device=eval_env.device)
                 callback = EvalCallback(eval_env, n_eval_episodes=48, eval_freq=T, reward=eval_reward, seed=9, targets=eval_targets, chunk=4)
             model.learn(2 * B * T, callback=callback)
-            result = _snapshot(model)
+            result = snapshot(model)
             if with_callback:
                 assert int(eval_targets.calls.min()) > 1 and float(eval_targets.target.abs().max()) > 0.5, "the evaluation env draws from its own ranges"
                 assert len(callback.evaluations["timesteps"]) == 2 and all("eval/mean_reward" in r for r in model.records)
@@ -424,9 +387,9 @@ def test_an_eval_callback_with_targets_of_its_own_leaves_training_alone():
 
     plain, evald = learn(False), learn(True)
     for k in plain[0]:
-        assert _same(plain[0][k], evald[0][k]), k
+        assert same(plain[0][k], evald[0][k]), k
     strip = lambda records: [{k: v for k, v in r.items() if not k.startswith("eval/")} for r in records]  # noqa: E731
-    assert _same(strip(plain[1]), strip(evald[1]))
+    assert same(strip(plain[1]), strip(evald[1]))
 
 
 def test_refusals_on_the_device():
@@ -439,7 +402,7 @@ def test_refusals_on_the_device():
         dev = env.device
         targets = _targets(env)
         assert targets.obs_dim == D and targets.dim == D + G and set(targets.state_tensors()) == {k.split(".")[1] for k in TARGET_KEYS}
-        wide = MlpActorCritic.from_modules(_tower(D + G, 2).to(dev), _tower(D + G, 1).to(dev), nn.Parameter(torch.zeros(2, device=dev)),
+        wide = MlpActorCritic.from_modules(tower(D + G, 2).to(dev), tower(D + G, 1).to(dev), nn.Parameter(torch.zeros(2, device=dev)),
                                            action_low=[-1.0, -1.0], action_high=[1.0, 1.0], seed=0)
         other = RewardTerms(4, D + G, 2, dt=DT, terms={"alive": Term(1.0, taps=[one()])}, device=dev)
         with pytest.raises(ValueError, match="the curriculum reads the reward term 'track'"):
@@ -447,7 +410,7 @@ def test_refusals_on_the_device():
         reward = RewardTerms(4, D + G, 2, dt=DT, terms=_terms(), device=dev)
         with pytest.raises(ValueError, match="TargetCurriculum with a process_group"):
             Ppo(env, wide, reward=reward, targets=targets, process_group=object())
-        narrow = MlpActorCritic.from_modules(_tower(D, 2).to(dev), _tower(D, 1).to(dev), nn.Parameter(torch.zeros(2, device=dev)),
+        narrow = MlpActorCritic.from_modules(tower(D, 2).to(dev), tower(D, 1).to(dev), nn.Parameter(torch.zeros(2, device=dev)),
                                              action_low=[-1.0, -1.0], action_high=[1.0, 1.0], seed=0)
         with pytest.raises(ValueError, match=f"the policy reads {D} raw observation words, the env's {D} and the {G} targets make {D + G}"):
             Ppo(env, narrow, targets=_targets(env, curriculum=False))

@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from tests import vecnorm_reference as R
+from tests.training_rig import reset_pendulum, tower
 from upkie_amd.exceptions import UpkieRuntimeError
 from upkie_amd.graphs import GraphedLoop
 from upkie_amd.normalize import RunningNormalizer, packed_offsets
@@ -180,14 +181,10 @@ def test_determinism_and_graph_replay(two_launch):
     assert int(norm.workspace[:4].cpu().view(torch.int32)) == 0
 
 
-def _tower(d_in, d_out):
-    return nn.Sequential(nn.Linear(d_in, 64), nn.Tanh(), nn.Linear(64, 64), nn.Tanh(), nn.Linear(64, d_out))
-
-
 def test_policy_coupling():
     N, D = 1001, 5
     torch.manual_seed(2)
-    actor, critic = _tower(D, 2).to(DEV), _tower(D, 1).to(DEV)
+    actor, critic = tower(D, 2, 64).to(DEV), tower(D, 1, 64).to(DEV)
     log_std = nn.Parameter(torch.zeros(2, device=DEV))
     policy = MlpActorCritic.from_modules(actor, critic, log_std, [-1.0, -1.0], [1.0, 1.0])
     norm = RunningNormalizer(N, D, clip_obs=3.0, device=DEV)
@@ -222,25 +219,14 @@ def test_policy_coupling():
         RunningNormalizer(N, D, device=DEV).attach(policy)  # (already called)
 
 
-def _pendulum(n, seed=0):
-    import upkie_amd.envs as envs
-    from upkie_amd.utils.robot_state import RobotState
-    from upkie_amd.utils.robot_state_randomization import RobotStateRandomization
-
-    env = envs.make("Upkie-HIP-Pendulum-Vec", num_envs=n, frequency=200.0, init_state=RobotState(randomization=RobotStateRandomization(pitch=0.1)),
-                    autoreset_mode="same_step", max_episode_steps=400)
-    env.reset(seed=seed)
-    return env
-
-
 def test_closed_loop_eager_against_the_twin_and_graphed_bit_equal():
     N, T = 4096, 128
     results = []
     for graphed in (False, True):
         torch.manual_seed(0)
-        with _pendulum(N) as env:
+        with reset_pendulum(N) as env:
             dev = env.device
-            actor, critic = _tower(4, 1).to(dev), _tower(4, 1).to(dev)
+            actor, critic = tower(4, 1, 64).to(dev), tower(4, 1, 64).to(dev)
             policy = MlpActorCritic.from_modules(actor, critic, nn.Parameter(torch.zeros(1, device=dev)), [-1.0], [1.0], seed=0)
             norm = RunningNormalizer.for_env(env)
             norm.attach(policy)
@@ -299,7 +285,7 @@ def test_closed_loop_eager_against_the_twin_and_graphed_bit_equal():
 def test_rollout_buffer_add_policy_step_allocates_nothing():
     N, T = 1000, 4
     torch.manual_seed(1)
-    actor, critic = _tower(6, 2).to(DEV), _tower(6, 1).to(DEV)
+    actor, critic = tower(6, 2, 64).to(DEV), tower(6, 1, 64).to(DEV)
     policy = MlpActorCritic.from_modules(actor, critic, nn.Parameter(torch.zeros(2, device=DEV)), [-1.0, -1.0], [1.0, 1.0])
     norm = RunningNormalizer(N, 6, device=DEV)
     norm.attach(policy)

@@ -21,7 +21,8 @@ import torch
 from . import abi, lib
 from .agent_step import AgentStep
 from .exceptions import UpkieRuntimeError
-from .launch import check, device_tensor, launcher, ptr
+from .launch import check, device_tensor, ptr
+from .on_policy import OnPolicyDriver
 from .ppo import PackedTrainerState, Schedule, _at
 
 STAT_NAMES = abi.DISTILL_STAT_NAMES
@@ -69,26 +70,15 @@ class DistillTrainer(PackedTrainerState):
             raise ValueError("n_epochs and batch_size must be positive")
         if not float(max_grad_norm) > 0.0 or not (float(lr) >= 0.0 and math.isfinite(float(lr))):
             raise ValueError("max_grad_norm must be positive, lr finite and not negative")
-        self.policy = student
-        self.device = student.device
+        super().__init__(student, seed)
         self.n_epochs, self.batch_size, self.max_grad_norm = int(n_epochs), int(batch_size), float(max_grad_norm)
         self.obs_normalized = bool(obs_normalized)
         self.betas, self.eps = (0.9, 0.999), float(adam_eps)
-        self._lib = lib.load()
         lib.require(self._lib, "upkie_distill_minibatch_update")
-        self._launcher = launcher(self.device)
-        f32 = dict(dtype=torch.float32, device=self.device)
-        words = student.packed.numel()
-        self.m = torch.zeros(words, **f32)
-        self.v = torch.zeros(words, **f32)
         self.scalars = torch.zeros(2, dtype=torch.float64, device=self.device)  # lr, t: where a PPO control block has them
         self.scalars[0] = float(lr)
         self._lr = float(lr)
-        self.generator = torch.Generator(device=self.device)
-        self.generator.manual_seed(int(seed))
-        self._sizes = [t.numel() for t in student.sources()]
-        self._flat = torch.zeros(sum(self._sizes) + 1, **f32)
-        self._total = self._data = None
+        self._data = None  # (addresses of the two tensors a captured update reads)
 
     def _check(self, observations, labels) -> int:
         D, A = int(self.policy.shape.obs_dim), int(self.policy.shape.act_dim)
@@ -106,19 +96,12 @@ class DistillTrainer(PackedTrainerState):
         return observations.numel() // D
 
     def _allocate(self, total: int) -> None:
-        if self._total == total:
+        if not super()._allocate(total):
             return
-        if self._total is not None:
-            raise ValueError(f"this trainer serves datasets of {self._total} samples (its buffers are sized by the first prepare()); build "
-                             f"another for {total}")
-        mb = min(self.batch_size, total)
-        self.n_minibatches = (total + mb - 1) // mb
-        nbytes = int(self._lib.upkie_distill_workspace_bytes(C.byref(self.policy.shape), mb))
+        nbytes = int(self._lib.upkie_distill_workspace_bytes(C.byref(self.policy.shape), self._mb))
         check(nbytes)
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-        self.perm = torch.empty((self.n_epochs, total), dtype=torch.int32, device=self.device)
         self.stats = torch.zeros((self.n_epochs, self.n_minibatches, abi.DISTILL_STATS), dtype=torch.float32, device=self.device)
-        self._mb, self._total = mb, total
 
     def prepare(self, observations: torch.Tensor, labels: torch.Tensor) -> None:
         """Outside any capture: size the buffers (first call), bind the two tensors and draw this iteration's
@@ -130,13 +113,6 @@ class DistillTrainer(PackedTrainerState):
         elif addresses != self._data:
             raise ValueError("this trainer serves one pair of tensors (a captured update reads them): build another trainer")
         self.shuffle()
-
-    def shuffle(self) -> None:
-        """One ``randperm`` per epoch into the persistent index buffer (outside any capture)."""
-        if self._total is None:
-            raise UpkieRuntimeError("call prepare(observations, labels) first (it sizes the buffers)")
-        for e in range(self.n_epochs):
-            self.perm[e].copy_(torch.randperm(self._total, generator=self.generator, device=self.device))
 
     def update(self, observations: torch.Tensor, labels: torch.Tensor, sync: bool = True) -> torch.Tensor:
         """Every epoch and minibatch on the current permutations (no randperm, no allocation, no host synchronisation:
@@ -271,7 +247,7 @@ class LinearTeacher:
         return out
 
 
-class Distillation:
+class Distillation(OnPolicyDriver):
     """``Distillation(env, student, teacher).learn(total_timesteps)``: rsl_rl's ``Distillation`` on the device.
 
     ``teacher``: an `MlpActorCritic` (its own frozen packed statistics normalise its input; the label is its unclamped
@@ -288,8 +264,8 @@ class Distillation:
     in `Ppo`). No bootstrap, no values, no GAE. With ``graph=True`` an iteration is two graph replays: ``n_steps`` rollout
     steps through `GraphedLoop` (ONE real warm-up step first, not counted), then the update.
 
-    `learn` follows `Ppo.learn`: after each rollout ``progress_remaining`` sets the learning rate and ``beta`` through
-    their device words (floats or callables of ``progress_remaining``); every ``log_interval`` iterations a record
+    `learn` is `Ppo`'s (`upkie_amd.on_policy.OnPolicyDriver`, as are the slots, the captures and the file): after each
+    rollout ``progress_remaining`` sets the learning rate and ``beta`` through their device words (floats or callables of ``progress_remaining``); every ``log_interval`` iterations a record
     (``distill/loss``, ``distill/grad_norm``, ``distill/clip_coef``, ``distill/learning_rate``, ``distill/beta``,
     ``distill/teacher_drove_frac``, ``rollout/ep_rew_mean``, ``rollout/ep_len_mean``, ``time/*``; one device-to-host copy)
     is appended to ``records`` and handed to ``callback(model, record)``; `upkie_amd.evaluation.EvalCallback` works
@@ -338,28 +314,21 @@ class Distillation:
         self.mix = None
         self._trainer_args = dict(lr=_at(learning_rate, 1.0), n_epochs=n_epochs, batch_size=batch_size, max_grad_norm=max_grad_norm,
                                   obs_normalized=self.normalize, seed=seed)
-        self.num_timesteps, self.iterations, self.total_timesteps, self.progress_remaining = 0, 0, 0, 1.0
-        self.records = []
+        super().__init__()
         self.trainer = self.normalizer = self.episodes = self.observations = None
-        self._loop = self._update_graph = None
 
     # ---- the objects, built by the first learn() (or by load())
     def _setup(self) -> None:
         if self.observations is not None:
             return
         from .episodes import EpisodeStatistics
-        from .normalize import RunningNormalizer
 
         env, pol, N, T = self.env, self.student, self.n_envs, self.n_steps
         dev = self.device = torch.device(env.device)
         D, A = int(pol.shape.obs_dim), int(pol.shape.act_dim)
         self.mix = DaggerMix(env.sim, A, pol.action_low, pol.action_high, self._beta)
         if self.normalize:
-            if self.pipeline is None and self.targets is None:
-                self.normalizer = RunningNormalizer.for_env(env, gamma=self.gamma)
-            else:
-                self.normalizer = RunningNormalizer(N, D, gamma=self.gamma, device=dev)
-            self.normalizer.attach(pol)
+            self.normalizer = self._observation_normalizer(pol)
         self.episodes = EpisodeStatistics(N, window=self.window, device=dev)
         self.trainer = DistillTrainer(pol, **self._trainer_args)
         f32 = dict(dtype=torch.float32, device=dev)
@@ -374,11 +343,7 @@ class Distillation:
             self.teacher_observation.reset(self._agent.raw_observation)
         if self.normalizer is not None:
             self.normalizer.reset(self._agent.observation)
-        self._slot = self.n_steps - 1 if self.graph else 0  # (the capture's warm-up step takes the last slot)
-        if self.graph:
-            from .graphs import GraphedLoop
-
-            self._loop = GraphedLoop(self._rollout_step, unroll=T, warmup=1, device=dev)
+        self._begin_rollouts()
 
     def _label(self, rows: torch.Tensor, out: torch.Tensor) -> None:
         from .policies import MlpActorCritic
@@ -408,16 +373,7 @@ class Distillation:
         next_obs, _ = agent.observe()
         if self.normalizer is not None:
             self.normalizer.step(next_obs, reward, terminated, truncated, out={"reward": self._norm_reward, "episode_starts": self._starts})
-        self._slot = (t + 1) % self.n_steps
-
-    def collect_rollouts(self) -> None:
-        """``n_steps`` steps of every env into ``observations``, ``labels`` and ``drove``."""
-        if self._loop is not None:
-            self._loop.replay()
-        else:
-            for _ in range(self.n_steps):
-                self._rollout_step()
-        self.num_timesteps += self.n_steps * self.n_envs
+        self._advance_slot()
 
     def train(self) -> None:
         """The update on the collected rollout: `DistillTrainer.prepare`, then `update` (a graph replay when ``graph``)."""
@@ -425,18 +381,8 @@ class Distillation:
         tr.prepare(obs, labels)
         if not self.graph:
             tr.update(obs, labels)
-            return
-        if self._update_graph is None:
-            kept = (self.student.packed, tr.m, tr.v, tr.scalars, tr.stats)
-            state = [x.clone() for x in kept]
-            tr.update(obs, labels)  # (warm-up off the capture, undone below: the first replay is the first update)
-            torch.cuda.synchronize(self.device)
-            self._update_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._update_graph):
-                tr.update(obs, labels)
-            for dst, src in zip(kept, state):
-                dst.copy_(src)
-        self._update_graph.replay()
+        else:
+            self._replay_update(lambda: tr.update(obs, labels), (self.student.packed, tr.m, tr.v, tr.scalars, tr.stats))
 
     def set_progress(self, progress_remaining: float) -> None:
         """Evaluate the callables among ``learning_rate`` and ``beta`` at ``progress_remaining`` and write their device
@@ -465,83 +411,33 @@ class Distillation:
                        "distill/teacher_drove_frac": float(host[-1])})
         return record
 
-    def learn(self, total_timesteps: int, callback: Optional[Callable] = None, log_interval: int = 1, reset_num_timesteps: bool = True):
-        """Distil for ``total_timesteps`` env steps (whole iterations of ``n_steps * n_envs``). With
-        ``reset_num_timesteps=False`` it continues: ``total_timesteps`` more. Returns self."""
-        self._setup()
-        if reset_num_timesteps:
-            self.num_timesteps, self.iterations = 0, 0
-            self.total_timesteps = int(total_timesteps)
-        else:
-            self.total_timesteps = int(total_timesteps) + self.num_timesteps
-        while self.num_timesteps < self.total_timesteps:
-            self.collect_rollouts()
-            self.iterations += 1
-            beta_ran = self._beta  # (what this rollout ran under: the record's distill/beta)
-            self.set_progress(1.0 - float(self.num_timesteps) / float(self.total_timesteps))  # (this update's lr, the next rollout's beta)
-            self.train()
-            record = None
-            if log_interval and self.iterations % int(log_interval) == 0:
-                record = self.log()
-                record.update({"distill/beta": beta_ran, "rollout/ep_rew_mean": self.episodes.ep_rew_mean(),
-                               "rollout/ep_len_mean": self.episodes.ep_len_mean(), "time/total_timesteps": self.num_timesteps,
-                               "time/iterations": self.iterations})
-                self.records.append(record)
-            if callback is not None and callback(self, record) is False:
-                break
-        return self
+    def _after_rollout(self) -> None:
+        self._beta_ran = self._beta  # (what this rollout ran under: the record's distill/beta)
+        self.set_progress(self.progress_remaining)  # (this update's lr, the next rollout's beta)
 
-    # ---- saving and loading
-    def _env_tensors(self):
-        named = dict(self.env.state_tensors())
-        named.setdefault("observation", self._agent.raw_observation)
-        return {k: v for k, v in named.items() if isinstance(v, torch.Tensor)}
+    def _record(self) -> dict:
+        record = self.log()
+        record["distill/beta"] = self._beta_ran
+        record.update(self._rollout_record())
+        return record
 
-    _STAGES = {"policy": "", "trainer": "", "episodes": "episodes.", "pipeline": "pipeline.", "reward": "reward.", "events": "events.",
-               "teacher_observation": "teacher_observation.", "targets": "targets.", "mix": "mix."}
+    # ---- saving and loading: the weights, Adam's state, the device words, the mix counters, the normaliser, the episode
+    # statistics, every stage's state and the env
+    _FILE_NAMES = {"policy": ("", {}), "trainer": ("", {}), "episodes": ("episodes.", {}), "pipeline": ("pipeline.", {}), "reward": ("reward.", {}),
+                   "events": ("events.", {}), "teacher_observation": ("teacher_observation.", {}), "targets": ("targets.", {}), "mix": ("mix.", {})}
 
-    def _state_tensors(self):
-        named = {}
-        named.update({f"env.{k}": v for k, v in self._env_tensors().items()})
-        for stage, prefix in self._STAGES.items():
-            if getattr(self, stage) is not None:
-                named.update({prefix + k: v for k, v in getattr(self, stage).state_tensors().items()})
-        return {k: v for k, v in named.items() if v is not None}
+    def _save_own(self, sd: dict) -> None:
+        sd["counters"].update(beta=self._beta, lr=self.trainer._lr)
 
-    def save(self, path) -> None:
-        """``torch.save`` of the training state (tensors and numbers only): the weights, Adam's state, the device words,
-        the mix counters, the normaliser, the episode statistics, every stage's state and the env."""
-        self._setup()
-        torch.cuda.synchronize(self.device)
-        sd = {"tensors": {k: v.cpu() for k, v in self._state_tensors().items()}, "generator": self.trainer.generator.get_state().cpu(),
-              "normalizer": self.normalizer.state_dict() if self.normalizer is not None else None,
-              "counters": {"num_timesteps": self.num_timesteps, "iterations": self.iterations, "total_timesteps": self.total_timesteps,
-                           "progress_remaining": self.progress_remaining, "policy_seed": int(self.student.seed), "beta": self._beta,
-                           "lr": self.trainer._lr},
-              "sizes": {"n_envs": self.n_envs, "n_steps": self.n_steps}}
-        torch.save(sd, path)
+    def _before_restore(self) -> None:
+        self.student._buffers(self.n_envs)  # (the noise counters exist before they are restored)
+
+    def _restore_own(self, sd: dict) -> None:
+        self._beta, self.trainer._lr = sd["counters"]["beta"], sd["counters"]["lr"]
 
     @classmethod
     def load(cls, path, env, student, teacher, **kwargs):
         """A `Distillation` on fresh ``env`` and ``student`` objects (same sizes, same keyword arguments as the saved one;
         the teacher and the schedules are code: give them again) that continues the saved run:
         ``learn(more, reset_num_timesteps=False)``."""
-        sd = torch.load(path, map_location="cpu", weights_only=True)
-        model = cls(env, student, teacher, **kwargs)
-        if sd["sizes"] != {"n_envs": model.n_envs, "n_steps": model.n_steps}:
-            raise ValueError(f"the file holds a run of {sd['sizes']}, this one is {model.n_envs} envs x {model.n_steps} steps")
-        model._setup()
-        student.reseed(sd["counters"]["policy_seed"])
-        student._buffers(model.n_envs)  # (the noise counters exist before they are restored)
-        for name, dst in model._state_tensors().items():
-            if name not in sd["tensors"]:
-                raise ValueError(f"the file has no {name}: it was saved from another kind of env, student or stage")
-            dst.copy_(sd["tensors"][name])
-        model.trainer.generator.set_state(sd["generator"])
-        if model.normalizer is not None:
-            model.normalizer.load_state_dict(sd["normalizer"])
-        c = sd["counters"]
-        model.num_timesteps, model.iterations, model.total_timesteps = c["num_timesteps"], c["iterations"], c["total_timesteps"]
-        model.progress_remaining, model._beta, model.trainer._lr = c["progress_remaining"], c["beta"], c["lr"]
-        model.trainer.sync_modules()
-        return model
+        return cls._load(path, env, student, teacher, **kwargs)

@@ -13,6 +13,7 @@ from . import abi, lib
 from .agent_step import AgentStep
 from .exceptions import UpkieRuntimeError
 from .launch import check, launcher, ptr
+from .on_policy import OnPolicyDriver
 
 STAT_NAMES = ("policy_gradient_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction", "grad_norm")
 Schedule = Union[float, Callable[[float], float]]  # a constant, or SB3's schedule: a function of progress_remaining (1 -> 0)
@@ -36,9 +37,46 @@ def trainable_offset(shape) -> int:
 
 class PackedTrainerState:
     """What the trainers of an `MlpActorCritic`'s packed buffer share (`PpoTrainer`, `upkie_amd.distill.DistillTrainer`):
-    the write-back of the trained words into the tensors the policy was built from, and the conversion between the packed
-    layout of Adam's moments and lists in ``policy.sources()`` order. A subclass sets ``policy``, ``device``, ``_sizes``
-    (the element counts of ``policy.sources()``) and ``_flat`` (``sum(_sizes) + 1`` float32 words on the device)."""
+    Adam's moments ``m`` and ``v`` in the packed layout, the seeded device ``generator`` of the epochs' permutations and
+    the index buffer they are drawn into (`_allocate`, `shuffle`), the write-back of the trained words into the tensors
+    the policy was built from, and the conversion between the packed layout of the moments and lists in
+    ``policy.sources()`` order. ``_sizes`` holds the element counts of ``policy.sources()``, ``_flat``
+    ``sum(_sizes) + 1`` float32 words on the device. The learning rate and Adam's step count are per class: their device
+    words live where the class's launches read them."""
+
+    def __init__(self, policy, seed: int):
+        self.policy = policy
+        self.device = policy.device
+        self._lib = lib.load()
+        self._launcher = launcher(self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.m = torch.zeros(policy.packed.numel(), **f32)
+        self.v = torch.zeros(policy.packed.numel(), **f32)
+        self.generator = torch.Generator(device=self.device)
+        self.generator.manual_seed(int(seed))
+        self._sizes = [t.numel() for t in policy.sources()]
+        self._flat = torch.zeros(sum(self._sizes) + 1, **f32)  # (sync_modules' scatter target)
+        self._total = None
+
+    def _allocate(self, total: int) -> bool:
+        """Size the minibatches and the index buffer for ``total`` samples (the first call; one size per trainer). False
+        when they are sized already; the caller then allocates nothing either."""
+        if self._total == total:
+            return False
+        if self._total is not None:
+            raise ValueError(f"this trainer serves {self._total} samples (its buffers are sized by the first call); build another for {total}")
+        self._mb = min(self.batch_size, total)
+        self.n_minibatches = (total + self._mb - 1) // self._mb
+        self.perm = torch.empty((self.n_epochs, total), dtype=torch.int32, device=self.device)
+        self._total = total
+        return True
+
+    def shuffle(self) -> None:
+        """One ``randperm`` per epoch into the persistent index buffer (outside any capture)."""
+        if self._total is None:
+            raise UpkieRuntimeError("call prepare() first (it sizes the buffers)")
+        for e in range(self.n_epochs):
+            self.perm[e].copy_(torch.randperm(self._total, generator=self.generator, device=self.device))
 
     def sync_modules(self) -> None:
         """Write the packed weights back into the tensors the policy was built from (the modules' parameters, or the
@@ -157,8 +195,7 @@ class PpoTrainer(PackedTrainerState):
         self.controlled = uses if controlled is None else bool(controlled)
         self._clip_range, self._clip_range_vf = clip_range, clip_range_vf
         self._target_kl = float(target_kl) if target_kl is not None else None
-        self.policy = policy
-        self.device = policy.device
+        super().__init__(policy, seed)
         self.n_epochs, self.batch_size = int(n_epochs), int(batch_size)
         self.normalize_advantage = bool(normalize_advantage)
         self.obs_normalized = bool(obs_normalized)
@@ -168,16 +205,10 @@ class PpoTrainer(PackedTrainerState):
         cfg.adam_beta1, cfg.adam_beta2, cfg.adam_eps = 0.9, 0.999, 1e-5  # (torch.optim.Adam as SB3 builds it: eps 1e-5)
         cfg.obs_normalized = int(self.obs_normalized)
         self.config = cfg
-        self._lib = lib.load()
         lib.require(self._lib, "upkie_ppo_minibatch_update")
         self.asymmetric = bool(getattr(policy, "asymmetric", False))
         if self.asymmetric:
             lib.require(self._lib, "upkie_ppo_minibatch_update_asym", "for an asymmetric policy")
-        self._launcher = launcher(self.device)
-        words = policy.packed.numel()
-        f32 = dict(dtype=torch.float32, device=self.device)
-        self.m = torch.zeros(words, **f32)
-        self.v = torch.zeros(words, **f32)
         if self.controlled:
             lib.require(self._lib, "upkie_ppo_minibatch_update_controlled", "for target_kl and schedules")
         # the control block (include/upkie_hip.h: UPKIE_PPO_CTRL_*); `scalars` (lr, t) is its first two words
@@ -190,13 +221,7 @@ class PpoTrainer(PackedTrainerState):
         self._values = None  # (the buffer's value tensor: explained_variance reads it)
         self._log_words = torch.zeros(2, dtype=torch.float64, device=self.device)  # explained variance, std
         self._ev_exchange = None
-        self.generator = torch.Generator(device=self.device)
-        self.generator.manual_seed(int(seed))
-        self._total = None
         self._buffer = None  # (addresses of the buffer's observations, actions, values and log-probs)
-        sizes = [t.numel() for t in policy.sources()]
-        self._sizes = sizes
-        self._flat = torch.zeros(sum(sizes) + 1, **f32)  # (sync_modules' scatter target)
         self.process_group = process_group
         self._grad_exchange = self._adv_exchange = None
         if process_group is not None:
@@ -208,23 +233,16 @@ class PpoTrainer(PackedTrainerState):
 
     # ---- buffers, allocated by the first train() (one rollout size per trainer)
     def _allocate(self, total: int) -> None:
-        if self._total == total:
+        if not super()._allocate(total):
             return
-        if self._total is not None:
-            raise ValueError(f"this trainer serves rollouts of {self._total} samples (its buffers are sized by the first train()); "
-                             f"build another for {total}")
-        mb = min(self.batch_size, total)
-        self.n_minibatches = (total + mb - 1) // mb
+        mb = self._mb
         nbytes = int(self._lib.upkie_ppo_workspace_bytes(C.byref(self.policy.shape), mb))
         check(nbytes)
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-        self.perm = torch.empty((self.n_epochs, total), dtype=torch.int32, device=self.device)
         self.adv_stats = torch.zeros((self.n_epochs, self.n_minibatches, 2), dtype=torch.float64, device=self.device)
         self.stats = torch.zeros((self.n_epochs, self.n_minibatches, 7), dtype=torch.float32, device=self.device)
         self.advantages = torch.zeros(total, dtype=torch.float32, device=self.device)  # (fixed addresses: what update() reads)
         self.returns = torch.zeros(total, dtype=torch.float32, device=self.device)
-        self._mb = mb
-        self._total = total
         if self.process_group is not None:
             from .distributed import SlotExchange
 
@@ -307,13 +325,6 @@ class PpoTrainer(PackedTrainerState):
             broadcast_tensor_(t, src, self.process_group)
         self._lr = None
         self.sync_modules()
-
-    def shuffle(self) -> None:
-        """One ``randperm`` per epoch into the persistent index buffer (outside any capture)."""
-        if self._total is None:
-            raise UpkieRuntimeError("call prepare(buffer) first (it sizes the buffers)")
-        for e in range(self.n_epochs):
-            self.perm[e].copy_(torch.randperm(self._total, generator=self.generator, device=self.device))
 
     def update(self, buffer, sync: bool = True) -> torch.Tensor:
         """Every epoch and minibatch on the current permutations (no randperm, no allocation, no host synchronisation:
@@ -532,7 +543,7 @@ class PpoTrainer(PackedTrainerState):
         self._lr = float(sd["lr"])
 
 
-class Ppo:
+class Ppo(OnPolicyDriver):
     """Stable-Baselines3's ``PPO(...).learn(...)`` on the device: the driver that owns the `RolloutBuffer`, the
     `RunningNormalizer` (``normalize``), the `EpisodeStatistics`, the `PpoTrainer` and the rollout's `GraphedLoop`, and
     runs them in the order examples/ppo_mlp_train_time_limits.py establishes. One rollout step is: store the episode
@@ -546,7 +557,7 @@ class Ppo:
     its own env, policy replica and `Ppo`) nothing is captured, because the normaliser and the update exchange slots
     through collectives; ``num_timesteps`` then counts this rank's steps.
 
-    `learn` follows ``OnPolicyAlgorithm.learn``: ``num_timesteps += n_envs`` per step; after each rollout
+    `learn` (`upkie_amd.on_policy.OnPolicyDriver`, shared with `Distillation`) follows ``OnPolicyAlgorithm.learn``: ``num_timesteps += n_envs`` per step; after each rollout
     ``progress_remaining = 1 - num_timesteps / total_timesteps`` goes to the trainer's schedules (`set_progress`) BEFORE
     the update; every ``log_interval`` iterations one `PpoTrainer.log` (one device-to-host copy) plus
     ``rollout/ep_rew_mean``, ``rollout/ep_len_mean``, ``time/total_timesteps`` and ``time/iterations`` make a record,
@@ -630,10 +641,8 @@ class Ppo:
         self._trainer_args = dict(lr=learning_rate, n_epochs=n_epochs, batch_size=batch_size, clip_range=clip_range, clip_range_vf=clip_range_vf,
                                   normalize_advantage=normalize_advantage, ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm,
                                   target_kl=target_kl, obs_normalized=self.normalize, seed=seed, process_group=process_group)
-        self.num_timesteps, self.iterations, self.total_timesteps, self.progress_remaining = 0, 0, 0, 1.0
-        self.records = []
+        super().__init__()
         self.trainer = self.buffer = self.normalizer = self.critic_normalizer = self.episodes = None
-        self._loop = self._update_graph = None
 
     # ---- the objects, built by the first learn() (or by load())
     def _setup(self) -> None:
@@ -660,12 +669,8 @@ class Ppo:
                     raise ValueError(f"the policy's normaliser serves {int(live.num_envs)} envs at gamma {float(live.gamma)}, this run has {N} at "
                                      f"{self.gamma}: hand the policy over on an env of the same size, with the same gamma")
                 self.normalizer = live
-            elif self.pipeline is None and self.targets is None:
-                self.normalizer = RunningNormalizer.for_env(env, gamma=self.gamma, **kw)
-            else:  # (SB3: VecNormalize over VecFrameStack, so its columns are the stack's, not the env's; with targets: D + G)
-                self.normalizer = RunningNormalizer(N, D, gamma=self.gamma, device=dev, **kw)
-            if self.normalizer is not live:
-                self.normalizer.attach(pol)
+            else:
+                self.normalizer = self._observation_normalizer(pol, **kw)
             if self.critic_observation is not None:  # (the privileged rows' own statistics; the reward is the first one's)
                 self.critic_normalizer = RunningNormalizer(N, int(pol.critic_obs_dim), gamma=self.gamma, norm_reward=False, device=dev, **kw)
                 self.critic_normalizer.attach(pol, tower="critic")
@@ -689,11 +694,7 @@ class Ppo:
             self.critic_normalizer.reset(cobs.observation)
         self._env_action = torch.empty(N, A, device=dev)
         self._starts = torch.ones(N, dtype=torch.uint8, device=dev)
-        self._slot = self.n_steps - 1 if self.graph else 0  # (the capture's warm-up step takes the last slot)
-        if self.graph:
-            from .graphs import GraphedLoop
-
-            self._loop = GraphedLoop(self._rollout_step, unroll=T, warmup=1, device=dev)
+        self._begin_rollouts()
 
     # the env's latest (raw) observation: the agent step's
     _obs = property(lambda self: self._agent.raw_observation, lambda self, obs: setattr(self._agent, "raw_observation", obs))
@@ -734,16 +735,11 @@ class Ppo:
             self.critic_normalizer.step(cobs.observation, reward, terminated, truncated)
         if self.bootstrap:
             pol.bootstrap_time_limits(final_obs if cobs is None else cobs.final_observation, terminated, truncated, buf.rewards[t], self.gamma)
-        self._slot = (t + 1) % self.n_steps
+        self._advance_slot()
 
     def collect_rollouts(self) -> None:
         """``n_steps`` steps of every env into the buffer, then GAE (SB3's ``collect_rollouts``)."""
-        if self._loop is not None:
-            self._loop.replay()
-        else:
-            for _ in range(self.n_steps):
-                self._rollout_step()
-        self.num_timesteps += self.n_steps * self.n_envs
+        super().collect_rollouts()
         buf = self.buffer
         buf.pos, buf.full = self.n_steps, True
         last = self._agent.observation if self.critic_observation is None else self.critic_observation.observation
@@ -756,111 +752,48 @@ class Ppo:
         tr.prepare(self.buffer)
         if not self.graph:
             tr.update(self.buffer)
-            return
-        if self._update_graph is None:
-            state = [t.clone() for t in (self.policy.packed, tr.m, tr.v, tr.control, tr.stats)]
-            tr.update(self.buffer)  # (warm-up off the capture, undone below: the first replay is the first update)
-            torch.cuda.synchronize(self.device)
-            self._update_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._update_graph):
-                tr.update(self.buffer)
-            for dst, src in zip((self.policy.packed, tr.m, tr.v, tr.control, tr.stats), state):
-                dst.copy_(src)
-        self._update_graph.replay()
-
-    def learn(self, total_timesteps: int, callback: Optional[Callable] = None, log_interval: int = 1, reset_num_timesteps: bool = True):
-        """Train for ``total_timesteps`` env steps (whole iterations of ``n_steps * n_envs``, as SB3). With
-        ``reset_num_timesteps=False`` training continues: ``total_timesteps`` more steps, ``progress_remaining`` over
-        the sum, as SB3's ``_setup_learn``. Returns self."""
-        self._setup()
-        if reset_num_timesteps:
-            self.num_timesteps, self.iterations = 0, 0
-            self.total_timesteps = int(total_timesteps)
         else:
-            self.total_timesteps = int(total_timesteps) + self.num_timesteps
-        while self.num_timesteps < self.total_timesteps:
-            self.collect_rollouts()
-            if self._curriculum_term is not None:  # (one launch: the ranges of the next rollout's draws)
-                self.targets.curriculum_step(self.reward.term_last[self._curriculum_term], self.reward.finished)
-            self.iterations += 1
-            self.progress_remaining = 1.0 - float(self.num_timesteps) / float(self.total_timesteps)
-            self.trainer.set_progress(self.progress_remaining)
-            self.train()
-            record = None
-            if log_interval and self.iterations % int(log_interval) == 0:
-                record = {f"train/{k}": v for k, v in self.trainer.log().items()}
-                record.update({"rollout/ep_rew_mean": self.episodes.ep_rew_mean(), "rollout/ep_len_mean": self.episodes.ep_len_mean(),
-                               "time/total_timesteps": self.num_timesteps, "time/iterations": self.iterations})
-                if self.reward is not None:
-                    record.update({f"rollout/ep_rew_{name}_mean": mean for name, mean in self.reward.term_means().items()})
-                if self.targets is not None:
-                    record.update({f"rollout/{name}": value for name, value in self.targets.log().items()})
-                if hasattr(self.events, "log"):  # (a push curriculum's levels, live push settings; a plain stage adds nothing)
-                    record.update({f"rollout/{name}": value for name, value in self.events.log().items()})
-                self.records.append(record)
-            if callback is not None and callback(self, record) is False:
-                break
-        return self
+            self._replay_update(lambda: tr.update(self.buffer), (self.policy.packed, tr.m, tr.v, tr.control, tr.stats))
+
+    def _after_rollout(self) -> None:
+        if self._curriculum_term is not None:  # (one launch: the ranges of the next rollout's draws)
+            self.targets.curriculum_step(self.reward.term_last[self._curriculum_term], self.reward.finished)
+        self.trainer.set_progress(self.progress_remaining)
+
+    def _record(self) -> dict:
+        record = {f"train/{k}": v for k, v in self.trainer.log().items()}
+        record.update(self._rollout_record())
+        if self.reward is not None:
+            record.update({f"rollout/ep_rew_{name}_mean": mean for name, mean in self.reward.term_means().items()})
+        if self.targets is not None:
+            record.update({f"rollout/{name}": value for name, value in self.targets.log().items()})
+        if hasattr(self.events, "log"):  # (a push curriculum's levels, live push settings; a plain stage adds nothing)
+            record.update({f"rollout/{name}": value for name, value in self.events.log().items()})
+        return record
 
     # ---- saving and loading
-    def _env_tensors(self):
-        named = dict(self.env.state_tensors())
-        named.setdefault("observation", self._obs)  # (an env without a persistent buffer: the one its latest step handed out)
-        return {k: v for k, v in named.items() if isinstance(v, torch.Tensor)}
-
     # where a stage's `state_tensors` go under "tensors" in the file: stage -> (prefix, the names that differ from the stage's own)
     _FILE_NAMES = {"policy": ("", {}), "trainer": ("", {}), "episodes": ("", {"counters": "ep_counters", "means": "ep_means"}),
                    "pipeline": ("pipeline.", {}), "reward": ("reward.", {}), "events": ("events.", {}),
                    "critic_observation": ("critic_observation.", {}), "targets": ("targets.", {})}
 
-    def _state_tensors(self):
-        named = {"starts": self._starts}
-        named.update({f"env.{k}": v for k, v in self._env_tensors().items()})
-        for stage, (prefix, renamed) in self._FILE_NAMES.items():
-            if getattr(self, stage) is not None:
-                named.update({renamed.get(k, prefix + k): v for k, v in getattr(self, stage).state_tensors().items()})
-        return {k: v for k, v in named.items() if v is not None}
+    def _own_tensors(self) -> dict:
+        return {"starts": self._starts}
 
-    def save(self, path) -> None:
-        """``torch.save`` of the training state (tensors and numbers only)."""
-        self._setup()
-        torch.cuda.synchronize(self.device)
-        tr = self.trainer
-        sd = {"tensors": {k: v.cpu() for k, v in self._state_tensors().items()}, "generator": tr.generator.get_state().cpu(),
-              "normalizer": self.normalizer.state_dict() if self.normalizer is not None else None,
-              "counters": {"num_timesteps": self.num_timesteps, "iterations": self.iterations, "total_timesteps": self.total_timesteps,
-                           "progress_remaining": self.progress_remaining, "policy_seed": int(self.policy.seed)},
-              "trainer": tr.host_state(),
-              "sizes": {"n_envs": self.n_envs, "n_steps": self.n_steps}}
+    def _save_own(self, sd: dict) -> None:
+        sd["trainer"] = self.trainer.host_state()
         if self.critic_normalizer is not None:  # (a run without a privileged critic writes the names it always did)
             sd["critic_normalizer"] = self.critic_normalizer.state_dict()
-        torch.save(sd, path)
+
+    def _restore_own(self, sd: dict) -> None:
+        if self.critic_normalizer is not None:
+            if sd.get("critic_normalizer") is None:
+                raise ValueError("the file has no critic_normalizer: it was saved from a run without critic_observation")
+            self.critic_normalizer.load_state_dict(sd["critic_normalizer"])
+        self.trainer.load_host_state(sd["trainer"], self.progress_remaining)
 
     @classmethod
     def load(cls, path, env, policy, **kwargs):
         """A `Ppo` on fresh ``env`` and ``policy`` objects (same sizes, same keyword arguments as the saved one) that
         continues the saved run: ``learn(more, reset_num_timesteps=False)``."""
-        sd = torch.load(path, map_location="cpu", weights_only=True)
-        model = cls(env, policy, **kwargs)
-        if sd["sizes"] != {"n_envs": model.n_envs, "n_steps": model.n_steps}:
-            raise ValueError(f"the file holds a run of {sd['sizes']}, this one is {model.n_envs} envs x {model.n_steps} steps")
-        model._setup()
-        policy.reseed(sd["counters"]["policy_seed"])
-        tr = model.trainer
-        for name, dst in model._state_tensors().items():
-            if name not in sd["tensors"]:
-                raise ValueError(f"the file has no {name}: it was saved from another kind of env or policy")
-            dst.copy_(sd["tensors"][name])
-        tr.generator.set_state(sd["generator"])
-        if model.normalizer is not None:
-            model.normalizer.load_state_dict(sd["normalizer"])
-        if model.critic_normalizer is not None:
-            if sd.get("critic_normalizer") is None:
-                raise ValueError("the file has no critic_normalizer: it was saved from a run without critic_observation")
-            model.critic_normalizer.load_state_dict(sd["critic_normalizer"])
-        c = sd["counters"]
-        model.num_timesteps, model.iterations, model.total_timesteps = c["num_timesteps"], c["iterations"], c["total_timesteps"]
-        model.progress_remaining = c["progress_remaining"]
-        tr.load_host_state(sd["trainer"], model.progress_remaining)
-        tr.sync_modules()
-        return model
+        return cls._load(path, env, policy, **kwargs)
