@@ -208,7 +208,8 @@ enum UpkieStructId {
   UPKIE_STRUCT_PPO_CONFIG = 10,
   UPKIE_STRUCT_EPISODE_EVENTS = 11,
   UPKIE_STRUCT_TASK_TARGETS = 12,
-  UPKIE_STRUCT_COUNT = 13
+  UPKIE_STRUCT_PPO_MIRROR = 13,
+  UPKIE_STRUCT_COUNT = 14
 };
 int64_t upkie_hip_struct_bytes(int which);
 
@@ -1497,6 +1498,85 @@ int upkie_ppo_minibatch_gradient_asym(const UpkieMlpShape* shape, const UpkiePpo
                                       const float* old_log_prob, const float* advantages, const float* returns,
                                       const double* adv_stats, float* packed, void* workspace, void* slot,
                                       double* control, void* stream);
+
+/* ---- PPO update with mirror symmetry: augmented samples, mirror loss ------
+ * (rsl_rl's symmetry_cfg.) A mirror is a signed permutation per row kind:
+ * (M_o x)[k] = obs_sign[k] x[obs_index[k]] for the observation, (act_index,
+ * act_sign) for the action and, for an asymmetric shape, (critic_index,
+ * critic_sign) for the critic's row. Each is an involution: index[index[k]]
+ * == k and sign[index[k]] == sign[k]; a fixed point may carry either sign.
+ * The mirrored partner of a stored sample s has
+ *   - the stored rows M_o obs_s and M_c critic_obs_s; everything the update
+ *     does to a stored row applies afterwards, unchanged: with obs_normalized
+ *     = 0 the mirrored raw row is normalised with the statistics of word k;
+ *     with obs_normalized = 1 the stored normalised row is mirrored as it is
+ *     (under a live normaliser the mirror thus acts on normalised rows: a
+ *     sign-flipped word with a non-zero running mean is slightly off);
+ *   - the action M_a action_s (the raw Gaussian sample);
+ *   - the original's old_log_prob, old_values, returns and normalised
+ *     advantage (adv_stats are those of the B originals: the advantage
+ *     statistics launch is unchanged).
+ * P = the B originals plus, when augment, their B partners; n = |P|.
+ *   loss = (1/n) sum over P [ -min(adv ratio, adv clamp(ratio))
+ *                             + vf_coef (returns - values_pred)^2 ]
+ *          + ent_coef entropy_loss + mirror_coef L_m
+ *   L_m  = 1/(B A) sum_s sum_a ( mu(M_o x_s)[a]
+ *                                - act_sign[a] sg(mu(x_s))[act_index[a]] )^2
+ * sg stops the gradient: L_m trains through the mirrored forward only. L_m is
+ * always computed and reported, also with mirror_coef = 0. Clip, tie and clamp
+ * rules, the norm clip and Adam are upkie_ppo_minibatch_update's.
+ * stats[UPKIE_PPO_MIRROR_STATS] = policy_loss and value_loss (means over n),
+ * entropy_loss, loss (the mirror term included), approx_kl and clip_fraction
+ * over the B ORIGINALS ONLY (a partner's ratio against the original's old
+ * log-prob is not 1 before the first step unless the policy is symmetric, and
+ * target_kl keeps its meaning), ||g||_2 before the clip, mirror_loss = L_m.
+ * Three launches: the gradient launch runs 2 B positions (an original and its
+ * partner adjacent in one 16-sample tile) whatever augment is; no float
+ * atomics, the same bits every call. */
+enum { UPKIE_PPO_MIRROR_STATS = 8 };
+
+typedef struct {
+  int32_t augment;    /* 0 / 1: the partners' surrogate and value terms count */
+  float mirror_coef;  /* finite, >= 0 */
+  const void* tables; /* DEVICE memory written by upkie_ppo_mirror_set */
+} UpkiePpoMirror;
+
+/* 32-bit words of the device table block of `shape` (index then sign of the
+ * observation, of the critic's row, of the action), or
+ * UPKIE_ERR_INVALID_ARGUMENT. Needs no device. */
+int64_t upkie_ppo_mirror_words(const UpkieMlpShape* shape);
+
+/* Validates the HOST tables (obs: [obs_dim], critic: [critic_obs_dim], act:
+ * [act_dim]; index int32, sign float) and copies them to `tables` (device,
+ * upkie_ppo_mirror_words words). Checked on the host before any device use:
+ * every index in range, every sign +1 or -1, index an involution, partners'
+ * signs equal; critic tables are required for an asymmetric shape and refused
+ * (must be NULL) for a symmetric one. No unvalidated index ever reaches a
+ * gather: the update reads `tables` only. Synchronises `stream`: call it once,
+ * outside a capture. */
+int upkie_ppo_mirror_set(const UpkieMlpShape* shape, const int32_t* obs_index, const float* obs_sign,
+                         const int32_t* critic_index, const float* critic_sign, const int32_t* act_index,
+                         const float* act_sign, void* tables, void* stream);
+
+/* Bytes of the workspace of upkie_ppo_minibatch_update_mirror (the plain
+ * layout for twice the positions and one loss sum more per block; zeroed once
+ * before the first call). max_minibatch <= 2^30 - 1. Needs no device. */
+int64_t upkie_ppo_mirror_workspace_bytes(const UpkieMlpShape* shape, int32_t max_minibatch);
+
+/* One minibatch of the mirrored update (above). The arguments of
+ * upkie_ppo_minibatch_update_asym -- critic_obs NULL for a symmetric shape,
+ * control NULL for the plain form -- plus `mirror` and an 8-word stats row.
+ * Capturable, no allocation, every argument constant across iterations. With
+ * a control block it honours `stopped` as the controlled form does (all 8
+ * words NaN, nothing else written) and stops on the ORIGINALS' approx_kl. */
+int upkie_ppo_minibatch_update_mirror(const UpkieMlpShape* shape, const UpkiePpoConfig* config,
+                                      const UpkiePpoMirror* mirror, int32_t total, int32_t minibatch_start,
+                                      int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm,
+                                      const float* obs, const float* critic_obs, const float* actions,
+                                      const float* old_values, const float* old_log_prob, const float* advantages,
+                                      const float* returns, const double* adv_stats, float* packed, float* adam_m,
+                                      float* adam_v, double* adam_scalars, double* control, void* workspace,
+                                      float* stats, void* stream);
 
 /* SB3's train/explained_variance of the critic over the `total` samples of a
  * rollout: out[0] = 1 - Var(returns - values) / Var(returns), population

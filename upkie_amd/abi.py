@@ -320,6 +320,19 @@ class UpkiePpoConfig(C.Structure):
     ]
 
 
+class UpkiePpoMirror(C.Structure):
+    """The mirror of `upkie_ppo_minibatch_update_mirror` (include/upkie_hip.h, "PPO update with mirror symmetry")."""
+
+    _fields_ = [
+        ("augment", C.c_int32),
+        ("mirror_coef", C.c_float),
+        ("tables", C.c_void_p),  # device memory written by upkie_ppo_mirror_set
+    ]
+
+
+PPO_MIRROR_STATS = 8  # UPKIE_PPO_MIRROR_STATS: the plain row's 7 words, then mirror_loss
+
+
 class UpkieEpisodeEvents(C.Structure):
     """The settings of `upkie_sim_episode_events_step` (include/upkie_hip.h, "Episode events")."""
 
@@ -369,11 +382,12 @@ STRUCT_IDS = {
     10: UpkiePpoConfig,
     11: UpkieEpisodeEvents,
     12: UpkieTaskTargets,
+    13: UpkiePpoMirror,
 }
 # structs that only newer, optional entry points read: a build without that entry point (an older library loaded through
 # UPKIE_HIP_LIBRARY for an A/B run) answers -1 for them, and lib.load() still accepts it
 OPTIONAL_STRUCTS = {9: "upkie_mlp_actor_critic", 10: "upkie_ppo_minibatch_update", 11: "upkie_sim_episode_events_step",
-                    12: "upkie_sim_task_targets_step"}
+                    12: "upkie_sim_task_targets_step", 13: "upkie_ppo_minibatch_update_mirror"}
 MAX_GRAPH_CAPTURES = 8  # UPKIE_MAX_GRAPH_CAPTURES
 
 # the PPO control block's fp64 words (enum UPKIE_PPO_CTRL_*)

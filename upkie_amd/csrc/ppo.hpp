@@ -56,6 +56,18 @@
 // so the weights, m, v and t are those after the last minibatch that ran. The flag is written by one launch and read
 // by later ones: stream order makes it visible, no fence is added. ppo_begin_kernel re-arms the block per update.
 //
+// Mirrored form (MIR = true; upkie_ppo_minibatch_update_mirror): every sample s of the minibatch has a mirrored partner --
+// observation row M_o obs_s (word k = sign[k] * row[index[k]], gathered by ppo_stage_x BEFORE its normalisation, which then
+// uses the statistics of word k), critic row M_c critic_obs_s, action M_a action_s, and the original's old log-prob, old
+// value, return and normalised advantage. Original and partner are adjacent samples 2j, 2j + 1 of one 16-sample tile (lane
+// parity r & 1 tells them apart; a tail never splits a pair), so the launch runs tiles(2 B) tiles through the same towers.
+// The partner's PPO terms count only when `augment` (the loss means then run over n = 2 B positions); approx_kl and the
+// clip fraction run over the originals alone. The mirror loss L_m = 1/(B A) sum (mu(M_o x_s)[a] - sign[a] mu(x_s)[index[a]])^2
+// trains through the mirrored forward only: the tile's means go through the wave's own head rows of the stage, the mirrored
+// lane reads its partner's unit index[a] there ([index[a]][r ^ 1]; a dot head with one action needs one shuffle) and adds
+// mirror_coef 2 e / (B A) to its head dZ. A fifth fp64 loss sum collects e^2; the fold (ppo_fold<true>) writes 8 statistics
+// words. MIR = false compiles to what the kernels were before the parameter.
+//
 // Explained variance (ppo_explained_variance_kernel): 1 - Var(returns - values) / Var(returns) over the T N samples,
 // one block, the same two fp64 passes and LDS tree as launch 0.
 #pragma once
@@ -80,6 +92,7 @@ enum {
   PPO_LDS_MAX = 4 * 16 * (256 + 4 * 256 + 64 + 64),
   PPO_MAX_GRID = 512,          // blocks of launch A
   PPO_STATS = 4,               // per-block loss sums: min(surrogates), (R - v_pred)^2, approx_kl terms, clipped count
+  PPO_MIRROR_STATS = 5,        // the mirrored form's: those, then the mirror loss's squared errors
   // the control block's fp64 words (UPKIE_PPO_CTRL_* of include/upkie_hip.h); lr and t where adam_scalars has them
   PPO_CTRL_LR = 0,
   PPO_CTRL_T = 1,
@@ -133,6 +146,15 @@ struct PpoDev {
   float* grad;            // [train_words]
   double* sq_partials;    // [fold_blocks]
   float* slot;            // launch B': this rank's slot (ppo_slot_words floats)
+  // the mirrored form (MIR instantiations only; at the end, so that every other field stays where it was)
+  int mir_augment;        // 0 / 1: the partners' PPO terms count
+  float mirror_coef;
+  const int32_t* mir_obs_index;  // the validated tables (ppo_mirror_words): word k of a mirrored row = sign[k] * row[index[k]]
+  const float* mir_obs_sign;
+  const int32_t* mir_critic_index;  // (the observation's for a symmetric shape: never read there)
+  const float* mir_critic_sign;
+  const int32_t* mir_act_index;
+  const float* mir_act_sign;
 };
 
 struct PpoPlan {
@@ -192,6 +214,15 @@ inline int64_t ppo_workspace_bytes(const PpoPlan& p, int g) { return ppo_sq_at(p
 // fp64 loss sums, in fp32 words (an even count: every slot of a [world][words] array stays 8-byte aligned).
 inline int ppo_slot_stats_at(const PpoPlan& p) { return (p.train_words + 1) & ~1; }
 inline int ppo_slot_words(const PpoPlan& p) { return ppo_slot_stats_at(p) + 2 * PPO_STATS; }
+
+// The mirrored form: its table block (32-bit words: index then sign, for the observation, the critic's row of an
+// asymmetric shape, and the action), the grid of a minibatch of n samples (2 n positions), and its workspace -- the plain
+// layout with PPO_MIRROR_STATS loss sums per block.
+inline int64_t ppo_mirror_words(const UpkieMlpShape& s) { return 2 * ((int64_t)s.obs_dim + s.critic_obs_dim + s.act_dim); }
+inline int ppo_mirror_grid(const PpoPlan& p, int n) { return ppo_grid(p, 2 * n); }  // (n <= INT_MAX / 2: the entry points check)
+inline int64_t ppo_mirror_grad_at(const PpoPlan& p, int g) { return ppo_stat_partials_at(p, g) + 8 * (int64_t)g * PPO_MIRROR_STATS; }
+inline int64_t ppo_mirror_sq_at(const PpoPlan& p, int g) { return ppo_mirror_grad_at(p, g) + 4 * (int64_t)p.train_words; }
+inline int64_t ppo_mirror_workspace_bytes(const PpoPlan& p, int g) { return ppo_mirror_sq_at(p, g) + 8 * (int64_t)p.fold_blocks; }
 
 #if defined(__HIPCC__)
 
@@ -333,16 +364,21 @@ __device__ __forceinline__ float ppo_uniform(float x) {  // (a value every lane 
 // group 0 only). BC (distill.hpp; ACTOR only): the behaviour-cloning head instead of the surrogate -- the labels are read
 // where the actions are, dZ = 2 (mean - label) / (count A), st[0] collects every lane's own (mean - label)^2, and
 // log_std gets no stage rows and no partial words. BC = false compiles to what it did before the parameter.
-template <int WT, int ACT, bool ACTOR, bool BC = false>
+// MIR (the mirrored form, not with BC): odd samples of the tile are the mirrored partners of the even ones -- their action is
+// M_a action, their PPO terms count only under `augment` (`live`), the means run over n positions, the KL and clip sums skip
+// them, and the actor adds the mirror loss's dZ to theirs and its squared errors to st[4]. MIR = false likewise.
+template <int WT, int ACT, bool ACTOR, bool BC = false, bool MIR = false>
 __device__ __forceinline__ void ppo_tower(const PpoDev& P, const PpoClip& K, float* stage, int sample, bool valid, float* part, bool first,
-                                          double (&st)[PPO_STATS], int wave, int lane) {
+                                          double (&st)[MIR ? PPO_MIRROR_STATS : PPO_STATS], int wave, int lane) {
   const int q = lane >> 4, r = lane & 15, tid = wave * 64 + lane;
   const MlpTowerDev& T = ACTOR ? P.net.actor : P.net.critic;
   const PpoStage& S = P.stage[ACTOR ? 0 : 1];
   const int in_dim = ACTOR ? P.net.obs_dim : P.net.critic_obs_dim;  // (the tower's input width)
   const float* __restrict__ packed = P.packed;
   float* my = stage + wave * P.tile_floats;
-  const float inv_b = 1.f / (float)P.count;
+  const float inv_b = MIR ? 1.f / ((float)P.count * (float)(1 + P.mir_augment)) : 1.f / (float)P.count;
+  const bool mir = MIR && (r & 1);                             // (a mirrored partner)
+  const bool live = MIR ? valid && (!mir || P.mir_augment) : valid;  // (its PPO terms count)
   float cur[WT][4] = {};  // dZ of the current layer (accumulator layout)
   float dz_dot = 0.f;     // dZ of a dot head (every lane of the sample)
   {
@@ -389,6 +425,34 @@ __device__ __forceinline__ void ppo_tower(const PpoDev& P, const PpoClip& K, flo
           }
         }
       } else {
+        if constexpr (MIR) {
+          // the mirror loss: e = mu(M_o x)[a] - sign[a] mu(x)[index[a]] on the mirrored lanes, the partner's means read from
+          // the wave's own head rows ([unit][sample]); its dZ waits in `cur` for the surrogate's
+          float partner = 0.f;
+          if (T.head_dot) {
+            partner = __shfl_xor(m1, 1);
+          } else {
+            ppo_store<WT>(my, S.head_off, T.head.out_tiles, head, lane);
+            __syncthreads();
+          }
+          const float c = 2.f * P.mirror_coef / ((float)P.count * (float)P.net.act_dim);
+#pragma unroll
+          for (int o = 0; o < (WT < 4 ? WT : 4); ++o) {
+            if (o < P.net.act_tiles) {
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const int a = 16 * o + 4 * q + i;
+                if (mir && valid && a < P.net.act_dim) {
+                  const float target = T.head_dot ? partner : my[S.head_off + P.mir_act_index[a] * 16 + (r ^ 1)];
+                  const float e = head[o][i] - P.mir_act_sign[a] * target;
+                  st[4] += (double)e * (double)e;
+                  cur[o][i] = c * e;
+                }
+              }
+            }
+          }
+          if (!T.head_dot) __syncthreads();  // (the means are read: the head's dZ goes over them)
+        }
         constexpr float HALF_LOG_2PI = 0.91893853320467274f;
         float lp = 0.f, d[4][4] = {}, sig2[4][4] = {};
 #pragma unroll
@@ -401,7 +465,10 @@ __device__ __forceinline__ void ppo_tower(const PpoDev& P, const PpoClip& K, flo
               const int a = a0 + i;
               if (a < P.net.act_dim) {
                 const float sigma = expf(log_std[i]);
-                const float dd = P.actions[(size_t)sample * P.net.act_dim + a] - head[o][i];
+                float action = P.actions[(size_t)sample * P.net.act_dim + a];
+                if constexpr (MIR)
+                  if (mir) action = P.mir_act_sign[a] * P.actions[(size_t)sample * P.net.act_dim + P.mir_act_index[a]];
+                const float dd = action - head[o][i];
                 d[o][i] = dd, sig2[o][i] = sigma * sigma;
                 lp += -(dd * dd) / (2.f * sigma * sigma) - log_std[i] - HALF_LOG_2PI;
               }
@@ -418,9 +485,9 @@ __device__ __forceinline__ void ppo_tower(const PpoDev& P, const PpoClip& K, flo
         const float a1 = adv * ratio, a2 = adv * fminf(fmaxf(ratio, K.lo), K.hi);
         const float w1 = a1 < a2 ? 1.f : a1 == a2 ? 0.5f : 0.f, w2 = 1.f - w1;
         const float pass = ratio >= K.lo && ratio <= K.hi ? 1.f : 0.f;
-        const float g_lp = valid ? -inv_b * (w1 * adv + w2 * adv * pass) * ratio : 0.f;
-        if (valid && q == 0) {
-          st[0] += (double)fminf(a1, a2);
+        const float g_lp = live ? -inv_b * (w1 * adv + w2 * adv * pass) * ratio : 0.f;
+        if (live && q == 0) st[0] += (double)fminf(a1, a2);
+        if (valid && !mir && q == 0) {
           st[2] += (double)((ratio - 1.f) - log_ratio);
           st[3] += fabsf(ratio - 1.f) > K.range ? 1.0 : 0.0;
         }
@@ -432,7 +499,7 @@ __device__ __forceinline__ void ppo_tower(const PpoDev& P, const PpoClip& K, flo
             for (int i = 0; i < 4; ++i) {
               const bool on = 16 * o + 4 * q + i < P.net.act_dim;
               const float dmu = on ? g_lp * d[o][i] / sig2[o][i] : 0.f;
-              cur[o][i] = dmu;
+              cur[o][i] = MIR ? cur[o][i] + dmu : dmu;
               my[S.ls_off + (16 * o + 4 * q + i) * 16 + r] = on ? g_lp * (d[o][i] * d[o][i] / sig2[o][i] - 1.f) : 0.f;
             }
           }
@@ -454,8 +521,8 @@ __device__ __forceinline__ void ppo_tower(const PpoDev& P, const PpoClip& K, flo
         pass = dv >= -K.vf && dv <= K.vf ? 1.f : 0.f;
       }
       const float e = ret - vp;
-      dz_dot = valid ? P.vf_coef * 2.f * (vp - ret) * inv_b * pass : 0.f;
-      if (valid && q == 0) st[1] += (double)e * (double)e;
+      dz_dot = live ? P.vf_coef * 2.f * (vp - ret) * inv_b * pass : 0.f;
+      if (live && q == 0) st[1] += (double)e * (double)e;
       if (q == 0) my[S.head_off + r] = dz_dot;
     }
   }
@@ -503,9 +570,11 @@ __device__ __forceinline__ void ppo_tower(const PpoDev& P, const PpoClip& K, flo
 
 // The x rows of the wave's tile from `src` [total][dim]: element k of the sample, normalised as act() does (statistics at
 // mean_off / std_off) unless the buffer holds normalised observations; all 16 rows of every tile below dim, zeros past it.
-template <int WT>
+// MIR: a mirrored partner's (odd r) element k is sign[k] * row[index[k]], then normalised as word k. MIR = false compiles to
+// what it did before the parameter.
+template <int WT, bool MIR = false>
 __device__ __forceinline__ void ppo_stage_x(const PpoDev& P, float* my, const float* __restrict__ src, int dim, int mean_off, int std_off, int sample,
-                                            int q, int r) {
+                                            int q, int r, const int32_t* __restrict__ index = nullptr, const float* __restrict__ sign = nullptr) {
 #pragma unroll
   for (int t = 0; t < WT; ++t) {
     if (16 * t < dim) {
@@ -515,6 +584,8 @@ __device__ __forceinline__ void ppo_stage_x(const PpoDev& P, float* my, const fl
         float u = 0.f;
         if (k < dim) {
           u = src[(size_t)sample * dim + k];
+          if constexpr (MIR)
+            if (r & 1) u = sign[k] * src[(size_t)sample * dim + index[k]];
           if (P.net.normalize && !P.obs_normalized)
             u = fminf(fmaxf((u - P.packed[mean_off + k]) / P.packed[std_off + k], -P.net.clip_obs), P.net.clip_obs);
         }
@@ -526,15 +597,18 @@ __device__ __forceinline__ void ppo_stage_x(const PpoDev& P, float* my, const fl
 
 // BC (distill.hpp): the actor tower alone under the behaviour-cloning head; the partials then span the actor's words
 // (train_off = the actor's first weight word), so no log_std word and no critic word is written or folded.
-template <int W, int ACT, bool BC = false>
+// MIR: the mirrored form -- position j of the 2 mb_size is sample j >> 1, mirrored when j is odd -- with PPO_MIRROR_STATS sums.
+template <int W, int ACT, bool BC = false, bool MIR = false>
 __global__ __launch_bounds__(256) void ppo_grad_kernel(const PpoDev P) {
+  static_assert(!(BC && MIR), "the behaviour-cloning head has no mirrored form");
+  constexpr int NS = MIR ? PPO_MIRROR_STATS : PPO_STATS;
   extern __shared__ float stage[];
-  __shared__ double red[4][PPO_STATS];
+  __shared__ double red[4][NS];
   constexpr int WT = W / 16;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15;
   float* part = P.partials + (size_t)blockIdx.x * P.train_words;
   float* my = stage + wave * P.tile_floats;
-  double st[PPO_STATS] = {0.0, 0.0, 0.0, 0.0};
+  double st[NS] = {};
   PpoClip K = {P.clip_lo, P.clip_hi, P.clip_range, P.clip_vf, P.vf_clip};
   if (P.ctrl) {  // (uniform over the grid: one scalar load; the clip constants as ppo_fill forms them from the config)
     if (P.ctrl[PPO_CTRL_STOPPED] != 0.0) return;
@@ -542,44 +616,49 @@ __global__ __launch_bounds__(256) void ppo_grad_kernel(const PpoDev P) {
     K.range = ppo_uniform(cr), K.lo = ppo_uniform((float)(1.0 - (double)cr)), K.hi = ppo_uniform((float)(1.0 + (double)cr));
     K.vf = ppo_uniform(cv), K.vf_on = K.vf > 0.f;
   }
-  const int chunks = (ppo_tiles(P.mb_size) + P.nw - 1) / P.nw;
+  const int chunks = (ppo_tiles(MIR ? 2 * P.mb_size : P.mb_size) + P.nw - 1) / P.nw;
   for (int c = blockIdx.x; c < chunks; c += gridDim.x) {
     const bool first = c == (int)blockIdx.x;
-    const int64_t j = ((int64_t)c * P.nw + wave) * 16 + r;  // position in the minibatch (64-bit: no overflow near INT_MAX)
+    const int64_t at = ((int64_t)c * P.nw + wave) * 16 + r;  // position in the minibatch (64-bit: no overflow near INT_MAX)
+    const int64_t j = MIR ? at >> 1 : at;                    // (MIR: positions 2j, 2j + 1 are sample j and its partner)
     const bool valid = j < P.mb_size;
     const int sample = P.perm[(int64_t)P.mb_start + (valid ? j : 0)];
     __syncthreads();  // (the previous chunk's critic is done reading x)
-    ppo_stage_x<WT>(P, my, P.obs, P.net.obs_dim, P.net.mean_off, P.net.std_off, sample, q, r);
-    ppo_tower<WT, ACT, true, BC>(P, K, stage, sample, valid, part, first, st, wave, lane);
+    ppo_stage_x<WT, MIR>(P, my, P.obs, P.net.obs_dim, P.net.mean_off, P.net.std_off, sample, q, r, P.mir_obs_index, P.mir_obs_sign);
+    ppo_tower<WT, ACT, true, BC, MIR>(P, K, stage, sample, valid, part, first, st, wave, lane);
     if constexpr (BC) continue;
     if (P.asym) {
       __syncthreads();  // (every wave is done reading the actor's x: its first-layer dW reads every wave's rows)
-      ppo_stage_x<WT>(P, my, P.critic_obs, P.net.critic_obs_dim, P.net.critic_mean_off, P.net.critic_std_off, sample, q, r);
+      ppo_stage_x<WT, MIR>(P, my, P.critic_obs, P.net.critic_obs_dim, P.net.critic_mean_off, P.net.critic_std_off, sample, q, r, P.mir_critic_index,
+                           P.mir_critic_sign);
     }
-    ppo_tower<WT, ACT, false>(P, K, stage, sample, valid, part, first, st, wave, lane);
+    ppo_tower<WT, ACT, false, false, MIR>(P, K, stage, sample, valid, part, first, st, wave, lane);
   }
   // loss sums: a fixed shuffle tree per wave, then the waves in order
 #pragma unroll
-  for (int k = 0; k < PPO_STATS; ++k) {
+  for (int k = 0; k < NS; ++k) {
     double x = st[k];
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) x += __shfl_xor(x, m);
     if (lane == 0) red[wave][k] = x;
   }
   __syncthreads();
-  if (threadIdx.x < PPO_STATS) {
+  if (threadIdx.x < NS) {
     double s = 0.0;
     for (int w = 0; w < P.nw; ++w) s += red[w][threadIdx.x];
-    P.stat_partials[blockIdx.x * PPO_STATS + threadIdx.x] = s;
+    P.stat_partials[blockIdx.x * NS + threadIdx.x] = s;
   }
 }
 
-// Launch B: fold the partials, ||g||^2 per block, and the last block's scalars (see the top of the file).
-__global__ __launch_bounds__(PPO_THREADS) void ppo_fold_kernel(const PpoDev P) {
+// Launch B: fold the partials, ||g||^2 per block, and the last block's scalars (see the top of the file). MIR: the
+// mirrored form's PPO_MIRROR_STATS sums and 8 statistics words; MIR = false is the kernel as it was.
+template <bool MIR>
+__device__ __forceinline__ void ppo_fold(const PpoDev& P) {
+  constexpr int NS = MIR ? PPO_MIRROR_STATS : PPO_STATS;
   __shared__ double lds[PPO_THREADS + 1];
   const int tid = threadIdx.x, i = blockIdx.x * PPO_THREADS + tid;
   if (P.ctrl && P.ctrl[PPO_CTRL_STOPPED] != 0.0) {  // (read before any block's ticket, written after the last: no race)
-    if (blockIdx.x == 0 && tid < 7) P.stats[tid] = __builtin_nanf("");
+    if (blockIdx.x == 0 && tid < (MIR ? 8 : 7)) P.stats[tid] = __builtin_nanf("");
     return;
   }
   double sq = 0.0;
@@ -600,21 +679,28 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fold_kernel(const PpoDev P) {
   for (int b = 0; b < P.fold_blocks; ++b) total += P.sq_partials[b];
   const double norm = sqrt(total);
   const double coef = fmin(1.0, (double)P.max_grad_norm / (norm + 1e-6));
-  double sums[PPO_STATS] = {0.0, 0.0, 0.0, 0.0};
+  double sums[NS] = {};
   for (int b = 0; b < P.grid; ++b)
 #pragma unroll
-    for (int k = 0; k < PPO_STATS; ++k) sums[k] += P.stat_partials[(size_t)b * P.stat_stride + k];
-  const double n = (double)P.count;
+    for (int k = 0; k < NS; ++k) sums[k] += P.stat_partials[(size_t)b * P.stat_stride + k];
+  const double originals = (double)P.count;
+  const double n = MIR ? originals * (double)(1 + P.mir_augment) : originals;  // (the positions the loss means run over)
   double entropy = 0.0;
   for (int a = 0; a < P.net.act_dim; ++a) entropy += 0.5 + 0.91893853320467274 + (double)P.packed[P.net.log_std_off + a];
   const double pg = -sums[0] / n, vl = sums[1] / n, ent_loss = -entropy;
   P.stats[0] = (float)pg;
   P.stats[1] = (float)vl;
   P.stats[2] = (float)ent_loss;
-  P.stats[3] = (float)(pg + (double)P.ent_coef * ent_loss + (double)P.vf_coef * vl);
-  const float approx_kl = (float)(sums[2] / n);
+  if constexpr (MIR) {
+    const double lm = sums[4] / (originals * (double)P.net.act_dim);
+    P.stats[3] = (float)(pg + (double)P.ent_coef * ent_loss + (double)P.vf_coef * vl + (double)P.mirror_coef * lm);
+    P.stats[7] = (float)lm;
+  } else {
+    P.stats[3] = (float)(pg + (double)P.ent_coef * ent_loss + (double)P.vf_coef * vl);
+  }
+  const float approx_kl = (float)(sums[2] / originals);
   P.stats[4] = approx_kl;
-  P.stats[5] = (float)(sums[3] / n);
+  P.stats[5] = (float)(sums[3] / originals);
   P.stats[6] = (float)norm;
   if (P.ctrl) {
     // SB3: n_updates counts the epochs entered; the losses are logged, then approx_kl (a float32) is held to 1.5 target_kl
@@ -633,6 +719,9 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fold_kernel(const PpoDev P) {
   P.header[5] = (float)(P.scalars[0] / (1.0 - pow((double)P.beta1, t)));
   P.header[6] = (float)sqrt(1.0 - pow((double)P.beta2, t));
 }
+
+__global__ __launch_bounds__(PPO_THREADS) void ppo_fold_kernel(const PpoDev P) { ppo_fold<false>(P); }
+__global__ __launch_bounds__(PPO_THREADS) void ppo_mirror_fold_kernel(const PpoDev P) { ppo_fold<true>(P); }
 
 // Launch B' (data-parallel form): word i of this rank's slot = the sum of word i of the G partials in block order, as
 // launch B sums them but without the entropy term; block 0 also sums the loss-sum partials in block order and zeroes the

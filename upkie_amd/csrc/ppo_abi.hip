@@ -1,7 +1,7 @@
 // ppo_abi.hip -- the PPO update of include/upkie_hip.h (one rank, data-parallel and controlled forms): host code around
 // the kernels of ppo.hpp, and the distillation update (distill.hpp), whose launches are ppo.hpp's kernels under another head
 // and so live in the unit that defines them. Handle-free like trainer_abi.hip, and a unit of its own because its gradient-
-// kernel instantiations (ten of PPO, ten of the behaviour-cloning head) take as long to compile as everything else outside
+// kernel instantiations (ten of PPO, ten of its mirrored form, ten of the behaviour-cloning head) take as long to compile as everything else outside
 // the step kernels.
 #include <hip/hip_runtime.h>
 
@@ -9,7 +9,9 @@
 #include <climits>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <string>
+#include <vector>
 
 #include "distill.hpp"
 #include "mlp_instances.hpp"
@@ -112,10 +114,11 @@ static int ppo_gradient_setup(const UpkieMlpShape* shape, const UpkiePpoConfig* 
   return UPKIE_OK;
 }
 
-// The gradient launch (launch A) of a minibatch, and its status.
+// The gradient launch (launch A) of a minibatch, and its status. MIR: the mirrored form's instantiation.
+template <bool MIR = false>
 static int ppo_launch_gradient(const UpkieMlpShape& shape, const upkie::PpoDev& P, const upkie::PpoPlan& plan, hipStream_t s) {
   return for_mlp_instance(shape, [&](auto w, auto act) {
-    auto kernel = upkie::ppo_grad_kernel<w(), act()>;
+    auto kernel = upkie::ppo_grad_kernel<w(), act(), false, MIR>;
     if (plan.lds_bytes > upkie::PPO_LDS_BUDGET) {
       // (one tile of the widest shapes needs more than 64 KiB; MI355X has 160 KiB per CU). Raised once per instantiation, to
       // what any valid shape of it can need, so that a later shape with a larger stage is covered too: `raised` is a static
@@ -279,6 +282,110 @@ extern "C" int upkie_ppo_minibatch_gradient_asym(const UpkieMlpShape* shape, con
   return ppo_minibatch_gradient(shape, config, total, minibatch_start, minibatch_size, global_minibatch_size, max_minibatch, perm, obs,
                                 critic_obs, actions, old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, slot, control,
                                 stream);
+}
+
+// ---- the mirrored form: augmented samples and the mirror loss (include/upkie_hip.h)
+extern "C" int64_t upkie_ppo_mirror_words(const UpkieMlpShape* shape) {
+  upkie::PpoPlan plan;
+  if (check_ppo_shape(shape, &plan)) return UPKIE_ERR_INVALID_ARGUMENT;
+  return upkie::ppo_mirror_words(*shape);
+}
+
+// One table of a mirror: every index in range, every sign +1 or -1, index an involution whose partners carry equal signs.
+static int check_mirror_table(const char* name, int dim, const int32_t* index, const float* sign) {
+  const std::string what = std::string("mirror: ") + name;
+  for (int k = 0; k < dim; ++k) {
+    if (index[k] < 0 || index[k] >= dim)
+      return fail(UPKIE_ERR_INVALID_ARGUMENT, what + "_index[" + std::to_string(k) + "] = " + std::to_string(index[k]) + " is out of range [0, " +
+                                                  std::to_string(dim) + ")");
+    if (!(sign[k] == 1.f || sign[k] == -1.f))
+      return fail(UPKIE_ERR_INVALID_ARGUMENT, what + "_sign[" + std::to_string(k) + "] must be +1 or -1");
+  }
+  for (int k = 0; k < dim; ++k) {
+    if (index[index[k]] != k)
+      return fail(UPKIE_ERR_INVALID_ARGUMENT, what + "_index is not an involution: index[index[" + std::to_string(k) + "]] != " + std::to_string(k));
+    if (sign[index[k]] != sign[k])
+      return fail(UPKIE_ERR_INVALID_ARGUMENT,
+                  what + "_sign differs between the partners " + std::to_string(k) + " and " + std::to_string(index[k]) + " (the mirror would not be an involution)");
+  }
+  return UPKIE_OK;
+}
+
+extern "C" int upkie_ppo_mirror_set(const UpkieMlpShape* shape, const int32_t* obs_index, const float* obs_sign, const int32_t* critic_index,
+                                    const float* critic_sign, const int32_t* act_index, const float* act_sign, void* tables, void* stream) {
+  upkie::PpoPlan plan;
+  if (check_ppo_shape(shape, &plan)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!obs_index || !obs_sign || !act_index || !act_sign || !tables) return fail(UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  const int D = shape->obs_dim, Dc = shape->critic_obs_dim, A = shape->act_dim;
+  if (Dc != 0 && (!critic_index || !critic_sign))
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "mirror: the shape is asymmetric (critic_obs_dim " + std::to_string(Dc) +
+                                                "): the critic's row needs critic_index and critic_sign of its own");
+  if (Dc == 0 && (critic_index || critic_sign))
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "mirror: the shape is symmetric (critic_obs_dim 0): the critic reads the observation, critic tables are superfluous");
+  if (check_mirror_table("obs", D, obs_index, obs_sign) || (Dc && check_mirror_table("critic", Dc, critic_index, critic_sign)) ||
+      check_mirror_table("act", A, act_index, act_sign))
+    return UPKIE_ERR_INVALID_ARGUMENT;
+  if (no_device()) return UPKIE_ERR_NO_DEVICE;
+  // the device block: index then sign of the observation, of the critic's row, of the action (ppo_mirror_words words)
+  std::vector<uint32_t> block((size_t)upkie::ppo_mirror_words(*shape));
+  size_t at = 0;
+  auto put = [&](int dim, const int32_t* index, const float* sign) {
+    if (dim == 0) return;
+    std::memcpy(block.data() + at, index, 4 * (size_t)dim), at += dim;
+    std::memcpy(block.data() + at, sign, 4 * (size_t)dim), at += dim;
+  };
+  put(D, obs_index, obs_sign), put(Dc, critic_index, critic_sign), put(A, act_index, act_sign);
+  const hipStream_t s = (hipStream_t)stream;
+  hipError_t err = hipMemcpyAsync(tables, block.data(), 4 * block.size(), hipMemcpyHostToDevice, s);
+  if (err == hipSuccess) err = hipStreamSynchronize(s);  // (`block` ends with this call)
+  return launch_status(err);
+}
+
+extern "C" int64_t upkie_ppo_mirror_workspace_bytes(const UpkieMlpShape* shape, int32_t max_minibatch) {
+  upkie::PpoPlan plan;
+  if (check_ppo_shape(shape, &plan)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (max_minibatch < 1 || max_minibatch > INT_MAX / 2) return fail(UPKIE_ERR_INVALID_ARGUMENT, "max_minibatch must be positive and at most 2^30 - 1");
+  return upkie::ppo_mirror_workspace_bytes(plan, upkie::ppo_mirror_grid(plan, max_minibatch));
+}
+
+extern "C" int upkie_ppo_minibatch_update_mirror(const UpkieMlpShape* shape, const UpkiePpoConfig* config, const UpkiePpoMirror* mirror, int32_t total,
+                                                 int32_t minibatch_start, int32_t minibatch_size, int32_t max_minibatch, const int32_t* perm,
+                                                 const float* obs, const float* critic_obs, const float* actions, const float* old_values,
+                                                 const float* old_log_prob, const float* advantages, const float* returns, const double* adv_stats,
+                                                 float* packed, float* adam_m, float* adam_v, double* adam_scalars, double* control, void* workspace,
+                                                 float* stats, void* stream) {
+  upkie::PpoPlan plan;
+  upkie::PpoDev P;
+  if (!mirror || !mirror->tables) return fail(UPKIE_ERR_INVALID_ARGUMENT, "null mirror (or mirror->tables)");
+  if (!(mirror->mirror_coef >= 0.f) || !std::isfinite(mirror->mirror_coef))
+    return fail(UPKIE_ERR_INVALID_ARGUMENT, "mirror: mirror_coef must be finite and not negative");
+  if (max_minibatch > INT_MAX / 2) return fail(UPKIE_ERR_INVALID_ARGUMENT, "mirror: max_minibatch must be at most 2^30 - 1");
+  if (control && check_ppo_control(control)) return UPKIE_ERR_INVALID_ARGUMENT;
+  if (!adam_m || !adam_v || !adam_scalars || !stats) return fail(UPKIE_ERR_INVALID_ARGUMENT, "null argument");
+  int status = ppo_gradient_setup(shape, config, total, minibatch_start, minibatch_size, minibatch_size, max_minibatch, perm, obs, critic_obs, actions,
+                                  old_values, old_log_prob, advantages, returns, adv_stats, packed, workspace, &P, &plan);
+  if (status != UPKIE_OK) return status;
+  P.m = adam_m, P.v = adam_v, P.scalars = control ? control : adam_scalars, P.ctrl = control, P.stats = stats;
+  // the mirrored grid (2 B positions) and workspace layout (PPO_MIRROR_STATS sums per block)
+  const int ws_grid = upkie::ppo_mirror_grid(plan, max_minibatch);
+  char* ws = (char*)workspace;
+  P.grid = upkie::ppo_mirror_grid(plan, minibatch_size);
+  P.stat_stride = upkie::PPO_MIRROR_STATS;
+  P.stat_partials = (double*)(ws + upkie::ppo_stat_partials_at(plan, ws_grid));
+  P.grad = (float*)(ws + upkie::ppo_mirror_grad_at(plan, ws_grid));
+  P.sq_partials = (double*)(ws + upkie::ppo_mirror_sq_at(plan, ws_grid));
+  P.mir_augment = mirror->augment ? 1 : 0, P.mirror_coef = mirror->mirror_coef;
+  const int D = shape->obs_dim, Dc = shape->critic_obs_dim, A = shape->act_dim;
+  const int32_t* t = (const int32_t*)mirror->tables;
+  P.mir_obs_index = t, P.mir_obs_sign = (const float*)(t + D), t += 2 * D;
+  P.mir_critic_index = Dc ? t : P.mir_obs_index, P.mir_critic_sign = Dc ? (const float*)(t + Dc) : P.mir_obs_sign, t += 2 * Dc;
+  P.mir_act_index = t, P.mir_act_sign = (const float*)(t + A);
+  const hipStream_t s = (hipStream_t)stream;
+  status = ppo_launch_gradient<true>(*shape, P, plan, s);
+  if (status != UPKIE_OK) return status;
+  hipLaunchKernelGGL(upkie::ppo_mirror_fold_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
+  hipLaunchKernelGGL(upkie::ppo_adam_kernel, dim3((unsigned)P.fold_blocks), dim3(upkie::PPO_THREADS), 0, s, P);
+  return launch_status();
 }
 
 static int ppo_minibatch_apply(const UpkieMlpShape* shape, const UpkiePpoConfig* config, int32_t minibatch_start, int32_t global_minibatch_size,

@@ -335,6 +335,7 @@ extern "C" int64_t upkie_hip_struct_bytes(int which) {
     case UPKIE_STRUCT_PPO_CONFIG: return (int64_t)sizeof(UpkiePpoConfig);
     case UPKIE_STRUCT_EPISODE_EVENTS: return (int64_t)sizeof(UpkieEpisodeEvents);
     case UPKIE_STRUCT_TASK_TARGETS: return (int64_t)sizeof(UpkieTaskTargets);
+    case UPKIE_STRUCT_PPO_MIRROR: return (int64_t)sizeof(UpkiePpoMirror);
     default: return -1;
   }
 }

@@ -77,6 +77,7 @@ def _abi_table():
     asym = "upkie_mlp_actor_critic_asym"
     distill = "upkie_distill_minibatch_update"
     levels = "upkie_sim_episode_events_step_levels"
+    mirror = "upkie_ppo_minibatch_update_mirror"
     return (
         ("upkie_hip_device_count", status, None, None),
         ("upkie_hip_struct_bytes", C.c_int64, [C.c_int], "upkie_hip_struct_bytes"),  # (see _check_struct_sizes)
@@ -197,6 +198,11 @@ def _abi_table():
         ("upkie_distill_workspace_bytes", C.c_int64, [shape_p, i32], distill),
         ("upkie_distill_minibatch_update", status, [shape_p] + [i32] * 4 + [vp] * 7 + [f64] * 4 + [i32, vp, vp, vp], distill),
         ("upkie_sim_distill_mix", status, [vp, i32] + [vp] * 9, distill),
+        # the PPO update with mirror symmetry
+        ("upkie_ppo_mirror_words", C.c_int64, [shape_p], mirror),
+        ("upkie_ppo_mirror_set", status, [shape_p] + [vp] * 8, mirror),
+        ("upkie_ppo_mirror_workspace_bytes", C.c_int64, [shape_p, i32], mirror),
+        ("upkie_ppo_minibatch_update_mirror", status, [shape_p, cfg_p, P(abi.UpkiePpoMirror)] + [i32] * 4 + [vp] * 17, mirror),
     )
 
 

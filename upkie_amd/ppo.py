@@ -16,6 +16,7 @@ from .launch import check, launcher, ptr
 from .on_policy import OnPolicyDriver
 
 STAT_NAMES = ("policy_gradient_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction", "grad_norm")
+MIRROR_STAT_NAMES = STAT_NAMES + ("mirror_loss",)  # the statistics row of a trainer with ``symmetry``
 Schedule = Union[float, Callable[[float], float]]  # a constant, or SB3's schedule: a function of progress_remaining (1 -> 0)
 
 
@@ -164,14 +165,25 @@ class PpoTrainer(PackedTrainerState):
     `set_clip_range`, `set_target_kl` and across iterations that stop at different minibatches. Without them the
     trainer issues exactly the launches it always did. With a process group every rank takes the same decision from
     the same exchanged bits; the collectives of the minibatches after a stop still run (the host cannot see the flag
-    without a synchronisation) and change nothing. `log` returns SB3's ``train/*`` record with one device-to-host copy."""
+    without a synchronisation) and change nothing. `log` returns SB3's ``train/*`` record with one device-to-host copy.
+
+    ``symmetry`` (a `upkie_amd.symmetry.MirrorSymmetry`): every minibatch goes through
+    ``upkie_ppo_minibatch_update_mirror`` -- each sample next to its mirrored partner in the gradient launch (twice the
+    tiles of the plain update through the same towers), the partners' surrogate and value terms in the loss when
+    ``augment``, and ``mirror_coef`` times the mirror loss. The statistics are then ``[n_epochs, n_minibatches, 8]``
+    (`MIRROR_STAT_NAMES`: ``mirror_loss`` last), ``approx_kl`` and ``clip_fraction`` run over the originals alone, so
+    ``target_kl`` means what it means in SB3, and `log` gains ``mirror_loss``. With ``obs_normalized`` the mirror acts on
+    the stored normalised rows (`upkie_amd.symmetry`). The tables are validated on the host and written to the device
+    once, here. A ``process_group`` with ``symmetry`` is refused: the ranks' slots would need the mirror loss's sum.
+    ``symmetry=None`` issues exactly the launches and bits it always did."""
 
     asymmetric = False  # (set per object by __init__: whether the policy's critic reads rows of its own)
+    symmetry, _mirror, stat_names = None, None, STAT_NAMES  # (set per object by __init__: the mirrored form)
 
     def __init__(self, policy, lr: Schedule = 3e-4, n_epochs: int = 10, batch_size: int = 64, clip_range: Schedule = 0.2,
                  clip_range_vf: Optional[Schedule] = None, normalize_advantage: bool = True, ent_coef: float = 0.0, vf_coef: float = 0.5,
                  max_grad_norm: float = 0.5, obs_normalized: bool = False, seed: int = 0, process_group=None,
-                 target_kl: Optional[float] = None, controlled: Optional[bool] = None):
+                 target_kl: Optional[float] = None, controlled: Optional[bool] = None, symmetry=None):
         from .policies import MlpActorCritic
 
         if not isinstance(policy, MlpActorCritic):
@@ -180,6 +192,17 @@ class PpoTrainer(PackedTrainerState):
             raise ValueError("PPO needs a critic: the policy has none")
         if int(n_epochs) < 1 or int(batch_size) < 1:
             raise ValueError("n_epochs and batch_size must be positive")
+        if symmetry is not None:
+            from .symmetry import MirrorSymmetry
+
+            if not isinstance(symmetry, MirrorSymmetry):
+                raise TypeError("symmetry must be a upkie_amd.symmetry.MirrorSymmetry (or None)")
+            if process_group is not None:
+                raise ValueError("symmetry with a process_group is not supported: the ranks' slots carry four loss sums and the mirror "
+                                 "loss needs a fifth (train with symmetry on one rank, or without it on several)")
+            symmetry.check_shape(policy.shape)
+        self.symmetry = symmetry
+        self.stat_names = STAT_NAMES if symmetry is None else MIRROR_STAT_NAMES
         self._schedules = {"lr": lr, "clip_range": clip_range, "clip_range_vf": clip_range_vf}
         self.progress_remaining = 1.0
         lr, clip_range, clip_range_vf = (_at(x, 1.0) for x in (lr, clip_range, clip_range_vf))
@@ -218,6 +241,9 @@ class PpoTrainer(PackedTrainerState):
         self._lr = float(lr)
         if self.controlled:
             self._write_control(float(lr))
+        self._mirror = None
+        if symmetry is not None:
+            self._mirror = self._mirror_tables(symmetry)
         self._values = None  # (the buffer's value tensor: explained_variance reads it)
         self._log_words = torch.zeros(2, dtype=torch.float64, device=self.device)  # explained variance, std
         self._ev_exchange = None
@@ -231,16 +257,33 @@ class PpoTrainer(PackedTrainerState):
             self._grad_exchange = SlotExchange(int(self._lib.upkie_ppo_slot_bytes(C.byref(policy.shape))) // 4, self.device, process_group)
             self._ev_exchange = SlotExchange(8, self.device, process_group)  # (4 doubles per rank)
 
+    def _mirror_tables(self, symmetry) -> abi.UpkiePpoMirror:
+        """The library's own validation of the tables (host), then their one copy to the device; the struct every
+        mirrored minibatch launch is given."""
+        lb, shape = self._lib, self.policy.shape
+        lib.require(lb, "upkie_ppo_minibatch_update_mirror", "for symmetry")
+        words = int(lb.upkie_ppo_mirror_words(C.byref(shape)))
+        check(words)
+        self.mirror_tables = torch.zeros(words, dtype=torch.int32, device=self.device)
+        host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        sym = symmetry
+        self._launcher(lb.upkie_ppo_mirror_set, C.byref(shape), host(sym.obs_index), host(sym.obs_sign), host(sym.critic_index), host(sym.critic_sign),
+                       host(sym.act_index), host(sym.act_sign), ptr(self.mirror_tables))
+        mirror = abi.UpkiePpoMirror()
+        mirror.augment, mirror.mirror_coef, mirror.tables = int(sym.augment), float(sym.mirror_coef), self.mirror_tables.data_ptr()
+        return mirror
+
     # ---- buffers, allocated by the first train() (one rollout size per trainer)
     def _allocate(self, total: int) -> None:
         if not super()._allocate(total):
             return
         mb = self._mb
-        nbytes = int(self._lib.upkie_ppo_workspace_bytes(C.byref(self.policy.shape), mb))
+        workspace_bytes = self._lib.upkie_ppo_workspace_bytes if self._mirror is None else self._lib.upkie_ppo_mirror_workspace_bytes
+        nbytes = int(workspace_bytes(C.byref(self.policy.shape), mb))
         check(nbytes)
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self.adv_stats = torch.zeros((self.n_epochs, self.n_minibatches, 2), dtype=torch.float64, device=self.device)
-        self.stats = torch.zeros((self.n_epochs, self.n_minibatches, 7), dtype=torch.float32, device=self.device)
+        self.stats = torch.zeros((self.n_epochs, self.n_minibatches, len(self.stat_names)), dtype=torch.float32, device=self.device)
         self.advantages = torch.zeros(total, dtype=torch.float32, device=self.device)  # (fixed addresses: what update() reads)
         self.returns = torch.zeros(total, dtype=torch.float32, device=self.device)
         if self.process_group is not None:
@@ -376,6 +419,11 @@ class PpoTrainer(PackedTrainerState):
         with ``minibatch_start`` first (the apply half)."""
         lb, launch, gx, ctl, mb = self._lib, self._launcher, self._grad_exchange, self.controlled, self._mb
         adv_stats, packed, work, stats = ptr(self.adv_stats[e, j]), ptr(self.policy.packed), ptr(self.workspace), ptr(self.stats[e, j])
+        if self._mirror is not None:  # (one entry point: a nullable critic_obs after obs, a nullable control block)
+            rows = data if self.asymmetric else data[:1] + (None,) + data[1:]
+            launch(lb.upkie_ppo_minibatch_update_mirror, *head, C.byref(self._mirror), total, start, size, mb, perm, *rows, adv_stats, packed,
+                   ptr(self.m), ptr(self.v), ptr(self.scalars), ptr(self.control) if ctl else None, work, stats)
+            return
         if self.asymmetric:  # (one entry point per half serves the plain and the controlled form: a nullable control block)
             control = ptr(self.control) if ctl else None
             if gx is None:
@@ -494,9 +542,9 @@ class PpoTrainer(PackedTrainerState):
         torch.mean(torch.exp(self.policy.packed[off:off + A]).double(), dim=0, out=self._log_words[1])
         host = torch.cat([self.stats.reshape(-1).double(), self.control, self._log_words]).cpu().numpy()  # the one copy
         n = self.stats.numel()
-        rows, ctrl, words = host[:n].reshape(-1, len(STAT_NAMES)), host[n:n + abi.PPO_CTRL_WORDS], host[n + abi.PPO_CTRL_WORDS:]
+        rows, ctrl, words = host[:n].reshape(-1, len(self.stat_names)), host[n:n + abi.PPO_CTRL_WORDS], host[n + abi.PPO_CTRL_WORDS:]
         ran = rows[~(rows != rows).any(axis=1)]
-        record = {name: float(ran[:, k].mean()) if len(ran) else math.nan for k, name in enumerate(STAT_NAMES)}
+        record = {name: float(ran[:, k].mean()) if len(ran) else math.nan for k, name in enumerate(self.stat_names)}
         stopped = self.controlled and ctrl[abi.PPO_CTRL_STOPPED] != 0.0
         record.update(explained_variance=float(words[0]), std=float(words[1]), n_updates=self._n_updates(ctrl),
                       clip_range=float(ctrl[abi.PPO_CTRL_CLIP_RANGE]) if self.controlled else float(self._clip_range),
@@ -594,6 +642,14 @@ class Ppo(OnPolicyDriver):
     ``process_group`` it is refused); a record carries ``rollout/target_<name>_low`` and ``_high``. `save` / `load`
     carry ``targets.*``, the ranges included. ``targets=None``: every launch and every bit as without.
 
+    ``symmetry`` (a `upkie_amd.symmetry.MirrorSymmetry` of the words the POLICY reads: `MirrorSymmetry.gyropod(targets)` for
+    a Gyropod env with targets, ``.for_pipeline(pipeline)`` behind a pipeline) adds the robot's left/right symmetry to the
+    update, as rsl_rl's ``symmetry_cfg`` does: mirrored samples join every minibatch (``augment``) and ``mirror_coef``
+    weighs the mirror loss (`PpoTrainer`). The rollout does not change; the update's graph holds the mirrored launches; a
+    record gains ``train/mirror_loss``. With ``normalize`` the mirror acts on the normalised rows the rollout stored: a
+    sign-flipped word with a non-zero running mean is slightly off. Symmetry is code, like a schedule: give it to `load`
+    again. With a ``process_group`` it is refused. ``symmetry=None``: every launch and every bit as without.
+
     A ``policy`` that arrives with a live `RunningNormalizer` and has been called (a student of
     `upkie_amd.distill.Distillation`) keeps that normaliser: with ``normalize`` the run goes on under the statistics the
     policy was fitted under, on an env of the same size and with the same ``gamma`` (another size or ``gamma`` is refused).
@@ -605,9 +661,12 @@ class Ppo(OnPolicyDriver):
                  normalize_advantage: bool = True, ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5,
                  target_kl: Optional[float] = None, normalize: bool = True, bootstrap_time_limits: bool = True, stats_window_size: int = 100,
                  reward_fn: Optional[Callable] = None, graph: bool = True, seed: int = 0, process_group=None, pipeline=None, reward=None,
-                 events=None, critic_observation=None, targets=None):
+                 events=None, critic_observation=None, targets=None, symmetry=None):
         if int(n_steps) < 1:
             raise ValueError("n_steps must be positive")
+        if symmetry is not None and process_group is not None:
+            raise ValueError("symmetry with a process_group is not supported: the ranks' slots carry four loss sums and the mirror "
+                             "loss needs a fifth (train with symmetry on one rank, or without it on several)")
         curriculum = getattr(targets, "curriculum", None)
         if curriculum is not None and process_group is not None:
             raise ValueError("a TargetCurriculum with a process_group is not supported: every rank would widen its own ranges from its own "
@@ -641,6 +700,9 @@ class Ppo(OnPolicyDriver):
         self._trainer_args = dict(lr=learning_rate, n_epochs=n_epochs, batch_size=batch_size, clip_range=clip_range, clip_range_vf=clip_range_vf,
                                   normalize_advantage=normalize_advantage, ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm,
                                   target_kl=target_kl, obs_normalized=self.normalize, seed=seed, process_group=process_group)
+        if symmetry is not None:  # (a run without it builds its trainer with the arguments it always did)
+            self._trainer_args["symmetry"] = symmetry
+        self.symmetry = symmetry
         super().__init__()
         self.trainer = self.buffer = self.normalizer = self.critic_normalizer = self.episodes = None
 
